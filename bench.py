@@ -11,7 +11,9 @@ synthetic 480x480x100 LES cloud domain (nadir radiance,
 absorption, Lambert surface), and -- for N > 1 -- one RCCL all-reduce of the radiance tally.  Photon ids are
 disjoint across ranks and steps.  `--scaling weak` (default): `--photons` per GPU, per-GPU work fixed; `--scaling
 strong`: `--photons` in all, split over the ranks (config 4 as written: 1e9 photons on 8 GPUs).  Inputs are resident in
-HBM before the timed region.  Rank 0 prints ONE JSON line.
+HBM before the timed region.  Rank 0 prints ONE JSON line.  `--dump-outputs DIR`: rank 0 also writes what the last timed step
+computed (the normalised field and the raw tally) as DIR/<name>.npy; the inputs and photon ids depend on the arguments alone, so two
+builds run with the same arguments can be compared output for output.
 
 Extra objects on the line
   roofline     : algorithmic bytes per launch (measured with the instrumented kernel build on a sub-sample of the
@@ -53,6 +55,32 @@ HBM_PEAK_GBS = 8000.0      # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E peak 
 # transcendentals 8.1: profiles/r05/mix_rates_ops.log, mix_rates_ops2.log.  Round 4 priced every instruction at 4 cycles and 2.4 GHz
 # and read 1.02-1.05 of the issue rate -- a fraction above 1.)  issue_frac = wave-instructions per second of the run / this ceiling.
 VALU_MIX_CEILING = 7.52e11
+DUMP_LIMIT_BYTES = 64*10**6      # --dump-outputs: at most this many bytes in all
+DUMP_SAMPLE_SEED = 20251015      # ... beyond it, the same seeded sample of flat indices in every run
+
+
+def dump_outputs(outdir, arrays, limit=DUMP_LIMIT_BYTES, seed=DUMP_SAMPLE_SEED):
+    """Write {name: array} as outdir/<name>.npy, float32 or float64 as the arrays are.  Where they hold more than `limit` bytes in all
+    (arrays of one size: a field and its tally), every array is cut to the same fixed, seeded sample of its flat indices, and the
+    indices go to outdir/sample_index.npy (float64, exact).  Returns {file name: shape}."""
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    for k, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise ValueError('--dump-outputs: %s is %s, not float32 / float64' % (k, a.dtype))
+    os.makedirs(outdir, exist_ok=True)
+    if sum(a.nbytes for a in arrays.values()) > limit - 4096:      # (4 KB kept for the .npy headers)
+        sizes = {a.size for a in arrays.values()}
+        if len(sizes) != 1:
+            raise ValueError('--dump-outputs: arrays of different sizes cannot share one sample')
+        n = sizes.pop()
+        m = min(n, (limit - 4096)//(8 + sum(a.itemsize for a in arrays.values())))
+        idx = np.sort(np.random.default_rng(seed).choice(n, size=m, replace=False))
+        arrays = dict({name: a.reshape(-1)[idx] for name, a in arrays.items()}, sample_index=idx.astype(np.float64))
+    written = {}
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + '.npy'), np.ascontiguousarray(a))
+        written[name + '.npy'] = list(a.shape)
+    return written
 
 
 def parity_stats(g, o, nblk=16, min_block_rel=0.0):
@@ -552,7 +580,13 @@ def main():
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'], help='gloo: rehearsal of the N-rank plumbing')
     ap.add_argument('--dry-run', action='store_true',
                     help='no transport at all (CPU test of the launcher and the exchange): the line says so and is not a measurement')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed as DIR/<name>.npy: the normalised field a caller of the '
+                         'solver receives (radiance.npy or flux.npy, float32) and the raw tally (tally.npy, float64); at most 64 MB in all, '
+                         'a fixed, seeded sample of larger outputs (DIR/sample_index.npy)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(spawn(args, sys.argv[1:]))
@@ -644,6 +678,15 @@ def main():
         elapsed = float(tt.item())
     kernel_ms, launches = sol.timing()
     kernel_name = sol.kernel_name()
+
+    # ---- --dump-outputs: the last timed step's results, read before anything else runs on this handle or writes the tally
+    if args.dump_outputs and rank == 0:
+        field = sol.flux(Ptot) if is_flux else sol.radiance(Ptot)         # (normalised on the device from the bound tally)
+        torch.cuda.synchronize(dev)
+        tally = rad.cpu().numpy()
+        written = dump_outputs(args.dump_outputs, {'flux' if is_flux else 'radiance': field,
+                                                   'tally': tally.reshape(field.shape) if tally.size == field.size else tally})
+        print('bench.py: last timed step written to %s: %s' % (args.dump_outputs, written), file=sys.stderr)
 
     # ---- N > 1: BASELINE config 4 as it is written -- `--photons` IN ALL, sharded over the ranks -- timed beside the weak-scaling headline
     #      (the driver runs `--scaling weak`; the strong line is the config's own wording).  Same barrier / max-over-ranks bracket.
