@@ -98,6 +98,16 @@ struct mi3d_solver {
     float sfc_param[5] = {0, 0, 0, 0, 0};
     std::vector<float> sfc2d_host;
     double src_flx = 1.0, src_qmax = 0.0, src_the = 180.0, src_phi = 0.0;
+    // thermal source (mi3d_set_thermal): Src_mtype 3, band-centre wavelength, interface / voxel / surface temperatures; the
+    // emitted power of every cell as a CDF on the device (k_thermal_power, k_scan_*), rebuilt by mi3d_prepare when dirty
+    int src_mtype = 1;
+    double th_wlen = 0.0, th_ptot = 0.0, th_ms = 0.0;
+    std::vector<float> th_tlev;
+    size_t th_ntmpa = 0, th_ntmps = 0;   // elements of the anomalies handed over (0: none)
+    DevBuf<float> d_th_tlev, d_th_tmpa, d_th_tmps;
+    DevBuf<double> d_th_cdf, d_th_bsum;
+    DevBuf<DevThermal> d_th;
+    bool dirty_thermal = false;
     int nview = 0, nxr = 1, nyr = 1;
     double view_the[MI3D_MAX_VIEW], view_phi[MI3D_MAX_VIEW], view_zloc[MI3D_MAX_VIEW], zref = 0.0;
     // cameras (mi3d_set_cameras): rad_kind 1, the views are point sensors
@@ -490,6 +500,7 @@ int fill_scene(mi3d_solver *h, DevScene &S) {
         // (a source cone much wider than the solar disc -- er3t hard-wires 0.533 deg, mcarats.py:378 -- spreads the path
         //  lengths of the direct beam: then every crossing is tallied like anywhere else)
         if (h->src_qmax > 1.0) h->kdir = nz + 1;
+        if (h->src_mtype == 3) h->kdir = nz + 1;   // (thermal: there is no direct beam)
         S.kdir = h->kdir;
         h->dir_level.assign(nz + 1, 0.0);
         const double mu0 = std::fabs(std::cos(th));
@@ -610,6 +621,63 @@ int check_handle(mi3d_solver *h) {
     return MI3D_OK;
 }
 
+// The power per unit domain area a job's photons stand for in all: Src_flx mu0 (solar), Src_flx P_tot / (Lx Ly) (thermal)
+double src_amp(const mi3d_solver *h) {
+    if (h->src_mtype == 3) return h->src_flx * h->th_ptot / ((h->dx * h->nx) * (h->dy * h->ny));
+    return h->src_flx * std::fabs(std::cos(h->src_the * 3.14159265358979323846 / 180.0));
+}
+
+// Thermal source: emitted power of every cell (k_thermal_power), its CDF and P_tot (k_scan_*), the photon loop's DevThermal.
+int build_thermal(mi3d_solver *h) {
+    if ((int)h->th_tlev.size() != h->nz + 1)
+        return fail(MI3D_ESTATE, "thermal source: %d interface temperatures for Atm_nz=%d (call mi3d_set_thermal again)", (int)h->th_tlev.size(), h->nz);
+    const size_t nvox = (size_t)h->nx * h->ny * h->nz3;
+    if (h->th_ntmpa && h->th_ntmpa != nvox)
+        return fail(MI3D_ESTATE, "thermal source: Atm_tmpa3d holds %zu voxels, the 3-D region %zu (call mi3d_set_thermal again)", h->th_ntmpa, nvox);
+    const bool sfc2d = !h->sfc2d_host.empty();
+    const size_t nsfc = sfc2d ? (size_t)h->nxb * h->nyb : 1;
+    if (h->th_ntmps && (!sfc2d || h->th_ntmps != nsfc))
+        return fail(MI3D_ESTATE, "thermal source: Sfc_tmps2d holds %zu cells, the surface %zu (call mi3d_set_thermal again)", h->th_ntmps, sfc2d ? nsfc : 0);
+    if (!h->sfc_lambert_only) return fail(MI3D_EUNSUP, "thermal source: only Lambertian surfaces emit (Sfc_mtype / jsfc2d = 1)");
+    const size_t ncell = nvox + (size_t)h->nz + nsfc;
+    if (ncell > 4294967295ull) return fail(MI3D_EUNSUP, "thermal source: more than 2^32 cells");
+    const size_t nblk = (ncell + kScanChunk - 1) / kScanChunk;
+    int rc;
+    if ((rc = h->d_th_cdf.alloc(ncell)) || (rc = h->d_th_bsum.alloc(nblk)) || (rc = h->d_th.alloc(1))) return rc;
+    if ((rc = h->d_th_tlev.upload(h->th_tlev.data(), h->th_tlev.size()))) return rc;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+    HIPCHK(hipEventRecord(e0, h->stream));
+    const int k3lo = h->nz3 > 0 ? h->iz3l - 1 : 0;
+    hipLaunchKernelGGL(k_thermal_power, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, h->stream, h->nx, h->ny, h->nz, h->nz3, k3lo, h->np1d,
+                       h->np3d, h->dx, h->dy, h->th_wlen, (const LayerRec *)h->d_lay.p, (const float4 *)(h->nz3 > 0 ? h->d_vrec.p : nullptr), h->vcol_f4, h->vrow_f4,
+                       (const float2 *)h->d_csca.p, (const float *)h->d_th_tlev.p, (const float *)(h->th_ntmpa ? h->d_th_tmpa.p : nullptr),
+                       sfc2d ? h->nxb : 1, sfc2d ? h->nyb : 1, (const float *)(sfc2d ? h->d_sfc2d.p : nullptr), h->sfc_param[0],
+                       (const float *)(h->th_ntmps ? h->d_th_tmps.p : nullptr), h->d_th_cdf.p);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_scan_chunk, dim3((unsigned)nblk), dim3(kScanT), 0, h->stream, h->d_th_cdf.p, (unsigned long)ncell, h->d_th_bsum.p);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, h->stream, h->d_th_bsum.p, (unsigned long)nblk);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_scan_add, dim3((unsigned)nblk), dim3(256), 0, h->stream, h->d_th_cdf.p, (unsigned long)ncell, (const double *)h->d_th_bsum.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e1, h->stream));
+    double ptot = 0.0;
+    HIPCHK(hipMemcpyAsync(&ptot, h->d_th_cdf.p + (ncell - 1), sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    float ms = 0.0f;
+    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    h->th_ms = ms;
+    if (!(ptot >= 0.0) || !std::isfinite(ptot)) return fail(MI3D_EINVAL, "thermal source: total emitted power %g", ptot);
+    h->th_ptot = ptot;
+    DevThermal T;
+    T.cdf = h->d_th_cdf.p; T.ptot = ptot; T.ncell = (unsigned)ncell; T.nvox = (unsigned)nvox;
+    T.nxb = sfc2d ? h->nxb : 1; T.nyb = sfc2d ? h->nyb : 1;
+    if ((rc = h->d_th.upload(&T, 1))) return rc;
+    return MI3D_OK;
+}
+
 } // namespace
 
 // =================================================================================================
@@ -720,6 +788,7 @@ int mi3d_destroy(mi3d_solver *h) {
     h->d_tl_rec.release(); h->d_tl_binned.release(); h->d_tl_words.release(); h->d_tl_cursor.release(); h->d_tl_stats.release();
     for (int w = 0; w < 2; ++w) { h->d_run_own[w].release(); h->d_sum[w].release(); h->d_sumsq[w].release(); h->d_factor[w].release(); }
     h->d_stat_out.release(); h->d_dir_level.release(); h->d_get_out.release(); h->d_get_add.release();
+    h->d_th_tlev.release(); h->d_th_tmpa.release(); h->d_th_tmps.release(); h->d_th_cdf.release(); h->d_th_bsum.release(); h->d_th.release();
     h->d_views.release(); h->d_cold.release(); h->d_tabrange.release(); h->d_bt1d.release(); h->d_dz.release(); h->d_bmin.release(); h->d_bmax.release();
     delete h;
     return MI3D_OK;
@@ -797,6 +866,7 @@ int mi3d_set_surface(mi3d_solver *h, int mtype, const float param[5]) {
     for (int i = 0; i < 5; ++i) h->sfc_param[i] = param[i];
     h->sfc2d_host.clear(); h->nxb = h->nyb = 0;
     h->dirty_sfc = true;
+    h->dirty_thermal = true;
     ev_forget(h);   // (a brighter surface: more events per photon; the next run with marched views starts with a pilot launch)
     return MI3D_OK;
 }
@@ -820,6 +890,7 @@ int mi3d_set_surface2d(mi3d_solver *h, int nxb, int nyb, const float *tmps, cons
     h->sfc_lambert_only = lambert_only;
     h->nxb = nxb; h->nyb = nyb;
     h->dirty_sfc = true;
+    h->dirty_thermal = true;
     ev_forget(h);
     return MI3D_OK;
 }
@@ -831,6 +902,44 @@ int mi3d_set_source(mi3d_solver *h, double flx, double qmax_deg, double the_deg,
     if (!(qmax_deg >= 0.0 && qmax_deg < 90.0)) return fail(MI3D_EINVAL, "Src_qmax=%g out of range", qmax_deg);
     if (h->src_the != the_deg || h->src_phi != phi_deg || h->src_qmax != qmax_deg) ev_forget(h);
     h->src_flx = flx; h->src_qmax = qmax_deg; h->src_the = the_deg; h->src_phi = phi_deg;
+    return MI3D_OK;
+}
+
+int mi3d_set_thermal(mi3d_solver *h, int mtype, double wlen_um, int nlev, const float *tmp1d, const float *tmpa3d,
+                     const float *tmps2d) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (mtype == 1) {
+        if (h->src_mtype != 1) ev_forget(h);
+        h->src_mtype = 1; h->th_ptot = 0.0; h->dirty_thermal = false;
+        return MI3D_OK;
+    }
+    if (mtype == 0 || mtype == 2) return fail(MI3D_EUNSUP, "Src_mtype=%d: only the solar (1) and the thermal (3) source are supported", mtype);
+    if (mtype != 3) return fail(MI3D_EINVAL, "unknown Src_mtype=%d", mtype);
+    if (!h->have_1d) return fail(MI3D_ESTATE, "mi3d_set_atm1d has not been called");
+    if (!(wlen_um > 0.0) || !std::isfinite(wlen_um)) return fail(MI3D_EINVAL, "Src_wlen=%g um must be positive", wlen_um);
+    if (nlev != h->nz + 1) return fail(MI3D_EINVAL, "Atm_tmp1d: %d values for Atm_nz=%d -- the thermal source needs the nz+1 INTERFACE temperatures", nlev, h->nz);
+    if (!tmp1d) return fail(MI3D_EINVAL, "NULL Atm_tmp1d");
+    for (int i = 0; i < nlev; ++i)
+        if (!(tmp1d[i] > 0.0f) || !std::isfinite(tmp1d[i])) return fail(MI3D_EINVAL, "Atm_tmp1d(%d)=%g K must be positive", i + 1, tmp1d[i]);
+    const size_t nvox = (size_t)h->nx * h->ny * h->nz3;
+    h->th_ntmpa = 0; h->th_ntmps = 0;
+    if (tmpa3d && nvox > 0) {
+        for (size_t i = 0; i < nvox; ++i) if (!std::isfinite(tmpa3d[i])) return fail(MI3D_EINVAL, "non-finite Atm_tmpa3d");
+        if ((rc = h->d_th_tmpa.upload(tmpa3d, nvox))) return rc;
+        h->th_ntmpa = nvox;
+    }
+    if (tmps2d) {
+        if (h->sfc2d_host.empty()) return fail(MI3D_EINVAL, "Sfc_tmps2d given for a uniform surface (mi3d_set_surface2d first)");
+        const size_t nsfc = (size_t)h->nxb * h->nyb;
+        for (size_t i = 0; i < nsfc; ++i) if (!std::isfinite(tmps2d[i])) return fail(MI3D_EINVAL, "non-finite Sfc_tmps2d");
+        if ((rc = h->d_th_tmps.upload(tmps2d, nsfc))) return rc;
+        h->th_ntmps = nsfc;
+    }
+    if (h->src_mtype != 3) ev_forget(h);
+    h->src_mtype = 3; h->th_wlen = wlen_um;
+    h->th_tlev.assign(tmp1d, tmp1d + nlev);
+    h->dirty_thermal = true;
     return MI3D_OK;
 }
 
@@ -1008,6 +1117,7 @@ int mi3d_prepare(mi3d_solver *h) {
         if ((rc = h->d_lay.upload(lay.data(), lay.size()))) return rc;
         h->lay_host = lay;
         h->dirty_grid = false;
+        h->dirty_thermal = true;
         h->dirty_views = true;
         // another scene (or another g of it: the gas absorption moves the events per photon too): the next run with marched views
         // starts with a pilot launch again -- an event list that runs full fails the run.  The tally-record lists of flux jobs KEEP what
@@ -1046,6 +1156,10 @@ int mi3d_prepare(mi3d_solver *h) {
             HIPCHK(hipMemsetAsync(h->d_heat_own.p, 0, h->heat_elems() * sizeof(double), h->stream));
         }
         h->dirty_tally = false;
+    }
+    if (h->src_mtype == 3 && h->dirty_thermal) {
+        if ((rc = build_thermal(h))) return rc;
+        h->dirty_thermal = false;
     }
     return MI3D_OK;
 }
@@ -1432,7 +1546,13 @@ int mi3d_run(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_of
         return fail(MI3D_ESTATE, "radiance requested but no view is set (mi3d_set_views)");
     if ((h->target & MI3D_TARGET_RADIANCE) && h->rad_kind == 1 && h->solver != MI3D_SOLVER_3D)
         return fail(MI3D_EUNSUP, "cameras (Rad_mrkind=1) need the 3-D solver");
+    const bool thermal = h->src_mtype == 3;
+    if (thermal && (h->target & MI3D_TARGET_RADIANCE) && h->rad_kind == 1)
+        return fail(MI3D_EUNSUP, "thermal source: all-sky cameras (Rad_mrkind=1) are not supported");
+    if (thermal && (h->target & MI3D_TARGET_HEAT))
+        return fail(MI3D_EUNSUP, "thermal source: heating rates are not supported");
     if (nphoton == 0) return MI3D_OK;
+    if (thermal && !(h->th_ptot > 0.0)) { h->last_kernel = "k_transport [thermal: nothing emits]"; return MI3D_OK; }   // (the tallies stay 0)
     {   // the kernels index every table with 32-bit arithmetic
         const double lim = 2147483647.0;
         const double nvox = (double)h->nx * h->ny * (h->nz3 + 1) * (h->np3d > 0 ? h->np3d : 1);
@@ -1444,7 +1564,7 @@ int mi3d_run(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_of
     std::memset(&G, 0, sizeof(G));
     int ntile = 1;
     {
-        int tc = choose_tile_cols(h);
+        int tc = thermal ? 0 : choose_tile_cols(h);   // (a thermal photon does not start at the top: id order)
         if (tc > 0) {
             while ((long)((h->nx + tc - 1) / tc) * ((h->ny + tc - 1) / tc) > kMaxTiles) tc *= 2;
             G.Lx = (float)(h->dx * h->nx); G.Ly = (float)(h->dy * h->ny);
@@ -1487,11 +1607,11 @@ int mi3d_run(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_of
     const bool tabs_ok = !tabs || h->tab_n > 0;
     // (tables the scene refers to, staged in LDS by the lean kernels when they fit the budget of fill_scene: mu, p, cdf and the bucket indices)
     const size_t lds_tab = (gen && h->tab_n > 0) ? lean_tab_floats(h->nang, h->tab_n) * sizeof(float) : 0;
-    bool use_col = !flux && h->nview > 0 && (h->rad_kind == 2 || cam_ok) && h->np3d <= 2 && tabs_ok &&
+    bool use_col = !thermal && !flux && h->nview > 0 && (h->rad_kind == 2 || cam_ok) && h->np3d <= 2 && tabs_ok &&
                    (double)h->ny * h->vrow_f4 * 16.0 < 4.0e9 && h->kernel_choice != 1;
     const size_t lds_col = (size_t)(h->nz + 2) * sizeof(LayerRec) + MI3D_MAX_VIEW * sizeof(ViewRec) + sizeof(DevCold);   // (+2: the lean loop's end records)
     // the lean flux kernel (mi3d_kernel_flux.hip): flux / heating rates without radiance, the same scenes as the lean radiance kernel
-    bool use_fl = flux && !((h->target & MI3D_TARGET_RADIANCE) && h->nview > 0) && h->np3d <= 2 && tabs_ok &&
+    bool use_fl = !thermal && flux && !((h->target & MI3D_TARGET_RADIANCE) && h->nview > 0) && h->np3d <= 2 && tabs_ok &&
                   (double)h->ny * h->vrow_f4 * 16.0 < 4.0e9 && h->kernel_choice != 1 && h->nx < 65536 && h->ny < 65536 && h->nz < 65535;
     TallyList TL, TL2;
     std::memset(&TL, 0, sizeof(TL));
@@ -1751,11 +1871,12 @@ int mi3d_run(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_of
         if (use_fl) snprintf(nm, sizeof(nm), TL.cap ? "k_transport_flux<%d,%d,%d> + k_tl_scatter + k_tl_sum" : "k_transport_flux<%d,%d,%d>", h->counting ? 1 : 0, h->solver == MI3D_SOLVER_P3D ? 1 : 0, mix);
         else if (use_col) snprintf(nm, sizeof(nm), split ? "k_transport_lean<%d,%d,2,%d> + k_rays" : "k_transport_lean<%d,%d,0,%d>", h->counting ? 1 : 0,
                               h->solver == MI3D_SOLVER_P3D ? 1 : 0, mix_lean);
-        else snprintf(nm, sizeof(nm), "k_transport<%d,%d,%d,%d>", h->counting ? 1 : 0, march ? 1 : 0, flux ? 1 : 0, h->solver == MI3D_SOLVER_P3D ? 1 : 0);
+        else snprintf(nm, sizeof(nm), thermal ? "k_transport<%d,%d,%d,%d> [thermal]" : "k_transport<%d,%d,%d,%d>", h->counting ? 1 : 0, march ? 1 : 0, flux ? 1 : 0,
+                      h->solver == MI3D_SOLVER_P3D ? 1 : 0);
         h->last_kernel = nm;
         // A job that was not sent to the general loop by its caller (mi3d_set_kernel 1) but landed there says so, once per handle: the loop of
         // round 1 serves it correctly and at a fraction of the lean loops' speed (bench.py's `general_kernel` leg has the figure)
-        if (!use_fl && !use_col && h->kernel_choice == 0 && !h->general_warned && nphoton >= 4096) {
+        if (!use_fl && !use_col && h->kernel_choice == 0 && !h->general_warned && nphoton >= 4096 && !thermal) {   // (thermal jobs: the general loop by design)
             const bool both = flux && (h->target & MI3D_TARGET_RADIANCE) && h->nview > 0;
             const char *why = both ? "flux (or heating rates) TOGETHER with radiance: two jobs, one per target, as er3t's mcarats_ng submits them (mcarats.py:238-245), each take a lean loop"
                               : h->np3d > 2 ? "more than two 3-D constituents" : !tabs_ok ? "phase tables too large for the LDS (or none loaded where a selector asks for one)"
@@ -1988,13 +2109,15 @@ int mi3d_run(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_of
                     err = launch_rays(h, rs, Sx, true, lds_col + rays_lds_extra(h->nz) + lds_tab, seed);
             }
         } else if (err == hipSuccess) {
-#define MI3D_LAUNCH(C, M, F)                                                                                              \
+            const DevThermal *th = thermal ? h->d_th.p : nullptr;
+#define MI3D_LAUNCH_T(C, M, F, T)                                                                                          \
     do {                                                                                                                 \
         if (h->solver == MI3D_SOLVER_P3D)                                                                                \
-            hipLaunchKernelGGL((k_transport<C, M, F, true>), dim3(grid), dim3(tb), lds, h->stream, S, nb, seed, off);    \
-        else                                                                                                             \
-            hipLaunchKernelGGL((k_transport<C, M, F, false>), dim3(grid), dim3(tb), lds, h->stream, S, nb, seed, off);   \
+            hipLaunchKernelGGL((k_transport<C, M, F, true, T>), dim3(grid), dim3(tb), lds, h->stream, S, nb, seed, off, th);    \
+        else                                                                                                                     \
+            hipLaunchKernelGGL((k_transport<C, M, F, false, T>), dim3(grid), dim3(tb), lds, h->stream, S, nb, seed, off, th);   \
     } while (0)
+#define MI3D_LAUNCH(C, M, F) do { if (thermal) MI3D_LAUNCH_T(C, M, F, true); else MI3D_LAUNCH_T(C, M, F, false); } while (0)
             switch (variant) {
                 case 0: MI3D_LAUNCH(false, false, false); break;
                 case 1: MI3D_LAUNCH(false, false, true); break;
@@ -2006,6 +2129,7 @@ int mi3d_run(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_of
                 default: MI3D_LAUNCH(true, true, true); break;
             }
 #undef MI3D_LAUNCH
+#undef MI3D_LAUNCH_T
             err = hipGetLastError();
         }
         if (err == hipSuccess && !run_timed) err = hipEventRecord(e1, h->stream);
@@ -2185,12 +2309,11 @@ int mi3d_get_radiance(mi3d_solver *h, uint64_t nphoton_total, float *out) {
     HIPCHK(sync_main(h));
     if ((rc = ev_settle(h))) return rc;
     const size_t n = (size_t)h->nview * h->nxr * h->nyr;
-    const double pi = 3.14159265358979323846;
-    const double mu0 = std::fabs(std::cos(h->src_the * pi / 180.0));
+    const double amp = src_amp(h);
     // satellite: radiance averaged over the pixel's share of the domain area; camera: the tallies hold 1 / (r^2 dOmega) already and
-    // a photon stands for Src_flx mu0 Lx Ly / N of power
-    const double fac = h->rad_kind == 1 ? h->src_flx * mu0 * (h->dx * h->nx) * (h->dy * h->ny) / (double)nphoton_total
-                                        : h->src_flx * mu0 * (double)h->nxr * (double)h->nyr / (double)nphoton_total;
+    // a photon stands for Src_flx mu0 Lx Ly / N of power (thermal: Src_flx P_tot / N)
+    const double fac = h->rad_kind == 1 ? amp * (h->dx * h->nx) * (h->dy * h->ny) / (double)nphoton_total
+                                        : amp * (double)h->nxr * (double)h->nyr / (double)nphoton_total;
     // (scaled on the device, k_get_field: nine views of 480 x 480 pixels were 16 MB of float64 to the host and a loop over them)
     if (n == 0) return MI3D_OK;
     if ((rc = h->d_get_out.alloc(n))) return rc;
@@ -2209,13 +2332,11 @@ int mi3d_get_flux(mi3d_solver *h, uint64_t nphoton_total, float *out) {
     if (!h->flux_ptr()) return fail(MI3D_ESTATE, "no flux tally (nothing has run)");
     HIPCHK(sync_main(h));
     const size_t n = h->flux_elems();
-    const double pi = 3.14159265358979323846;
-    const double mu0 = std::fabs(std::cos(h->src_the * pi / 180.0));
-    const double fac = h->src_flx * mu0 * (double)h->nx * (double)h->ny / (double)nphoton_total;
+    const double amp = src_amp(h);
+    const double fac = amp * (double)h->nx * (double)h->ny / (double)nphoton_total;
     // the raw planes are direct-down, diffuse-down, up (one atomic per crossing); the result planes direct-down, total-down, up.
-    // At the levels above the 3-D region the direct beam is not tallied but known: Src_flx*mu0*exp(-tau/mu0).
+    // At the levels above the 3-D region the direct beam is not tallied but known: Src_flx*mu0*exp(-tau/mu0) (thermal: none, 0).
     // (normalised on the device, k_get_field: float32 crosses to the host)
-    const double amp = h->src_flx * mu0;
     const double *add = nullptr;
     if (!h->dir_level.empty()) {
         std::vector<double> a(h->dir_level);
@@ -2238,8 +2359,7 @@ int mi3d_get_direct_levels(mi3d_solver *h, double *out) {
     if (rc) return rc;
     if (!out) return fail(MI3D_EINVAL, "out is NULL");
     if ((int)h->dir_level.size() != h->nz + 1) return fail(MI3D_ESTATE, "no job has run on this handle since its grid was set");
-    const double pi = 3.14159265358979323846;
-    const double amp = h->src_flx * std::fabs(std::cos(h->src_the * pi / 180.0));
+    const double amp = src_amp(h);
     for (int L = 0; L <= h->nz; ++L) out[L] = amp * h->dir_level[L];
     return MI3D_OK;
 }
@@ -2322,8 +2442,7 @@ int mi3d_stats_add(mi3d_solver *h, uint64_t nphoton_total, const float *factor_r
     if (rc) return rc;
     if (!h->stats_on) return fail(MI3D_ESTATE, "mi3d_stats_begin has not been called");
     if (nphoton_total == 0) return fail(MI3D_EINVAL, "nphoton_total is 0");
-    const double pi = 3.14159265358979323846;
-    const double mu0 = std::fabs(std::cos(h->src_the * pi / 180.0));
+    const double amp = src_amp(h);
     for (int w = 0; w < 2; ++w) {
         if (!(h->target & (w == 0 ? MI3D_TARGET_RADIANCE : MI3D_TARGET_FLUX))) continue;
         const size_t n = h->stat_elems(w);
@@ -2341,14 +2460,14 @@ int mi3d_stats_add(mi3d_solver *h, uint64_t nphoton_total, const float *factor_r
         // (this call reads the tallies of the job that has just run: a launch of it whose event list ran full fails the call HERE -- the next
         //  mi3d_reset would forget it, and the short tallies would be part of the run's mean and standard deviation for good)
         if ((rc = ev_settle(h))) return rc;
-        const double norm = w == 0 ? (h->rad_kind == 1 ? h->src_flx * mu0 * (h->dx * h->nx) * (h->dy * h->ny) / (double)nphoton_total
-                                                       : h->src_flx * mu0 * (double)h->nxr * (double)h->nyr / (double)nphoton_total)
-                                   : h->src_flx * mu0 * (double)h->nx * (double)h->ny / (double)nphoton_total; // as mi3d_get_*
+        const double norm = w == 0 ? (h->rad_kind == 1 ? amp * (h->dx * h->nx) * (h->dy * h->ny) / (double)nphoton_total
+                                                       : amp * (double)h->nxr * (double)h->nyr / (double)nphoton_total)
+                                   : amp * (double)h->nx * (double)h->ny / (double)nphoton_total; // as mi3d_get_*
         const tally_t *tally = w == 0 ? h->rad_ptr() : h->flux_ptr();
         const double *dir_dev = nullptr;
         if (w == 1 && !h->dir_level.empty()) {
             std::vector<double> a(h->dir_level);
-            for (double &x : a) x *= h->src_flx * mu0 * h->analytic_share;
+            for (double &x : a) x *= amp * h->analytic_share;
             if ((rc = h->d_dir_level.upload(a.data(), a.size()))) return rc;
             dir_dev = h->d_dir_level.p;
         }

@@ -11,6 +11,7 @@
 //                    flown through like 1-D layers: no voxel walk, no extinction reads)
 //   k_build_column   per-column optical depth from every 3-D level up to the top of atmosphere
 //   k_transport      persistent photon loop (see the comment on the kernel)
+//   k_thermal_power  thermal source (Src_mtype = 3): emitted power of every cell, float64; k_scan_* make its CDF
 //   k_stats_*        per-run g-sum and sum / sum of squares over runs of the result fields
 //   k_philox         test hook
 //
@@ -135,6 +136,130 @@ __global__ void k_philox(uint64_t seed, uint64_t id0, uint32_t draw, int n, uint
     uint32_t w[4];
     philox4x32_10((uint32_t)id, (uint32_t)(id >> 32), draw, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), w);
     out[4 * i + 0] = w[0]; out[4 * i + 1] = w[1]; out[4 * i + 2] = w[2]; out[4 * i + 3] = w[3];
+}
+
+// ---------------------------------------------------------------------------------------------
+// thermal source (Src_mtype = 3, include/mi3d.h: mi3d_set_thermal)
+// ---------------------------------------------------------------------------------------------
+// Planck's law at wavelength wl_um [um] and temperature T [K] in W m-2 sr-1 um-1 (CODATA 2018 h, c, k).  Also used on the host.
+__host__ __device__ inline double planck_um(double wl_um, double T) {
+    const double h = 6.62607015e-34, c = 299792458.0, kb = 1.380649e-23;
+    if (!(T > 0.0) || !(wl_um > 0.0)) return 0.0;
+    const double wl = wl_um * 1.0e-6;
+    const double wl5 = wl * wl * wl * wl * wl;
+    return 2.0 * h * c * c / wl5 / expm1(h * c / (wl * kb * T)) * 1.0e-6;
+}
+
+// What the photon loop needs to start a thermal photon (one copy in device memory, mi3d_prepare).  The cells, in CDF order:
+//   [0, nvox)              voxels of the 3-D region, file order (k3 * ny + iy) * nx + ix
+//   [nvox, nvox + nz)      layers of the 1-D grid (0 inside the 3-D region: its voxels emit instead)
+//   [nvox + nz, ncell)     surface cells: nxb x nyb of a 2-D surface, or one for a uniform surface
+struct DevThermal {
+    const double *cdf;     // [ncell] inclusive prefix sums of the cells' emitted power [W um-1]
+    double ptot;           // cdf[ncell - 1]
+    unsigned ncell, nvox;
+    int nxb, nyb;          // surface cells (1 x 1: uniform surface)
+};
+
+// One thread per cell: emitted power in float64 from the scene as the transport kernel sees it.  Absorption coefficient of a
+// cell = total extinction - total scattering coefficient of the same float32 records the photon loop reads, so that what a cell
+// emits matches what it absorbs (Kirchhoff).  Volume: 4 pi ka B(T) V; surface: pi (1 - albedo) B(Ts) A (Lambertian only).
+__global__ void __launch_bounds__(256)
+k_thermal_power(int nx, int ny, int nz, int nz3, int k3lo, int np1d, int np3d, double dx, double dy, double wl_um,
+                const LayerRec *lay, const float4 *vrec, unsigned vcol_f4, unsigned vrow_f4, const float2 *csca,
+                const float *tlev, const float *tmpa3d, int nxb, int nyb, const float *sfc2d, float albedo, const float *tmps2d,
+                double *pw) {
+    const unsigned long nvox = (unsigned long)nx * ny * nz3, nsfc = (unsigned long)nxb * nyb;
+    const unsigned long i = (unsigned long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nvox + nz + nsfc) return;
+    const double four_pi = 4.0 * 3.14159265358979323846;
+    double p = 0.0;
+    if (i < nvox) {
+        const unsigned long ncol = (unsigned long)nx * ny;
+        const int k3 = (int)(i / ncol), col = (int)(i % ncol), iy = col / nx, ix = col % nx, k = k3lo + k3;
+        const LayerRec L = lay[k];
+        const float4 r = vrec[(size_t)iy * vrow_f4 + (size_t)ix * vcol_f4 + k3];
+        float ks = r.z;
+        for (int ip = 0; ip < np1d; ++ip) ks += L.ks1d[ip];
+        for (int ip = 1; ip < np3d; ++ip) ks += csca[((size_t)col * nz3 + k3) * np3d + ip].x;
+        const double ka = fmax((double)r.x - (double)ks, 0.0);
+        const double T = 0.5 * ((double)tlev[k] + (double)tlev[k + 1]) + (tmpa3d ? (double)tmpa3d[i] : 0.0);
+        p = four_pi * ka * planck_um(wl_um, T) * dx * dy * (double)L.dz;
+    } else if (i < nvox + nz) {
+        const int k = (int)(i - nvox);
+        if (!(nz3 > 0 && k >= k3lo && k < k3lo + nz3)) {
+            const LayerRec L = lay[k];
+            float ks = 0.0f;
+            for (int ip = 0; ip < np1d; ++ip) ks += L.ks1d[ip];
+            const double ka = fmax((double)L.bt - (double)ks, 0.0);
+            const double T = 0.5 * ((double)tlev[k] + (double)tlev[k + 1]);
+            p = four_pi * ka * planck_um(wl_um, T) * dx * nx * dy * ny * (double)L.dz;
+        }
+    } else {
+        const unsigned long s = i - nvox - nz;
+        const double a = sfc2d ? (double)sfc2d[s * 8 + 1] : (double)albedo;
+        const double eps = 1.0 - fmin(fmax(a, 0.0), 1.0);
+        const double T = (double)tlev[0] + (tmps2d ? (double)tmps2d[s] : 0.0);
+        p = 3.14159265358979323846 * eps * planck_um(wl_um, T) * (dx * nx / nxb) * (dy * ny / nyb);
+    }
+    pw[i] = p;
+}
+
+// Inclusive prefix sum of n doubles in place, in three passes: every block scans kScanChunk elements and leaves its total,
+// one block scans the totals (exclusive), every block adds its offset.
+constexpr int kScanT = 256, kScanR = 8, kScanChunk = kScanT * kScanR;
+__global__ void __launch_bounds__(256)
+k_scan_chunk(double *a, unsigned long n, double *bsum) {
+    __shared__ double s[kScanT];
+    const unsigned t = threadIdx.x;
+    const unsigned long base = (unsigned long)blockIdx.x * kScanChunk + (unsigned long)t * kScanR;
+    double v[kScanR], run = 0.0;
+#pragma unroll
+    for (int r = 0; r < kScanR; ++r) { run += base + r < n ? a[base + r] : 0.0; v[r] = run; }
+    s[t] = run;
+    __syncthreads();
+    for (unsigned off = 1; off < kScanT; off <<= 1) {
+        const double x = t >= off ? s[t - off] : 0.0;
+        __syncthreads();
+        s[t] += x;
+        __syncthreads();
+    }
+    const double before = t > 0 ? s[t - 1] : 0.0;
+#pragma unroll
+    for (int r = 0; r < kScanR; ++r) if (base + r < n) a[base + r] = v[r] + before;
+    if (t == kScanT - 1) bsum[blockIdx.x] = s[kScanT - 1];
+}
+__global__ void __launch_bounds__(1024)
+k_scan_top(double *bsum, unsigned long nb) {
+    __shared__ double s[1024];
+    const unsigned t = threadIdx.x;
+    double carry = 0.0;
+    for (unsigned long c0 = 0; c0 < nb; c0 += 1024) {
+        const double x0 = c0 + t < nb ? bsum[c0 + t] : 0.0;
+        s[t] = x0;
+        __syncthreads();
+        for (unsigned off = 1; off < 1024; off <<= 1) {
+            const double x = t >= off ? s[t - off] : 0.0;
+            __syncthreads();
+            s[t] += x;
+            __syncthreads();
+        }
+        if (c0 + t < nb) bsum[c0 + t] = carry + s[t] - x0;   // exclusive
+        carry += s[1023];
+        __syncthreads();
+    }
+}
+__global__ void __launch_bounds__(256)
+k_scan_add(double *a, unsigned long n, const double *bsum) {
+    const double off = bsum[blockIdx.x];
+    const unsigned long base = (unsigned long)blockIdx.x * kScanChunk;
+    for (unsigned r = threadIdx.x; r < (unsigned)kScanChunk; r += blockDim.x)
+        if (base + r < n) a[base + r] += off;
+}
+
+// a uniform number in (0, 1) with 46 random bits from two Philox words (the CDF of a large grid needs more than float's 24)
+__device__ inline double u01_pair(uint32_t a, uint32_t b) {
+    return ((double)(a >> 9) + ((double)(b >> 9) + 0.5) * (1.0 / 8388608.0)) * (1.0 / 8388608.0);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -369,10 +494,12 @@ enum : int {
     M_FINISH = 8,  // all views served: new direction and weight
     M_NEED = 9,    // history over: take the next photon id
     M_DRAW = 10,   // needs its next Philox block (what for: `kind`)
-    M_DONE = 11    // no photons left
+    M_DONE = 11,   // no photons left
+    M_EMIT = 12    // thermal photon just emitted: its local estimates are made by phase B like those of a collision
 };
 enum : int { E_SCATTER = 0, E_SURFACE = 1, E_LAUNCH = 2,      // kind of event being finished
-             D_FLIGHT = 3, D_ROULETTE = 4, D_LAUNCH = 5 };    // what the pending draw is for
+             D_FLIGHT = 3, D_ROULETTE = 4, D_LAUNCH = 5,      // what the pending draw is for
+             E_EMIT = 6, E_EMIT_SFC = 7 };                    // thermal emission from a volume cell / from the surface
 
 #ifndef MI3D_THRESH
 #define MI3D_THRESH 16   // phase A keeps stepping while at least this many lanes of the wave are in flight
@@ -506,9 +633,13 @@ __device__ inline void flux_add(const DevScene &S, int ix, int iy, float w, bool
 // cell by cell; without it the LE-ray modes, their state and the stash vanish), FLUX (flux tallies on).
 // P3D (partial 3-D solver): the direct beam travels in 3-D up to its first event, everything after it (scattered photons
 // and every local-estimate ray) stays in the column of that event like under the independent-pixel approximation.
-template <bool COUNT, bool MARCH, bool FLUX, bool P3D>
+// THERM (th != nullptr): thermal source (Src_mtype = 3); the solar builds carry none of its code.  A new photon starts in a cell drawn from the CDF of emitted power (block B6,
+// D_LAUNCH), at a uniform position in it, with weight 1 (the normalisation applies P_tot / N); its emission is served by block
+// B2 as an event (M_EMIT) whose local estimates carry 1 / 4 pi (volume) or cos / pi (surface), then block B5 gives it an
+// isotropic (volume) or cosine-weighted (surface) direction.  No photon is direct: under P3D everything stays in its column.
+template <bool COUNT, bool MARCH, bool FLUX, bool P3D, bool THERM>
 __global__ void __launch_bounds__(256, MI3D_WAVES(MARCH, COUNT))
-k_transport(const DevScene S, const uint64_t nphoton, const uint64_t seed, const uint64_t offset) {
+k_transport(const DevScene S, const uint64_t nphoton, const uint64_t seed, const uint64_t offset, const DevThermal *th) {
     extern __shared__ float4 smem[];
     const LayerRec *lay = reinterpret_cast<const LayerRec *>(smem);
     const float4 *lay4 = smem;
@@ -828,8 +959,9 @@ k_transport(const DevScene S, const uint64_t nphoton, const uint64_t seed, const
 
         MI3D_MARK("B2");
         // ---- B2: a new event: weight update, column-table views, stash for marched views
-        if (EVT && (mode == M_COLL || (full && mode == M_SURF))) {
-            kind = (mode == M_SURF) ? E_SURFACE : E_SCATTER;
+        if (EVT && (mode == M_COLL || (THERM && mode == M_EMIT) || (full && mode == M_SURF))) {
+            const bool emit = THERM && (mode == M_EMIT);   // (its kind, E_EMIT or E_EMIT_SFC, was set by the launch)
+            if (!emit) kind = (mode == M_SURF) ? E_SURFACE : E_SCATTER;
             const LayerRec &Lk = lay[k];
             const bool in3d = (Lk.flags & kLayIn3d) != 0;
             if (!(Lk.flags & kLayStep3d)) fold_xy(S, cold, px, py, ix, iy, IPA_NOW(false));
@@ -857,7 +989,7 @@ k_transport(const DevScene S, const uint64_t nphoton, const uint64_t seed, const
                 if (!(Lk.flags & kLayStep3d)) bt_ev = Lk.bt;
                 // the surface record travels to the later blocks in the event registers a scattering event uses for its voxel
                 ev_ks0 = sf.p0; ev_apf0 = sf.p1; ev_sfc = sf.p2; kind = E_SURFACE | (sf.type << 4);
-            } else {
+            } else if (!emit) {
                 if (COUNT) cnt.scatter++;
                 for (int ip = 0; ip < S.np1d; ++ip) kstot += Lk.ks1d[ip];
                 if (in3d) {
@@ -887,6 +1019,10 @@ k_transport(const DevScene S, const uint64_t nphoton, const uint64_t seed, const
                         float c;
                         if ((kind & 15) == E_SURFACE) {
                             c = w * surface_R(sf, ux, uy, uz, V.vx, V.vy, V.vz) * V.vz * (1.0f / kPi);
+                        } else if (THERM && kind == E_EMIT) {
+                            c = w * (0.25f / kPi);
+                        } else if (THERM && kind == E_EMIT_SFC) {
+                            c = w * V.vz * (1.0f / kPi);
                         } else {
                             const float mu = ux * V.vx + uy * V.vy + uz * V.vz;
                             float P = 0.0f;
@@ -943,7 +1079,7 @@ k_transport(const DevScene S, const uint64_t nphoton, const uint64_t seed, const
             // skip the views answered from the column table, the sensors on the wrong side of the event, and -- for a surface
             // event -- the up-looking ones
             while (iv < S.nview && !views[iv].point &&
-                   (views[iv].column || (views[iv].vz > 0.0f ? zev >= views[iv].zs : (zev <= views[iv].zs || (kind & 15) == E_SURFACE)))) ++iv;
+                   (views[iv].column || (views[iv].vz > 0.0f ? zev >= views[iv].zs : (zev <= views[iv].zs || (kind & 15) == E_SURFACE || (THERM && kind == E_EMIT_SFC))))) ++iv;
             if (iv >= S.nview) {
                 mode = M_FINISH;
             } else {
@@ -974,6 +1110,10 @@ k_transport(const DevScene S, const uint64_t nphoton, const uint64_t seed, const
                     // (three parameters travel in the event registers; the five of the diffuse-specular mixture are read again)
                     const Sfc sf = (kind >> 4) == MI3D_SFC_DSM ? load_sfc(S, cold, ix, iy, px, py) : Sfc{kind >> 4, ev_ks0, ev_apf0, ev_sfc, 0.0f, 0.0f};
                     c = w * surface_R(sf, ux, uy, uz, V.vx, V.vy, V.vz) * V.vz * (1.0f / kPi);
+                } else if (THERM && kind == E_EMIT) {
+                    c = w * (0.25f / kPi);
+                } else if (THERM && kind == E_EMIT_SFC) {
+                    c = V.vz > 0.0f ? w * V.vz * (1.0f / kPi) : 0.0f;
                 } else {
                     const float mu = ux * V.vx + uy * V.vy + uz * V.vz;
                     float P = 0.0f, kstot = 0.0f;
@@ -1069,6 +1209,11 @@ k_transport(const DevScene S, const uint64_t nphoton, const uint64_t seed, const
                 sf = (kind >> 4) == MI3D_SFC_DSM ? load_sfc(S, cold, ix, iy, px, py) : Sfc{kind >> 4, ev_ks0, ev_apf0, ev_sfc, 0.0f, 0.0f};
                 bx = 0.0f; by = 0.0f; bz = 1.0f;
                 mu_rot = fsqrt(u2);
+            } else if (THERM && (kind == E_EMIT || kind == E_EMIT_SFC)) {
+                // emission: isotropic, or cosine-weighted into the upper hemisphere; a surface photon crosses level 0 upwards
+                bx = 0.0f; by = 0.0f; bz = 1.0f;
+                mu_rot = kind == E_EMIT ? 2.0f * u2 - 1.0f : fsqrt(u2);
+                if (kind == E_EMIT_SFC && do_flux) flux_add<COUNT>(S, ix, iy, w, false, 0, true, cnt);
             } else if ((kind & 15) == E_SCATTER) {
                 const LayerRec &Lk = lay[k];
                 const bool in3d = (Lk.flags & kLayIn3d) != 0;
@@ -1133,6 +1278,54 @@ k_transport(const DevScene S, const uint64_t nphoton, const uint64_t seed, const
             } else if (dkind == D_ROULETTE) {
                 if (r0 * S.wfac < w) { w = S.wfac; dkind = D_FLIGHT; }
                 else { if (COUNT) cnt.killed++; mode = M_NEED; }
+            } else if (THERM) { // D_LAUNCH of a thermal photon: a cell by its share of the emitted power, a position in it
+                uint32_t q[4];
+                philox4x32_10((uint32_t)id, (uint32_t)(id >> 32), draw++, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), q);
+                const double *cdf = th->cdf;
+                const double target = u01_pair(q[0], q[1]) * th->ptot;
+                unsigned lo = 0, hi = th->ncell - 1;   // the first cell whose cumulative power exceeds the target (it emits)
+                while (lo < hi) {
+                    const unsigned mid = (lo + hi) >> 1;
+                    if (cdf[mid] > target) hi = mid; else lo = mid + 1;
+                }
+                const unsigned nvox = th->nvox;
+                float x, y;
+                if (lo < nvox) {                     // a voxel
+                    const unsigned ncol = (unsigned)(S.nx * S.ny), col = lo % ncol;
+                    k = S.k3lo + (int)(lo / ncol);
+                    x = ((float)(col % (unsigned)S.nx) + r0) * S.dx; y = ((float)(col / (unsigned)S.nx) + r1) * S.dy;
+                    kind = E_EMIT;
+                } else if (lo < nvox + (unsigned)S.nz) {   // a layer of the 1-D grid
+                    k = (int)(lo - nvox);
+                    x = r0 * cold->Lx; y = r1 * cold->Ly;
+                    kind = E_EMIT;
+                } else {                             // a surface cell
+                    const unsigned sc = lo - nvox - (unsigned)S.nz;
+                    k = 0;
+                    x = ((float)(sc % (unsigned)th->nxb) + r0) * (cold->Lx / (float)th->nxb);
+                    y = ((float)(sc / (unsigned)th->nxb) + r1) * (cold->Ly / (float)th->nyb);
+                    kind = E_EMIT_SFC;
+                }
+                if (x >= cold->Lx) x = 0.0f;
+                if (y >= cold->Ly) y = 0.0f;
+                ix = min((int)(x * cold->inv_dx), S.nx - 1);
+                iy = min((int)(y * cold->inv_dy), S.ny - 1);
+                px = fminf(fmaxf(x - (float)ix * S.dx, 0.0f), S.dx);
+                py = fminf(fmaxf(y - (float)iy * S.dy, 0.0f), S.dy);
+                const LayerRec &Lk = lay[k];
+                pz = kind == E_EMIT_SFC ? 0.0f : fminf(r2 * Lk.dz, Lk.dz);
+                // the cell's record, as a voxel step would have brought it to block B2
+                bt_ev = Lk.bt; ev_tab = 0.0f; ev_ks0 = 0.0f; ev_apf0 = 0.0f;
+                if (Lk.flags & kLayIn3d) {
+                    const float4 r4 = S.vrec[(unsigned)iy * S.vrow_f4 + (unsigned)ix * S.vcol_f4 + (unsigned)(k - S.k3lo)];
+                    bt_ev = r4.x; ev_tab = r4.y; ev_ks0 = r4.z; ev_apf0 = r4.w;
+                }
+                ux = 0.0f; uy = 0.0f; uz = 1.0f;
+                u2 = r3; u3 = u01(q[2]);
+                asm volatile("" : "+v"(u3)); // (as in the solar launch below)
+                w = 1.0f;
+                direct = false;
+                mode = M_EMIT;
             } else { // D_LAUNCH: position at the top of the atmosphere, solar direction; jitter + free path follow
                 float x = r0 * cold->Lx, y = r1 * cold->Ly;
                 if (x >= cold->Lx) x = 0.0f;
@@ -1179,8 +1372,10 @@ k_transport(const DevScene S, const uint64_t nphoton, const uint64_t seed, const
 }
 
 #undef IPA_NOW
-#define MI3D_INST(C, M, F) template __global__ void k_transport<C, M, F, false>(const DevScene, const uint64_t, const uint64_t, const uint64_t); \
-                           template __global__ void k_transport<C, M, F, true>(const DevScene, const uint64_t, const uint64_t, const uint64_t);
+#define MI3D_INST(C, M, F) template __global__ void k_transport<C, M, F, false, false>(const DevScene, const uint64_t, const uint64_t, const uint64_t, const DevThermal *); \
+                           template __global__ void k_transport<C, M, F, true, false>(const DevScene, const uint64_t, const uint64_t, const uint64_t, const DevThermal *); \
+                           template __global__ void k_transport<C, M, F, false, true>(const DevScene, const uint64_t, const uint64_t, const uint64_t, const DevThermal *); \
+                           template __global__ void k_transport<C, M, F, true, true>(const DevScene, const uint64_t, const uint64_t, const uint64_t, const DevThermal *);
 MI3D_INST(false, false, false) MI3D_INST(false, false, true) MI3D_INST(false, true, false) MI3D_INST(false, true, true)
 MI3D_INST(true, false, false) MI3D_INST(true, false, true) MI3D_INST(true, true, false) MI3D_INST(true, true, true)
 #undef MI3D_INST

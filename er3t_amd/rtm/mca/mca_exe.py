@@ -28,7 +28,7 @@ __all__ = ['JobRunner', 'run_job', 'main']
 _WARNED = set()
 
 
-def _check_supported(nml):
+def _check_supported(nml, fdir=None):
     if int(nml.get('Wld_moptim', 0) or 0) != 0 and 'moptim' not in _WARNED and world_info()[0] == 0:
         # (MCARaTS' biasing optimisations, er3t/rtm/mca/mca_inp.py:27-33; er3t sets 2 for tune=True, mcarats.py:257-260)
         _WARNED.add('moptim')
@@ -37,8 +37,37 @@ def _check_supported(nml):
         raise OSError('Error [mca_exe]: <Wld_mtarget=%s> is not supported (1: flux, 2: radiance).' % nml.get('Wld_mtarget'))
     if int(nml.get('Wld_mtarget', 1)) == 2 and int(nml.get('Rad_mrkind', 2)) not in (1, 2):
         raise OSError('Error [mca_exe]: <Rad_mrkind=%s> is not supported (1: all-sky camera, 2: satellite sensor).' % nml.get('Rad_mrkind'))
-    if int(nml.get('Src_mtype', 1)) != 1:
-        raise OSError('Error [mca_exe]: only the solar source (<Src_mtype=1>) is supported.')
+    mtype = int(nml.get('Src_mtype', 1))
+    if mtype in (0, 2):
+        raise OSError('Error [mca_exe]: <Src_mtype=%d> (%s) is not supported: only the solar (1) or the thermal (3) source; '
+                      'solar+thermal in one job is out of scope (er3t splits the spectrum: thermal from 5 um on).' % (mtype, 'local' if mtype == 0 else 'solar+thermal'))
+    if mtype not in (1, 3):
+        raise OSError('Error [mca_exe]: unknown <Src_mtype=%d>.' % mtype)
+    if mtype == 3:
+        _check_thermal(nml, fdir)
+
+
+def _check_thermal(nml, fdir):
+    """what a thermal job (Src_mtype = 3) needs and what it cannot have (include/mi3d.h: mi3d_set_thermal)"""
+    if nml.get('Src_wlen') is None:
+        raise OSError('Error [mca_exe]: a thermal job (<Src_mtype=3>) needs <Src_wlen>, the band-centre wavelength in micrometres.')
+    nz = int(nml.get('Atm_nz', np.size(nml.get('Atm_zgrd0', [])) - 1))
+    ntmp = np.size(nml.get('Atm_tmp1d', []))
+    if ntmp != nz + 1:
+        raise OSError('Error [mca_exe]: a thermal job needs <Atm_tmp1d> at the %d layer INTERFACES (nz+1); %d values %s.'
+                      % (nz+1, ntmp, 'are ambiguous (nz: the layer temperatures a solar job carries)' if ntmp == nz else 'do not fit'))
+    if int(nml.get('Wld_mtarget', 1)) == 1 and int(nml.get('Flx_mhrt', 0) or 0) == 1:
+        raise OSError('Error [mca_exe]: <target=\'heating rate\'> (Flx_mhrt=1) is not supported for a thermal job.')
+    if int(nml.get('Wld_mtarget', 1)) == 2 and int(nml.get('Rad_mrkind', 2)) == 1:
+        raise OSError('Error [mca_exe]: all-sky cameras (<Rad_mrkind=1>) are not supported for a thermal job.')
+    if nml.get('Sfc_inpfile') and int(nml.get('Sfc_nxb', 0) or 0) > 0:
+        if fdir is not None:
+            nxb, nyb = int(nml['Sfc_nxb']), int(nml['Sfc_nyb'])
+            raw = np.fromfile(os.path.join(fdir, nml['Sfc_inpfile']), dtype='<f4')
+            if raw.size == 7*nxb*nyb and np.any(np.rint(raw.reshape(7, nyb, nxb)[1]) != 1):
+                raise OSError('Error [mca_exe]: a thermal job needs a Lambertian surface (jsfc2d = 1 everywhere): non-Lambertian (BRDF) surfaces do not emit here.')
+    elif int(nml.get('Sfc_mtype', 1)) != 1:
+        raise OSError('Error [mca_exe]: a thermal job needs a Lambertian surface (<Sfc_mtype=1>): non-Lambertian (BRDF) surfaces do not emit here.')
 
 
 class JobRunner:
@@ -107,7 +136,7 @@ class JobRunner:
         return tuple(keys)
 
     def load(self, nml, fdir, solver, slot=0):
-        _check_supported(nml)
+        _check_supported(nml, fdir)
         sol = self.sols[slot]
         key = (self._file_key(nml, fdir), int(solver))
         if key == self._key3d[slot]:
@@ -118,6 +147,9 @@ class JobRunner:
             s1 = Scene.from_nml(nml1, fdir, solver=solver)
             if s1.nz != scene.nz or s1.np1d != scene.np1d:      # (the key holds Atm_nz and Atm_np1d: cannot happen)
                 raise OSError('Error [mca_exe]: the 1-D grid changed shape between two jobs that share their 3-D inputs.')
+            if scene.src_mtype == 3:      # (the interface temperatures are per-job keys; the anomalies stay those of the side files)
+                scene.tmp1d = s1.tmp1d
+                sol.set_thermal(3, scene.src_wlen, scene.tmp1d, scene.tmpa3d, scene.tmps2d)
             sol.update_atm1d(s1)
             scene.zgrd, scene.ext1d, scene.omg1d, scene.apf1d, scene.abs1d = s1.zgrd, s1.ext1d, s1.omg1d, s1.apf1d, s1.abs1d
         else:

@@ -112,11 +112,18 @@ def g_factors(mca_obj, abs_obj, Nz):
     function of the top level taken from the layer below it (reference: er3t/rtm/mca/mca_out.py:313-328)
     """
 
+    weight = abs_obj.coef['weight']['data']
+    if getattr(mca_obj, 'source', 'solar') == 'thermal':
+        # thermal source (Src_mtype = 3): every job's result is in W m-2 (sr-1) um-1 already -- no solar spectrum, no Earth-Sun
+        # distance, no slit function: sum_g weight[ig] x_g, per nm like the solar output
+        factors = np.zeros((Nz, mca_obj.Ng), dtype=np.float32)
+        for ig in range(mca_obj.Ng):
+            factors[:, ig] = np.float32(weight[ig]*1.0e-3)
+        return factors, 0.0
     zz = np.arange(Nz)
     if Nz > 1:
         zz[-1] = zz[-2]
     sol_fac = cal_sol_fac(mca_obj.date)
-    weight = abs_obj.coef['weight']['data']
     solar  = abs_obj.coef['solar']['data']
     slit   = abs_obj.coef['slit_func']['data']
     factors = np.zeros((Nz, mca_obj.Ng), dtype=np.float32)
@@ -287,6 +294,13 @@ def read_radiance_mca_out(mca_obj, abs_obj, mode='mean', squeeze=True):
         data['rad_std'] = {'data': np.std(rad, axis=-1), 'name': 'Radiance (standard deviation)', 'units': 'W/m^2/nm/sr', 'dims_info': dims_info[:-1]}
     else:
         raise OSError('Error [read_radiance_mca_out]: Do not support <mode=%s>.' % mode)
+    if getattr(mca_obj, 'source', 'solar') == 'thermal':
+        # brightness temperature of the g-combined radiance at the band centre (W m-2 sr-1 nm-1 -> um-1)
+        from er3t_amd.thermal import brightness_temperature
+        data['toa']['name'] = 'TOA without SZA (none: thermal source)'
+        data['bt'] = {'data': brightness_temperature(mca_obj.wlen_um, data['rad']['data'].astype(np.float64)*1.0e3).astype(np.float32),
+                      'name': 'Brightness temperature' + (' (of the mean radiance)' if mode == 'mean' else ''), 'units': 'K',
+                      'dims_info': data['rad']['dims_info']}
     data['N_photon'] = {'data': mca_obj.photons, 'name': 'Number of photons', 'units': 'N/A'}
     data['N_run']    = {'data': mca_obj.Nrun, 'name': 'Number of runs', 'units': 'N/A'}
     return data

@@ -79,6 +79,11 @@ class mcarats_ng:
                            instead of reading Nrun*Ng files back.
         keep_files [True]: with abs_obj, False skips writing the r%02d.g%03d.out.bin files altogether
                            (a flux job on 480 x 480 x 100 is 0.3 GB per file).
+        source ['solar']  : 'thermal' writes Src_mtype=3 and Src_wlen (the band-centre wavelength in micrometres, a key of this
+                           project: include/mi3d.h, mi3d_set_thermal) and Atm_tmp1d as the nz+1 INTERFACE temperatures of
+                           atm_1ds[0]'s atmosphere (atm_obj.lev['temperature']); the solar-only arguments are ignored
+        wavelength [None] : thermal: Src_wlen in nm (default: the wavelength of atm_1ds[0]'s absorption object)
+        surface_temperature [None]: thermal: replaces the lowest interface temperature (the surface's) [K]
 
     Afterwards: input and output files under <fdir>; attributes Ng, Nrun, Nx, Ny, dx, dy, date, target, solver,
     photons (Nrun*Ng,), photons_per_set, fnames_inp[ir][ig], fnames_out[ir][ig], nml (list of Ng dictionaries).
@@ -91,7 +96,7 @@ class mcarats_ng:
                  surface_albedo=0.03, solar_zenith_angle=30.0, solar_azimuth_angle=0.0, sensor_zenith_angle=0.0,
                  sensor_azimuth_angle=0.0, sensor_altitude=705000.0, sensor_type='satellite', sensor_xpos=0.5,
                  sensor_ypos=0.5, solver='3d', photons=1e7, base_ratio=0.05, verbose=False, quiet=False,
-                 abs_obj=None, keep_files=True):
+                 abs_obj=None, keep_files=True, source='solar', wavelength=None, surface_temperature=None):
 
         # one process per GPU (torch.distributed): rank 0 writes the job files, all ranks transport their share of every job
         from er3t_amd.dist import world_info, barrier
@@ -115,6 +120,12 @@ class mcarats_ng:
         self.mp_mode = mp_mode.lower()
         self.Nview = max(int(np.size(sensor_zenith_angle)), int(np.size(sensor_azimuth_angle)))     # (several views: not in the reference, init_wld)
         self.abs_obj, self.keep_files, self.fused = abs_obj, keep_files, None
+        self.source = str(source).lower()
+        if self.source not in ('solar', 'thermal'):
+            raise OSError('Error [mcarats_ng]: <source=%s> must be \'solar\' or \'thermal\'.' % source)
+        self.wavelength, self.surface_temperature = wavelength, surface_temperature
+        if self.source == 'thermal' and not quiet and (solar_zenith_angle != 30.0 or solar_azimuth_angle != 0.0):
+            print('Message [mcarats_ng]: <source=\'thermal\'>: <solar_zenith_angle> and <solar_azimuth_angle> are ignored.')
         self.solver  = _match(solver, _SOLVERS, 'solver')
         self.Nx, self.Ny = (atm_3ds[0].nml['Atm_nx']['data'], atm_3ds[0].nml['Atm_ny']['data']) if len(atm_3ds) > 0 else (1, 1)
 
@@ -216,6 +227,17 @@ class mcarats_ng:
             for atm_1d in atm_1ds:
                 nml.update({key: item['data'] for key, item in atm_1d.nml[ig].items()})
 
+        if self.source == 'thermal':
+            # the thermal source needs the temperatures at the nz+1 layer INTERFACES (MCARaTS: Atm_tmp1d(KNZ+1)); what a solar job
+            # carries are er3t's nz layer temperatures
+            atm0 = atm_1ds[0]
+            tlev = np.array(atm0.atm.lev['temperature']['data'], dtype=np.float64)
+            if self.surface_temperature is not None:
+                tlev[0] = float(self.surface_temperature)
+            wvl_nm = self.wavelength if self.wavelength is not None else atm0.abs.wvl
+            self.wlen_um = float(wvl_nm)*1.0e-3
+            self._all({'Atm_tmp1d': tlev})
+
         for atm_3d in atm_3ds:
             _relative_side_file(atm_3d.nml, 'Atm_inpfile', self.fdir)
             self._all({key: item['data'] for key, item in atm_3d.nml.items() if key not in _VOXEL_ARRAYS})
@@ -229,6 +251,9 @@ class mcarats_ng:
                     self._all({'Rad_nxr': 500, 'Rad_nyr': 500})
 
     def init_src(self, solar_zenith_angle=0.0, solar_azimuth_angle=0.0):
+        if self.source == 'thermal':
+            self._all(dict(_SRC_FIXED, Src_mtype=3, Src_wlen=float(self.wlen_um), Src_the=180.0, Src_phi=0.0))
+            return
         self._all(dict(_SRC_FIXED, Src_the=180.0-solar_zenith_angle, Src_phi=cal_mca_azimuth(solar_azimuth_angle)))
 
     def init_sfc(self, surface_albedo=0.03):

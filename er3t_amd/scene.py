@@ -71,6 +71,13 @@ class Scene:
     src_qmax: float = 0.533133
     src_the : float = 150.0
     src_phi : float = 270.0
+    # thermal source (Src_mtype = 3, include/mi3d.h: mi3d_set_thermal): band-centre wavelength Src_wlen [um], the nz+1 interface
+    # temperatures Atm_tmp1d [K], voxel anomalies Atm_tmpa3d (nz3, ny, nx) and surface anomalies Sfc_tmps2d (nyb, nxb) [K] or None
+    src_mtype: int = 1
+    src_wlen : float = None
+    tmp1d : np.ndarray = None
+    tmpa3d: np.ndarray = None
+    tmps2d: np.ndarray = None
 
     # radiance views (Rad_the, Rad_phi, Rad_zloc, Rad_zref, Rad_nxr, Rad_nyr)
     view_the : list = field(default_factory=list)
@@ -156,6 +163,23 @@ class Scene:
                 setattr(self, name, v)
         elif self.rad_kind != 2:
             raise ValueError('Error [Scene]: <rad_kind=%s> (Rad_mrkind) must be 1 or 2.' % self.rad_kind)
+        if self.src_mtype == 3:
+            if self.src_wlen is None or not (float(self.src_wlen) > 0.0):
+                raise ValueError('Error [Scene]: a thermal source (Src_mtype=3) needs the band-centre wavelength <Src_wlen> [um].')
+            self.tmp1d = _f32(np.ravel(self.tmp1d)) if self.tmp1d is not None else None
+            if self.tmp1d is None or self.tmp1d.size != nz + 1:
+                raise ValueError('Error [Scene]: a thermal source needs the %d interface temperatures <Atm_tmp1d> (nz+1), got %s.'
+                                 % (nz+1, None if self.tmp1d is None else self.tmp1d.size))
+            if self.tmpa3d is not None:
+                self.tmpa3d = _f32(self.tmpa3d)
+                if self.tmpa3d.shape != (self.nz3, self.ny, self.nx):
+                    raise ValueError('Error [Scene]: <tmpa3d> must be (nz3, ny, nx).')
+            if self.tmps2d is not None:
+                self.tmps2d = _f32(self.tmps2d)
+                if self.jsfc is None or self.tmps2d.shape != self.jsfc.shape:
+                    raise ValueError('Error [Scene]: <tmps2d> must have the (nyb, nxb) shape of a 2-D surface.')
+        elif self.src_mtype != 1:
+            raise ValueError('Error [Scene]: <Src_mtype=%s> is not supported (1: solar, 3: thermal).' % self.src_mtype)
 
     # convenient sizes
     @property
@@ -235,7 +259,7 @@ class Scene:
                 raise OSError('Error [Scene]: <%s> holds %d values, expected %d.' % (fname, raw.size, nvox*(2+3*np3d)))
             blocks = raw.reshape(2+3*np3d, nz3, ny, nx)
             fext3d = np.resize(np.asarray(get('Atm_fext3d', 1.0), dtype=np.float32), np3d)
-            kw.update(nz3=nz3, iz3l=int(get('Atm_iz3l', 1)),
+            kw.update(nz3=nz3, iz3l=int(get('Atm_iz3l', 1)), tmpa3d=blocks[0],
                       abst=blocks[1]*np.float32(get('Atm_fabs3d', 1.0)),
                       extp=blocks[2::3]*fext3d[:, None, None, None], omgp=blocks[3::3], apfp=blocks[4::3])
 
@@ -254,7 +278,7 @@ class Scene:
             if raw.size != 7*nxb*nyb:
                 raise OSError('Error [Scene]: surface file holds %d values, expected %d.' % (raw.size, 7*nxb*nyb))
             blocks = raw.reshape(7, nyb, nxb)
-            kw.update(jsfc=blocks[1], psfc=blocks[2:7])
+            kw.update(jsfc=blocks[1], psfc=blocks[2:7], tmps2d=blocks[0])
         else:
             param = np.zeros(5, dtype=np.float32)
             if get('Sfc_param') is not None:
@@ -268,6 +292,20 @@ class Scene:
 
         kw.update(src_flx=float(get('Src_flx', 1.0)), src_qmax=float(get('Src_qmax', 0.0)),
                   src_the=float(get('Src_the', 120.0)), src_phi=float(get('Src_phi', 0.0)))
+
+        mtype = int(get('Src_mtype', 1))
+        if mtype == 3:
+            if get('Src_wlen') is None:
+                raise OSError('Error [Scene]: a thermal job (Src_mtype=3) needs <Src_wlen>, the band-centre wavelength in micrometres.')
+            tmp = np.ravel(np.asarray(get('Atm_tmp1d', []), dtype=np.float64))
+            if tmp.size != nz + 1:
+                raise OSError('Error [Scene]: a thermal job needs the %d INTERFACE temperatures <Atm_tmp1d> (nz+1); %d values (%s) are ambiguous.'
+                              % (nz+1, tmp.size, 'nz: layer temperatures' if tmp.size == nz else 'neither nz nor nz+1'))
+            kw.update(src_mtype=3, src_wlen=float(np.ravel(get('Src_wlen'))[0]), tmp1d=tmp)
+        elif mtype != 1:
+            raise OSError('Error [Scene]: <Src_mtype=%d> is not supported (1: solar, 3: thermal).' % mtype)
+        else:
+            kw.pop('tmpa3d', None); kw.pop('tmps2d', None)
 
         mtarget = int(get('Wld_mtarget', 1))
         if mtarget == 2:

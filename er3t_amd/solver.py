@@ -41,6 +41,7 @@ _SIGNATURES = [
     ('mi3d_set_surface'        , C.c_int   , [C.c_void_p, C.c_int, _fp]),
     ('mi3d_set_surface2d'      , C.c_int   , [C.c_void_p, C.c_int, C.c_int, _fp, _fp, _fp]),
     ('mi3d_set_source'         , C.c_int   , [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double]),
+    ('mi3d_set_thermal'        , C.c_int   , [C.c_void_p, C.c_int, C.c_double, C.c_int, _fp, _fp, _fp]),
     ('mi3d_set_views'          , C.c_int   , [C.c_void_p, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int, C.c_int]),
     ('mi3d_set_cameras'        , C.c_int   , [C.c_void_p, C.c_int] + [_dp]*10 + [C.c_int, C.c_int]),
     ('mi3d_set_options'        , C.c_int   , [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int]),
@@ -211,6 +212,20 @@ class Mi3dSolver:
     def set_source(self, flx=1.0, qmax=0.533133, the=150.0, phi=270.0):
         self._chk(self.lib.mi3d_set_source(self._h, float(flx), float(qmax), float(the), float(phi)))
 
+    def set_thermal(self, mtype=3, wlen=None, tmp1d=None, tmpa3d=None, tmps2d=None):
+        """thermal source (Src_mtype = 3): band-centre wavelength <wlen> [um], (nz+1,) interface temperatures <tmp1d> [K], optional
+        voxel anomalies <tmpa3d> (nz3, ny, nx) and surface anomalies <tmps2d> (nyb, nxb) [K]; mtype=1 switches back to the sun"""
+        if int(mtype) == 1:
+            self._chk(self.lib.mi3d_set_thermal(self._h, 1, 0.0, 0, None, None, None))
+            return
+        tmp1d = np.ascontiguousarray(np.ravel(tmp1d), dtype=np.float32)
+        if tmpa3d is not None:
+            tmpa3d = np.ascontiguousarray(tmpa3d, dtype=np.float32)
+        if tmps2d is not None:
+            tmps2d = np.ascontiguousarray(tmps2d, dtype=np.float32)
+        self._chk(self.lib.mi3d_set_thermal(self._h, int(mtype), float(wlen if wlen is not None else 0.0), tmp1d.size, _ptr(tmp1d),
+                                            _ptr(tmpa3d), _ptr(tmps2d)))
+
     def set_views(self, the, phi, zloc, zref=0.0, nxr=1, nyr=1):
         the = np.ascontiguousarray(np.atleast_1d(the), dtype=np.float64)
         phi = np.ascontiguousarray(np.atleast_1d(phi), dtype=np.float64)
@@ -249,6 +264,10 @@ class Mi3dSolver:
         else:
             self.set_surface(s.sfc_mtype, s.sfc_param)
         self.set_source(s.src_flx, s.src_qmax, s.src_the, s.src_phi)
+        if getattr(s, 'src_mtype', 1) == 3:
+            self.set_thermal(3, s.src_wlen, s.tmp1d, s.tmpa3d, s.tmps2d)
+        else:
+            self.set_thermal(1)
         if getattr(s, 'rad_kind', 2) == 1 and s.nview > 0:
             self.set_cameras(s.view_the, s.view_phi, s.cam_psi, s.cam_xpos, s.cam_ypos, s.view_zloc, s.cam_qmax, s.cam_umax, s.cam_vmax,
                              s.cam_apsize, s.nxr, s.nyr)

@@ -84,6 +84,20 @@ class abs_synth:
         dz = atm_obj.lay['thickness']['data']
         ig = np.arange(Ng)
         weight = weights_16g() if Ng == 16 else np.repeat(1.0/Ng, Ng)
+        # er3t's own front end calls everything from 5025 nm on thermal (er3t/pre/abs/abs_rep.py:58-61): there a window channel's
+        # water-vapour-like absorber -- column optical depth 0.02 ... 1.8 over the g-points, scale height 2 km -- and no sunlight
+        self.source = 'thermal' if wavelength >= 5025.0 else 'solar'
+        if self.source == 'thermal':
+            tau_col = 0.02*(90.0**(ig/max(Ng-1, 1)))
+            prof = np.exp(-z/2.0)*dz
+            self.coef = {
+                'wavelength': {'data': wavelength},
+                'abso_coef' : {'data': prof[:, None]/prof.sum()*tau_col[None, :]},
+                'weight'    : {'data': weight},
+                'solar'     : {'data': np.zeros(Ng)},
+                'slit_func' : {'data': np.ones((z.size, Ng))},
+                }
+            return
         self.coef = {
             'wavelength': {'data': wavelength},
             'abso_coef' : {'data': 1.0e-3*((ig[None, :]+1.0)/Ng)*np.exp(-z[:, None]/8.0)*dz[:, None]},

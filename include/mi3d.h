@@ -121,7 +121,8 @@ int mi3d_set_atm1d(mi3d_solver *h, int nz, const double *zgrd, int np1d, const f
  *   abst[nz3][ny][nx]  gas-absorption perturbation added to abs1d of the layer (may be NULL = 0)
  *   extp/omgp/apfp [np3d][nz3][ny][nx]
  * iz3l is the 1-based index of the lowest 3-D layer exactly as the namelist carries it.
- * Atm_tmpa3d (temperature perturbation) is not needed for solar transport and is not passed.
+ * Atm_tmpa3d (temperature perturbation) is not needed for solar transport and is not passed here: a thermal job hands it
+ * to mi3d_set_thermal.
  * nz3 == 0 removes the 3-D region (then nx, ny give the horizontal tally grid only). */
 int mi3d_set_atm3d(mi3d_solver *h, int nx, int ny, int nz3, int iz3l, int np3d, double dx,
                    double dy, const float *abst, const float *extp, const float *omgp,
@@ -137,13 +138,39 @@ int mi3d_set_phase(mi3d_solver *h, int nang, int npf, const float *ang, const fl
 int mi3d_set_surface(mi3d_solver *h, int mtype, const float param[5]);
 
 /* 2-D surface = keys Sfc_nxb, Sfc_nyb and the side file Sfc_inpfile
- * (er3t/rtm/mca/mca_sfc.py:81-146), file layout: tmps[nyb][nxb] (ignored, may be NULL),
+ * (er3t/rtm/mca/mca_sfc.py:81-146), file layout: tmps[nyb][nxb] (ignored, may be NULL: a thermal job hands it to mi3d_set_thermal),
  * jsfc[nyb][nxb] (model id stored as float), psfc[5][nyb][nxb]. */
 int mi3d_set_surface2d(mi3d_solver *h, int nxb, int nyb, const float *tmps, const float *jsfc,
                        const float *psfc);
 
 /* Solar source = keys Src_flx, Src_qmax, Src_the, Src_phi (er3t/rtm/mca/mcarats.py:374-383). */
 int mi3d_set_source(mi3d_solver *h, double flx, double qmax_deg, double the_deg, double phi_deg);
+
+/* Thermal source = keys Src_mtype, Src_wlen, Atm_tmp1d, the Atm_tmpa3d block of Atm_inpfile and the Sfc_tmps2d block of
+ * Sfc_inpfile (er3t/rtm/mca/mca_inp.py:287 "0:local 1:solar 2:solar+thermal 3:thermal"; mca_atm.py:73,175-214; mca_sfc.py:74).
+ * Src_wlen, the band-centre wavelength in micrometres, is a key of THIS project in the Src group: MCARaTS' own thermal inputs cannot
+ * be confirmed, its source is not in the reference.  Src_dwlen is accepted and ignored: the source is monochromatic at Src_wlen.
+ *   mtype    3 thermal; 1 switches the handle back to the solar source (the other arguments are then ignored); 0 and 2
+ *            (local, solar+thermal): MI3D_EUNSUP
+ *   wlen_um  Src_wlen [um], > 0
+ *   nlev     must be nz+1: tmp1d[nz+1] holds the INTERFACE temperatures [K] from the surface up (MCARaTS: Atm_tmp1d(KNZ+1))
+ *   tmpa3d   [nz3][ny][nx] voxel temperature anomalies [K] in the file layout of mi3d_set_atm3d, or NULL (0)
+ *   tmps2d   [nyb][nxb] surface temperature anomalies [K] of the 2-D surface of mi3d_set_surface2d, or NULL (0)
+ * Call after mi3d_set_atm1d / mi3d_set_atm3d / mi3d_set_surface2d of the scene: mi3d_prepare checks the sizes again.
+ * Physics contract ("Thermal source"):
+ *   B(wl, T) = 2 h c^2 / wl^5 / (exp(h c / (wl k T)) - 1) in W m-2 sr-1 um-1 (CODATA 2018 h, c, k), times Src_flx;
+ *            B(10 um, 300 K) = 9.92403, B(11 um, 288 K) = 7.96577, B(4 um, 250 K) = 0.0656295
+ *   a 1-D layer emits at the mean of its two interface temperatures, a voxel at that mean plus its anomaly, the surface at
+ *   tmp1d[0] (plus its anomaly).  Emitted power: 4 pi ka B(T) V per cell, ka = gas absorption (abs1d + abst3d) + ext (1 - omega)
+ *   summed over every constituent; pi (1 - albedo) B(Ts) A per surface cell, Lambertian surfaces only (else MI3D_EUNSUP at
+ *   mi3d_prepare).  Volume emission is isotropic, surface emission follows the cosine law.
+ *   Results: radiance (Rad_mrkind = 2) in W m-2 sr-1 um-1, fluxes in W m-2 um-1 (mi3d_get_radiance / mi3d_get_flux /
+ *   mi3d_stats_add: the normalisation is Src_flx P_tot / N in place of Src_flx mu0 Lx Ly / N).  No direct beam: the direct-down
+ *   plane is 0 and the analytic direct-beam levels are off.  A thermal job always runs on the general photon loop
+ *   (mi3d_last_kernel: "k_transport<...> [thermal]"); cameras (Rad_mrkind = 1) and heating rates: MI3D_EUNSUP.  Under
+ *   MI3D_SOLVER_P3D every thermal photon stays in its column (no photon is direct). */
+int mi3d_set_thermal(mi3d_solver *h, int mtype, double wlen_um, int nlev, const float *tmp1d, const float *tmpa3d,
+                     const float *tmps2d);
 
 /* Radiance views = keys Rad_nrad, Rad_the, Rad_phi, Rad_zloc, Rad_zref, Rad_nxr, Rad_nyr for
  * Rad_mrkind = 2 (pixel-averaged radiance; er3t/rtm/mca/mcarats.py:285-307,360-367).  The

@@ -1,0 +1,66 @@
+"""
+Thermal source (Src_mtype = 3): photons per second of the general photon loop on the synthetic cloud scenes of BASELINE
+configs 2 (128 x 128 x 50) and 4 (480 x 480 x 100), nadir radiance and flux, and what building the source costs per job
+(k_thermal_power + the prefix scan + reading P_tot back: the wall time of mi3d_prepare after mi3d_set_thermal).
+
+    python tools/thermal_rate.py [--photons 5e7] [--reps 3]
+"""
+
+import argparse
+import dataclasses
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from er3t_amd.scene import TARGET_FLUX, TARGET_RADIANCE      # noqa: E402
+from er3t_amd.solver import Mi3dSolver                        # noqa: E402
+from er3t_amd.synth import les_scene, z_levels_config4, atm_synth   # noqa: E402
+
+
+def thermal(scene, levels, wl=11.0):
+    atm = atm_synth(levels)
+    omgp = np.where(scene.extp > 0.0, np.float32(0.95), np.float32(1.0)).astype(np.float32)   # a cloud that absorbs at 11 um
+    return dataclasses.replace(scene, src_mtype=3, src_wlen=wl, tmp1d=atm.lev['temperature']['data'], omgp=omgp)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--photons', type=float, default=5e7)
+    ap.add_argument('--reps', type=int, default=3)
+    a = ap.parse_args()
+    sol = Mi3dSolver(0)
+    n = int(a.photons)
+    rows = []
+    for name, kw, levels in (('les128', dict(nx=128, ny=128, nz3=50), None),
+                             ('les480', dict(nx=480, ny=480, nz3=100, levels=z_levels_config4(), z_top=1.6, seed=20251004), z_levels_config4())):
+        from er3t_amd.synth import z_levels_config2
+        lev = levels if levels is not None else z_levels_config2()
+        for target in ('radiance', 'flux'):
+            s = thermal(les_scene(target=target, **kw), lev)
+            sol.load_scene(s)
+            # the per-job cost of the source: set again (dirty), then prepare
+            build = []
+            for _ in range(a.reps):
+                sol.set_thermal(3, s.src_wlen, s.tmp1d, s.tmpa3d, s.tmps2d)
+                t0 = time.perf_counter(); sol.prepare(); build.append((time.perf_counter()-t0)*1e3)
+            sol.reset(); sol.run(min(n, 2000000), seed=1); sol.sync()        # warm-up
+            rates = []
+            for r in range(a.reps):
+                sol.reset()
+                sol.run(n, seed=2, offset=r*n)
+                ms, _ = sol.timing()
+                rates.append(n/(ms*1e-3))
+            row = dict(scene=name, target=target, kernel=sol.kernel_name(), photons=n, photons_per_s=float(np.median(rates)),
+                       thermal_build_ms=float(np.median(build)))
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    return rows
+
+
+if __name__ == '__main__':
+    main()
