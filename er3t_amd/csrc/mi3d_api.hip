@@ -114,7 +114,12 @@ struct mi3d_solver {
     int rad_kind = 2;
     double cam_psi[MI3D_MAX_VIEW], cam_xpos[MI3D_MAX_VIEW], cam_ypos[MI3D_MAX_VIEW], cam_qmax[MI3D_MAX_VIEW], cam_umax[MI3D_MAX_VIEW],
            cam_vmax[MI3D_MAX_VIEW], cam_apsize[MI3D_MAX_VIEW];
-    DevBuf<CamRec> d_cams;
+    DevBuf<CamRec> d_cams;            // [nview] CamRec, then the float table [nview][nxr] of the rectangular map (cam_pixel)
+    int cam_mpmap = 1, cam_mrproj = 0;   // mi3d_set_camera_map: Rad_mpmap, Rad_mrproj
+    // the direct sun in the cameras (k_cam_direct): [nview][nyr][nxr] per unit Src_flx, rebuilt by mi3d_prepare when dirty
+    DevBuf<double> d_camdir, d_zgrd;
+    bool dirty_camdir = true;
+    bool camdir_ok = false;           // d_camdir holds the direct sun of the scene and source set now (false: the march was too long, see build_camdir)
     int target = MI3D_TARGET_FLUX, solver = MI3D_SOLVER_3D, column_le = 1, counting = 0;
     double wmin = 0.2, wfac = 1.0, le_tau1 = 0.0, le_cmin = 0.0;
     std::vector<LayerRec> lay_host;  // the layer table as uploaded (mi3d_prepare)
@@ -402,7 +407,11 @@ int build_views(mi3d_solver *h) {
     h->col0 = -1;
     if (h->rad_kind == 1) {
         // cameras: axes = world axes turned by Rz(phi) Ry(the) Rz(psi) (er3t/rtm/mca/mca_inp.py:324-330)
-        std::vector<CamRec> cams(h->nview > 0 ? h->nview : 1);
+        // the CamRec records, then the rectangular map's table [nview][nxr] (cam_pixel) in the same buffer
+        const size_t ncr = h->nview > 0 ? h->nview : 1, ntab = ((size_t)ncr * h->nxr * sizeof(float) + sizeof(CamRec) - 1) / sizeof(CamRec);
+        std::vector<CamRec> cams(ncr + ntab);
+        std::memset(cams.data(), 0, cams.size() * sizeof(CamRec));
+        float *rowf = reinterpret_cast<float *>(cams.data() + (h->nview > 0 ? h->nview : 0));
         const double Lx = h->dx * h->nx, Ly = h->dy * h->ny;
         for (int iv = 0; iv < h->nview; ++iv) {
             const double t = h->view_the[iv] * pi / 180.0, p = h->view_phi[iv] * pi / 180.0, q = h->cam_psi[iv] * pi / 180.0;
@@ -417,12 +426,29 @@ int build_views(mi3d_solver *h) {
             C.xx = (float)X[0]; C.xy = (float)X[1]; C.xz = (float)X[2];
             C.yx = (float)Y[0]; C.yy = (float)Y[1]; C.yz = (float)Y[2];
             C.cos_half = (float)std::cos(0.5 * h->cam_qmax[iv] * pi / 180.0);
+            const bool rect = h->cam_mpmap == 2;
+            if (rect && !(h->cam_umax[iv] <= 180.0 && h->cam_vmax[iv] <= 180.0))
+                return fail(MI3D_EINVAL, "camera %d: the rectangular map (Rad_mpmap=2) needs Rad_umax <= 180 and Rad_vmax <= 180 (%g, %g)", iv + 1,
+                            h->cam_umax[iv], h->cam_vmax[iv]);
+            if (rect && h->cam_mrproj == 1 && !(h->cam_umax[iv] <= 90.0))
+                return fail(MI3D_EINVAL, "camera %d: cosine weighting (Rad_mrproj=1) on the rectangular map needs Rad_umax <= 90 (%g)", iv + 1, h->cam_umax[iv]);
             C.inv_du = (float)(h->nxr / (h->cam_umax[iv] * pi / 180.0));
-            C.inv_dv = (float)(h->nyr / (h->cam_vmax[iv] * pi / 180.0));
+            C.inv_dv = (float)(h->nyr / ((rect ? 2.0 : 1.0) * h->cam_vmax[iv] * pi / 180.0));   // (rectangular: V spans [-vmax, vmax])
+            if (rect) {
+                // 1 / W: the exact weighted solid angle of a pixel of column ir, (cos t0 - cos t1) dphi or (sin^2 t1 - sin^2 t0) dphi / 2
+                const double du = h->cam_umax[iv] * pi / 180.0 / h->nxr, dphi = 2.0 * h->cam_vmax[iv] * pi / 180.0 / h->nyr;
+                for (int ir = 0; ir < h->nxr; ++ir) {
+                    const double t0 = ir * du, t1 = (ir + 1) * du;
+                    const double W = h->cam_mrproj == 1 ? 0.5 * (std::sin(t1) * std::sin(t1) - std::sin(t0) * std::sin(t0)) * dphi
+                                                        : 2.0 * std::sin(0.5 * (t0 + t1)) * std::sin(0.5 * (t1 - t0)) * dphi;
+                    rowf[(size_t)iv * h->nxr + ir] = W > 0.0 ? (float)(1.0 / W) : 0.0f;
+                }
+            }
             ViewRec &V = v[iv];
             std::memset(&V, 0, sizeof(V));
             V.vx = C.zx; V.vy = C.zy; V.vz = C.zz; V.zs = C.cz; V.zreg = C.cz;
-            V.column = 0; V.point = 1;
+            V.column = 0;
+            V.point = kCamPoint | (rect ? kCamRect : 0) | (h->cam_mrproj == 1 ? kCamCos : 0) | (rect && h->cam_vmax[iv] >= 180.0 ? kCamWrap : 0);
             V.roulette = h->le_tau1 > 0.0 ? 1 : 0;
             h->nmarch++;
         }
@@ -678,6 +704,36 @@ int build_thermal(mi3d_solver *h) {
     return MI3D_OK;
 }
 
+// The direct sun in the cameras (k_cam_direct), per unit Src_flx; thermal jobs have none (zeros).
+constexpr double kCamDirMaxCells = 1048576.0;   // voxels one march may cross (a few hundred milliseconds of one thread at most)
+int build_camdir(mi3d_solver *h) {
+    const size_t n = (size_t)h->nview * h->nxr * h->nyr;
+    HIPCHK(sync_streams(h));   // (the uploads are synchronous copies; a statistics kernel of the last job may still read the image)
+    int rc;
+    if ((rc = h->d_camdir.alloc(n)) || (rc = h->d_zgrd.upload(h->zgrd.data(), h->zgrd.size()))) return rc;
+    HIPCHK(hipMemsetAsync(h->d_camdir.p, 0, n * sizeof(double), h->stream));
+    h->camdir_ok = true;
+    if (h->src_mtype == 1) {
+        const double pi = 3.14159265358979323846;
+        const double th = h->src_the * pi / 180.0, ph = h->src_phi * pi / 180.0;
+        const int k3lo = h->nz3 > 0 ? h->iz3l - 1 : 0;
+        // the most voxels a march through the 3-D region can cross: one thread walks them, so a sun within a few thousandths of a degree
+        // of the horizon (cells in proportion to 1 / cos) is not marched -- mi3d_get_camera_direct then fails; no job has to read it
+        if (h->nz3 > 0) {
+            const double h3 = h->zgrd[k3lo + h->nz3] - h->zgrd[k3lo], sz = -std::cos(th);
+            const double cells = h->nz3 + 2.0 + h3 / sz * (std::fabs(std::sin(th) * std::cos(ph)) / h->dx + std::fabs(std::sin(th) * std::sin(ph)) / h->dy);
+            if (!(cells <= kCamDirMaxCells)) { h->camdir_ok = false; return MI3D_OK; }
+        }
+        // (towards the sun: against the direction the photons of the direct beam travel in)
+        hipLaunchKernelGGL(k_cam_direct, dim3((unsigned)((h->nview + 63) / 64)), dim3(64), 0, h->stream, h->nview, h->nxr, h->nyr,
+                           (const CamRec *)h->d_cams.p, (const ViewRec *)h->d_views.p, (const double *)h->d_zgrd.p, (const LayerRec *)h->d_lay.p,
+                           h->nz, h->nx, h->ny, h->nz3, k3lo, h->dx, h->dy, (const float *)(h->nz3 > 0 ? h->d_bext3.p : nullptr),
+                           -std::sin(th) * std::cos(ph), -std::sin(th) * std::sin(ph), -std::cos(th), h->d_camdir.p);
+        HIPCHK(hipGetLastError());
+    }
+    return MI3D_OK;
+}
+
 } // namespace
 
 // =================================================================================================
@@ -778,7 +834,7 @@ int mi3d_destroy(mi3d_solver *h) {
     h->d_lay.release(); h->d_vrec.release(); h->d_bext3.release(); h->d_tcol0.release(); h->d_tmu.release(); h->d_tp.release();
     h->d_tcdf.release(); h->d_tmuidx.release(); h->d_tcdfidx.release(); h->d_sfc2d.release(); h->d_csca.release(); h->d_rad_own.release();
     h->d_flux_own.release(); h->d_heat_own.release(); h->d_counters.release(); h->d_next.release();
-    h->d_rad_acc.release(); h->d_cams.release();
+    h->d_rad_acc.release(); h->d_cams.release(); h->d_camdir.release(); h->d_zgrd.release();
     h->d_order.release(); h->d_hist.release(); h->d_cursor.release(); h->d_tile.release(); h->d_entry.release();
     h->d_events.release(); h->d_evctr.release(); h->d_hvlist.release();
     for (hipEvent_t &e : h->tl_done) if (e) (void)hipEventDestroy(e);
@@ -902,6 +958,7 @@ int mi3d_set_source(mi3d_solver *h, double flx, double qmax_deg, double the_deg,
     if (!(qmax_deg >= 0.0 && qmax_deg < 90.0)) return fail(MI3D_EINVAL, "Src_qmax=%g out of range", qmax_deg);
     if (h->src_the != the_deg || h->src_phi != phi_deg || h->src_qmax != qmax_deg) ev_forget(h);
     h->src_flx = flx; h->src_qmax = qmax_deg; h->src_the = the_deg; h->src_phi = phi_deg;
+    h->dirty_camdir = true;
     return MI3D_OK;
 }
 
@@ -909,6 +966,7 @@ int mi3d_set_thermal(mi3d_solver *h, int mtype, double wlen_um, int nlev, const 
                      const float *tmps2d) {
     int rc = check_handle(h);
     if (rc) return rc;
+    h->dirty_camdir = true;
     if (mtype == 1) {
         if (h->src_mtype != 1) ev_forget(h);
         h->src_mtype = 1; h->th_ptot = 0.0; h->dirty_thermal = false;
@@ -981,6 +1039,16 @@ int mi3d_set_cameras(mi3d_solver *h, int ncam, const double *the_deg, const doub
     h->nview = ncam; h->nxr = nxr; h->nyr = nyr; h->zref = 0.0;
     h->rad_kind = 1;
     h->dirty_views = true;
+    return MI3D_OK;
+}
+
+int mi3d_set_camera_map(mi3d_solver *h, int mpmap, int mrproj) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (mpmap != 1 && mpmap != 2) return fail(MI3D_EINVAL, "Rad_mpmap=%d: 1 (polar) or 2 (rectangular)", mpmap);
+    if (mrproj != 0 && mrproj != 1) return fail(MI3D_EINVAL, "Rad_mrproj=%d: 0 (mean radiance) or 1 (cosine-weighted)", mrproj);
+    if (h->cam_mpmap != mpmap || h->cam_mrproj != mrproj) h->dirty_views = true;
+    h->cam_mpmap = mpmap; h->cam_mrproj = mrproj;
     return MI3D_OK;
 }
 
@@ -1130,6 +1198,7 @@ int mi3d_prepare(mi3d_solver *h) {
     if (h->dirty_views) {
         if ((rc = build_views(h))) return rc;
         h->dirty_views = false;
+        h->dirty_camdir = true;
     }
     if (h->dirty_phase) {
         if ((rc = build_tables(h))) return rc;
@@ -1160,6 +1229,10 @@ int mi3d_prepare(mi3d_solver *h) {
     if (h->src_mtype == 3 && h->dirty_thermal) {
         if ((rc = build_thermal(h))) return rc;
         h->dirty_thermal = false;
+    }
+    if (h->rad_kind == 1 && h->nview > 0 && h->dirty_camdir) {
+        if ((rc = build_camdir(h))) return rc;
+        h->dirty_camdir = false;
     }
     return MI3D_OK;
 }
@@ -2364,6 +2437,22 @@ int mi3d_get_direct_levels(mi3d_solver *h, double *out) {
     return MI3D_OK;
 }
 
+int mi3d_get_camera_direct(mi3d_solver *h, double *out) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (!out) return fail(MI3D_EINVAL, "out is NULL");
+    if (h->rad_kind != 1) return fail(MI3D_ESTATE, "the views are not cameras (mi3d_set_cameras)");
+    if ((rc = mi3d_prepare(h))) return rc;
+    const size_t n = (size_t)h->nview * h->nxr * h->nyr;
+    if (n == 0) return MI3D_OK;
+    if (!h->camdir_ok)
+        return fail(MI3D_EUNSUP, "the cameras' direct sun: Src_the=%g lies too close to the horizon (more than %.0f voxels to march)", h->src_the, kCamDirMaxCells);
+    HIPCHK(hipMemcpyAsync(out, h->d_camdir.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (size_t i = 0; i < n; ++i) out[i] *= h->src_flx;
+    return MI3D_OK;
+}
+
 int mi3d_get_heating(mi3d_solver *h, uint64_t nphoton_total, float *out) {
     int rc = check_handle(h);
     if (rc) return rc;
@@ -2471,8 +2560,14 @@ int mi3d_stats_add(mi3d_solver *h, uint64_t nphoton_total, const float *factor_r
             if ((rc = h->d_dir_level.upload(a.data(), a.size()))) return rc;
             dir_dev = h->d_dir_level.p;
         }
+        // (cameras with the rectangular map -- point radiometers: the direct sun joins the run field like the flux's analytic direct beam,
+        //  on the ranks with an analytic share.  The polar map's run field stays diffuse only, as mi3d_get_radiance and its files are)
+        const bool camdir = w == 0 && h->rad_kind == 1 && h->cam_mpmap == 2 && h->src_mtype == 1 && h->analytic_share > 0.0;
+        if (camdir && !h->camdir_ok)
+            return fail(MI3D_EUNSUP, "the cameras' direct sun: Src_the=%g lies too close to the horizon (more than %.0f voxels to march)", h->src_the, kCamDirMaxCells);
         hipLaunchKernelGGL(k_stats_add, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, tally, h->run_ptr(w),
-                           h->d_factor[w].p, norm, plane, nlevel, w == 0 ? -1 : (int)(n / 3), dir_dev, (int)n);
+                           h->d_factor[w].p, norm, plane, nlevel, w == 0 ? -1 : (int)(n / 3), dir_dev, (int)n,
+                           camdir ? (const double *)h->d_camdir.p : (const double *)nullptr, h->src_flx * h->analytic_share);
         HIPCHK(hipGetLastError());
     }
     return stats_mark(h);

@@ -54,7 +54,8 @@ struct ViewRec {
     int roulette;     // bit 0: the view's local-estimate rays play Russian roulette beyond DevCold::le_tau1; bit 1: ... and on their weight
                       // below DevCold::le_cmin (le_weight_roulette)
     float zreg;       // height at which the line of sight is registered to a pixel: Rad_zref (down-looking), zs (up-looking)
-    int point;        // 1: a camera (Rad_mrkind = 1): a point sensor, described by CamRec[view]; vx..vz, zreg unused
+    int point;        // bit 0 (kCamPoint): a camera (Rad_mrkind = 1): a point sensor, described by CamRec[view]; vx..vz, zreg unused.
+                      // Bits 1..3: its pixel map and weighting (cam_pixel): kCamRect, kCamCos, kCamWrap
 };
 static_assert(sizeof(ViewRec) == 32, "ViewRec layout");
 
@@ -70,6 +71,10 @@ struct CamRec {
     float inv_dv;            // pixels per radian along V (nyr / Rad_vmax)
 };
 static_assert(sizeof(CamRec) == 64, "CamRec layout");
+// Bits of ViewRec::point.  kCamRect: the rectangular pixel map (Rad_mpmap = 2), U = theta in [0, umax], V = phi in [-vmax, vmax];
+// without it the polar one (Rad_mpmap = 1).  kCamCos: cosine-weighted pixel values (Rad_mrproj = 1).  kCamWrap: the rectangular map
+// spans the full circle in phi (vmax >= 180), so that phi = pi falls into the first column.
+constexpr int kCamPoint = 1, kCamRect = 2, kCamCos = 4, kCamWrap = 8;
 
 // Rarely used scene data lives in device memory behind a pointer and is copied to LDS when the transport kernel
 // starts; only what the voxel walk and the common collision path touch travels in SGPRs as kernel arguments.  (The
@@ -103,7 +108,7 @@ struct DevCold {
     const uint32_t *order; // [nphoton of the launch] photon indices sorted by launch tile (k_bin_*), or nullptr: identity
     float sfc_p4;
     int ev_cap;            // capacity of each XCD's event list
-    const CamRec *cams;    // [nview] cameras (views with ViewRec::point), else nullptr
+    const CamRec *cams;    // [nview] cameras (views with ViewRec::point), else nullptr; followed by the float table rowf [nview][nxr] of cam_pixel
     float4 *ev_list;       // [8][ev_list_f4(ev_cap)] event records in blocks of 64, one list per XCD (k_transport_lean<.,.,2> writes, k_rays reads): ev_index, ev_word
     unsigned long long *ev_ctr;   // [kCtrWords][kCtrStride]: [x] events in list x; [8]: set when a list ran full; [kCtrCursor + x]: k_rays'
                                   // cursor into list x; [kCtrHeavyFill + x], [kCtrHeavyCursor + x]: the same for hv_list
@@ -714,6 +719,35 @@ __device__ inline float surface_R(const Sfc &sf, float dix, float diy, float diz
     if (sf.type == MI3D_SFC_LSRT) return lsrt_R(sf.p0, sf.p1, sf.p2, dix, diy, diz, dox, doy, doz);
     if (sf.type == MI3D_SFC_DSM) return dsm_R(sf.p0, sf.p1, sf.p2, sf.p3, sf.p4, dix, diy, diz, dox, doy, doz);
     return fminf(fmaxf(sf.p0, 0.0f), 1.0f);
+}
+
+// The pixel of a camera a direction falls into, and the pixel's value for a contribution c (a radiance times the solid angle it
+// stands for: a local estimate's w P / 4 pi exp(-tau) / r^2, or the direct sun's flux).  (dxc, dyc, dzc): the direction the camera
+// looks in, in its own axes (image x, image y, its axis); theta is measured from the axis, phi about it from the image x axis.
+//   polar map (Rad_mpmap = 1): U = theta cos(phi), V = theta sin(phi), centred; the value is c / (sinc(theta) dU dV), the solid angle
+//     of the pixel taken per direction.  A cosine weight (Rad_mrproj = 1) would multiply c by cos(theta) and the per-direction
+//     solid angle by the same cos(theta): it cancels, and the polar map gives the same image for both weightings.
+//   rectangular map (Rad_mpmap = 2): U = theta in [0, umax] (nxr columns), V = phi in [-vmax, vmax] (nyr rows); the value is
+//     w(theta) c / W_ir, W_ir the exact weighted solid angle of the pixel, 1 / W_ir from the host's table rowf[ir] (rect_rowf).
+// Returns false where the direction falls outside the image.
+__device__ inline bool cam_pixel(const CamRec &Cm, int mode, const float *rowf, int nxr, int nyr, float dxc, float dyc, float dzc,
+                                 float c, int &ir, int &jr, float &value) {
+    const float rho2 = dxc * dxc + dyc * dyc;
+    if (!(mode & kCamRect)) {
+        const float theta = acosf(dzc);
+        const float sc = rho2 > 1e-24f ? theta * frsq(rho2) : 0.0f;
+        ir = (int)floorf(dxc * sc * Cm.inv_du + 0.5f * (float)nxr); jr = (int)floorf(dyc * sc * Cm.inv_dv + 0.5f * (float)nyr);
+        if (!(ir >= 0 && ir < nxr && jr >= 0 && jr < nyr)) return false;
+        const float sinc = theta > 1e-6f ? sinf(theta) / theta : 1.0f;
+        value = c * Cm.inv_du * Cm.inv_dv / sinc;
+        return true;
+    }
+    const float th = acosf(fmaxf(dzc, -1.0f)), phi = rho2 > 1e-24f ? atan2f(dyc, dxc) : 0.0f;
+    ir = (int)floorf(th * Cm.inv_du); jr = (int)floorf(phi * Cm.inv_dv + 0.5f * (float)nyr);
+    if ((mode & kCamWrap) && jr == nyr) jr = 0;
+    if (!(ir < nxr && jr >= 0 && jr < nyr)) return false;
+    value = ((mode & kCamCos) ? c * dzc : c) * rowf[ir];
+    return true;
 }
 
 } // namespace mi3d

@@ -466,17 +466,16 @@ k_rays(const DevScene S, const uint64_t seed) {
                         if (V.roulette & 2) c = le_weight_roulette_base(c, cold->le_cmin, ehb, jv);
                         c *= fimg;
                         if (c > 0.0f) {
-                            // the pixel: where the direction the camera looks in to see the event falls in the polar map (k_transport's B1)
+                            // the pixel: where the direction the camera looks in to see the event falls in the camera's pixel map (cam_pixel)
                             const float dxc = -(vx * Cm.xx + vy * Cm.xy + vz * Cm.xz), dyc = -(vx * Cm.yx + vy * Cm.yy + vz * Cm.yz);
                             const float dzc = fminf(-(vx * Cm.zx + vy * Cm.zy + vz * Cm.zz), 1.0f);
-                            const float theta = acosf(dzc), rho2 = dxc * dxc + dyc * dyc;
-                            const float sc = rho2 > 1e-24f ? theta * frsq(rho2) : 0.0f;
-                            const int ir = (int)floorf(dxc * sc * Cm.inv_du + 0.5f * (float)S.nxr), jr = (int)floorf(dyc * sc * Cm.inv_dv + 0.5f * (float)S.nyr);
-                            if (ir >= 0 && ir < S.nxr && jr >= 0 && jr < S.nyr) {
-                                const float sinc = theta > 1e-6f ? sinf(theta) / theta : 1.0f;
+                            int ir, jr;
+                            float val;
+                            if (cam_pixel(Cm, V.point, reinterpret_cast<const float *>(cold->cams + S.nview) + jv * S.nxr, S.nxr, S.nyr, dxc, dyc, dzc,
+                                          c * inv_r2, ir, jr, val)) {
                                 const float tk = (V.roulette & 1) ? cold->le_tau1 - 0.69314718f * __builtin_amdgcn_logf(le_roulette_from_base(ehb, jv + 64 * (int)isub)) : kTauCut;
                                 q0 = make_float4(E0.x, E0.y, E0.z, __int_as_float(ecell));
-                                q1 = make_float4(__int_as_float((ekk & 0xffff) | (jv << 16)), c * inv_r2 * Cm.inv_du * Cm.inv_dv / sinc, tk, __int_as_float((jv * S.nyr + jr) * S.rad_row + ir));
+                                q1 = make_float4(__int_as_float((ekk & 0xffff) | (jv << 16)), val, tk, __int_as_float((jv * S.nyr + jr) * S.rad_row + ir));
                                 q2 = make_float4(vx, vy, vz, Cm.cz);
                                 push = true;
                             }

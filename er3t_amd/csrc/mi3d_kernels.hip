@@ -419,14 +419,16 @@ k_fold_rad(tally_t *__restrict__ acc, tally_t *__restrict__ tally, int stride, i
 // [down_lo, 2 down_lo) hold the diffuse downward flux, to which the direct beam [0, down_lo) is added.
 __global__ void __launch_bounds__(256)
 k_stats_add(const tally_t *__restrict__ tally, float *__restrict__ run_acc, const float *__restrict__ factor,
-            double norm, int plane, int nlevel, int down_lo, const double *__restrict__ dir_level, int n) {
+            double norm, int plane, int nlevel, int down_lo, const double *__restrict__ dir_level, int n,
+            const double *__restrict__ add_px, double add_scale) {
 #pragma clang fp contract(off) // a fused multiply-add would round once where numpy rounds twice
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     double t = tally[i];
     if (down_lo >= 0 && i >= down_lo && i < 2 * down_lo) t += tally[i - down_lo]; // total-down = direct + diffuse
-    // (flux: the analytic direct beam of the levels above the 3-D region joins the direct and the total downward flux)
-    const double a = (dir_level && i < 2 * down_lo) ? dir_level[(i / plane) % nlevel] : 0.0;
+    // (flux: the analytic direct beam of the levels above the 3-D region joins the direct and the total downward flux; cameras: the
+    //  direct sun, add_px[i] x add_scale, per pixel)
+    const double a = add_px ? add_px[i] * add_scale : (dir_level && i < 2 * down_lo) ? dir_level[(i / plane) % nlevel] : 0.0;
     const float v = (float)(t * norm + a);
     const float f = factor[(i / plane) % nlevel];
     const float prod = v * f;
@@ -453,6 +455,61 @@ k_get_field(const tally_t *__restrict__ tally, float *__restrict__ out, double n
         out[i] = (float)(t * norm + a);
     } else if (add) out[i] = (float)(t * norm / add[lev]);
     else out[i] = (float)(t * norm);      // (radiance: a scale)
+}
+
+// The direct sun in the cameras (Rad_mrkind = 1), one thread per camera, once per job (mi3d_prepare): the optical depth from the
+// camera to the top of the atmosphere along the direction towards the sun's centre (sx, sy, sz), float64, through the voxels of the
+// 3-D region (bext3, the domain cyclic in x and y) and the 1-D layers (LayerRec::bt); then Src_flx exp(-tau) per unit Src_flx
+// into the pixel the sun falls in (cam_pixel, contribution 1), if it is in the cone of view.  `out` [nview][nyr][nxr] is zeroed
+// by the caller; every camera writes one pixel of its own image.  The march ends once tau exceeds kCamDirTauMax (the pixel stays 0:
+// a sun near the horizon crosses cells in proportion to 1 / sz); the host bounds the cells a march can cross before it launches.
+constexpr double kCamDirTauMax = 100.0;   // exp(-100) = 4e-44 of Src_flx
+__global__ void __launch_bounds__(64)
+k_cam_direct(int nview, int nxr, int nyr, const CamRec *__restrict__ cams, const ViewRec *__restrict__ views, const double *__restrict__ zgrd,
+             const LayerRec *__restrict__ lay, int nz, int nx, int ny, int nz3, int k3lo, double dx, double dy, const float *__restrict__ bext3,
+             double sx, double sy, double sz, double *__restrict__ out) {
+    const int iv = blockIdx.x * blockDim.x + threadIdx.x;
+    if (iv >= nview) return;
+    const CamRec Cm = cams[iv];
+    const float dxc = (float)sx * Cm.xx + (float)sy * Cm.xy + (float)sz * Cm.xz, dyc = (float)sx * Cm.yx + (float)sy * Cm.yy + (float)sz * Cm.yz;
+    const float dzc = fminf((float)sx * Cm.zx + (float)sy * Cm.zy + (float)sz * Cm.zz, 1.0f);
+    if (dzc < Cm.cos_half) return;                       // outside the cone of view
+    int ir, jr;
+    float val;
+    if (!cam_pixel(Cm, views[iv].point, reinterpret_cast<const float *>(cams + nview) + iv * nxr, nxr, nyr, dxc, dyc, dzc, 1.0f, ir, jr, val)) return;
+    double x = Cm.cx, y = Cm.cy, z = fmax((double)Cm.cz, zgrd[0]);
+    double tau = 0.0;
+    int k = 0;
+    while (k < nz && zgrd[k + 1] <= z) ++k;
+    for (; k < nz && tau <= kCamDirTauMax; ++k) {
+        const double ztop = zgrd[k + 1];
+        if (!(nz3 > 0 && k >= k3lo && k < k3lo + nz3)) {   // a 1-D layer: straight through
+            const double t = (ztop - z) / sz;
+            tau += (double)lay[k].bt * t;
+            x += sx * t; y += sy * t; z = ztop;
+            continue;
+        }
+        // a 3-D layer: cell by cell; the column is tracked by integer steps (unwrapped), its voxel found modulo the domain
+        long ixu = (long)floor(x / dx), iyu = (long)floor(y / dy);
+        for (;;) {
+            const double tz = (ztop - z) / sz;
+            const double tx = sx > 0.0 ? ((double)(ixu + 1) * dx - x) / sx : sx < 0.0 ? ((double)ixu * dx - x) / sx : INFINITY;
+            const double ty = sy > 0.0 ? ((double)(iyu + 1) * dy - y) / sy : sy < 0.0 ? ((double)iyu * dy - y) / sy : INFINITY;
+            double t = tz;
+            int axis = 2;
+            if (tx < t) { t = tx; axis = 0; }
+            if (ty < t) { t = ty; axis = 1; }
+            t = fmax(t, 0.0);
+            const long ix = ((ixu % nx) + nx) % nx, iy = ((iyu % ny) + ny) % ny;
+            tau += (double)bext3[((size_t)iy * nx + ix) * nz3 + (k - k3lo)] * t;
+            x += sx * t; y += sy * t; z += sz * t;
+            if (axis == 2) { z = ztop; break; }
+            if (tau > kCamDirTauMax) break;
+            if (axis == 0) ixu += sx > 0.0 ? 1 : -1;
+            else iyu += sy > 0.0 ? 1 : -1;
+        }
+    }
+    if (tau <= kCamDirTauMax) out[((size_t)iv * nyr + jr) * nxr + ir] = exp(-tau) * (double)val;
 }
 
 // End of a run: fold the run's field into the sum and the sum of squares over runs (float64).
@@ -922,20 +979,16 @@ k_transport(const DevScene S, const uint64_t nphoton, const uint64_t seed, const
         if (MARCH && mode == M_LEEND) {
             if (acc <= tkill && views[iv].point) {
                 // camera: the ray has reached the point sensor; its pixel is where the direction the camera looks in to see the
-                // event falls in the polar map U = theta cos(phi), V = theta sin(phi) (theta from the camera's axis); the value
-                // already holds 1 / r^2, the patch dU dV has the solid angle (sin theta / theta) dU dV
+                // event falls in the camera's pixel map (cam_pixel); the value already holds 1 / r^2
                 const CamRec Cm = cold->cams[iv];
                 const float dxc = -(ux * Cm.xx + uy * Cm.xy + uz * Cm.xz), dyc = -(ux * Cm.yx + uy * Cm.yy + uz * Cm.yz);
                 const float dzc = fminf(-(ux * Cm.zx + uy * Cm.zy + uz * Cm.zz), 1.0f);
-                const float theta = acosf(dzc), rho2 = dxc * dxc + dyc * dyc;
-                const float sc = rho2 > 1e-24f ? theta * frsq(rho2) : 0.0f;
-                const int ir = (int)floorf(dxc * sc * Cm.inv_du + 0.5f * (float)S.nxr), jr = (int)floorf(dyc * sc * Cm.inv_dv + 0.5f * (float)S.nyr);
-                if (ir >= 0 && ir < S.nxr && jr >= 0 && jr < S.nyr) {
-                    const float sinc = theta > 1e-6f ? sinf(theta) / theta : 1.0f;
-                    const ViewRec V = views[iv];
-                    RAD_ADD(&S.rad[(unsigned)((iv * S.nyr + jr) * S.rad_row + ir) * (unsigned)S.rad_stride],
-                            contrib * fexp_neg((V.roulette & 1) ? fminf(acc, cold->le_tau1) : acc) * Cm.inv_du * Cm.inv_dv / sinc);
-                }
+                const ViewRec V = views[iv];
+                int ir, jr;
+                float val;
+                if (cam_pixel(Cm, V.point, reinterpret_cast<const float *>(cold->cams + S.nview) + iv * S.nxr, S.nxr, S.nyr, dxc, dyc, dzc,
+                              contrib * fexp_neg((V.roulette & 1) ? fminf(acc, cold->le_tau1) : acc), ir, jr, val))
+                    RAD_ADD(&S.rad[(unsigned)((iv * S.nyr + jr) * S.rad_row + ir) * (unsigned)S.rad_stride], val);
             } else if (acc <= tkill) {
                 const ViewRec V = views[iv];
                 // event position and height from the stash; pixel = where the line of sight meets zref

@@ -70,6 +70,20 @@ def _check_thermal(nml, fdir):
         raise OSError('Error [mca_exe]: a thermal job needs a Lambertian surface (<Sfc_mtype=1>): non-Lambertian (BRDF) surfaces do not emit here.')
 
 
+def wants_rdir(scene):
+    """does the radiance out.bin of this job carry the direct sun (`rdir`, include/mi3d.h: mi3d_get_camera_direct) as a second
+    variable?  Cameras with the rectangular map or cosine weighting -- the point radiometers; every other file stays as it was"""
+    return getattr(scene, 'rad_kind', 2) == 1 and (getattr(scene, 'cam_mpmap', 1) == 2 or getattr(scene, 'cam_mrproj', 0) == 1) \
+        and bool(scene.target & TARGET_RADIANCE)
+
+
+def direct_in_run_field(scene):
+    """does mi3d_stats_add put the direct sun into this job's radiance run field?  Cameras with the rectangular map -- point
+    radiometers (include/mi3d.h: mi3d_get_camera_direct); the fused route's reader separates it again (mca_out._from_fused)"""
+    return getattr(scene, 'rad_kind', 2) == 1 and getattr(scene, 'cam_mpmap', 1) == 2 and bool(scene.target & TARGET_RADIANCE) \
+        and getattr(scene, 'src_mtype', 1) == 1
+
+
 class JobRunner:
 
     def __init__(self, device=None, column_le=True):
@@ -197,6 +211,8 @@ class JobRunner:
         out = {}
         if self.scene.target & TARGET_RADIANCE:
             out['rad'] = self.sol.radiance(nphoton)
+            if wants_rdir(self.scene):
+                out['rdir'] = self.sol.camera_direct().astype(np.float32)
         if self.scene.target & TARGET_FLUX:
             out['flux'] = self.sol.flux(nphoton)
         if self.scene.target & TARGET_HEAT:
@@ -211,6 +227,8 @@ class JobRunner:
         out = {}
         if scene.target & TARGET_RADIANCE:
             out['rad'] = sol.radiance(int(nphoton))
+            if wants_rdir(scene):
+                out['rdir'] = sol.camera_direct().astype(np.float32)
         if scene.target & TARGET_FLUX:
             out['flux'] = sol.flux(int(nphoton))
         if scene.target & TARGET_HEAT:
@@ -268,6 +286,7 @@ class JobRunner:
                 self.photons_done += cnt
                 metas.append(dict(fname_out=fname_out, nphoton=int(nphoton), slot=slot, scene=sc,
                                   direct=sol.direct_levels() if sc.target & TARGET_FLUX else None,
+                                  rdir=sol.camera_direct() if wants_rdir(sc) else None,
                                   norm=dict(src_flx=sc.src_flx, mu0=sc.mu0, rad_kind=getattr(sc, 'rad_kind', 2), area=sc.nx*sc.dx*sc.ny*sc.dy,
                                             dz=np.diff(sc.zgrd))))
                 i += 1
@@ -311,6 +330,8 @@ class JobRunner:
         if a:
             fac = p['src_flx']*p['mu0']*(p['area'] if p['rad_kind'] == 1 else sc.nxr*sc.nyr)/n
             out['rad'] = (row[:a]*fac).to(torch.float32).reshape(max(sc.nview, 1), sc.nyr, sc.nxr)[:sc.nview]
+            if m.get('rdir') is not None:                              # the direct sun in the cameras: known, taken job by job
+                out['rdir'] = torch.as_tensor(np.asarray(m['rdir'], dtype=np.float32), device=row.device)
         if b:
             raw = row[a:a+b].reshape(3, sc.nz+1, sc.ny, sc.nx).clone()
             raw[1] += raw[0]                                           # raw planes: direct-down, DIFFUSE-down, up
@@ -408,7 +429,10 @@ class JobRunner:
             mca_out_write(fname_out, variables)
         else:
             r = result['rad']                                    # (nview, nyr, nxr) -> (nxr, nyr, nview)
-            mca_out_write(fname_out, [('rad', 'pixel-averaged radiance', np.transpose(r, (2, 1, 0)))])
+            variables = [('rad', 'pixel-averaged radiance', np.transpose(r, (2, 1, 0)))]
+            if 'rdir' in result:                                 # point radiometers: the direct sun, a second variable of the same shape
+                variables.append(('rdir', 'direct solar radiance', np.transpose(result['rdir'], (2, 1, 0))))
+            mca_out_write(fname_out, variables)
 
 
 _RUNNER = None

@@ -12,7 +12,8 @@ import numpy as np
 
 from er3t_amd.util import cal_sol_fac
 
-__all__ = ['mca_out_raw', 'mca_out_ng', 'mca_out_write', 'read_flux_mca_out', 'read_radiance_mca_out', 'read_heating_mca_out']
+__all__ = ['mca_out_raw', 'mca_out_ng', 'mca_out_write', 'read_flux_mca_out', 'read_radiance_mca_out', 'read_heating_mca_out',
+           'read_radiometer_mca_out']
 
 
 def mca_out_write(fname_bin, variables):
@@ -147,7 +148,7 @@ def _accumulate(mca_obj, abs_obj, nvar, squeeze):
     dims_info = list(out0.data[0]['dims_info'])
     dims = list(out0.data[0]['dims'])
     Nz = dims[dims_info.index('Nz')]
-    if nvar == 1 and Nz > 1 and getattr(mca_obj, 'Nview', 1) > 1:
+    if nvar in (1, 2) and Nz > 1 and getattr(mca_obj, 'Nview', 1) > 1:
         # (a radiance file of several views -- mcarats_ng with sequences of sensor angles, not in the reference --: its third axis counts
         #  views, not levels; every view is scaled like the reference's one view)
         factors, toa = g_factors(mca_obj, abs_obj, 1)
@@ -192,7 +193,10 @@ def _from_fused(fused, nvar, squeeze):
 
     """per-run fields gathered on the device by `mcarats_ng(abs_obj=...)`, brought to the file route's shapes"""
 
-    runs = fused['flux']['runs'] if nvar == 3 else fused['rad']['runs'][None]      # (nvar, Nz, Ny, Nx, Nr)
+    if nvar == 2:       # point radiometers: the run field holds diffuse + direct, the direct part is known per run -> (diffuse, direct)
+        runs = np.stack([fused['rad']['runs']-fused['rdir']['runs'], fused['rdir']['runs']])
+    else:
+        runs = fused['flux']['runs'] if nvar == 3 else fused['rad']['runs'][None]      # (nvar, Nz, Ny, Nx, Nr)
     dims_info = ['Nx', 'Ny', 'Nz', 'Nt', 'Nr']
     sums = []
     for iv in range(nvar):
@@ -306,6 +310,37 @@ def read_radiance_mca_out(mca_obj, abs_obj, mode='mean', squeeze=True):
     return data
 
 
+def read_radiometer_mca_out(mca_obj, abs_obj, mode='mean', squeeze=True):
+
+    """
+    sensor_type 'irradiance' | 'actinic' (point radiometers, one pixel over the hemisphere around the sensor's axis): per sensor
+    (the view axis), summed over g, per run ('all') or mean and population standard deviation over runs ('mean').
+    keys: f, f_diffuse, f_direct (+ *_std for 'mean'), toa, N_photon, N_run.  The files hold the cosine-weighted (irradiance) or
+    plain (actinic) mean radiance over the hemisphere: scattered light as `rad`, the direct sun as `rdir`; the fluxes are pi (irradiance)
+    or 2 pi (actinic flux) times them.
+    """
+
+    mode = mode.lower()
+    (rad, rdir), dims_info, toa = _accumulate(mca_obj, abs_obj, 2, squeeze)
+    solid = np.float32(np.pi if str(mca_obj.sensor_type).lower() == 'irradiance' else 2.0*np.pi)
+    f_diffuse, f_direct = rad*solid, rdir*solid
+    fields = [('f', f_diffuse+f_direct, 'Total'), ('f_diffuse', f_diffuse, 'Diffuse'), ('f_direct', f_direct, 'Direct')]
+    what = 'irradiance' if str(mca_obj.sensor_type).lower() == 'irradiance' else 'actinic flux'
+    data = {'toa': {'data': toa, 'name': 'TOA without SZA', 'units': 'W/m^2/nm'}}
+    for key, arr, name in fields:
+        if mode == 'all':
+            data[key] = {'data': arr, 'name': '%s %s' % (name, what), 'units': 'W/m^2/nm', 'dims_info': dims_info}
+        elif mode == 'mean':
+            data[key] = {'data': np.mean(arr, axis=-1), 'name': '%s %s (mean)' % (name, what), 'units': 'W/m^2/nm', 'dims_info': dims_info[:-1]}
+            data[key+'_std'] = {'data': np.std(arr, axis=-1), 'name': '%s %s (standard deviation)' % (name, what), 'units': 'W/m^2/nm',
+                                'dims_info': dims_info[:-1]}
+        else:
+            raise OSError('Error [read_radiometer_mca_out]: Do not support <mode=%s>.' % mode)
+    data['N_photon'] = {'data': mca_obj.photons, 'name': 'Number of photons', 'units': 'N/A'}
+    data['N_run']    = {'data': mca_obj.Nrun, 'name': 'Number of runs', 'units': 'N/A'}
+    return data
+
+
 class mca_out_ng:
 
     """
@@ -350,6 +385,8 @@ class mca_out_ng:
             print('Message [mca_out_ng]: Reading <%s> ...' % self.mca.target.lower())
         if self.mca.target in ['flux', 'flux0']:
             self.data = read_flux_mca_out(self.mca, self.abs, mode=self.mode, squeeze=self.squeeze)
+        elif self.mca.target == 'radiance' and str(getattr(self.mca, 'sensor_type', '')).lower() in ('irradiance', 'actinic'):
+            self.data = read_radiometer_mca_out(self.mca, self.abs, mode=self.mode, squeeze=self.squeeze)
         elif self.mca.target == 'radiance':
             self.data = read_radiance_mca_out(self.mca, self.abs, mode=self.mode, squeeze=self.squeeze)
         elif self.mca.target == 'heating rate':

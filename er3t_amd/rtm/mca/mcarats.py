@@ -38,6 +38,10 @@ _WLD_FIXED = {'Wld_mbswap': 0, 'Wld_njob': 1}
 _FLX_FLAGS = {'flux': (3, 0), 'flux0': (1, 0), 'heating rate': (3, 1)}            # (Flx_mflx, Flx_mhrt)
 _RAD_FIXED = {'Rad_mplen': 0, 'Rad_mpmap': 1, 'Rad_nrad': 1, 'Rad_difr0': 7.5, 'Rad_difr1': 0.0025}
 _RAD_ALLSKY = {'Rad_mrkind': 1, 'Rad_qmax': 178.0, 'Rad_apsize': 0.05}
+# point radiometers: a camera with the rectangular map and one pixel over the hemisphere around its axis (er3t/rtm/mca/mca_inp.py:306-311);
+# Rad_mrproj 1: irradiance, 0: actinic flux
+_RAD_SENSOR = {'Rad_mrkind': 1, 'Rad_mpmap': 2, 'Rad_nxr': 1, 'Rad_nyr': 1, 'Rad_umax': 90.0, 'Rad_vmax': 180.0, 'Rad_apsize': 0.05}
+_SENSOR_MRPROJ = {'irradiance': 1, 'actinic': 0}
 _SRC_FIXED = {'Src_flx': 1.0, 'Src_qmax': 0.533133, 'Src_dwlen': 0.0, 'Src_mtype': 1, 'Src_mphi': 0}
 _VOXEL_ARRAYS = ('Atm_tmpa3d', 'Atm_abst3d', 'Atm_extp3d', 'Atm_omgp3d', 'Atm_apfp3d')   # travel in the side file
 
@@ -119,6 +123,8 @@ class mcarats_ng:
             setattr(self, name, locals()[name])
         self.mp_mode = mp_mode.lower()
         self.Nview = max(int(np.size(sensor_zenith_angle)), int(np.size(sensor_azimuth_angle)))     # (several views: not in the reference, init_wld)
+        if str(sensor_type).lower() in _SENSOR_MRPROJ:
+            self.Nview = max(int(np.size(a)) for a in (sensor_zenith_angle, sensor_azimuth_angle, sensor_altitude, sensor_xpos, sensor_ypos))
         self.abs_obj, self.keep_files, self.fused = abs_obj, keep_files, None
         self.source = str(source).lower()
         if self.source not in ('solar', 'thermal'):
@@ -185,9 +191,15 @@ class mcarats_ng:
             #  er3t/rtm/mca/mca_inp.py:27-33,52-54,193-199; the input files carry the flag as the reference writes it)
             print('Warning [mcarats_ng]: <tune=True> (Wld_moptim=2) is written to the input files, but the GPU solver runs its unbiased estimator (Wld_moptim=0) whatever the flag says.')
 
+        if sensor_type.lower() in _SENSOR_MRPROJ and self.target != 'radiance':
+            raise OSError('Error [mcarats_ng]: <sensor_type=%r> is a radiance job: use <target=\'radiance\'>.' % sensor_type)
         if self.target != 'radiance':
             mflx, mhrt = _FLX_FLAGS[self.target]
             self._all({'Wld_mtarget': 1, 'Flx_mflx': mflx, 'Flx_mhrt': mhrt})
+            return
+
+        if sensor_type.lower() in _SENSOR_MRPROJ:
+            self._init_radiometers(sensor_type.lower(), sensor_zenith_angle, sensor_azimuth_angle, sensor_altitude, sensor_xpos, sensor_ypos)
             return
 
         # Not in the reference: SEVERAL views in one simulation (sequences of sensor zenith / azimuth angles, a scalar stands for every
@@ -209,6 +221,31 @@ class mcarats_ng:
             rad['Rad_mrkind'] = 2
         elif 'all-sky' in sensor_type.lower():
             rad.update(_RAD_ALLSKY, Rad_xpos=sensor_xpos, Rad_ypos=sensor_ypos)
+        self._all(rad)
+
+    def _init_radiometers(self, kind, zenith, azimuth, altitude, xpos, ypos):
+
+        """
+        sensor_type 'irradiance' | 'actinic': point radiometers, up to 16 (MI3D_MAX_VIEW) in one simulation -- a scalar stands for every
+        sensor, sequences give one value each.  Sensor i stands at (xpos Lx, ypos Ly, altitude); its axis has the zenith angle
+        sensor_zenith_angle (0: looking up, 180: looking down) and is tilted towards the compass azimuth sensor_azimuth_angle (0 north,
+        90 east).  Written as cameras with the rectangular map and one pixel spanning the hemisphere around the axis.
+        """
+
+        arrs = [np.atleast_1d(np.asarray(a, dtype=np.float64)) for a in (zenith, azimuth, altitude, xpos, ypos)]
+        n = max(a.size for a in arrs)
+        if n > 16 or any(a.size not in (1, n) for a in arrs):
+            raise OSError('Error [mcarats_ng]: <sensor_type=%r>: up to 16 sensors, every sensor_* sequence of the same length (or a scalar).' % kind)
+        if np.any(arrs[0] < 0.0) or np.any(arrs[0] > 180.0):
+            raise OSError('Error [mcarats_ng]: <sensor_zenith_angle> of a radiometer is its axis, 0 (looking up) to 180 (looking down).')
+        zen, azi, alt, xp, yp = [np.resize(a, n) for a in arrs]
+        self.Nview = n
+        phi = np.mod(90.0-azi, 360.0)          # compass azimuth of the axis -> counter-clockwise from east
+        rad = dict(_RAD_FIXED, Wld_mtarget=2, Rad_nrad=n, Rad_the=zen, Rad_phi=phi, Rad_zloc=alt, Rad_xpos=xp, Rad_ypos=yp,
+                   Rad_mrproj=_SENSOR_MRPROJ[kind])
+        rad.update(_RAD_SENSOR)
+        if n == 1:
+            rad.update({k: float(rad[k][0]) for k in ('Rad_the', 'Rad_phi', 'Rad_zloc', 'Rad_xpos', 'Rad_ypos')})
         self._all(rad)
 
     def init_sca(self, sca=None):
@@ -308,7 +345,7 @@ class mcarats_ng:
         with arrays in the solver's layout, rad (nview, ny, nx), flux (3: direct-down, total-down, up; nz+1; ny; nx).
         """
 
-        from er3t_amd.rtm.mca.mca_exe import get_runner
+        from er3t_amd.rtm.mca.mca_exe import get_runner, wants_rdir, direct_in_run_field
         from er3t_amd.rtm.mca.mca_inp import mca_inp_read
         from er3t_amd.rtm.mca.mca_out import g_factors
 
@@ -318,7 +355,7 @@ class mcarats_ng:
         solver = _SOLVER_IDS[self.solver]
         ms0, n0 = runner.kernel_ms, runner.photons_done
         photons = self.photons.reshape((self.Nrun, self.Ng))
-        factors, runs = None, []
+        factors, runs, rdir_runs = None, [], None
         # Two solver handles take turns (unless the per-job files are wanted: they are read back job by job): job i+1 is
         # launched before job i is folded into the run, so the tail of a launch -- as long as its longest history -- runs
         # beside the next launch.  The run field is still summed in job order (JobRunner.stats_add).
@@ -336,9 +373,16 @@ class mcarats_ng:
                     else:
                         factors, toa = g_factors(self, self.abs_obj, scene.nz+1)
                     runner.stats_begin()
+                if direct_in_run_field(scene):
+                    # the direct sun is known, the same on every rank: its g-sum per run, as the file route sums it, for mca_out_ng
+                    # (the run field itself holds diffuse + direct: mi3d_stats_add adds the direct part on rank 0)
+                    rdir = runner.sols[slot].camera_direct().astype(np.float32)
+                    rdir_run = (rdir_run if ig > 0 else np.zeros_like(rdir)) + rdir*factors[:, ig][:, None, None]
                 runner.launch(photons[ir, ig], int(nml['Wld_jseed']), slot=slot)
                 if self.keep_files:
                     result = {'rad': runner.sol.radiance(photons[ir, ig])} if self.target == 'radiance' else {'flux': runner.sol.flux(photons[ir, ig])}
+                    if wants_rdir(scene):
+                        result['rdir'] = runner.sol.camera_direct().astype(np.float32)
                     runner.write(self.fnames_out[ir][ig], result)
                 # (a job is folded into the run before its slot is launched on again: with one slot at once, with two after the
                 #  next job's launch)
@@ -351,9 +395,13 @@ class mcarats_ng:
             if waiting is not None:
                 runner.stats_add(*waiting)
             runs.append(runner.stats_end_run(keep=True))
+            if rdir_runs is not None or direct_in_run_field(scene):
+                rdir_runs = (rdir_runs or []) + [rdir_run]
         self.fused = runner.stats_result()
         for key in self.fused:
             self.fused[key]['runs'] = np.stack([r[key] for r in runs], axis=-1)
+        if rdir_runs is not None:
+            self.fused['rdir'] = {'runs': np.stack(rdir_runs, axis=-1)}
         self.fused['toa'] = toa
         self.kernel_ms = runner.kernel_ms - ms0
         self.photons_done = runner.photons_done - n0
@@ -371,7 +419,11 @@ class mcarats_ng:
                 ('Date (DOY)', '%s (%d)' % (self.date.strftime('%Y-%m-%d'), self.date.timetuple().tm_yday)),
                 ('Solar Zenith Angle', '%.4f° (0 at local zenith)' % self.solar_zenith_angle),
                 ('Solar Azimuth Angle', '%.4f° (0 at north; 90° at east)' % self.solar_azimuth_angle)]
-        if self.target == 'radiance':
+        if self.target == 'radiance' and str(self.sensor_type).lower() in _SENSOR_MRPROJ:
+            rows += [('Sensor Type', '%s radiometer x %d (zenith angle of the axis: 0 looking up)' % (self.sensor_type, self.Nview)),
+                     ('Sensor Zenith Angles', ', '.join('%.1f°' % a for a in np.atleast_1d(self.sensor_zenith_angle))),
+                     ('Sensor Altitudes', ', '.join('%.3f km' % (a/1000.0) for a in np.atleast_1d(self.sensor_altitude)))]
+        elif self.target == 'radiance':
             if getattr(self, 'Nview', 1) > 1:
                 rows += [('Sensor Zenith Angles', ', '.join('%.1f°' % a for a in np.atleast_1d(self.sensor_zenith_angle)) + ' (%d views, one set of photons)' % self.Nview),
                          ('Sensor Azimuth Angles', ', '.join('%.1f°' % a for a in np.atleast_1d(self.sensor_azimuth_angle))),

@@ -99,6 +99,11 @@ class Scene:
     cam_umax : list = field(default_factory=list)
     cam_vmax : list = field(default_factory=list)
     cam_apsize: list = field(default_factory=list)
+    # cameras' pixel map and weighting (Rad_mpmap, Rad_mrproj; include/mi3d.h: mi3d_set_camera_map): 1 polar / 2 rectangular
+    # (U = theta in [0, umax], V = phi in [-vmax, vmax]); 0 mean radiance / 1 cosine-weighted.  One pixel over the hemisphere with
+    # the rectangular map is a point irradiance (mrproj 1) or actinic-flux (mrproj 0) sensor (er3t/rtm/mca/mca_inp.py:306-311)
+    cam_mpmap : int = 1
+    cam_mrproj: int = 0
     cam_images: int = -1                  # (-1: 2 where the ray kernel serves the job -- the default route --, else the nearest image alone, with a warning) the domain is cyclic: an event contributes to the periodic images of a camera within this many
                                           # domain lengths of the nearest one, the farther ones by Russian roulette on (r0 / r)^2 (unbiased).  er3t's
                                           # camera looks 89 degrees off its axis (mcarats.py:291-296); on the 12.8 km bench grid the nearest image
@@ -161,6 +166,9 @@ class Scene:
                                   ('cam_vmax', 180.0), ('cam_apsize', 0.0)):
                 v = list(np.resize(np.asarray(getattr(self, name) if len(getattr(self, name)) else [default], dtype=np.float64), n))
                 setattr(self, name, v)
+            if self.cam_mpmap not in (1, 2) or self.cam_mrproj not in (0, 1):
+                raise ValueError('Error [Scene]: <cam_mpmap=%s> (Rad_mpmap) must be 1 or 2 and <cam_mrproj=%s> (Rad_mrproj) 0 or 1.'
+                                 % (self.cam_mpmap, self.cam_mrproj))
         elif self.rad_kind != 2:
             raise ValueError('Error [Scene]: <rad_kind=%s> (Rad_mrkind) must be 1 or 2.' % self.rad_kind)
         if self.src_mtype == 3:
@@ -317,13 +325,16 @@ class Scene:
                       zref=float(get('Rad_zref', 0.0)), nxr=int(get('Rad_nxr', 1)), nyr=int(get('Rad_nyr', 1)))
             mrkind = int(get('Rad_mrkind', 2))
             if mrkind == 1:
-                if int(get('Rad_mpmap', 1)) != 1:
-                    raise OSError('Error [Scene]: only the polar pixel map (<Rad_mpmap=1>) is supported for <Rad_mrkind=1>.')
+                mpmap, mrproj = int(get('Rad_mpmap', 1)), int(get('Rad_mrproj', 0))
+                if mpmap not in (1, 2):
+                    raise OSError('Error [Scene]: <Rad_mpmap=%d> is not supported for <Rad_mrkind=1> (1: polar, 2: rectangular).' % mpmap)
+                if mrproj not in (0, 1):
+                    raise OSError('Error [Scene]: <Rad_mrproj=%d> is not supported (0: mean radiance, 1: cosine-weighted).' % mrproj)
                 def per_view(key, default):
                     return list(np.resize(np.asarray(get(key, default), dtype=np.float64), nrad))
                 kw.update(rad_kind=1, cam_xpos=per_view('Rad_xpos', 0.5), cam_ypos=per_view('Rad_ypos', 0.5),
                           cam_psi=per_view('Rad_psi', 0.0), cam_qmax=per_view('Rad_qmax', 180.0), cam_umax=per_view('Rad_umax', 180.0),
-                          cam_vmax=per_view('Rad_vmax', 180.0), cam_apsize=per_view('Rad_apsize', 0.0))
+                          cam_vmax=per_view('Rad_vmax', 180.0), cam_apsize=per_view('Rad_apsize', 0.0), cam_mpmap=mpmap, cam_mrproj=mrproj)
             elif mrkind != 2:
                 raise OSError('Error [Scene]: <Rad_mrkind=%d> is not supported (1: camera, 2: satellite).' % mrkind)
         elif mtarget == 1:

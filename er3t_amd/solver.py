@@ -44,6 +44,7 @@ _SIGNATURES = [
     ('mi3d_set_thermal'        , C.c_int   , [C.c_void_p, C.c_int, C.c_double, C.c_int, _fp, _fp, _fp]),
     ('mi3d_set_views'          , C.c_int   , [C.c_void_p, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int, C.c_int]),
     ('mi3d_set_cameras'        , C.c_int   , [C.c_void_p, C.c_int] + [_dp]*10 + [C.c_int, C.c_int]),
+    ('mi3d_set_camera_map'     , C.c_int   , [C.c_void_p, C.c_int, C.c_int]),
     ('mi3d_set_options'        , C.c_int   , [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int]),
     ('mi3d_set_le_roulette'    , C.c_int   , [C.c_void_p, C.c_double]),
     ('mi3d_set_le_weight_roulette', C.c_int, [C.c_void_p, C.c_double]),
@@ -61,6 +62,7 @@ _SIGNATURES = [
     ('mi3d_get_radiance'       , C.c_int   , [C.c_void_p, _u64, _fp]),
     ('mi3d_get_flux'           , C.c_int   , [C.c_void_p, _u64, _fp]),
     ('mi3d_get_direct_levels'  , C.c_int   , [C.c_void_p, _dp]),
+    ('mi3d_get_camera_direct'  , C.c_int   , [C.c_void_p, _dp]),
     ('mi3d_get_heating'        , C.c_int   , [C.c_void_p, _u64, _fp]),
     ('mi3d_get_counters'       , C.c_int   , [C.c_void_p, C.POINTER(_u64)]),
     ('mi3d_stats_begin'        , C.c_int   , [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -242,6 +244,10 @@ class Mi3dSolver:
             raise ValueError('Error [Mi3dSolver]: camera arrays differ in length.')
         self._chk(self.lib.mi3d_set_cameras(self._h, n, *[_ptr(a, _dp) for a in arrs], int(nxr), int(nyr)))
 
+    def set_camera_map(self, mpmap=1, mrproj=0):
+        """cameras' pixel map (Rad_mpmap: 1 polar, 2 rectangular) and weighting (Rad_mrproj: 0 mean radiance, 1 cosine-weighted)"""
+        self._chk(self.lib.mi3d_set_camera_map(self._h, int(mpmap), int(mrproj)))
+
     def set_options(self, target=TARGET_FLUX, solver=0, wmin=0.2, wfac=1.0, column_le=True):
         self._chk(self.lib.mi3d_set_options(self._h, int(target), int(solver), float(wmin), float(wfac), 1 if column_le else 0))
 
@@ -271,6 +277,7 @@ class Mi3dSolver:
         if getattr(s, 'rad_kind', 2) == 1 and s.nview > 0:
             self.set_cameras(s.view_the, s.view_phi, s.cam_psi, s.cam_xpos, s.cam_ypos, s.view_zloc, s.cam_qmax, s.cam_umax, s.cam_vmax,
                              s.cam_apsize, s.nxr, s.nyr)
+            self.set_camera_map(getattr(s, 'cam_mpmap', 1), getattr(s, 'cam_mrproj', 0))
             self.set_tuning(cam_images=int(getattr(s, 'cam_images', -1)))
         else:
             self.set_views(s.view_the, s.view_phi, s.view_zloc, zref=s.zref, nxr=s.nxr, nyr=s.nyr)
@@ -340,6 +347,14 @@ class Mi3dSolver:
         """(nz+1,) the known part of the direct beam that mi3d_get_flux adds to the tallies, for the job that ran last"""
         out = np.zeros(self.scene.nz+1, dtype=np.float64)
         self._chk(self.lib.mi3d_get_direct_levels(self._h, _ptr(out, _dp)))
+        return out
+
+    def camera_direct(self):
+        """(nview, nyr, nxr) float64: the direct sun in the cameras (include/mi3d.h: mi3d_get_camera_direct), units of radiance();
+        known, not tallied, and not part of radiance()"""
+        out = np.zeros(self._shape_rad, dtype=np.float64)
+        if out.size:
+            self._chk(self.lib.mi3d_get_camera_direct(self._h, _ptr(out, _dp)))
         return out
 
     def heating(self, nphoton_total):

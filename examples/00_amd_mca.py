@@ -4,7 +4,7 @@ clear sky, flux and radiance of a 3-D cloud field), with the synthetic atmospher
 er3t_amd.synth standing in for er3t.pre.* (whose data bases are not part of this repository; er3t's own objects can be
 passed instead, attribute for attribute).
 
-    python examples/00_amd_mca.py [clear_sky_flux | cloud_flux | cloud_radiance | cloud_radiance_fused | cloud_radiance_multi_angle | cloud_heating_rate] [fdir]
+    python examples/00_amd_mca.py [clear_sky_flux | cloud_flux | cloud_radiance | cloud_radiance_fused | cloud_radiance_multi_angle | cloud_heating_rate | cloud_irradiance_sensors] [fdir]
 """
 
 import datetime
@@ -115,10 +115,27 @@ def cloud_heating_rate(fdir):
     return out
 
 
+def cloud_irradiance_sensors(fdir):
+    """3-D cloud field: a row of sixteen up-looking irradiance sensors 10 m above the ground (point radiometers: sensor_type
+    'irradiance', one simulation for all of them); global, diffuse and direct irradiance per sensor"""
+    ab, atm1d, atm3d = _cloud(fdir)
+    n = 16
+    sim = mca.mcarats_ng(atm_1ds=[atm1d], atm_3ds=[atm3d], Ng=ab.Ng, weights=ab.coef['weight']['data'], target='radiance', surface_albedo=0.03,
+                         solar_zenith_angle=30.0, solar_azimuth_angle=45.0, sensor_type='irradiance', sensor_zenith_angle=0.0,
+                         sensor_altitude=10.0, sensor_xpos=list((np.arange(n)+0.5)/n), sensor_ypos=0.5, fdir=os.path.join(fdir, 'irr'),
+                         Nrun=3, photons=1e7, solver='3D', date=DATE)
+    out = mca.mca_out_ng(mca_obj=sim, abs_obj=ab, mode='mean', squeeze=True)
+    f, fdif, fdir_ = out.data['f']['data'], out.data['f_diffuse']['data'], out.data['f_direct']['data']
+    for i in range(n):
+        print('sensor %2d at x = %.3f Lx: global %.4f = diffuse %.4f + direct %.4f W/m^2/nm (std over runs %.4f)'
+              % (i, (i+0.5)/n, f[i], fdif[i], fdir_[i], out.data['f_std']['data'][i]))
+    return out
+
+
 if __name__ == '__main__':
     what = sys.argv[1] if len(sys.argv) > 1 else 'clear_sky_flux'
     fdir = sys.argv[2] if len(sys.argv) > 2 else os.path.join('tmp-data', '00_amd_mca', what)
     os.makedirs(fdir, exist_ok=True)
     {'clear_sky_flux': clear_sky_flux, 'cloud_flux': cloud_flux, 'cloud_radiance': cloud_radiance,
      'cloud_radiance_fused': lambda d: cloud_radiance(d, fused=True), 'cloud_radiance_multi_angle': cloud_radiance_multi_angle,
-     'cloud_heating_rate': cloud_heating_rate}[what](fdir)
+     'cloud_heating_rate': cloud_heating_rate, 'cloud_irradiance_sensors': cloud_irradiance_sensors}[what](fdir)

@@ -199,6 +199,19 @@ int mi3d_set_views(mi3d_solver *h, int nview, const double *the_deg, const doubl
 int mi3d_set_cameras(mi3d_solver *h, int ncam, const double *the_deg, const double *phi_deg, const double *psi_deg,
                      const double *xpos, const double *ypos, const double *zloc, const double *qmax_deg,
                      const double *umax_deg, const double *vmax_deg, const double *apsize, int nxr, int nyr);
+/* Pixel map and weighting of the cameras = keys Rad_mpmap, Rad_mrproj (er3t/rtm/mca/mca_inp.py:306-311: a camera with the
+ * rectangular map, one pixel, Rad_umax = 90 is an irradiance (mrproj = 1) or actinic-flux (mrproj = 0) sensor).  Default (1, 0): the
+ * polar map above, the mean radiance over the pixel -- what mi3d_set_cameras alone gives.
+ *   mpmap 2  rectangular map: U = theta in [0, umax] over nxr columns, V = phi in [-vmax, vmax] over nyr rows, theta measured from the
+ *            camera's axis and phi about it from the image x axis.  MCARaTS' own convention for this map is not in the reference
+ *            tree; this reading (a key value of THIS project's choosing, like Src_wlen) makes the documented sensor, Rad_umax = 90 with
+ *            the default Rad_vmax = 180, a full hemisphere.  Needs umax, vmax <= 180 (MI3D_EINVAL from the next run otherwise).
+ *            Pixel value = (sum of w L dOmega over the pixel) / W, W its exact weighted solid angle: (cos t_i - cos t_i+1) dphi
+ *            (mrproj 0, w = 1) or (sin^2 t_i+1 - sin^2 t_i) dphi / 2 (mrproj 1, w = cos theta; needs umax <= 90).
+ *   mrproj 1 on the polar map: the same weight; its per-direction solid angle times cos theta is the denominator, so the weight
+ *            cancels direction by direction and the image equals that of mrproj 0.
+ * mi3d_get_radiance holds the scattered light only, for every map: the direct sun is mi3d_get_camera_direct. */
+int mi3d_set_camera_map(mi3d_solver *h, int mpmap, int mrproj);
 
 /* Job options = 1st/2nd CLI arguments and keys Wld_mtarget, Flx_mflx, Pho_wmin
  * (er3t/rtm/mca/mcarats.py:267-287,450-454; er3t/rtm/mca/mca_inp.py:196-198).
@@ -342,6 +355,18 @@ int mi3d_get_flux(mi3d_solver *h, uint64_t nphoton_total, float *out);
  * mi3d_get_flux adds it by itself; a caller that normalises all-reduced RAW tallies of several jobs at once (one exchange per
  * batch of jobs instead of one per job) takes it from here, job by job. */
 int mi3d_get_direct_levels(mi3d_solver *h, double *out);
+/* The direct sun in the cameras (mi3d_set_cameras, solar source): out[nview][nyr][nxr] in the units of mi3d_get_radiance, known
+ * rather than tallied and so free of noise, for the scene and source set now (worked out once per job by mi3d_prepare, k_cam_direct).
+ * The optical depth tau from the camera to the top of the atmosphere is integrated in float64 along the sun's CENTRAL direction
+ * through the voxels (cyclic in x and y) and the 1-D layers; Src_qmax is ignored for this term.  Where that direction lies in a
+ * camera's cone of view and image, its pixel holds Src_flx exp(-tau) w(theta_sun) / W (mi3d_set_camera_map), every other pixel 0
+ * (also where tau > 100: the march stops there).  mi3d_get_radiance never includes it.  mi3d_stats_add adds it to the radiance run
+ * field (times the analytic share) for cameras with the RECTANGULAR map only -- point radiometers, whose reader separates it again;
+ * the run field of a polar camera stays diffuse only, like its mi3d_get_radiance.  A caller that normalises all-reduced RAW tallies
+ * takes it from here, job by job, as mi3d_get_direct_levels.  One thread marches each camera: a sun so close to the horizon that the
+ * march could cross more than 2^20 voxels is not marched, and this call (and mi3d_stats_add of a rectangular-map job) fails with
+ * MI3D_EUNSUP; other jobs are not affected. */
+int mi3d_get_camera_direct(mi3d_solver *h, double *out);
 /*   heating  out[nz][ny][nx]        absorbed radiant power per unit volume of every cell, per unit Src_flx [1/m x the unit of
  *                                    Src_flx]: (weight absorbed in the cell) x Src_flx mu0 nx ny / N / layer thickness.  The
  *                                    fourth variable ("hrt", nz layers) of the flux out.bin of a job with Flx_mhrt = 1; divided by
