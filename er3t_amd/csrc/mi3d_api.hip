@@ -25,6 +25,7 @@ using namespace mi3d;
 #include <algorithm>
 
 static constexpr size_t kTabLdsBudget = 24 * 1024; // LDS bytes a workgroup may spend on phase tables
+constexpr int kEvSlots = 4;   // launches whose fill counters may be on their way to the host at once
 
 namespace {
 
@@ -157,17 +158,21 @@ struct mi3d_solver {
     size_t heat_elems() const { return (size_t)nz * nx * ny; }
     double *heat_ptr() { return heat_ext ? heat_ext : d_heat_own.p; }
     DevBuf<unsigned long long> d_counters, d_next;
-    // photon order of a launch (k_bin_*): indices sorted by start tile, the tile of every index, histogram and cursors
-    DevBuf<uint32_t> d_order, d_hist, d_cursor;
+    // photon order of a launch (k_bin_*): indices sorted by start tile, the tile of every index (shared by both pre-pass sets), histogram
+    DevBuf<uint32_t> d_hist;
     DevBuf<uint16_t> d_tile;
-    DevBuf<float4> d_entry;          // entry records of the launch in flight (k_entry -> k_transport_lean), 48 bytes per photon
-    // a second set of what the pre-pass kernels of a launch write (photon order, tiles' ends, entry records): the pre-pass of launch i + 1
-    // runs on a stream of its own beside the photon loop of launch i (28 registers against the loop's 80 x 6: one more wave per SIMD fits)
-    DevBuf<uint32_t> d_order2, d_cursor2;
-    DevBuf<float4> d_entry2;
+    // What the pre-pass kernels of a launch write: photon order, tiles' ends (the cursors, which are also the tally window's tile_end) and
+    // entry records (k_entry -> k_transport_lean, 48 bytes per photon).  Set 1: the pre-pass of launch i + 1 runs on a stream of its own
+    // beside the photon loop of launch i (28 registers against the loop's 80 x 6: one more wave per SIMD fits).  release(): the large
+    // buffers (set 0's cursor is allocated by mi3d_create)
+    struct PreSet {
+        DevBuf<uint32_t> order, cursor;
+        DevBuf<float4> entry;
+        hipEvent_t done = nullptr, loop = nullptr; bool used = false;   // pre-pass written / photon loop through with the set
+        void release() { order.release(); entry.release(); }
+    };
+    PreSet pre[2];
     hipStream_t pre_stream = nullptr;
-    hipEvent_t pre_done[2] = {nullptr, nullptr}, pre_loop[2] = {nullptr, nullptr};   // pre-pass written / photon loop through with the set
-    bool pre_used[2] = {false, false};
     hipEvent_t pre_main = nullptr;   // the last pre-pass that ran on the MAIN stream (a one-stream launch): the pre-pass stream waits for it (shared d_hist / d_tile)
     bool pre_main_used = false;
     uint64_t pre_no = 0;             // launches so far: launch n uses set n & 1
@@ -178,17 +183,18 @@ struct mi3d_solver {
     bool cam_warned = false;         // the warning of that fall-back has been printed for this handle
     bool general_warned = false;     // ... and the one that says a job has landed on the general photon loop without having asked for it
     int entry_records = 1;           // mi3d_set_tuning "entry_records": 0: new photons are launched inside the photon loop
-    // marched views served by k_rays: event lists (one per XCD) and their counters; events per photon seen so far
-    DevBuf<float4> d_events;
-    DevBuf<unsigned long long> d_evctr, d_hvlist;
-    // a second set of lists (round 5): the ray kernel of launch i works through set i & 1 on a stream of its own while the photon loop of
-    // launch i + 1 fills the other set -- the tail of either kernel (a tenth of a launch) no longer leaves the chip half empty
-    DevBuf<float4> d_events2;
-    DevBuf<unsigned long long> d_evctr2, d_hvlist2;
-    DevCold cold_host2;              // the second set's DevCold (d_cold.p + 1): cold_host with the other lists
+    // marched views served by k_rays: event lists (one per XCD), their counters and the list of reflections off LSRT / DSM surfaces.  Set 1
+    // (round 5): the ray kernel of launch i works through set i & 1 on a stream of its own while the photon loop of launch i + 1 fills the
+    // other set -- the tail of either kernel (a tenth of a launch) no longer leaves the chip half empty.  release(): the lists
+    struct EvSet {
+        DevBuf<float4> events;
+        DevBuf<unsigned long long> evctr, hvlist;
+        hipEvent_t emit = nullptr, rays = nullptr; bool used = false;   // photon loop / ray kernels of the launch that used the set last
+        void release() { events.release(); hvlist.release(); }
+    };
+    EvSet ev[2];
+    DevCold cold_host2;              // the DevCold at d_cold.p + 1: cold_host with set 1's event lists OR set 1's pre-pass buffers (one spare: never both)
     hipStream_t rays_stream = nullptr;
-    hipEvent_t set_emit[2] = {nullptr, nullptr}, set_rays[2] = {nullptr, nullptr};   // photon loop / ray kernels of the launch that used the set last
-    bool set_used[2] = {false, false};
     int overlap_rays = 0;            // mi3d_set_tuning "overlap_rays" (MI3D_OVERLAP_RAYS): 0 (default): one stream, one set; 1: measured 2.4 % SLOWER on the nine-view
                                      // workload (profiles/r05/ab_overlap_rays.log): both kernels wait on memory, side by side they wait more
     int rays_wg = 0, emit_wg = 0;    // mi3d_set_tuning "rays_wg" / "emit_wg": workgroups per CU of the ray kernel's light build / of the event-writing
@@ -196,37 +202,35 @@ struct mi3d_solver {
     double ev_per_photon = 0.0;      // 0: nothing known, the next run with marched views starts with a pilot launch
     int n_xcd = 8;                   // XCDs workgroups of this device land on (k_xcc_census): that many event lists fill
     unsigned long long *h_evctr = nullptr;   // pinned: [kEvSlots][9 * kCtrStride] fill counters of the last launches, copied out in stream order
-    hipEvent_t ev_done[4] = {nullptr, nullptr, nullptr, nullptr};
-    uint64_t ev_nb[4] = {0, 0, 0, 0};
-    bool ev_busy[4] = {false, false, false, false};
-    uint64_t ev_capn[4] = {0, 0, 0, 0};   // capacity of the lists the launch of each slot wrote to
-    unsigned ev_epoch = 0, ev_epochn[4] = {0, 0, 0, 0};   // what ev_per_photon is an estimate FOR changes with the scene: a launch of an earlier epoch says nothing about it (ev_forget)
-    bool ev_void[4] = {false, false, false, false};   // the launch's tallies have been cleared since (mi3d_reset): a full list no longer matters
+    // a launch whose fill counters are on their way to the host (ev_note): its photons, the capacity of the lists it wrote to, ev_epoch at
+    // its launch; cleared: its tallies have been cleared since (mi3d_reset), a full list no longer matters
+    struct EvSlot { hipEvent_t done = nullptr; uint64_t nb = 0, cap = 0; unsigned epoch = 0; bool busy = false, cleared = false; };
+    EvSlot ev_slot[kEvSlots];
+    unsigned ev_epoch = 0;           // what ev_per_photon is an estimate FOR changes with the scene: a launch of an earlier epoch says nothing about it (ev_forget)
     int ev_cap_log2 = 28;            // records per XCD list at most, log2 (and never more than a quarter of the free memory in all: 1.5e8 per list on an otherwise empty
                                      // MI355X): 2^26 / 2^27 / 2^28 -> 3.53 / 3.73 / 3.76e8 photons/s with nine views (launch tails; profiles/r05/ab_evcap.log)
-    // flux jobs served by k_transport_flux: tally records, sorted into bins and summed after every launch (mi3d_kernel_flux.hip)
-    DevBuf<uint2> d_tl_rec, d_tl_binned;
-    DevBuf<uint32_t> d_tl_words;     // chunk fills, histogram, bin starts, placement cursors
-    DevBuf<unsigned long long> d_tl_cursor;
-    DevBuf<unsigned long long> d_tl_stats;   // [64][4] the counters of each launch in flight, copied there by its k_tl_prefix (tl_note reads them; slots as d_tldesc)
-    // a second set of record lists: the sort and the sums of launch i run on a stream of their own (memory-bound, a few waves per CU) while
-    // the photon loop of launch i + 1 (issue-bound) fills the other set; the sorted copy (d_tl_binned) is the sort stream's alone
-    DevBuf<uint2> d_tl_rec2;
-    DevBuf<uint2> d_tl_binned2;             // the second set's sorted copy (round 6: the sums of a launch wait on the main stream for the next launch of their set)
+    // Flux jobs served by k_transport_flux: tally records, sorted into bins and summed after every launch (mi3d_kernel_flux.hip).  Set 1: the
+    // sort and the sums of launch i run on a stream of their own (memory-bound, a few waves per CU) while the photon loop of launch i + 1
+    // (issue-bound) fills the other set.
     // The sums of a launch on two streams (k_tl_sum: 128 KB of LDS, no room on a CU the photon loop holds) are not queued behind its sort: on the
     // sort stream they crept along in the loop's tails and kept the NEXT launch's sort waiting for as long as the loop beside them ran.  They
     // are launched on the MAIN stream, between two photon loops: in front of the next launch of their set, or by whoever joins (tl_join).
     struct PendingSum { bool on = false; TallyList TL; double *flux = nullptr; unsigned nflux = 0; double *heat = nullptr; unsigned nheat = 0; int split = 1; };
-    PendingSum tl_pend[2];
-    DevBuf<float4> d_tl_runs, d_tl_runs2;   // run records (round 6: one 32-byte record per flight through uniform layers, expanded by k_tl_runs), one buffer per set
-    DevBuf<uint32_t> d_tl_words2;
-    DevBuf<unsigned long long> d_tl_cursor2;
+    struct TlSet {
+        DevBuf<uint2> rec, binned;   // the records the loop writes, their sorted copy
+        DevBuf<uint32_t> words;      // chunk fills, histogram, bin starts, placement cursors
+        DevBuf<unsigned long long> cursor;
+        DevBuf<float4> runs;         // run records (round 6: one 32-byte record per flight through uniform layers, expanded by k_tl_runs)
+        // photon loop / sums of the launch that used the set last; its sort is through the lists (its sums may still run)
+        hipEvent_t filled = nullptr, sorted = nullptr, scattered = nullptr; bool used = false;
+        PendingSum pend;             // that launch's sums, where they are still to come
+        void release() { rec.release(); binned.release(); words.release(); runs.release(); }
+    };
+    TlSet tl[2];
+    DevBuf<unsigned long long> d_tl_stats;   // [64][4] the counters of each launch in flight, copied there by its k_tl_prefix (tl_note reads them; slots as d_tldesc)
     hipStream_t tl_stream = nullptr;
-    hipEvent_t tl_filled[2] = {nullptr, nullptr}, tl_sorted[2] = {nullptr, nullptr};   // photon loop / sums of the launch that used the set last
-    bool tl_set_used[2] = {false, false};
     unsigned runs_unread = 0;        // runs since a call last looked at the tallies (sync_main): > 0 -- runs are queued back to back
     bool tl_unjoined = false;        // the main stream has not been made to wait for the last sorts yet (tl_join)
-    hipEvent_t tl_scattered[2] = {nullptr, nullptr};   // the sort of the launch that used the set last is through its lists (its sums may still run)
     uint64_t tl_launch_no = 0;       // launches with record lists so far: launch n uses set n & 1
     int overlap_sort = 1;            // mi3d_set_tuning "overlap_sort" (MI3D_OVERLAP_SORT): 1 two sets, the sort beside the next photon loop, where a run is long enough or
                                      // queued behind another (mi3d_run); 2: always; 0 one stream
@@ -242,9 +246,9 @@ struct mi3d_solver {
     char *h_tldesc = nullptr;        // pinned source of those copies
     hipEvent_t tldesc_ev[64] = {};   // the photon loop that read slot i is through: the host waits for it before it fills the slot again (it may be dozens of small launches ahead)
     bool tldesc_used[64] = {};
-    hipEvent_t tl_done[4] = {nullptr, nullptr, nullptr, nullptr};
-    uint64_t tl_nb[4] = {0, 0, 0, 0}, tl_cap[4] = {0, 0, 0, 0}, tl_bcap[4] = {0, 0, 0, 0}, tl_rcap[4] = {0, 0, 0, 0};
-    bool tl_busy[4] = {false, false, false, false};
+    // a launch whose record counters are on their way to the host (tl_note): its photons, the capacities of the three lists it wrote to
+    struct TlSlot { hipEvent_t done = nullptr; uint64_t nb = 0, cap = 0, bcap = 0, rcap = 0; bool busy = false; };
+    TlSlot tl_slot[kEvSlots];
     int kernel_choice = 0;           // 0: the lean kernels where they apply (marched views through k_rays), 1: always k_transport
                                      // (MI3D_KERNEL=generic); A/B and tests
     int tile_cols = -1;              // tile edge in columns: -1 choose from the scene, 0 no sorting (MI3D_TILE_COLS overrides)
@@ -377,7 +381,7 @@ int build_tables(mi3d_solver *h) {
     // bucket indices for the lean kernels' look-ups (lean_tab_find): per bucket edge the largest node whose (float) value does not exceed it
     if (n > 65535) return fail(MI3D_EINVAL, "phase tables of more than 65 535 angles");
     // (entry b: the last node whose bucket -- tab_bucket_mu / tab_bucket_u of its float value, the kernels' own arithmetic -- is below b)
-    auto build_idx = [&](const float *a, bool is_mu, uint16_t *out) {
+    auto build_idx = [n](const float *a, bool is_mu, uint16_t *out) {
         int i = -1;
         for (int b = 0; b <= kTabNB; ++b) {
             while (i + 1 < n && (is_mu ? tab_bucket_mu(a[i + 1]) : tab_bucket_u(a[i + 1])) < b) ++i;
@@ -477,6 +481,13 @@ int build_views(mi3d_solver *h) {
     return h->d_views.upload(v.data(), v.size());
 }
 
+// er3t's default 1-D part: Rayleigh scattering as the one 1-D constituent
+static bool rayleigh_1d(const mi3d_solver *h) {
+    bool ray1 = h->np1d == 1;
+    for (float a : h->apf1d) ray1 = ray1 && (a > -1.5f && a <= -1.0f);
+    return ray1;
+}
+
 int fill_scene(mi3d_solver *h, DevScene &S) {
     std::memset(&S, 0, sizeof(S));
     DevCold &C = h->cold_host;
@@ -501,15 +512,9 @@ int fill_scene(mi3d_solver *h, DevScene &S) {
     if (h->src_qmax <= 0.0) C.cos_cone = 1.0f;
     S.nview = h->nview; S.nmarch = h->nmarch; S.nxr = h->nxr; S.nyr = h->nyr; S.rad_row = h->nxr; S.col0 = h->col0 > 0 ? h->col0 : 0;
     S.target = h->target; S.solver = h->solver; S.wmin = (float)h->wmin; S.wfac = (float)h->wfac;
-    {   // er3t's default mixture (mca_atm.py:95-102,299-303): Rayleigh as the one 1-D constituent, Henyey-Greenstein in every voxel:
-        // the lean kernels then evaluate the two phase functions without looking at their selectors (bit 8 of the target word)
-        bool plain = h->np1d == 1 && h->hg3d;
-        for (float a : h->apf1d) plain = plain && (a > -1.5f && a <= -1.0f);
-        if (plain) S.target |= kTargetPlainPhase;
-        bool ray1 = h->np1d == 1;
-        for (float a : h->apf1d) ray1 = ray1 && (a > -1.5f && a <= -1.0f);
-        if (ray1) S.target |= kTargetRayleigh1d;
-    }
+    // er3t's default mixture (mca_atm.py:95-102,299-303): Rayleigh as the one 1-D constituent, Henyey-Greenstein in every voxel:
+    // the lean kernels then evaluate the two phase functions without looking at their selectors (bit 8 of the target word)
+    if (rayleigh_1d(h)) S.target |= kTargetRayleigh1d | (h->hg3d ? kTargetPlainPhase : 0);
     S.rad = h->rad_ptr(); S.flux = h->flux_ptr(); S.rad_stride = 1;
     C.next_photon = h->d_next.p;
     C.le_tau1 = (float)h->le_tau1;
@@ -584,9 +589,9 @@ int fill_scene(mi3d_solver *h, DevScene &S) {
 // The sorts and sums of a flux run's last launches may still be on their way on the sort stream when mi3d_run returns (the next run's
 // photon loops then start beside them): whoever reads the tallies, clears them or changes what the kernels work on makes the main
 // stream wait for them first.
-// the sums of the launch that used set q last (mi3d_solver::tl_pend), on stream st
+// the sums of the launch that used set q last (mi3d_solver::TlSet::pend), on stream st
 static hipError_t launch_sum(mi3d_solver *h, int q, hipStream_t st) {
-    mi3d_solver::PendingSum &P = h->tl_pend[q];
+    mi3d_solver::PendingSum &P = h->tl[q].pend;
     P.on = false;
     if ((sizeof(double) << P.TL.shift) > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_tl_sum), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) << P.TL.shift));
     hipLaunchKernelGGL(k_tl_sum, dim3((unsigned)(P.TL.nbins * P.split)), dim3(1024), sizeof(double) << P.TL.shift, st, P.TL, P.flux, P.nflux, P.heat, P.nheat, P.split);
@@ -597,8 +602,8 @@ static hipError_t tl_join(mi3d_solver *h) {
     if (!h->tl_unjoined) return hipSuccess;
     for (int q = 0; q < 2; ++q) {
         // (the main stream behind the sort of the set's last launch; that launch's sums, if they are still to come, on the main stream now)
-        if (h->tl_set_used[q] && h->tl_scattered[q]) { const hipError_t e = hipStreamWaitEvent(h->stream, h->tl_scattered[q], 0); if (e != hipSuccess) return e; }
-        if (h->tl_pend[q].on) { const hipError_t e = launch_sum(h, q, h->stream); if (e != hipSuccess) return e; }
+        if (h->tl[q].used && h->tl[q].scattered) { const hipError_t e = hipStreamWaitEvent(h->stream, h->tl[q].scattered, 0); if (e != hipSuccess) return e; }
+        if (h->tl[q].pend.on) { const hipError_t e = launch_sum(h, q, h->stream); if (e != hipSuccess) return e; }
     }
     h->tl_unjoined = false;
     return hipSuccess;
@@ -614,25 +619,24 @@ static hipError_t sync_streams(mi3d_solver *h) {
     hipError_t e = tl_join(h);     // (sums that are still to come: on the main stream, before it is waited for)
     h->tl_unjoined = false;
     { const hipError_t e2 = hipStreamSynchronize(h->stream); if (e == hipSuccess) e = e2; }
-    if (h->rays_stream) { const hipError_t e2 = hipStreamSynchronize(h->rays_stream); if (e == hipSuccess) e = e2; }
-    if (h->tl_stream) { const hipError_t e2 = hipStreamSynchronize(h->tl_stream); if (e == hipSuccess) e = e2; }
-    if (h->pre_stream) { const hipError_t e2 = hipStreamSynchronize(h->pre_stream); if (e == hipSuccess) e = e2; }
+    for (hipStream_t st : {h->rays_stream, h->tl_stream, h->pre_stream})
+        if (st) { const hipError_t e2 = hipStreamSynchronize(st); if (e == hipSuccess) e = e2; }
     return e;
 }
 
 // the launch's DevCold goes to the device: [0] with the first set of event lists, [1] the same with the second set
-static hipError_t upload_cold(mi3d_solver *h, bool two_sets, bool pre_two = false) {
+static hipError_t upload_cold(mi3d_solver *h, bool two_sets, bool pre_two) {
     hipError_t e = hipMemcpyAsync(h->d_cold.p, &h->cold_host, sizeof(DevCold), hipMemcpyHostToDevice, h->stream);
     if (e != hipSuccess || !(two_sets || pre_two)) return e;
     h->cold_host2 = h->cold_host;
     if (two_sets) {
-        h->cold_host2.ev_list = h->d_events2.p; h->cold_host2.ev_ctr = h->d_evctr2.p;
-        h->cold_host2.hv_list = h->cold_host.hv_list ? h->d_hvlist2.p : nullptr;
+        h->cold_host2.ev_list = h->ev[1].events.p; h->cold_host2.ev_ctr = h->ev[1].evctr.p;
+        h->cold_host2.hv_list = h->cold_host.hv_list ? h->ev[1].hvlist.p : nullptr;
     }
-    if (pre_two) {   // (the second set of what the pre-pass writes)
-        if (h->cold_host.order) h->cold_host2.order = h->d_order2.p;
-        if (h->cold_host.entry) h->cold_host2.entry = h->d_entry2.p;
-        if (h->cold_host.tile_end) h->cold_host2.tile_end = h->d_cursor2.p;
+    if (pre_two) {   // (the second set of what the pre-pass writes; its cursors are its tiles' ends)
+        if (h->cold_host.order) h->cold_host2.order = h->pre[1].order.p;
+        if (h->cold_host.entry) h->cold_host2.entry = h->pre[1].entry.p;
+        if (h->cold_host.tile_end) h->cold_host2.tile_end = h->pre[1].cursor.p;
     }
     return hipMemcpyAsync(h->d_cold.p + 1, &h->cold_host2, sizeof(DevCold), hipMemcpyHostToDevice, h->stream);
 }
@@ -767,7 +771,7 @@ int mi3d_create(int device, mi3d_solver **out) {
     { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, device) == hipSuccess && v >= 32768) h->lds_max = v; else (void)hipGetLastError(); }
     int rc;
     if ((rc = h->d_counters.alloc(MI3D_NCOUNTER)) || (rc = h->d_next.alloc(8 * kCtrStride)) ||
-        (rc = h->d_hist.alloc(kMaxTiles)) || (rc = h->d_cursor.alloc(kMaxTiles))) { delete h; return rc; }
+        (rc = h->d_hist.alloc(kMaxTiles)) || (rc = h->pre[0].cursor.alloc(kMaxTiles))) { delete h; return rc; }
     HIPCHK(hipMemset(h->d_counters.p, 0, MI3D_NCOUNTER * sizeof(unsigned long long)));
     HIPCHK(hipMemset(h->d_next.p, 0, 8 * kCtrStride * sizeof(unsigned long long)));
     {   // XCDs in use (eight on an MI355X in SPX mode; fewer in CPX / QPX partitions)
@@ -810,38 +814,24 @@ int mi3d_destroy(mi3d_solver *h) {
     if (!h) return MI3D_OK;
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
+    auto destroy_event = [](hipEvent_t e) { if (e) (void)hipEventDestroy(e); };
     for (auto &pr : h->pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-    if (h->stats_ev) (void)hipEventDestroy(h->stats_ev);
-    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-    for (hipEvent_t &e : h->ev_done) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t &e : h->set_emit) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t &e : h->set_rays) if (e) (void)hipEventDestroy(e);
-    if (h->rays_stream) (void)hipStreamDestroy(h->rays_stream);
-    for (hipEvent_t &e : h->tldesc_ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t &e : h->tl_filled) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t &e : h->tl_sorted) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t &e : h->tl_scattered) if (e) (void)hipEventDestroy(e);
-    if (h->tl_stream) (void)hipStreamDestroy(h->tl_stream);
-    for (hipEvent_t &e : h->pre_done) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t &e : h->pre_loop) if (e) (void)hipEventDestroy(e);
-    if (h->pre_main) (void)hipEventDestroy(h->pre_main);
-    if (h->pre_stream) (void)hipStreamDestroy(h->pre_stream);
-    h->d_order2.release(); h->d_cursor2.release(); h->d_entry2.release();
-    h->d_tl_rec2.release(); h->d_tl_words2.release(); h->d_tl_cursor2.release(); h->d_tl_runs.release(); h->d_tl_runs2.release(); h->d_tl_binned2.release();
-    h->d_events2.release(); h->d_evctr2.release(); h->d_hvlist2.release();
-    if (h->h_evctr) (void)hipHostFree(h->h_evctr);
+    destroy_event(h->stats_ev);
+    for (auto &S : h->ev_slot) destroy_event(S.done);
+    for (auto &S : h->tl_slot) destroy_event(S.done);
+    for (hipEvent_t e : h->tldesc_ev) destroy_event(e);
+    destroy_event(h->pre_main);
+    for (auto &P : h->pre) { destroy_event(P.done); destroy_event(P.loop); P.release(); P.cursor.release(); }
+    for (auto &E : h->ev) { destroy_event(E.emit); destroy_event(E.rays); E.release(); E.evctr.release(); }
+    for (auto &T : h->tl) { destroy_event(T.filled); destroy_event(T.sorted); destroy_event(T.scattered); T.release(); T.cursor.release(); }
+    for (hipStream_t st : {h->own_stream, h->rays_stream, h->tl_stream, h->pre_stream}) if (st) (void)hipStreamDestroy(st);
+    for (void *p : {(void *)h->h_evctr, (void *)h->h_tlctr, (void *)h->h_tldesc}) if (p) (void)hipHostFree(p);
     h->d_abst.release(); h->d_extp.release(); h->d_omgp.release(); h->d_apfp.release();
     h->d_lay.release(); h->d_vrec.release(); h->d_bext3.release(); h->d_tcol0.release(); h->d_tmu.release(); h->d_tp.release();
     h->d_tcdf.release(); h->d_tmuidx.release(); h->d_tcdfidx.release(); h->d_sfc2d.release(); h->d_csca.release(); h->d_rad_own.release();
     h->d_flux_own.release(); h->d_heat_own.release(); h->d_counters.release(); h->d_next.release();
     h->d_rad_acc.release(); h->d_cams.release(); h->d_camdir.release(); h->d_zgrd.release();
-    h->d_order.release(); h->d_hist.release(); h->d_cursor.release(); h->d_tile.release(); h->d_entry.release();
-    h->d_events.release(); h->d_evctr.release(); h->d_hvlist.release();
-    for (hipEvent_t &e : h->tl_done) if (e) (void)hipEventDestroy(e);
-    if (h->h_tlctr) (void)hipHostFree(h->h_tlctr);
-    if (h->h_tldesc) (void)hipHostFree(h->h_tldesc);
-    h->d_tldesc.release();
-    h->d_tl_rec.release(); h->d_tl_binned.release(); h->d_tl_words.release(); h->d_tl_cursor.release(); h->d_tl_stats.release();
+    h->d_hist.release(); h->d_tile.release(); h->d_tldesc.release(); h->d_tl_stats.release();
     for (int w = 0; w < 2; ++w) { h->d_run_own[w].release(); h->d_sum[w].release(); h->d_sumsq[w].release(); h->d_factor[w].release(); }
     h->d_stat_out.release(); h->d_dir_level.release(); h->d_get_out.release(); h->d_get_add.release();
     h->d_th_tlev.release(); h->d_th_tmpa.release(); h->d_th_tmps.release(); h->d_th_cdf.release(); h->d_th_bsum.release(); h->d_th.release();
@@ -1193,7 +1183,7 @@ int mi3d_prepare(mi3d_solver *h) {
         // one needed, and er3t's jobs -- sixteen g of one scene, a few million photons each -- are not cut in two by a pilot launch and a
         // wait each
         ev_forget(h);
-        for (bool &b : h->tl_busy) b = false;
+        for (auto &S : h->tl_slot) S.busy = false;
     }
     if (h->dirty_views) {
         if ((rc = build_views(h))) return rc;
@@ -1242,7 +1232,7 @@ int mi3d_reset(mi3d_solver *h) {
     if (rc) return rc;
     if ((rc = mi3d_prepare(h))) return rc;
     // (a run that failed half way may have left ray kernels on their own stream: the tallies are cleared after them)
-    for (int q = 0; q < 2; ++q) if (h->set_used[q] && h->set_rays[q]) HIPCHK(hipStreamWaitEvent(h->stream, h->set_rays[q], 0));
+    for (const auto &E : h->ev) if (E.used && E.rays) HIPCHK(hipStreamWaitEvent(h->stream, E.rays, 0));
     HIPCHK(tl_join(h));
     HIPCHK(hipMemsetAsync(h->rad_ptr(), 0, h->rad_elems() * sizeof(tally_t), h->stream));
     HIPCHK(hipMemsetAsync(h->flux_ptr(), 0, h->flux_elems() * sizeof(tally_t), h->stream));
@@ -1252,7 +1242,7 @@ int mi3d_reset(mi3d_solver *h) {
     //  list ran full, a launch failed -- leaves its partial tallies there)
     if (h->d_rad_acc.p) HIPCHK(hipMemsetAsync(h->d_rad_acc.p, 0, h->d_rad_acc.cap * sizeof(tally_t), h->stream));
     if ((rc = drain_events(h))) return rc;
-    for (int s = 0; s < 4; ++s) if (h->ev_busy[s]) h->ev_void[s] = true;   // (launches still on their way: their tallies are gone)
+    for (auto &S : h->ev_slot) if (S.busy) S.cleared = true;   // (launches still on their way: their tallies are gone)
     h->kernel_ms = 0.0;
     h->launches = 0;
     return MI3D_OK;
@@ -1356,6 +1346,37 @@ static hipError_t launch_rays(mi3d_solver *h, hipStream_t st, const DevScene &S,
     return hipGetLastError();
 }
 
+// as many workgroups as are resident at once (a workgroup that starts after the pool is empty only stages LDS and leaves)
+#ifndef MI3D_BLOCKS_PER_CU
+#define MI3D_BLOCKS_PER_CU(MARCH, COUNT) MI3D_WAVES(MARCH, COUNT)
+#endif
+
+// The general photon loop (mi3d_kernels.hip): every job the lean loops do not serve, the thermal source's among them
+static hipError_t launch_general(mi3d_solver *h, const DevScene &S, bool march, bool flux, unsigned grid, uint64_t nb, uint64_t seed, uint64_t off) {
+    const int tb = 256;
+    const size_t lds = (size_t)h->nz * sizeof(LayerRec) + MI3D_MAX_VIEW * sizeof(ViewRec) + sizeof(DevCold) + (size_t)9 * tb * sizeof(float) +
+                       (size_t)(h->tab_n > 0 ? (1 + 2 * h->tab_n) * h->nang * sizeof(float) : 0);
+    const bool thermal = h->src_mtype == 3;
+    const DevThermal *th = thermal ? h->d_th.p : nullptr;
+#define MI3D_LAUNCH_T(C, M, F, T)                                                                                                      \
+    do { if (h->solver == MI3D_SOLVER_P3D) hipLaunchKernelGGL((k_transport<C, M, F, true, T>), dim3(grid), dim3(tb), lds, h->stream, S, nb, seed, off, th); \
+         else hipLaunchKernelGGL((k_transport<C, M, F, false, T>), dim3(grid), dim3(tb), lds, h->stream, S, nb, seed, off, th); } while (0)
+#define MI3D_LAUNCH(C, M, F) do { if (thermal) MI3D_LAUNCH_T(C, M, F, true); else MI3D_LAUNCH_T(C, M, F, false); } while (0)
+    switch ((h->counting ? 4 : 0) | (march ? 2 : 0) | (flux ? 1 : 0)) {
+        case 0: MI3D_LAUNCH(false, false, false); break;
+        case 1: MI3D_LAUNCH(false, false, true); break;
+        case 2: MI3D_LAUNCH(false, true, false); break;
+        case 3: MI3D_LAUNCH(false, true, true); break;
+        case 4: MI3D_LAUNCH(true, false, false); break;
+        case 5: MI3D_LAUNCH(true, false, true); break;
+        case 6: MI3D_LAUNCH(true, true, false); break;
+        default: MI3D_LAUNCH(true, true, true); break;
+    }
+#undef MI3D_LAUNCH
+#undef MI3D_LAUNCH_T
+    return hipGetLastError();
+}
+
 // Photons a launch may have so that its events fit the lists, at `per_photon` events per photon (0: nothing known yet, a
 // pilot).  A launch of a few million photons fills the lists of the XCDs in use evenly (twice the room asked for); a smaller one is
 // taken by whichever workgroups start first, all on one XCD in the worst case: then ONE list must hold it.
@@ -1365,33 +1386,28 @@ static uint64_t photons_that_fit(uint64_t ev_cap, double per_photon, int n_xcd) 
     return (uint64_t)(even >= 2.0e6 ? even : std::max(16.0, (double)ev_cap / (1.5 * per_photon)));
 }
 
-constexpr int kEvSlots = 4;   // launches whose fill counters may be on their way to the host at once
-
 // The fill counters of a launch that has ended, as copied out in stream order (ev_note): how full the lists got sizes the
 // launches still to come; a list that ran full has dropped events.  wait: also for launches still running.
-static int ev_collect(mi3d_solver *h, uint64_t ev_cap, bool wait) {
+static int ev_collect(mi3d_solver *h, bool wait) {
     for (int s = 0; s < kEvSlots; ++s) {
-        if (!h->ev_busy[s]) continue;
-        if (wait) HIPCHK(hipEventSynchronize(h->ev_done[s]));
-        else {
-            const hipError_t q = hipEventQuery(h->ev_done[s]);
-            if (q == hipErrorNotReady) continue;
-            HIPCHK(q);
-        }
-        h->ev_busy[s] = false;
+        mi3d_solver::EvSlot &S = h->ev_slot[s];
+        if (!S.busy) continue;
+        const hipError_t q = wait ? hipEventSynchronize(S.done) : hipEventQuery(S.done);
+        if (q == hipErrorNotReady) continue;
+        HIPCHK(q);
+        S.busy = false;
         const unsigned long long *c = h->h_evctr + (size_t)s * 9 * kCtrStride;
         unsigned long long mx = 0, sum = 0;
         for (int x = 0; x < 8; ++x) { mx = std::max(mx, c[x * kCtrStride]); sum += c[x * kCtrStride]; }
-        ev_cap = h->ev_capn[s];
-        if ((c[8 * kCtrStride] != 0ull || mx > ev_cap) && !h->ev_void[s]) {
+        if ((c[8 * kCtrStride] != 0ull || mx > S.cap) && !S.cleared) {
             (void)sync_streams(h);   // what is still queued of this run ends; its counters are of no interest any more
-            for (bool &b : h->ev_busy) b = false;
+            for (auto &T : h->ev_slot) T.busy = false;
             return fail(MI3D_ESTATE, "an event list of the marched views ran full (%llu events on one XCD from %llu photons, room for %llu): "
                                      "the tallies of this run are incomplete; call mi3d_reset and run it again (MI3D_KERNEL=generic needs no lists)",
-                        mx, (unsigned long long)h->ev_nb[s], (unsigned long long)ev_cap);
+                        mx, (unsigned long long)S.nb, (unsigned long long)S.cap);
         }
         // (records reserved, unused ones included: what the lists must hold)
-        if (h->ev_epochn[s] == h->ev_epoch) h->ev_per_photon = std::max(0.5 * h->ev_per_photon, (double)sum / (double)h->ev_nb[s]);
+        if (S.epoch == h->ev_epoch) h->ev_per_photon = std::max(0.5 * h->ev_per_photon, (double)sum / (double)S.nb);
     }
     return MI3D_OK;
 }
@@ -1400,32 +1416,27 @@ static int ev_collect(mi3d_solver *h, uint64_t ev_cap, bool wait) {
 // look at the tallies -- mi3d_sync, the read-outs, the end of a statistics run -- settles them first.  A list that ran full fails
 // THAT call: never silently short.
 static int ev_settle(mi3d_solver *h) {
-    for (bool b : h->ev_busy) if (b) return ev_collect(h, 0, true);
+    for (const auto &S : h->ev_slot) if (S.busy) return ev_collect(h, true);
     return MI3D_OK;
 }
 
 // after the kernels of a launch: its fill counters go to a pinned slot (the next launch zeroes them on the device)
-static int ev_note(mi3d_solver *h, uint64_t ev_cap, uint64_t nb, hipStream_t st = nullptr, const unsigned long long *ctr = nullptr) {
-    if (!ctr) { st = h->stream; ctr = h->d_evctr.p; }
+static int ev_note(mi3d_solver *h, uint64_t ev_cap, uint64_t nb, hipStream_t st, const unsigned long long *ctr) {
     int s = -1;
-    for (int i = 0; i < kEvSlots; ++i) if (!h->ev_busy[i]) { s = i; break; }
-    if (s < 0) {   // every slot is on its way: wait for them
-        int rc = ev_collect(h, ev_cap, true);
-        if (rc) return rc;
-        s = 0;
-    }
-    if (!h->ev_done[s]) HIPCHK(hipEventCreateWithFlags(&h->ev_done[s], hipEventDisableTiming));
+    for (int i = 0; i < kEvSlots; ++i) if (!h->ev_slot[i].busy) { s = i; break; }
+    if (s < 0) { const int rc = ev_collect(h, true); if (rc) return rc; s = 0; }   // (every slot is on its way: wait for them)
+    mi3d_solver::EvSlot &S = h->ev_slot[s];
+    if (!S.done) HIPCHK(hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
     HIPCHK(hipMemcpyAsync(h->h_evctr + (size_t)s * 9 * kCtrStride, ctr, 9 * kCtrStride * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipEventRecord(h->ev_done[s], st));
-    h->ev_busy[s] = true;
-    h->ev_nb[s] = nb;
-    h->ev_capn[s] = ev_cap;
-    h->ev_void[s] = false;
-    h->ev_epochn[s] = h->ev_epoch;
+    HIPCHK(hipEventRecord(S.done, st));
+    S.busy = true; S.nb = nb; S.cap = ev_cap; S.cleared = false; S.epoch = h->ev_epoch;
     return MI3D_OK;
 }
 
-static hipError_t launch_flux(mi3d_solver *h, int tset, hipStream_t st, hipStream_t sort_st, hipEvent_t filled, hipEvent_t scattered, bool wait_scattered, const DevScene &S, const TallyList &TL0, int mix, unsigned grid, size_t lds, uint64_t nb, uint64_t seed, uint64_t off) {
+// the photon loop of a flux job and, with record lists, their sort (tset: the set of lists; two_streams: the sort on the sort stream)
+static hipError_t launch_flux(mi3d_solver *h, int tset, bool two_streams, const DevScene &S, const TallyList &TL0, int mix, unsigned grid, size_t lds, uint64_t nb, uint64_t seed, uint64_t off) {
+    hipStream_t st = h->stream;
+    mi3d_solver::TlSet &T = h->tl[tset];
     TallyList TL = TL0;
     TL.nwave = (int)grid * 4;   // (256-thread workgroups)
     TL.stats = (TL.cap && h->d_tl_stats.p) ? h->d_tl_stats.p + 4 * (h->launches % 64) : nullptr;
@@ -1443,10 +1454,10 @@ static hipError_t launch_flux(mi3d_solver *h, int tset, hipStream_t st, hipStrea
     const TallyList *TLd = reinterpret_cast<const TallyList *>(h->d_tldesc.p + (size_t)slot * sizeof(TallyList));
     // (two sets of lists: the set is free once the sort of the launch that used it last is through it -- that launch's sums read the sorted
     //  copy and the bins' starts, which this photon loop does not touch: they may still run beside it)
-    if (wait_scattered && (e0 = hipStreamWaitEvent(st, scattered, 0)) != hipSuccess) return e0;
+    if (two_streams && T.used && (e0 = hipStreamWaitEvent(st, T.scattered, 0)) != hipSuccess) return e0;
     // (the sums of that launch, if they are still to come: here, on the main stream, between two photon loops -- they read the set's sorted copy
     //  and bins' starts, which this launch's sort writes again)
-    if (h->tl_pend[tset].on && (e0 = launch_sum(h, tset, st)) != hipSuccess) return e0;
+    if (T.pend.on && (e0 = launch_sum(h, tset, st)) != hipSuccess) return e0;
     // (the set's cursors: behind the wait -- the sort of the launch that used the set last writes one of them and copies them out on its stream)
     if (TL.cap && (e0 = hipMemsetAsync(TL.cursor, 0, 3 * sizeof(unsigned long long), st)) != hipSuccess) return e0;
 #define MI3D_FLUX_LAUNCH(C, P)                                                                                              \
@@ -1471,22 +1482,21 @@ static hipError_t launch_flux(mi3d_solver *h, int tset, hipStream_t st, hipStrea
         h->tldesc_used[slot] = (err == hipSuccess);
     }
     if (err != hipSuccess || TL.cap == 0) return err;
-    const bool two_streams = sort_st != st;
     if (two_streams) {   // (two sets of lists: the sort on its own stream, behind this photon loop)
         // The sums of the launch BEFORE this one (the other set), whose sort has run beside this photon loop: on the main stream straight behind
         // the loop, alone on the chip for the millisecond or two they take -- this launch's sort waits for them too (`filled` below), so it does
         // not take their CUs, and starts together with the next launch's photon loop, beside which it runs.  (Queued behind their own sort they
         // crept along in the loop's tails -- 13 ms for 1.6 ms of work -- and held up every sort behind them.)
         const int other = tset ^ 1;
-        if (h->tl_pend[other].on) {
-            if (h->tl_set_used[other] && h->tl_scattered[other]) err = hipStreamWaitEvent(st, h->tl_scattered[other], 0);
+        if (h->tl[other].pend.on) {
+            if (h->tl[other].used && h->tl[other].scattered) err = hipStreamWaitEvent(st, h->tl[other].scattered, 0);
             if (err == hipSuccess) err = launch_sum(h, other, st);
             if (err != hipSuccess) return err;
         }
-        err = hipEventRecord(filled, st);
-        if (err == hipSuccess) err = hipStreamWaitEvent(sort_st, filled, 0);
+        err = hipEventRecord(T.filled, st);
+        if (err == hipSuccess) err = hipStreamWaitEvent(h->tl_stream, T.filled, 0);
         if (err != hipSuccess) return err;
-        st = sort_st;
+        st = h->tl_stream;
     }
     // the records of this launch: where every wave's share of every bin goes, counting sort, one LDS sum per bin
     double *heat = (h->target & MI3D_TARGET_HEAT) ? h->heat_ptr() : nullptr;
@@ -1530,13 +1540,12 @@ static hipError_t launch_flux(mi3d_solver *h, int tset, hipStream_t st, hipStrea
     // ... and the runs' records, level by level, behind each row's share of every bin
     if (TL.run_cap) MI3D_RUNS_LAUNCH(true);
 #undef MI3D_RUNS_LAUNCH
-    if (two_streams && (err = hipEventRecord(scattered, st)) != hipSuccess) return err;
+    if (two_streams && (err = hipEventRecord(T.scattered, st)) != hipSuccess) return err;
     const int split = std::max(1, std::min(64, (h->num_cu * 8) / TL.nbins));
-    mi3d_solver::PendingSum &P = h->tl_pend[tset];
+    mi3d_solver::PendingSum &P = T.pend;
     P.on = true; P.TL = TL; P.flux = S.flux; P.nflux = (unsigned)h->flux_elems(); P.heat = heat; P.nheat = (unsigned)(heat ? h->heat_elems() : 0); P.split = split;
     // one stream: the sums straight behind the sort.  Two: they wait for the main stream's next pause -- the next launch of this set, or a join
-    static const bool defer = !(getenv("MI3D_SUM_DEFER") && atoi(getenv("MI3D_SUM_DEFER")) == 0);   // (measurements: 0 -- the sums behind their own sort, as in round 5)
-    if (!two_streams || !defer) return launch_sum(h, tset, st);
+    if (!two_streams) return launch_sum(h, tset, st);
     return hipGetLastError();
 }
 
@@ -1544,23 +1553,21 @@ static hipError_t launch_flux(mi3d_solver *h, int tset, hipStream_t st, hipStrea
 // A list that ran full has lost nothing (the tallies went out as atomics from there on), only speed.
 static int tl_collect(mi3d_solver *h, bool wait) {
     for (int s = 0; s < kEvSlots; ++s) {
-        if (!h->tl_busy[s]) continue;
-        if (wait) HIPCHK(hipEventSynchronize(h->tl_done[s]));
-        else {
-            const hipError_t q = hipEventQuery(h->tl_done[s]);
-            if (q == hipErrorNotReady) continue;
-            HIPCHK(q);
-        }
-        h->tl_busy[s] = false;
+        mi3d_solver::TlSlot &S = h->tl_slot[s];
+        if (!S.busy) continue;
+        const hipError_t q = wait ? hipEventSynchronize(S.done) : hipEventQuery(S.done);
+        if (q == hipErrorNotReady) continue;
+        HIPCHK(q);
+        S.busy = false;
         // ([0] records the loop reserved, [1] records in all with the runs expanded (k_tl_prefix), [2] run records reserved)
-        auto upd = [&](double &pp, unsigned long long got, uint64_t cap) {
-            const double seen = (double)got / (double)h->tl_nb[s];
+        auto upd = [&S](double &pp, unsigned long long got, uint64_t cap) {
+            const double seen = (double)got / (double)S.nb;
             if (got > cap) pp = std::max(1.5 * pp, seen);   // ran full: what it needed is not known
             else pp = pp > 0.0 ? std::max(0.7 * pp, seen) : seen;
         };
-        upd(h->tl_per_photon, h->h_tlctr[4 * s], h->tl_cap[s]);
-        upd(h->tl_total_pp, h->h_tlctr[4 * s + 1], h->tl_bcap[s]);
-        if (h->tl_rcap[s]) upd(h->tl_runs_pp, h->h_tlctr[4 * s + 2], h->tl_rcap[s]);
+        upd(h->tl_per_photon, h->h_tlctr[4 * s], S.cap);
+        upd(h->tl_total_pp, h->h_tlctr[4 * s + 1], S.bcap);
+        if (S.rcap) upd(h->tl_runs_pp, h->h_tlctr[4 * s + 2], S.rcap);
     }
     return MI3D_OK;
 }
@@ -1568,19 +1575,19 @@ static int tl_collect(mi3d_solver *h, bool wait) {
 // (st: the stream behind whose work the counters are complete -- the sort stream where the sort runs on one of its own)
 static int tl_note(mi3d_solver *h, uint64_t cap, uint64_t bcap, uint64_t rcap, uint64_t nb, const unsigned long long *cursor, hipStream_t st) {
     int s = -1;
-    for (int i = 0; i < kEvSlots; ++i) if (!h->tl_busy[i]) { s = i; break; }
+    for (int i = 0; i < kEvSlots; ++i) if (!h->tl_slot[i].busy) { s = i; break; }
     if (s < 0) {
         // (every slot on its way: this launch's counters are not looked at -- the host does not wait here: the copies follow the SORT of their
         //  launch, and a host that waited for them could queue the next photon loop only when the sort before it was through, beside nothing)
-        int rc = tl_collect(h, false);
-        if (rc) return rc;
-        for (int i = 0; i < kEvSlots; ++i) if (!h->tl_busy[i]) { s = i; break; }
+        if (const int rc = tl_collect(h, false)) return rc;
+        for (int i = 0; i < kEvSlots; ++i) if (!h->tl_slot[i].busy) { s = i; break; }
         if (s < 0) return MI3D_OK;
     }
-    if (!h->tl_done[s]) HIPCHK(hipEventCreateWithFlags(&h->tl_done[s], hipEventDisableTiming));
+    mi3d_solver::TlSlot &S = h->tl_slot[s];
+    if (!S.done) HIPCHK(hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
     HIPCHK(hipMemcpyAsync(h->h_tlctr + 4 * s, cursor, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipEventRecord(h->tl_done[s], st));
-    h->tl_busy[s] = true; h->tl_nb[s] = nb; h->tl_cap[s] = cap; h->tl_bcap[s] = bcap; h->tl_rcap[s] = rcap;
+    HIPCHK(hipEventRecord(S.done, st));
+    S.busy = true; S.nb = nb; S.cap = cap; S.bcap = bcap; S.rcap = rcap;
     return MI3D_OK;
 }
 
@@ -1611,6 +1618,515 @@ static int choose_tile_cols(const mi3d_solver *h) {
     return (int)std::min(window_wanted(h) ? 48.0 : 64.0, std::max(24.0, cols));
 }
 
+// ---- mi3d_run: the route of a job, the room it needs, its launches -----------------------------------------------------------------
+
+// The photon loop a job takes.  The lean kernels (mi3d_kernel_lean.hip): radiance only, satellite views (Column: the column table;
+// ColumnRays: marched views and cameras, Rad_mrkind = 1 under the 3-D solver, through event lists and the ray kernel), at most two 3-D
+// constituents, byte offsets of the voxel records within 32 bits.  The lean flux kernel (mi3d_kernel_flux.hip, Flux): flux / heating
+// rates without radiance, the same scenes.  Everything else: the general loop, k_transport.
+enum class Loop { General, Column, ColumnRays, Flux };
+
+struct RunPlan {
+    Loop loop = Loop::General;
+    bool march = false, flux = false, thermal = false;
+    // builds of the lean loops (`mix`): 0 er3t's default scene -- one 1-D and one 3-D constituent, analytic phase functions --, 1 a second
+    // 3-D constituent, 2 (round 5) the general mixture: several 1-D constituents and / or TABULATED phase functions, in 1-D layers
+    // (func_ref_vs_cot's cloud slab, rtm/mca/util.py:153) or in voxels (the Mie branch as mca_atm.py:275-277 would write it).  mix_lean: the
+    // column view's build, where the general mixture's common scene -- one Rayleigh 1-D constituent, one 3-D constituent with tables -- has
+    // one of its own (3)
+    int mix = 0, mix_lean = 0;
+    size_t lds_tab = 0;          // the phase tables the scene refers to, staged in LDS by the lean kernels (mu, p, cdf, bucket indices)
+    const char *why = nullptr;   // why the lean route was not taken (set where it was not, or where a camera job goes without the ray kernel)
+    BinGeom G = {}; int ntile = 1; bool sorted = false;   // photon order: tiles of the domain (ntile 1: the launch runs in id order)
+};
+
+static RunPlan plan_run(const mi3d_solver *h, uint64_t nphoton) {
+    RunPlan plan;
+    plan.thermal = h->src_mtype == 3;
+    plan.march = (h->target & MI3D_TARGET_RADIANCE) && h->nmarch > 0;
+    plan.flux = (h->target & MI3D_TARGET_FLUX) != 0;
+    int tc = plan.thermal ? 0 : choose_tile_cols(h);   // (a thermal photon does not start at the top: id order)
+    if (tc > 0) {
+        while ((long)((h->nx + tc - 1) / tc) * ((h->ny + tc - 1) / tc) > kMaxTiles) tc *= 2;
+        BinGeom &G = plan.G;
+        G.Lx = (float)(h->dx * h->nx); G.Ly = (float)(h->dy * h->ny);
+        G.inv_tx = (float)(1.0 / (h->dx * tc)); G.inv_ty = (float)(1.0 / (h->dy * tc));
+        G.nx = h->nx; G.ny = h->ny; G.tcols = tc; G.ntx = (h->nx + tc - 1) / tc; G.nty = (h->ny + tc - 1) / tc;
+        plan.ntile = G.ntx * G.nty;
+    }
+    plan.sorted = plan.ntile > 1 && nphoton >= 4096;
+
+    bool gen = h->np1d > 1 || h->tab3d_hi >= 0, tabs = h->tab3d_hi >= 0;
+    for (float a : h->apf1d) if (a >= 1.0f) { gen = true; tabs = true; }
+    plan.mix = gen ? 2 : (h->np3d > 1 ? 1 : 0);
+    // (tables that do not fit the LDS budget of fill_scene, or none loaded where a selector asks for one: the general kernel, which reads them from global memory)
+    const bool tabs_ok = !tabs || h->tab_n > 0;
+    plan.lds_tab = (gen && h->tab_n > 0) ? lean_tab_floats(h->nang, h->tab_n) * sizeof(float) : 0;
+    const bool rad_job = (h->target & MI3D_TARGET_RADIANCE) && h->nview > 0;
+    const bool vox32 = (double)h->ny * h->vrow_f4 * 16.0 < 4.0e9;
+    const bool cells16 = h->nx < 65536 && h->ny < 65536 && h->nz < 65536;   // (cell numbers of the event records)
+    const bool lean = !plan.thermal && h->kernel_choice == 0 && h->np3d <= 2 && tabs_ok && vox32;
+    if (lean && plan.flux && !rad_job && h->nx < 65536 && h->ny < 65536 && h->nz < 65535) plan.loop = Loop::Flux;
+    else if (lean && !plan.flux && h->nview > 0 && (plan.march ? cells16 && (h->rad_kind == 2 || h->solver == MI3D_SOLVER_3D) : h->rad_kind == 2))
+        plan.loop = plan.march ? Loop::ColumnRays : Loop::Column;
+    plan.mix_lean = (plan.mix == 2 && plan.loop != Loop::ColumnRays && rayleigh_1d(h) && h->np3d == 1) ? 3 : plan.mix;
+    if (plan.loop == Loop::General || (h->rad_kind == 1 && plan.loop != Loop::ColumnRays))
+        plan.why = h->kernel_choice != 0 ? "kernel choice 1"
+                   : h->rad_kind == 1 && h->solver != MI3D_SOLVER_3D ? "cameras are served under the 3-D solver only"
+                   : plan.flux && rad_job ? "flux (or heating rates) TOGETHER with radiance: two jobs, one per target, as er3t's mcarats_ng submits them (mcarats.py:238-245), each take a lean loop"
+                   : h->np3d > 2 ? "more than two 3-D constituents"
+                   : !tabs_ok ? "phase tables too large for the LDS (or none loaded where a selector asks for one)"
+                   : !vox32 ? "voxel records beyond 4 GB"
+                   : plan.march && !cells16 ? "cell numbers beyond the event records' 16 bits"
+                   : "a scene the lean photon loops do not serve";
+    return plan;
+}
+
+// Cameras in the cyclic domain: the periodic images of a camera are served by the ray kernel's camera build.  A camera job that cannot
+// use it (plan.why), asked for explicitly ("cam_images" > 0), is refused; left to the default (-1) it runs with the nearest image alone and
+// says so.
+static int cam_fallback(mi3d_solver *h, const char *why) {
+    if (h->cam_images > 0)
+        return fail(MI3D_EUNSUP, "cam_images=%d: the periodic images of a camera are served by the ray kernel only, and this job cannot use it (%s)", h->cam_images, why);
+    if (h->cam_images < 0 && !h->cam_warned) {
+        fprintf(stderr, "Warning [mi3d_run]: this camera job cannot use the ray kernel (%s): the NEAREST periodic image of the camera alone is served -- "
+                        "lines of sight that leave the domain sideways miss what its continuation adds (set \"cam_images\" to 0 to say so yourself).\n", why);
+        h->cam_warned = true;
+    }
+    return MI3D_OK;
+}
+
+// The route's name (mi3d_last_kernel) and, once per handle, the warning of a job that was not sent to the general loop by its caller
+// (mi3d_set_kernel 1) but landed there: the loop of round 1 serves it correctly and at a fraction of the lean loops' speed (bench.py's
+// `general_kernel` leg has the figure).  Thermal jobs take the general loop by design.
+static void name_route(mi3d_solver *h, const RunPlan &plan, bool lists, uint64_t nphoton) {
+    const int c = h->counting ? 1 : 0, p3d = h->solver == MI3D_SOLVER_P3D ? 1 : 0;
+    char nm[96];
+    if (plan.loop == Loop::Flux) snprintf(nm, sizeof(nm), lists ? "k_transport_flux<%d,%d,%d> + k_tl_scatter + k_tl_sum" : "k_transport_flux<%d,%d,%d>", c, p3d, plan.mix);
+    else if (plan.loop == Loop::ColumnRays) snprintf(nm, sizeof(nm), "k_transport_lean<%d,%d,2,%d> + k_rays", c, p3d, plan.mix_lean);
+    else if (plan.loop == Loop::Column) snprintf(nm, sizeof(nm), "k_transport_lean<%d,%d,0,%d>", c, p3d, plan.mix_lean);
+    else snprintf(nm, sizeof(nm), plan.thermal ? "k_transport<%d,%d,%d,%d> [thermal]" : "k_transport<%d,%d,%d,%d>", c, plan.march ? 1 : 0, plan.flux ? 1 : 0, p3d);
+    h->last_kernel = nm;
+    if (plan.loop == Loop::General && h->kernel_choice == 0 && !h->general_warned && nphoton >= 4096 && !plan.thermal) {
+        fprintf(stderr, "Warning [mi3d_run]: this job runs on the general photon loop (k_transport), not on a lean one: %s.  Same results, a third to a half of the speed.\n", plan.why);
+        h->general_warned = true;
+    }
+}
+
+static bool new_event(hipEvent_t &e) { return e || hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess; }
+static size_t free_bytes(size_t unknown) { size_t f = 0, t = 0; if (hipMemGetInfo(&f, &t) == hipSuccess) return f; (void)hipGetLastError(); return unknown; }
+
+// Tally records per photon with a margin: records in all (what the sorted copy holds), records the loop writes one by one, run records.
+// Nothing known yet: a record per level and a half, every one of them written by the loop, a run for every kRunMin of them.
+struct TlRates { double tpp, dpp, rpp; };
+static TlRates tl_rates(const mi3d_solver *h, bool runs) {
+    const double tpp = h->tl_total_pp > 0.0 ? 1.15 * h->tl_total_pp : (h->tl_per_photon > 0.0 && !runs ? 1.15 * h->tl_per_photon : 1.5 * (h->nz + 1));
+    return {tpp, h->tl_per_photon > 0.0 ? 1.15 * h->tl_per_photon : tpp, !runs ? 0.0 : h->tl_runs_pp > 0.0 ? 1.15 * h->tl_runs_pp + 0.05 : tpp / kRunMin};
+}
+
+// The compact histogram of a workgroup of the photon loop (hist_wg, with run records): the bins of the levels around the layers that are
+// walked voxel by voxel, for the three planes and the heating cells -- merged where they touch; without run records: all bins
+static void tl_compact_hist(const mi3d_solver *h, TallyList &T) {
+    const int nbins = T.nbins, shift = T.shift;
+    T.run_min = kRunMin;
+    for (int r = 0; r < 4; ++r) { T.cb_lo[r] = 1; T.cb_hi[r] = 0; T.cb_off[r] = 0; }
+    T.cb_lo[0] = 0; T.cb_hi[0] = nbins - 1; T.ncb = nbins;
+    int ks_lo = h->nz, ks_hi = -1;
+    for (int kq = 0; kq < h->nz && kq < (int)h->lay_host.size(); ++kq) if (h->lay_host[kq].flags & kLayStep3d) { ks_lo = std::min(ks_lo, kq); ks_hi = std::max(ks_hi, kq); }
+    if (!T.hist_wg || !T.run_cap || ks_hi < ks_lo) return;
+    const size_t ncol_ = (size_t)h->nx * h->ny, nlev_ = (size_t)h->nz + 1, nflux_ = 3 * nlev_ * ncol_;
+    std::vector<std::pair<int, int>> rg;
+    for (size_t pl = 0; pl < 3; ++pl) rg.emplace_back((int)(((pl * nlev_ + ks_lo) * ncol_) >> shift), (int)((((pl * nlev_ + ks_hi + 2) * ncol_) - 1) >> shift));
+    if (h->target & MI3D_TARGET_HEAT) rg.emplace_back((int)((nflux_ + (size_t)ks_lo * ncol_) >> shift), (int)((nflux_ + ((size_t)ks_hi + 1) * ncol_ - 1) >> shift));
+    std::sort(rg.begin(), rg.end());
+    std::vector<std::pair<int, int>> mg;
+    for (auto &q : rg) { if (!mg.empty() && q.first <= mg.back().second + 1) mg.back().second = std::max(mg.back().second, q.second); else mg.push_back(q); }
+    int off = 0;   // (at least one range: the ones after it stay unused)
+    for (size_t r = 0; r < 4 && r < mg.size(); ++r) { T.cb_lo[r] = mg[r].first; T.cb_hi[r] = std::min(mg[r].second, nbins - 1); T.cb_off[r] = off; off += T.cb_hi[r] - T.cb_lo[r] + 1; }
+    T.ncb = std::max(off, 1);
+    T.run_min = 1;
+}
+
+// A set's buffers in the description of its lists (the sizes are in T already): the words are chunk fills, the waves' chunk lists, the
+// rows of the histograms, bin starts, then the same for the run records
+static void tl_lay_out(TallyList &T, const mi3d_solver::TlSet &S) {
+    const size_t nwave = (size_t)T.nwave, nrow = (size_t)tl_nrow(T);
+    T.rec = S.rec.p; T.binned = S.binned.p; T.cursor = S.cursor.p;
+    T.runs = T.run_cap ? S.runs.p : nullptr;
+    T.chunk_fill = S.words.p;
+    T.wave_chunks = T.chunk_fill + T.cap / kTlChunk; T.wave_nchunk = T.wave_chunks + nwave * T.wcap;
+    T.whist = T.wave_nchunk + nwave; T.wbase = T.whist + nrow * T.nbins;
+    T.hist = T.wbase + nrow * T.nbins; T.bin_start = T.hist + T.nbins;
+    T.run_fill = T.bin_start + T.nbins + 1; T.run_chunks = T.run_fill + T.run_cap / kRunChunk; T.run_nchunk = T.run_chunks + nwave * T.run_wcap;
+}
+
+// Tally records instead of atomics: bins of 2^shift tally cells, as many as one workgroup can sum in LDS in float64; the record lists
+// of nset sets take what launches of nb_max photons need at the records per photon seen so far, at most 2^31 records and a quarter of the
+// memory that is free (two lists of 8 bytes per record).  Not for tallies of more than 8192 bins (134 million tally cells).  Returns the
+// records a list holds and the sets' descriptions in TL; 0: no lists (TL as it was).
+static uint64_t size_tally_lists(mi3d_solver *h, uint64_t nb_max, int nset, TallyList TL[2]) {
+    TallyList T = {};
+    T.shift = 10;
+    while (T.shift < 14 && ((size_t)16 << T.shift) <= (size_t)h->lds_max) ++T.shift;
+    const size_t ncell = h->flux_elems() + ((h->target & MI3D_TARGET_HEAT) ? h->heat_elems() : 0);   // (heating-rate cells follow the flux cells)
+    if ((double)ncell > 4.0e9) return 0;
+    T.nbins = (int)((ncell + ((size_t)1 << T.shift) - 1) >> T.shift);
+    if (T.nbins > 8192 || ((size_t)3 * T.nbins + 16 + 2 * kTlIds) * sizeof(uint32_t) + (size_t)8 * 1024 * sizeof(uint2) > (size_t)h->lds_max) return 0;
+    T.hist_wg = T.nbins > 1024 ? 1 : 0;   // (four histograms per workgroup of the photon loop would not fit its LDS any more)
+    const bool runs = h->tally_runs != 0 && h->nz <= 1022;   // (a run record holds its first level and its count in ten bits each)
+    size_t free_b = free_bytes((size_t)8 << 30);
+    for (const auto &S : h->tl) free_b += (S.rec.cap + S.binned.cap) * sizeof(uint2) + S.runs.cap * sizeof(float4);
+    const TlRates r = tl_rates(h, runs);
+    const uint64_t waves = (uint64_t)h->num_cu * MI3D_FLUX_WAVES(h->counting != 0) * 4;
+    const uint64_t lim = ((uint64_t)1 << h->tl_cap_log2) - kTlChunk;
+    // the lists in all: a quarter of the memory that is free (the sorted copy once, records and runs once per set)
+    const double nb = std::min((double)nb_max, 0.25 * (double)free_b / (nset * (8.0 * r.tpp + 8.0 * r.dpp + 32.0 * r.rpp)));
+    auto cap_of = [nb, waves, lim](double pp, uint64_t chunk, uint64_t have, double item_bytes) -> uint64_t {
+        uint64_t c = (uint64_t)(pp * nb) + (waves + 1) * chunk;
+        // (lists only grow, and by a quarter at least: the rates per photon creep upwards by a per cent from launch to launch, and every
+        //  step of a list that is not at its limit would free and allocate gigabytes -- seen as one run in three taking seconds.
+        //  A LARGE list that is near enough stays where it is: a launch more per run costs less than moving sixteen gigabytes.  A small one
+        //  moves: er3t's jobs of a few million photons come by the dozen, one size, and a list 30 % short made two launches of every one
+        //  of them -- 7.3 instead of 5.6 ms per job of 6e6 photons, profiles/r06/small_flux_jobs_one_launch.log)
+        if (have > 0 && (double)have >= (double)c) c = have;
+        else if (have > 0 && (double)have >= 0.7 * (double)c && (double)have * item_bytes >= 1.6e10) c = have;
+        else if (c > have && have > 0) c = std::max<uint64_t>(c, have + have / 4);
+        c = std::min<uint64_t>(c, lim);
+        c = std::max<uint64_t>(c, std::min<uint64_t>(have, lim));
+        return c / chunk * chunk;
+    };
+    const mi3d_solver::TlSet &S0 = h->tl[0];
+    const uint64_t want_cap = cap_of(r.dpp, kTlChunk, S0.rec.cap, 8.0 * nset);
+    const uint64_t want_bcap = cap_of(r.tpp, kTlChunk, S0.binned.cap, 8.0 * nset);
+    const uint64_t want_rcap = runs ? std::max<uint64_t>(cap_of(r.rpp, kRunChunk, S0.runs.cap / 2, 32.0 * nset), 64 * kRunChunk) : 0;
+    if (want_cap < 64 * kTlChunk) return 0;
+    T.cap = (unsigned)want_cap; T.bcap = (unsigned)want_bcap; T.run_cap = (unsigned)want_rcap;
+    T.nwave = (int)waves;
+    T.wcap = (int)std::max<size_t>(64, 4 * (size_t)(want_cap / kTlChunk) / waves);
+    T.run_wcap = runs ? (int)std::max<size_t>(64, 4 * (size_t)(want_rcap / kRunChunk) / waves) : 0;
+    const size_t nrow = (size_t)tl_nrow(T);
+    const size_t nwords = (size_t)(want_cap / kTlChunk) + waves * T.wcap + waves + 2 * nrow * T.nbins + 2 * (size_t)T.nbins + 1 +
+                          (runs ? (size_t)(want_rcap / kRunChunk) + waves * T.run_wcap + waves : 0);
+    // (a list that moves: nothing may still be on its way that reads the old one -- launches, sorts, and the sums that are kept back for the main
+    //  stream's next pause, whose description holds the old pointers: everything joined and waited for first)
+    bool moves = false;
+    for (int q = 0; q < nset; ++q) moves = moves || want_cap > h->tl[q].rec.cap || want_bcap > h->tl[q].binned.cap || nwords > h->tl[q].words.cap || 2 * want_rcap > h->tl[q].runs.cap;
+    if (moves && sync_streams(h) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    int rc = MI3D_OK;
+    for (int q = 0; q < nset && !rc; ++q) {
+        mi3d_solver::TlSet &S = h->tl[q];
+        rc = S.rec.alloc(want_cap);
+        if (!rc) rc = S.binned.alloc(want_bcap);
+        if (!rc) rc = S.words.alloc(nwords);
+        if (!rc) rc = S.cursor.alloc(kCtrStride);
+        if (!rc && q == 0) rc = h->d_tl_stats.alloc(64 * 4);
+        if (!rc && runs) rc = S.runs.alloc(2 * want_rcap);
+    }
+    if (!rc && !h->h_tlctr && hipHostMalloc((void **)&h->h_tlctr, (size_t)4 * kEvSlots * sizeof(unsigned long long)) != hipSuccess) rc = MI3D_EDEVICE;
+    if (rc) {
+        (void)hipGetLastError();
+        for (auto &S : h->tl) S.release();
+        fprintf(stderr, "Warning [mi3d_run]: no device memory for the tally-record lists of this flux job (%.1f GB free); an atomic per level crossing instead (same results, slower).\n", (double)free_b / 1.0e9);
+        return 0;
+    }
+    tl_compact_hist(h, T);
+    // (each set: lists, counters, cursor and sorted copy of its own)
+    for (int q = 0; q < 2; ++q) { TL[q] = T; tl_lay_out(TL[q], h->tl[q < nset ? q : 0]); }
+    return want_cap;
+}
+
+// Capacity of each XCD's event list.  Nothing known about the scene yet: room for a pilot launch.  A short run: room for every
+// event of the run on ONE list (64 per photon: the workgroups that start first take most of its photons).  A long one: what
+// the run's events need at the number per photon seen so far, twice over (the lists fill unevenly), at most 2^ev_cap_log2
+// records -- and never more than a quarter of the memory that is free now (other handles, a host framework and smaller parts
+// share the device).  Lists only grow (mi3d_set_tuning "evcap_log2" and a job without marched views release them).  Returns the
+// capacity, with cold_host pointing at set 0's lists (0: no room).
+static uint64_t size_ev_lists(mi3d_solver *h, uint64_t nphoton, bool two_sets) {
+    const double per_rec = (double)kEvBlockF4 * 16.0 / 64.0 + (h->sfc_lambert_only ? 0.0 : 8.0);
+    size_t free_b = free_bytes((size_t)8 << 30);
+    for (const auto &E : h->ev) free_b += E.events.cap * sizeof(float4) + E.hvlist.cap * sizeof(unsigned long long);   // (what this handle holds already is reused)
+    const int nset = two_sets ? 2 : 1;
+    const uint64_t cap_mem = (uint64_t)(0.25 * (double)free_b / (8.0 * per_rec * nset));
+    const uint64_t cap_max = (uint64_t)1 << h->ev_cap_log2;
+    uint64_t want_cap = std::min<uint64_t>(cap_max, 64 * nphoton + 65536);
+    if (h->ev_per_photon > 0.0)
+        want_cap = std::min<uint64_t>(want_cap, std::max<uint64_t>((uint64_t)(4.0 * h->ev_per_photon * (double)nphoton / h->n_xcd), 65536));
+    else want_cap = std::min<uint64_t>(want_cap, (uint64_t)1 << 22);
+    want_cap = std::max<uint64_t>(want_cap, std::min<uint64_t>(h->ev[0].events.cap / ((size_t)8 * kEvBlockF4) * 64, cap_max));
+    want_cap = std::min<uint64_t>(want_cap, cap_mem);
+    want_cap &= ~(uint64_t)63;      // (the records stand in blocks of 64: ev_index)
+    // (an allocation that fails although the device reported the room -- fragmentation, another process -- is tried again at half the
+    //  size: launches are sized to the lists, so small lists cost launches, not results; below 65 536 records per list: the general kernel)
+    int r = MI3D_OK;
+    for (;;) {
+        r = want_cap < 65536 ? fail(MI3D_EDEVICE, "no memory for event lists") : MI3D_OK;
+        for (int q = 0; q < nset && !r; ++q) {
+            mi3d_solver::EvSet &E = h->ev[q];
+            r = E.events.alloc((size_t)8 * ev_list_f4(want_cap));
+            if (!r) r = E.evctr.alloc(kCtrWords * kCtrStride);
+            if (!r && !h->sfc_lambert_only) r = E.hvlist.alloc((size_t)8 * want_cap);
+        }
+        if (!r && !h->h_evctr && hipHostMalloc((void **)&h->h_evctr, (size_t)kEvSlots * 9 * kCtrStride * sizeof(unsigned long long)) != hipSuccess) r = MI3D_EDEVICE;
+        if (!r || want_cap < 65536) break;
+        (void)hipGetLastError();
+        for (auto &E : h->ev) E.release();
+        want_cap = (want_cap / 2) & ~(uint64_t)63;
+    }
+    if (r) {
+        (void)hipGetLastError();
+        fprintf(stderr, "Warning [mi3d_run]: no device memory for the event lists of the marched views (%.1f GB free); the general kernel marches them inside its photon loop (same results, slower).\n", (double)free_b / 1.0e9);
+        return 0;
+    }
+    h->cold_host.ev_list = h->ev[0].events.p; h->cold_host.ev_ctr = h->ev[0].evctr.p; h->cold_host.ev_cap = (int)want_cap;
+    h->cold_host.hv_list = h->sfc_lambert_only ? nullptr : h->ev[0].hvlist.p;
+    return want_cap;
+}
+
+// Entry records (k_entry, mi3d_kernel_lean.hip): the lean loop's builds without rays inside them take new photons where their
+// first voxel walk begins.  48 bytes per photon of a launch, never more than half of the memory that is free: without them
+// (no room, "entry_records" 0) the photons are launched inside the loop as before.  Points cold_host at the records.
+static bool use_entry_records(mi3d_solver *h, const RunPlan &plan, uint64_t nphoton) {
+#if MI3D_LEAN_FAST
+    if (plan.loop == Loop::General || !h->entry_records || h->nx >= 65536 || h->ny >= 65536 || h->nz >= 32768) return false;
+    DevBuf<float4> &E = h->pre[0].entry;
+    const size_t need = entry_f4((size_t)std::min<uint64_t>(nphoton, h->batch));
+    size_t free_b = free_bytes((size_t)8 << 30);
+    free_b += E.cap * sizeof(float4);
+    if (need > E.cap && need * sizeof(float4) > free_b / 2) return false;
+    if (E.alloc(need) == MI3D_OK) { h->cold_host.entry = E.p; return true; }
+    (void)hipGetLastError();
+#endif
+    return false;
+}
+
+// The pre-pass of a launch (photon order, entry records) on a stream of its own beside the photon loop of the launch before: a second set
+// of what it writes.  (Not together with the second set of event lists of "overlap_rays": one spare DevCold.)
+// Where the loop leaves room on a CU: the flux loop (four waves per SIMD) and the event-writing loop of jobs with marched views (+4 % for a flux
+// run alone, +2.6 % with nine views).  The column / tally-window loop holds six waves per SIMD and most of the LDS: there the pre-pass only finds
+// room in the loop's tail, and what runs beside it costs the loop more than it saves (-4 % on the 480 x 480 nadir bench, -3 % on 128 x 128:
+// profiles/r05/ab_overlap_pre.log; -4 % on a stream of its own of the lowest priority, profiles/r06/ab_pre_nadir_priority.log).
+// A run of a few million photons that is read before the next one has no loop before it to hide behind and pays for the hop between the streams.
+// Returns whether the run uses the second set ("overlap_pre" 2: whatever the run).
+static bool pre_second_set(mi3d_solver *h, const RunPlan &plan, bool use_entry, bool two_sets, uint64_t nphoton) {
+    mi3d_solver::PreSet &P0 = h->pre[0], &P1 = h->pre[1];
+    bool two = h->overlap_pre && !two_sets && (plan.sorted || use_entry) && (plan.loop == Loop::Flux || plan.loop == Loop::ColumnRays) &&
+               (h->overlap_pre > 1 || nphoton >= ((uint64_t)1 << 22) || h->runs_unread > 0);
+    if (two && !h->pre_stream && hipStreamCreateWithFlags(&h->pre_stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); two = false; }
+    for (auto &S : h->pre) two = two && new_event(S.done) && new_event(S.loop);
+    if (two && plan.sorted && (P1.order.alloc(P0.order.cap) != MI3D_OK || P1.cursor.alloc(kMaxTiles) != MI3D_OK)) { (void)hipGetLastError(); two = false; }
+    if (two && use_entry && P1.entry.cap < P0.entry.cap) {   // (a second set of the same size, where half of the free memory holds it)
+        const size_t free_b = free_bytes(0) + P1.entry.cap * sizeof(float4);
+        if (P0.entry.cap * sizeof(float4) > free_b / 2 || P1.entry.alloc(P0.entry.cap) != MI3D_OK) { (void)hipGetLastError(); two = false; }
+    }
+    // (a job that does not use the second set gives back what is large: a hipFree waits for the device -- not for every small job)
+    if (!two && (P1.entry.cap * sizeof(float4) + P1.order.cap * sizeof(uint32_t)) > ((size_t)256 << 20)) P1.release();
+    return two;
+}
+
+// The tally window of the lean loop (DevCold::tile_end ...): for the column view of a satellite image with one pixel per column,
+// when the launch is worked through tile by tile.  Its place relative to a tile: where the direct beam that enters the top of
+// the atmosphere above the tile reaches the height of the clouds, centred.
+static void set_tally_window(mi3d_solver *h, const RunPlan &plan) {
+    DevCold &C = h->cold_host;
+    C.tile_end = nullptr; C.win_tc = 0; C.win_ntx = 0; C.win_ntile = 0; C.win_off = 0u;
+    if (!(plan.loop == Loop::Column || plan.loop == Loop::ColumnRays) || !window_wanted(h) || !plan.sorted || h->nx >= 32768 || h->ny >= 32768 ||
+        h->nx < kWin || h->ny < kWin || !(h->z_cloud >= 0.0) || !(C.sdz < 0.0f))
+        return;
+    const double ztoa = h->zgrd[h->nz];
+    // (under the independent-pixel approximation a photon never leaves the column it was launched above)
+    const double way = h->solver == MI3D_SOLVER_IPA ? 0.0 : (ztoa - h->z_cloud) / std::fabs((double)C.sdz);
+    const int tcols = plan.G.tcols;
+    const int margin = (kWin - std::min(tcols, kWin)) / 2 - std::max(0, tcols - kWin) / 2;   // (a tile wider than the window: its middle)
+    auto wrap = [](long v, int n) { v %= n; if (v < 0) v += n; return (unsigned)v; };
+    // (the centring was checked by moving the window about: ±12 columns change the share of the tallies it catches by less than a
+    //  point, ±24 cost ten -- profiles/r04/win_offset_probe.log)
+    const unsigned ox = wrap(std::lround(C.sdx * way / h->dx) - margin, h->nx);
+    const unsigned oy = wrap(std::lround(C.sdy * way / h->dy) - margin, h->ny);
+    C.tile_end = h->pre[0].cursor.p;   // (the tiles' ends: each pre-pass set's cursors, upload_cold)
+    C.win_tc = tcols; C.win_ntx = plan.G.ntx; C.win_ntile = plan.ntile;
+    C.win_off = ox | (oy << 16);
+}
+
+// Radiance tallies go to an accumulation image with one pixel per 128-byte line and are folded into the tally buffer (the
+// library's own or the caller's) after the last launch of this call -- where the tallies are atomics from the photon loop itself
+// ("rad_spread" -1, the default).  Not where the ray kernel makes them (marched views, cameras): its tallies spread over the images
+// of several views or a wide camera image, and the compact image (8 bytes per pixel: 1.8 MB per view on the 480 x 480 scene, at home
+// in the L2s) serves them better than 29 MB per view -- nine views 2.83 -> 3.11e8 photons/s, the camera +1 %
+// (profiles/r04/ab_rad_line_density.log).  With the tally window either image does (2.79 / 2.78e9): the accumulation image stays.
+// Rows of the accumulation image an ODD number of 4 KiB pages apart (32 pixels of kRadLine * 8 bytes a page).  The atomics of an
+// XCD go to the pixels of one tile of columns, a few rows of which are busy at any time; with rows a multiple of four pages
+// apart they meet in a few of the L2's sixteen channels: 128 pixels per row (4 pages) 1.93e9 photons/s against 2.47e9 at 5 pages
+// and 2.52 at 4.5; 256 (8 pages) 1.63 against 2.25 at 9; 64 pixels padded to 4 pages 1.19 against 2.5; 512 (16) 2.11 against 2.25
+// at 17.  Odd page counts came within 2 % of the best stride on every size tried (192 ... 512 pixels: 7, 9, 11, 13, 15, 17
+// pages); half pages are good on some sizes and the worst choice on others (15.5 and 16.5 pages: 1.96 and 2.00 against 2.28).
+// profiles/r04/stride_probe4.log ... stride_probe6.log, ab_rad_row_pad*.log; tools/stride_probe*.py
+// rad_row: pixels per row of the image the run tallies into (0: none, the tally buffer itself)
+static int rad_acc_image(mi3d_solver *h, const RunPlan &plan, DevScene &S, int &rad_row) {
+    rad_row = 0;
+    const int row = h->rad_row_pad >= 0 ? h->nxr + h->rad_row_pad : 32 * (((h->nxr + 31) / 32) | 1);
+    const size_t acc_elems = (size_t)h->nview * h->nyr * row;
+    const bool spread = (h->target & MI3D_TARGET_RADIANCE) && h->nview > 0 && h->rad_spread != 0 && !(h->rad_spread < 0 && plan.loop == Loop::ColumnRays) &&
+                        (double)acc_elems * kRadLine * sizeof(tally_t) <= 1.0e9 && (double)acc_elems * kRadLine < 2147483647.0;
+    if (!spread) return MI3D_OK;
+    const size_t need = acc_elems * kRadLine;
+    if (h->d_rad_acc.cap < need || !h->d_rad_acc.p) {
+        int rc = h->d_rad_acc.alloc(need);
+        if (rc) return rc;
+        HIPCHK(hipMemsetAsync(h->d_rad_acc.p, 0, need * sizeof(tally_t), h->stream));
+    }
+    S.rad = h->d_rad_acc.p; S.rad_stride = kRadLine; S.rad_row = row;
+    rad_row = row;
+    return MI3D_OK;
+}
+
+// Photons of the next launch (per: those of the last one, in and out).  Equal launches (a short last one would be mostly tail).  With
+// k_rays a launch is as many photons as the event lists hold at the number of events per photon seen so far (twice the room: the lists
+// fill unevenly); with tally-record lists as many as the lists hold at the records per photon seen so far.
+static int launch_photons(mi3d_solver *h, const RunPlan &plan, uint64_t ev_cap, const TallyList &TL, bool tl_two, uint64_t nphoton, uint64_t done, uint64_t &per) {
+    const uint64_t left = nphoton - done;
+    int rc;
+    if (plan.loop == Loop::ColumnRays) {
+        if ((rc = ev_collect(h, false))) return rc;
+        const uint64_t room = photons_that_fit(ev_cap, h->ev_per_photon, h->n_xcd);
+        const uint64_t want_n = std::max<uint64_t>(std::min<uint64_t>(room, h->batch), 64);
+        const uint64_t nl = (left + want_n - 1) / want_n;
+        per = (left + nl - 1) / nl;
+    }
+    if (TL.cap) {
+        if ((rc = tl_collect(h, false))) return rc;
+        const uint64_t waves = (uint64_t)h->num_cu * MI3D_FLUX_WAVES(h->counting != 0) * 4;
+        // (what each of the three lists holds at its rate per photon seen so far: the loop's records, the sorted copy, the run records)
+        auto room_of = [waves](uint64_t cap_, uint64_t chunk, double pp_) -> uint64_t {
+            return (uint64_t)((double)(cap_ > 2 * waves * chunk ? cap_ - waves * chunk : cap_ / 2) / pp_);
+        };
+        const TlRates r = tl_rates(h, TL.run_cap != 0);
+        uint64_t room = std::min(room_of(TL.cap, kTlChunk, r.dpp), room_of(TL.bcap, kTlChunk, r.tpp));
+        if (TL.run_cap) room = std::min(room, room_of(TL.run_cap, kRunChunk, r.rpp));
+        const uint64_t want_n = std::max<uint64_t>(std::min<uint64_t>(room, h->batch), 4096);
+        uint64_t nl = (left + want_n - 1) / want_n;
+        // (the sort beside the next photon loop: a run in tl_split launches at least, of eight million photons or more -- all but the last sort are hidden)
+        if (tl_two && done == 0) nl = std::max<uint64_t>(nl, std::min<uint64_t>((uint64_t)h->tl_split, nphoton >> 23));
+        else if (tl_two) nl = std::max<uint64_t>(nl, std::min<uint64_t>((left + per - 1) / std::max<uint64_t>(per, 1), (uint64_t)h->tl_split));
+        nl = std::max<uint64_t>(nl, 1);
+        per = (left + nl - 1) / nl;
+    }
+    return MI3D_OK;
+}
+
+// The column-view loop of a launch (set: its event lists) and, with marched views, the ray kernels of the events it has written: on their
+// own stream rs beside the next launch's photon loop where there are two sets
+static hipError_t launch_column(mi3d_solver *h, const RunPlan &plan, const DevScene &Sl, int set, bool two_sets, hipStream_t rs, unsigned grid, uint64_t nb, uint64_t seed, uint64_t off) {
+    const bool split = plan.loop == Loop::ColumnRays;
+    mi3d_solver::EvSet &E = h->ev[set];
+    const size_t lds_col = (size_t)(h->nz + 2) * sizeof(LayerRec) + MI3D_MAX_VIEW * sizeof(ViewRec) + sizeof(DevCold);   // (+2: the lean loop's end records)
+    const int emit_wg = h->counting ? 4 : (h->emit_wg > 0 ? std::min(h->emit_wg, MI3D_LEAN_EMIT_GRID) : MI3D_LEAN_EMIT_GRID);
+    const unsigned gridp = split ? (unsigned)std::min<uint64_t>((nb + 255) / 256, (uint64_t)h->num_cu * emit_wg) : grid;
+    DevScene Sx = Sl;
+    if (set) Sx.cold = h->d_cold.p + 1;       // (this launch's set of event lists)
+    hipError_t err = hipSuccess;
+    // (the set is free once the ray kernels of the launch that used it last are through it)
+    if (two_sets && E.used) err = hipStreamWaitEvent(h->stream, E.rays, 0);
+    if (err == hipSuccess && split) err = hipMemsetAsync(E.evctr.p, 0, kCtrWords * kCtrStride * sizeof(unsigned long long), h->stream);
+    if (err == hipSuccess) {
+        // (the general mixture with staged tables AND a tally window: three workgroups of 512 threads keep six waves per SIMD where
+        //  six of 256 would not find the LDS)
+        const size_t lds_lean = lds_col + (h->cold_host.tile_end ? kWinLds : 0) + plan.lds_tab;
+        const bool wide = plan.mix >= 2 && !split && !h->counting && lds_lean * 3 <= (size_t)160 * 1024 && lds_lean * 6 > (size_t)160 * 1024;
+        unsigned gridw = wide ? (unsigned)std::min<uint64_t>((nb + 511) / 512, (uint64_t)h->num_cu * 3) : gridp;
+        // (the general mixture in workgroups of 256: as many as its registers -- five waves per SIMD -- and its LDS let a CU hold)
+        if (plan.mix >= 2 && !wide && !split && !h->counting) gridw = std::min<unsigned>(gridw, (unsigned)h->num_cu * (unsigned)std::max<size_t>(1, std::min<size_t>(MI3D_GEN_NARROW_WAVES, ((size_t)160 * 1024) / lds_lean)));
+        err = launch_lean(h, h->stream, Sx, split, plan.mix_lean, wide ? 512 : 256, gridw, lds_lean, nb, seed, off);
+    }
+    if (err != hipSuccess || !split) return err;
+    if (two_sets) {
+        err = hipEventRecord(E.emit, h->stream);
+        if (err == hipSuccess) err = hipStreamWaitEvent(rs, E.emit, 0);
+    }
+    const bool plain_scene = (Sl.target & kTargetPlainPhase) != 0 && h->rad_kind != 1;
+    if (err == hipSuccess) err = launch_rays(h, rs, Sx, false, lds_col + rays_lds_extra(h->nz, h->rad_kind == 1) + (plain_scene ? 0 : plan.lds_tab), seed);
+    if (err == hipSuccess && !h->sfc_lambert_only && h->rad_kind != 1)   // the reflections off LSRT / DSM surfaces it left aside
+        err = launch_rays(h, rs, Sx, true, lds_col + rays_lds_extra(h->nz) + plan.lds_tab, seed);
+    return err;
+}
+
+// The flux loop's tally-record lists (TL; tl_two: a second set, sorted on a stream of its own beside the next photon loop) and the LDS its
+// workgroups take (lds_fl)
+static int flux_lists(mi3d_solver *h, const RunPlan &plan, uint64_t nphoton, TallyList TL[2], bool &tl_two, size_t &lds_fl) {
+    int rc;
+    if ((rc = h->d_tldesc.alloc((size_t)64 * sizeof(TallyList)))) return rc;
+    if (!h->h_tldesc && hipHostMalloc((void **)&h->h_tldesc, (size_t)64 * sizeof(TallyList)) != hipSuccess) return fail(MI3D_EDEVICE, "no pinned memory for the tally-list descriptions");
+    // Two streams pay where something runs beside the sort: a run long enough for four launches of eight million photons (a run of 4e7 alone: +7 %;
+    // 1e7 / 2e7 in two or three launches: -2.5 %, tools/small_runs.py), or a run that follows another whose tallies nobody has looked at in between
+    // (runs queued back to back: +19 % at 5e6 photons a run).  A small run whose tallies are read before the next one -- er3t's jobs of a few
+    // million photons, one by one -- only pays for the launches' tails and the hops between the streams: one stream ("overlap_sort" 2: two
+    // streams whatever the run).
+    tl_two = h->overlap_sort != 0 && (h->overlap_sort == 2 || nphoton >= ((uint64_t)1 << 25) || h->runs_unread > 0);
+    // (the stream and its events only where they are used: every stream more of a process shares the device's few hardware queues with the
+    //  others -- two handles that each kept an idle sort stream ran their jobs 12 % slower side by side, tools/time_dropin.py)
+    if (tl_two && !h->tl_stream && hipStreamCreateWithFlags(&h->tl_stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); tl_two = false; }
+    for (auto &T : h->tl) tl_two = tl_two && new_event(T.filled) && new_event(T.sorted) && new_event(T.scattered);
+    // (nothing known about the scene's records per photon: lists for a pilot launch of two million photons -- sized by the guess "a record and a half
+    //  per level, a run for every three" they would take tens of gigabytes -- and the right size after it, below.  Not for short runs: the sort has
+    //  a fixed cost)
+    const bool tl_pilot = !(h->tl_total_pp > 0.0) && nphoton > ((uint64_t)1 << 21);
+    lds_fl = (size_t)(h->nz + 2) * sizeof(LayerRec) + sizeof(DevCold);
+    if (h->tally_lists && nphoton >= 4096 && size_tally_lists(h, tl_pilot ? (uint64_t)1 << 21 : std::min<uint64_t>(nphoton, h->batch), tl_two ? 2 : 1, TL))
+        lds_fl += TL[0].hist_wg ? ((size_t)TL[0].ncb + 3) / 4 * 16 : (size_t)TL[0].nbins * 16;   // (a histogram per wave, or one for the workgroup)
+    lds_fl += (size_t)4 * 128 * sizeof(float4) + (size_t)4 * kTlStage * sizeof(uint2);   // the waves' run records and staged tallies
+    lds_fl += plan.lds_tab;                                                              // ... and the phase tables behind them
+    if (!TL[0].cap) tl_two = false;
+    // (one stream after runs on two: the shared sorted copy and the first set of lists are free once the sorts before are through)
+    if (!tl_two && TL[0].cap) HIPCHK(tl_join(h));
+    return MI3D_OK;
+}
+
+// The event lists of a job with marched views (ev_cap: the records of each; two_sets: a second set, the ray kernels on a stream of their own
+// beside the next launch's photon loop).  No room for them: the general loop serves the job
+static int event_lists(mi3d_solver *h, RunPlan &plan, uint64_t nphoton, uint64_t &ev_cap, bool &two_sets) {
+    if (plan.loop == Loop::ColumnRays) {
+        two_sets = h->overlap_rays != 0;
+        if (two_sets && !h->rays_stream && hipStreamCreateWithFlags(&h->rays_stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); two_sets = false; }
+        for (auto &E : h->ev) two_sets = two_sets && new_event(E.emit) && new_event(E.rays);
+        if (!(ev_cap = size_ev_lists(h, nphoton, two_sets))) {
+            // no room for the lists: the general kernel marches the rays inside its photon loop instead (same results, slower) -- except for
+            // a camera that was to see its periodic images: the general kernel serves the nearest one only
+            for (auto &E : h->ev) E.release();
+            plan.loop = Loop::General; plan.why = "no device memory for its event lists"; two_sets = false;
+            if (h->rad_kind == 1) {
+                if (h->cam_images > 0) return fail(MI3D_EDEVICE, "no device memory for the event lists of a camera job with cam_images=%d (the general kernel serves the nearest image only)", h->cam_images);
+                return cam_fallback(h, plan.why);
+            }
+        }
+    } else if (h->ev[0].events.p) {   // this job needs no lists: what an earlier one held goes back to the device
+        HIPCHK(sync_streams(h));
+        for (auto &E : h->ev) E.release();
+    }
+    return MI3D_OK;
+}
+
+// The pre-pass of a launch: its photon order and entry records, into set pset (with two sets on the pre-pass stream, behind the photon loop
+// that read the set last and beside the one that is running)
+static hipError_t launch_pre(mi3d_solver *h, const RunPlan &plan, int pset, bool pre_two, bool pre_track, bool use_entry, const DevScene &S, uint64_t nb, uint64_t seed, uint64_t off) {
+    mi3d_solver::PreSet &PS = h->pre[pset];
+    hipStream_t const ps = pre_two ? h->pre_stream : h->stream;
+    hipError_t eb = hipSuccess;
+    // (set pset is free once the photon loop of the launch that read it last is through -- whichever stream arrangement that launch
+    //  had: a one-stream launch records set 0's loop event too, below -- and the histogram / tile scratch the two sets share once the last
+    //  pre-pass on the main stream is: ADVICE r5, a two-stream run queued straight behind a one-stream run)
+    if (pre_two && PS.used) eb = hipStreamWaitEvent(ps, PS.loop, 0);
+    if (eb == hipSuccess && pre_two && h->pre_main_used) { eb = hipStreamWaitEvent(ps, h->pre_main, 0); h->pre_main_used = false; }
+    if (eb == hipSuccess && plan.sorted) eb = launch_bins(h, ps, plan.G, plan.ntile, seed, off, nb, PS.order.p, PS.cursor.p);
+    if (eb == hipSuccess && use_entry)   // the photons of this launch up to their first voxel walk
+        eb = launch_entry(h, ps, S, nb, seed, off, plan.sorted ? (const uint32_t *)PS.order.p : (const uint32_t *)nullptr, PS.entry.p);
+    if (eb == hipSuccess && pre_two) eb = hipEventRecord(PS.done, ps);
+    if (eb == hipSuccess && pre_track && !pre_two) {
+        if (!h->pre_main) eb = hipEventCreateWithFlags(&h->pre_main, hipEventDisableTiming);
+        if (eb == hipSuccess) { eb = hipEventRecord(h->pre_main, h->stream); h->pre_main_used = true; }
+    }
+    if (eb == hipSuccess && pre_two) eb = hipStreamWaitEvent(h->stream, PS.done, 0);
+    return eb;
+}
+
 int mi3d_run(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_offset) {
     int rc = check_handle(h);
     if (rc) return rc;
@@ -1632,585 +2148,79 @@ int mi3d_run(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_of
         if (nvox > lim || (double)h->flux_elems() > lim || (double)h->rad_elems() > lim || (double)h->heat_elems() > lim)
             return fail(MI3D_EUNSUP, "grid too large for the 32-bit table indices of the transport kernel");
     }
-    // ---- photon order: tiles of the domain (none: the launch runs in id order)
-    BinGeom G;
-    std::memset(&G, 0, sizeof(G));
-    int ntile = 1;
-    {
-        int tc = thermal ? 0 : choose_tile_cols(h);   // (a thermal photon does not start at the top: id order)
-        if (tc > 0) {
-            while ((long)((h->nx + tc - 1) / tc) * ((h->ny + tc - 1) / tc) > kMaxTiles) tc *= 2;
-            G.Lx = (float)(h->dx * h->nx); G.Ly = (float)(h->dy * h->ny);
-            G.inv_tx = (float)(1.0 / (h->dx * tc)); G.inv_ty = (float)(1.0 / (h->dy * tc));
-            G.nx = h->nx; G.ny = h->ny; G.tcols = tc; G.ntx = (h->nx + tc - 1) / tc; G.nty = (h->ny + tc - 1) / tc;
-            ntile = G.ntx * G.nty;
-        }
-    }
-    const bool sorted = ntile > 1 && nphoton >= 4096;
-    if (sorted) {
-        const size_t cap = (size_t)std::min<uint64_t>(nphoton, h->batch);
-        if ((rc = h->d_order.alloc(cap)) || (rc = h->d_tile.alloc(cap))) return rc;
-    }
     DevScene S;
     if ((rc = fill_scene(h, S))) return rc;
-    h->cold_host.order = sorted ? h->d_order.p : nullptr;
+    RunPlan plan = plan_run(h, nphoton);
+    if (plan.sorted) {
+        const size_t cap = (size_t)std::min<uint64_t>(nphoton, h->batch);
+        if ((rc = h->pre[0].order.alloc(cap)) || (rc = h->d_tile.alloc(cap))) return rc;
+    }
+    h->cold_host.order = plan.sorted ? h->pre[0].order.p : nullptr;
 
-    const int tb = 256;
-    const size_t lds = (size_t)h->nz * sizeof(LayerRec) + MI3D_MAX_VIEW * sizeof(ViewRec) + sizeof(DevCold) + (size_t)9 * tb * sizeof(float) +
-                       (size_t)(h->tab_n > 0 ? (1 + 2 * h->tab_n) * h->nang * sizeof(float) : 0);
-    const bool march = (h->target & MI3D_TARGET_RADIANCE) && h->nmarch > 0;
-    const bool flux = (h->target & MI3D_TARGET_FLUX) != 0;
-    const int variant = (h->counting ? 4 : 0) | (march ? 2 : 0) | (flux ? 1 : 0);
-    // as many workgroups as are resident at once (a workgroup that starts after the pool is empty only stages LDS and leaves)
-#ifndef MI3D_BLOCKS_PER_CU
-#define MI3D_BLOCKS_PER_CU(MARCH, COUNT) MI3D_WAVES(MARCH, COUNT)
-#endif
-    // the lean kernel (mi3d_kernel_lean.hip): radiance only, satellite views (column table or marched), at most two 3-D constituents,
-    // byte offsets of the voxel records within 32 bits (cameras, Rad_mrkind = 1, 3-D solver: through the event lists and the ray
-    // kernel's camera build).  Its builds (`mix`): 0 er3t's default scene -- one 1-D and one 3-D constituent, analytic phase functions --,
-    // 1 a second 3-D constituent, 2 (round 5) the general mixture: several 1-D constituents and / or TABULATED phase functions, in 1-D
-    // layers (func_ref_vs_cot's cloud slab, rtm/mca/util.py:153) or in voxels (the Mie branch as mca_atm.py:275-277 would write it)
-    const bool cam_ok = h->rad_kind == 1 && h->solver == MI3D_SOLVER_3D && h->kernel_choice == 0;
-    bool gen = h->np1d > 1 || h->tab3d_hi >= 0, tabs = h->tab3d_hi >= 0;
-    for (float a : h->apf1d) if (a >= 1.0f) { gen = true; tabs = true; }
-    static const bool force_gen = getenv("MI3D_FORCE_GEN") && atoi(getenv("MI3D_FORCE_GEN")) != 0;   // (measurements: the general-mixture builds on any scene)
-    if (force_gen) gen = true;
-    const int mix = gen ? 2 : (h->np3d > 1 ? 1 : 0);
-    // (tables that do not fit the LDS budget of fill_scene, or none loaded where a selector asks for one: the general kernel, which reads them from global memory)
-    const bool tabs_ok = !tabs || h->tab_n > 0;
-    // (tables the scene refers to, staged in LDS by the lean kernels when they fit the budget of fill_scene: mu, p, cdf and the bucket indices)
-    const size_t lds_tab = (gen && h->tab_n > 0) ? lean_tab_floats(h->nang, h->tab_n) * sizeof(float) : 0;
-    bool use_col = !thermal && !flux && h->nview > 0 && (h->rad_kind == 2 || cam_ok) && h->np3d <= 2 && tabs_ok &&
-                   (double)h->ny * h->vrow_f4 * 16.0 < 4.0e9 && h->kernel_choice != 1;
-    const size_t lds_col = (size_t)(h->nz + 2) * sizeof(LayerRec) + MI3D_MAX_VIEW * sizeof(ViewRec) + sizeof(DevCold);   // (+2: the lean loop's end records)
-    // the lean flux kernel (mi3d_kernel_flux.hip): flux / heating rates without radiance, the same scenes as the lean radiance kernel
-    bool use_fl = !thermal && flux && !((h->target & MI3D_TARGET_RADIANCE) && h->nview > 0) && h->np3d <= 2 && tabs_ok &&
-                  (double)h->ny * h->vrow_f4 * 16.0 < 4.0e9 && h->kernel_choice != 1 && h->nx < 65536 && h->ny < 65536 && h->nz < 65535;
-    TallyList TL, TL2;
-    std::memset(&TL, 0, sizeof(TL));
-    bool tl_two = h->overlap_sort != 0;
-    size_t lds_fl = (size_t)(h->nz + 2) * sizeof(LayerRec) + sizeof(DevCold);
-    // Tally records instead of atomics: bins of 2^shift tally cells, as many as one workgroup can sum in LDS in float64; the
-    // record lists take what the launch needs at the records per photon seen so far, at most 2^31 records and a quarter of the
-    // memory that is free (two lists of 8 bytes per record).  Not for short runs (the sort has a fixed cost) or tallies of more
-    // than 8192 bins (134 million tally cells).
-    auto size_tally_lists = [&](uint64_t nb_max) -> uint64_t {
-        if (!use_fl || !h->tally_lists || nphoton < 4096) return 0;
-        int shift = 10;
-        while (shift < 14 && ((size_t)16 << shift) <= (size_t)h->lds_max) ++shift;
-        const size_t ncell = h->flux_elems() + ((h->target & MI3D_TARGET_HEAT) ? h->heat_elems() : 0);   // (heating-rate cells follow the flux cells)
-        if ((double)ncell > 4.0e9) return 0;
-        const int nbins = (int)((ncell + ((size_t)1 << shift) - 1) >> shift);
-        if (nbins > 8192 || ((size_t)3 * nbins + 16 + 2 * kTlIds) * sizeof(uint32_t) + (size_t)8 * 1024 * sizeof(uint2) > (size_t)h->lds_max) return 0;
-        const int hist_wg = nbins > 1024 ? 1 : 0;   // (four histograms per workgroup of the photon loop would not fit its LDS any more)
-        const bool runs = h->tally_runs != 0 && h->nz <= 1022;   // (a run record holds its first level and its count in ten bits each)
-        const int nset = tl_two ? 2 : 1;
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = (size_t)8 << 30; }
-        free_b += (h->d_tl_rec.cap + h->d_tl_binned.cap + h->d_tl_rec2.cap + h->d_tl_binned2.cap) * sizeof(uint2) + (h->d_tl_runs.cap + h->d_tl_runs2.cap) * sizeof(float4);
-        // per photon, with a margin: records in all (what the sorted copy holds), records the loop writes one by one, run records.  Nothing
-        // known yet: a record per level and a half, every one of them written by the loop, a run for every kRunMin of them
-        const double tpp = h->tl_total_pp > 0.0 ? 1.15 * h->tl_total_pp : (h->tl_per_photon > 0.0 && !runs ? 1.15 * h->tl_per_photon : 1.5 * (h->nz + 1));
-        const double dpp = h->tl_per_photon > 0.0 ? 1.15 * h->tl_per_photon : tpp;
-        const double rpp = !runs ? 0.0 : h->tl_runs_pp > 0.0 ? 1.15 * h->tl_runs_pp + 0.05 : tpp / kRunMin;
-        const uint64_t waves = (uint64_t)h->num_cu * MI3D_FLUX_WAVES(h->counting != 0) * 4;
-        const uint64_t lim = ((uint64_t)1 << h->tl_cap_log2) - kTlChunk;
-        // the lists in all: a quarter of the memory that is free (the sorted copy once, records and runs once per set)
-        double nb = (double)nb_max;
-        const double bytes_pp = nset * (8.0 * tpp + 8.0 * dpp + 32.0 * rpp);
-        nb = std::min(nb, 0.25 * (double)free_b / bytes_pp);
-        auto cap_of = [&](double pp, uint64_t chunk, uint64_t have, double item_bytes) -> uint64_t {
-            uint64_t c = (uint64_t)(pp * nb) + (waves + 1) * chunk;
-            // (lists only grow, and by a quarter at least: the rates per photon creep upwards by a per cent from launch to launch, and every
-            //  step of a list that is not at its limit would free and allocate gigabytes -- seen as one run in three taking seconds.
-            //  A LARGE list that is near enough stays where it is: a launch more per run costs less than moving sixteen gigabytes.  A small one
-            //  moves: er3t's jobs of a few million photons come by the dozen, one size, and a list 30 % short made two launches of every one
-            //  of them -- 7.3 instead of 5.6 ms per job of 6e6 photons, profiles/r06/small_flux_jobs_one_launch.log)
-            if (have > 0 && (double)have >= (double)c) c = have;
-            else if (have > 0 && (double)have >= 0.7 * (double)c && (double)have * item_bytes >= 1.6e10) c = have;
-            else if (c > have && have > 0) c = std::max<uint64_t>(c, have + have / 4);
-            c = std::min<uint64_t>(c, lim);
-            c = std::max<uint64_t>(c, std::min<uint64_t>(have, lim));
-            return c / chunk * chunk;
-        };
-        uint64_t want_cap = cap_of(dpp, kTlChunk, h->d_tl_rec.cap, 8.0 * nset);
-        const uint64_t want_bcap = cap_of(tpp, kTlChunk, h->d_tl_binned.cap, 8.0 * nset);
-        const uint64_t want_rcap = runs ? std::max<uint64_t>(cap_of(rpp, kRunChunk, h->d_tl_runs.cap / 2, 32.0 * nset), 64 * kRunChunk) : 0;
-        if (want_cap < 64 * kTlChunk) return 0;
-        const size_t nwave_max = (size_t)waves;
-        const size_t wcap = std::max<size_t>(64, 4 * (size_t)(want_cap / kTlChunk) / nwave_max);
-        const size_t rwcap = runs ? std::max<size_t>(64, 4 * (size_t)(want_rcap / kRunChunk) / nwave_max) : 0;
-        const size_t nrow_max = (hist_wg ? nwave_max / 4 : nwave_max) * (runs ? 2 : 1);
-        const size_t nwords = (size_t)(want_cap / kTlChunk) + nwave_max * wcap + nwave_max + 2 * nrow_max * nbins + 2 * (size_t)nbins + 1 +
-                              (runs ? (size_t)(want_rcap / kRunChunk) + nwave_max * rwcap + nwave_max : 0);
-        static const bool tl_verbose = getenv("MI3D_TL_VERBOSE") != nullptr;
-        if (tl_verbose && (want_cap > h->d_tl_rec.cap || want_bcap > h->d_tl_binned.cap || 2 * want_rcap > h->d_tl_runs.cap || (tl_two && (want_cap > h->d_tl_rec2.cap || 2 * want_rcap > h->d_tl_runs2.cap))))
-            fprintf(stderr, "[mi3d tally lists] records %.3g (had %.3g), sorted copy %.3g (%.3g), runs %.3g (%.3g), sets %d; per photon: %.2f / %.2f / %.3f known %d\n", (double)want_cap, (double)h->d_tl_rec.cap,
-                    (double)want_bcap, (double)h->d_tl_binned.cap, (double)want_rcap, (double)h->d_tl_runs.cap / 2, nset, dpp, tpp, rpp, h->tl_total_pp > 0.0 ? 1 : 0);
-        // (a list that moves: nothing may still be on its way that reads the old one -- launches, sorts, and the sums that are kept back for the main
-        //  stream's next pause, whose description holds the old pointers: everything joined and waited for first)
-        if (want_cap > h->d_tl_rec.cap || want_bcap > h->d_tl_binned.cap || nwords > h->d_tl_words.cap || 2 * want_rcap > h->d_tl_runs.cap ||
-            (tl_two && (want_cap > h->d_tl_rec2.cap || want_bcap > h->d_tl_binned2.cap || nwords > h->d_tl_words2.cap || 2 * want_rcap > h->d_tl_runs2.cap)))
-            if (sync_streams(h) != hipSuccess) { (void)hipGetLastError(); return 0; }
-        int r = h->d_tl_rec.alloc(want_cap);
-        if (!r) r = h->d_tl_binned.alloc(want_bcap);
-        if (!r) r = h->d_tl_words.alloc(nwords);
-        if (!r) r = h->d_tl_cursor.alloc(kCtrStride);
-        if (!r) r = h->d_tl_stats.alloc(64 * 4);
-        if (!r && runs) r = h->d_tl_runs.alloc(2 * want_rcap);
-        if (!r && tl_two) r = h->d_tl_rec2.alloc(want_cap);
-        if (!r && tl_two) r = h->d_tl_binned2.alloc(want_bcap);
-        if (!r && tl_two) r = h->d_tl_words2.alloc(nwords);
-        if (!r && tl_two) r = h->d_tl_cursor2.alloc(kCtrStride);
-        if (!r && tl_two && runs) r = h->d_tl_runs2.alloc(2 * want_rcap);
-        if (!r && !h->h_tlctr && hipHostMalloc((void **)&h->h_tlctr, (size_t)4 * kEvSlots * sizeof(unsigned long long)) != hipSuccess) r = MI3D_EDEVICE;
-        if (r) {
-            (void)hipGetLastError(); h->d_tl_rec.release(); h->d_tl_binned.release(); h->d_tl_rec2.release(); h->d_tl_runs.release(); h->d_tl_runs2.release(); h->d_tl_binned2.release();
-            fprintf(stderr, "Warning [mi3d_run]: no device memory for the tally-record lists of this flux job (%.1f GB free); an atomic per level crossing instead (same results, slower).\n", (double)free_b / 1.0e9);
-            return 0;
-        }
-        auto lay_out = [&](TallyList &T, uint32_t *words, uint2 *rec, uint2 *binned, float4 *runs_p, unsigned long long *cursor) {
-            T.rec = rec; T.binned = binned;
-            T.chunk_fill = words;
-            T.wave_chunks = T.chunk_fill + want_cap / kTlChunk; T.wave_nchunk = T.wave_chunks + nwave_max * wcap;
-            T.whist = T.wave_nchunk + nwave_max; T.wbase = T.whist + nrow_max * nbins;
-            T.hist = T.wbase + nrow_max * nbins; T.bin_start = T.hist + nbins;
-            T.run_fill = T.bin_start + nbins + 1; T.run_chunks = T.run_fill + (runs ? want_rcap / kRunChunk : 0); T.run_nchunk = T.run_chunks + nwave_max * rwcap;
-            T.runs = runs ? runs_p : nullptr; T.run_cap = (unsigned)want_rcap; T.run_wcap = (int)rwcap;
-            T.hist_wg = hist_wg;
-            T.wcap = (int)wcap; T.nwave = (int)nwave_max;
-            T.cursor = cursor;
-            T.cap = (unsigned)want_cap; T.bcap = (unsigned)want_bcap; T.shift = shift; T.nbins = nbins;
-            // the compact histogram of a workgroup of the photon loop (hist_wg, with run records): the bins of the levels around the layers that
-            // are walked voxel by voxel, for the three planes and the heating cells -- merged where they touch; without run records: all bins
-            T.run_min = kRunMin;
-            for (int r = 0; r < 4; ++r) { T.cb_lo[r] = 1; T.cb_hi[r] = 0; T.cb_off[r] = 0; }
-            T.cb_lo[0] = 0; T.cb_hi[0] = nbins - 1; T.ncb = nbins;
-            int ks_lo = h->nz, ks_hi = -1;
-            for (int kq = 0; kq < h->nz && kq < (int)h->lay_host.size(); ++kq) if (h->lay_host[kq].flags & kLayStep3d) { ks_lo = std::min(ks_lo, kq); ks_hi = std::max(ks_hi, kq); }
-            if (hist_wg && runs && ks_hi >= ks_lo) {
-                const size_t ncol_ = (size_t)h->nx * h->ny, nlev_ = (size_t)h->nz + 1, nflux_ = 3 * nlev_ * ncol_;
-                std::vector<std::pair<int, int>> rg;
-                for (size_t pl = 0; pl < 3; ++pl) rg.emplace_back((int)(((pl * nlev_ + ks_lo) * ncol_) >> shift), (int)((((pl * nlev_ + ks_hi + 2) * ncol_) - 1) >> shift));
-                if (h->target & MI3D_TARGET_HEAT) rg.emplace_back((int)((nflux_ + (size_t)ks_lo * ncol_) >> shift), (int)((nflux_ + ((size_t)ks_hi + 1) * ncol_ - 1) >> shift));
-                std::sort(rg.begin(), rg.end());
-                std::vector<std::pair<int, int>> mg;
-                for (auto &q : rg) { if (!mg.empty() && q.first <= mg.back().second + 1) mg.back().second = std::max(mg.back().second, q.second); else mg.push_back(q); }
-                int off = 0;
-                for (size_t r = 0; r < 4; ++r) {
-                    if (r < mg.size()) { T.cb_lo[r] = mg[r].first; T.cb_hi[r] = std::min(mg[r].second, nbins - 1); T.cb_off[r] = off; off += T.cb_hi[r] - T.cb_lo[r] + 1; }
-                    else { T.cb_lo[r] = 1; T.cb_hi[r] = 0; T.cb_off[r] = 0; }
-                }
-                T.ncb = std::max(off, 1);
-                T.run_min = 1;
-            }
-        };
-        lay_out(TL, h->d_tl_words.p, h->d_tl_rec.p, h->d_tl_binned.p, h->d_tl_runs.p, h->d_tl_cursor.p);
-        TL2 = TL;
-        // the second set: lists, counters, cursor and sorted copy of its own
-        if (tl_two) lay_out(TL2, h->d_tl_words2.p, h->d_tl_rec2.p, h->d_tl_binned2.p, h->d_tl_runs2.p, h->d_tl_cursor2.p);
-        return want_cap;
-    };
-    if (use_fl) {
-        use_col = false;
-        if ((rc = h->d_tldesc.alloc((size_t)64 * sizeof(TallyList)))) return rc;
-        if (!h->h_tldesc && hipHostMalloc((void **)&h->h_tldesc, (size_t)64 * sizeof(TallyList)) != hipSuccess) return fail(MI3D_EDEVICE, "no pinned memory for the tally-list descriptions");
-        // Two streams pay where something runs beside the sort: a run long enough for four launches of eight million photons (a run of 4e7 alone: +7 %;
-        // 1e7 / 2e7 in two or three launches: -2.5 %, tools/small_runs.py), or a run that follows another whose tallies nobody has looked at in between
-        // (runs queued back to back: +19 % at 5e6 photons a run).  A small run whose tallies are read before the next one -- er3t's jobs of a few
-        // million photons, one by one -- only pays for the launches' tails and the hops between the streams: one stream.
-        if (tl_two && h->overlap_sort < 2 && nphoton < ((uint64_t)1 << 25) && h->runs_unread == 0) tl_two = false;   // (before the lists are sized: no second set for such a run; "overlap_sort" 2: two streams whatever the run)
-        // (the stream and its events only where they are used: every stream more of a process shares the device's few hardware queues with the
-        //  others -- two handles that each kept an idle sort stream ran their jobs 12 % slower side by side, tools/time_dropin.py)
-        if (tl_two && !h->tl_stream && hipStreamCreateWithFlags(&h->tl_stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); tl_two = false; }
-        for (int q = 0; q < 2 && tl_two; ++q) {
-            if (!h->tl_filled[q] && hipEventCreateWithFlags(&h->tl_filled[q], hipEventDisableTiming) != hipSuccess) tl_two = false;
-            if (tl_two && !h->tl_sorted[q] && hipEventCreateWithFlags(&h->tl_sorted[q], hipEventDisableTiming) != hipSuccess) tl_two = false;
-            if (tl_two && !h->tl_scattered[q] && hipEventCreateWithFlags(&h->tl_scattered[q], hipEventDisableTiming) != hipSuccess) tl_two = false;
-        }
-        // (nothing known about the scene's records per photon: lists for a pilot launch of two million photons -- sized by the guess "a record and a half
-        //  per level, a run for every three" they would take tens of gigabytes -- and the right size after it, below)
-        const bool tl_pilot = !(h->tl_total_pp > 0.0) && nphoton > ((uint64_t)1 << 21);
-        if (size_tally_lists(tl_pilot ? (uint64_t)1 << 21 : std::min<uint64_t>(nphoton, h->batch))) lds_fl += TL.hist_wg ? ((size_t)TL.ncb + 3) / 4 * 16 : (size_t)TL.nbins * 16;   // (a histogram per wave, or one for the workgroup)
-        lds_fl += (size_t)4 * 128 * sizeof(float4) + (size_t)4 * kTlStage * sizeof(uint2);   // the waves' run records and staged tallies
-        lds_fl += lds_tab;                                                                   // ... and the phase tables behind them
-        if (!TL.cap) tl_two = false;
-        // (one stream after runs on two: the shared sorted copy and the first set of lists are free once the sorts before are through)
-        if (!tl_two && TL.cap) HIPCHK(tl_join(h));
-    }
-    // marched views (and cameras) of the lean build: by k_rays from event lists; a scene whose cell numbers do not fit the records' 16 bits goes
-    // to the general kernel
-    const bool can_split = march && h->nx < 65536 && h->ny < 65536 && h->nz < 65536;
-    if ((march || h->rad_kind == 1) && !can_split) use_col = false;
-    bool split = use_col && march;
-    // cameras in the cyclic domain: the periodic images of a camera are served by the ray kernel's camera build.  What keeps a camera job
-    // from it: kernel choice 1 / 2, more than one 1-D or two 3-D constituents, voxel records beyond 4 GB.  Asked for explicitly
-    // ("cam_images" > 0) such a job is refused; left to the default (-1) it runs with the nearest image alone and says so.
-    auto cam_fallback = [&](const char *why) -> int {
-        if (h->cam_images > 0)
-            return fail(MI3D_EUNSUP, "cam_images=%d: the periodic images of a camera are served by the ray kernel only, and this job cannot use it (%s)", h->cam_images, why);
-        if (h->cam_images < 0 && !h->cam_warned) {
-            fprintf(stderr, "Warning [mi3d_run]: this camera job cannot use the ray kernel (%s): the NEAREST periodic image of the camera alone is served -- "
-                            "lines of sight that leave the domain sideways miss what its continuation adds (set \"cam_images\" to 0 to say so yourself).\n", why);
-            h->cam_warned = true;
-        }
-        return MI3D_OK;
-    };
-    if (h->rad_kind == 1 && !split) {
-        // (the reason from the predicates that cleared use_col / split above)
-        const char *why = h->kernel_choice != 0 ? "kernel choice 1" : h->solver != MI3D_SOLVER_3D ? "cameras are served under the 3-D solver only" : h->np3d > 2 ? "more than two 3-D constituents"
-                          : flux ? "flux together with radiance" : !tabs_ok ? "phase tables too large for the LDS" : !can_split ? "cell numbers beyond the event records' 16 bits"
-                          : !((double)h->ny * h->vrow_f4 * 16.0 < 4.0e9) ? "voxel records beyond 4 GB" : "a scene the lean photon loop does not serve";
-        if ((rc = cam_fallback(why))) return rc;
-    }
+    // ---- the room the route needs: tally-record lists (flux loop), event lists (marched views), entry records, second sets
+    TallyList TL[2] = {};
+    bool tl_two = false, two_sets = false;
+    size_t lds_fl = 0;
     uint64_t ev_cap = 0;
-    // Capacity of each XCD's event list.  Nothing known about the scene yet: room for a pilot launch.  A short run: room for every
-    // event of the run on ONE list (64 per photon: the workgroups that start first take most of its photons).  A long one: what
-    // the run's events need at the number per photon seen so far, twice over (the lists fill unevenly), at most 2^ev_cap_log2
-    // records -- and never more than a quarter of the memory that is free now (other handles, a host framework and smaller parts
-    // share the device).  Lists only grow (mi3d_set_tuning "evcap_log2" and a job without marched views release them).
-    // (two sets of lists and a stream of its own for the ray kernels, so that they run beside the next launch's photon loop)
-    bool two_sets = h->overlap_rays && split;
-    if (two_sets && !h->rays_stream && hipStreamCreateWithFlags(&h->rays_stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); two_sets = false; }
-    for (int q = 0; q < 2 && two_sets; ++q) {
-        if (!h->set_emit[q] && hipEventCreateWithFlags(&h->set_emit[q], hipEventDisableTiming) != hipSuccess) two_sets = false;
-        if (two_sets && !h->set_rays[q] && hipEventCreateWithFlags(&h->set_rays[q], hipEventDisableTiming) != hipSuccess) two_sets = false;
-    }
-    auto size_lists = [&]() -> int {
-        const double per_rec = (double)kEvBlockF4 * 16.0 / 64.0 + (h->sfc_lambert_only ? 0.0 : 8.0);
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = (size_t)8 << 30; }
-        free_b += h->d_events.cap * sizeof(float4) + h->d_hvlist.cap * sizeof(unsigned long long);   // (what this handle holds already is reused)
-        free_b += h->d_events2.cap * sizeof(float4) + h->d_hvlist2.cap * sizeof(unsigned long long);
-        const int nset = two_sets ? 2 : 1;
-        const uint64_t cap_mem = (uint64_t)(0.25 * (double)free_b / (8.0 * per_rec * nset));
-        const uint64_t cap_max = (uint64_t)1 << h->ev_cap_log2;
-        uint64_t want_cap = std::min<uint64_t>(cap_max, 64 * nphoton + 65536);
-        if (h->ev_per_photon > 0.0)
-            want_cap = std::min<uint64_t>(want_cap, std::max<uint64_t>((uint64_t)(4.0 * h->ev_per_photon * (double)nphoton / h->n_xcd), 65536));
-        else want_cap = std::min<uint64_t>(want_cap, (uint64_t)1 << 22);
-        want_cap = std::max<uint64_t>(want_cap, std::min<uint64_t>(h->d_events.cap / ((size_t)8 * kEvBlockF4) * 64, cap_max));
-        want_cap = std::min<uint64_t>(want_cap, cap_mem);
-        want_cap &= ~(uint64_t)63;      // (the records stand in blocks of 64: ev_index)
-        // (an allocation that fails although the device reported the room -- fragmentation, another process -- is tried again at half the
-        //  size: launches are sized to the lists, so small lists cost launches, not results; below 65 536 records per list: the general kernel)
-        int r = MI3D_OK;
-        for (;;) {
-            r = MI3D_OK;
-            if (want_cap < 65536) r = fail(MI3D_EDEVICE, "no memory for event lists");
-            if (!r) r = h->d_events.alloc((size_t)8 * ev_list_f4(want_cap));
-            if (!r) r = h->d_evctr.alloc(kCtrWords * kCtrStride);
-            if (!r && !h->sfc_lambert_only) r = h->d_hvlist.alloc((size_t)8 * want_cap);
-            if (!r && two_sets) r = h->d_events2.alloc((size_t)8 * ev_list_f4(want_cap));
-            if (!r && two_sets) r = h->d_evctr2.alloc(kCtrWords * kCtrStride);
-            if (!r && two_sets && !h->sfc_lambert_only) r = h->d_hvlist2.alloc((size_t)8 * want_cap);
-            if (!r && !h->h_evctr && hipHostMalloc((void **)&h->h_evctr, (size_t)kEvSlots * 9 * kCtrStride * sizeof(unsigned long long)) != hipSuccess) r = MI3D_EDEVICE;
-            if (!r || want_cap < 65536) break;
-            (void)hipGetLastError();
-            h->d_events.release(); h->d_hvlist.release(); h->d_events2.release(); h->d_hvlist2.release();
-            want_cap = (want_cap / 2) & ~(uint64_t)63;
-        }
-        if (r) {
-            (void)hipGetLastError();
-            fprintf(stderr, "Warning [mi3d_run]: no device memory for the event lists of the marched views (%.1f GB free); the general kernel marches them inside its photon loop (same results, slower).\n", (double)free_b / 1.0e9);
-            return r;
-        }
-        ev_cap = want_cap;
-        h->cold_host.ev_list = h->d_events.p; h->cold_host.ev_ctr = h->d_evctr.p; h->cold_host.ev_cap = (int)ev_cap;
-        h->cold_host.hv_list = h->sfc_lambert_only ? nullptr : h->d_hvlist.p;
-        return MI3D_OK;
-    };
-    if (split) {
-        if (size_lists() != MI3D_OK) {
-            // no room for the lists: the general kernel marches the rays inside its photon loop instead (same results, slower) -- except for
-            // a camera that was to see its periodic images: the general kernel serves the nearest one only
-            h->d_events.release(); h->d_hvlist.release(); h->d_events2.release(); h->d_hvlist2.release();
-            split = false; use_col = false; two_sets = false;
-            if (h->rad_kind == 1) {
-                if (h->cam_images > 0) return fail(MI3D_EDEVICE, "no device memory for the event lists of a camera job with cam_images=%d (the general kernel serves the nearest image only)", h->cam_images);
-                if ((rc = cam_fallback("no device memory for its event lists"))) return rc;
-            }
-        }
-    } else if (h->d_events.p) {   // this job needs no lists: what an earlier one held goes back to the device
-        HIPCHK(sync_streams(h));
-        h->d_events.release(); h->d_hvlist.release(); h->d_events2.release(); h->d_hvlist2.release();
-    }
-    // (the general mixture's common scene -- one Rayleigh 1-D constituent, one 3-D constituent with tables -- has a build of its own where the column
-    //  view serves: k_transport_lean<.,.,0,3>)
-    static const bool no_mix3 = getenv("MI3D_NO_MIX3") && atoi(getenv("MI3D_NO_MIX3")) != 0;   // (measurements)
-    const int mix_lean = (mix == 2 && !split && !no_mix3 && (S.target & kTargetRayleigh1d) != 0 && h->np3d == 1) ? 3 : mix;
-    {
-        char nm[96];
-        if (use_fl) snprintf(nm, sizeof(nm), TL.cap ? "k_transport_flux<%d,%d,%d> + k_tl_scatter + k_tl_sum" : "k_transport_flux<%d,%d,%d>", h->counting ? 1 : 0, h->solver == MI3D_SOLVER_P3D ? 1 : 0, mix);
-        else if (use_col) snprintf(nm, sizeof(nm), split ? "k_transport_lean<%d,%d,2,%d> + k_rays" : "k_transport_lean<%d,%d,0,%d>", h->counting ? 1 : 0,
-                              h->solver == MI3D_SOLVER_P3D ? 1 : 0, mix_lean);
-        else snprintf(nm, sizeof(nm), thermal ? "k_transport<%d,%d,%d,%d> [thermal]" : "k_transport<%d,%d,%d,%d>", h->counting ? 1 : 0, march ? 1 : 0, flux ? 1 : 0,
-                      h->solver == MI3D_SOLVER_P3D ? 1 : 0);
-        h->last_kernel = nm;
-        // A job that was not sent to the general loop by its caller (mi3d_set_kernel 1) but landed there says so, once per handle: the loop of
-        // round 1 serves it correctly and at a fraction of the lean loops' speed (bench.py's `general_kernel` leg has the figure)
-        if (!use_fl && !use_col && h->kernel_choice == 0 && !h->general_warned && nphoton >= 4096 && !thermal) {   // (thermal jobs: the general loop by design)
-            const bool both = flux && (h->target & MI3D_TARGET_RADIANCE) && h->nview > 0;
-            const char *why = both ? "flux (or heating rates) TOGETHER with radiance: two jobs, one per target, as er3t's mcarats_ng submits them (mcarats.py:238-245), each take a lean loop"
-                              : h->np3d > 2 ? "more than two 3-D constituents" : !tabs_ok ? "phase tables too large for the LDS (or none loaded where a selector asks for one)"
-                              : !((double)h->ny * h->vrow_f4 * 16.0 < 4.0e9) ? "voxel records beyond 4 GB" : (march || h->rad_kind == 1) && !split ? "no room for the event lists of the marched views, or cell numbers beyond their 16 bits"
-                              : "a scene the lean photon loops do not serve";
-            fprintf(stderr, "Warning [mi3d_run]: this job runs on the general photon loop (k_transport), not on a lean one: %s.  Same results, a third to a half of the speed.\n", why);
-            h->general_warned = true;
-        }
-    }
-    static const int flux_wg_env = getenv("MI3D_FLUX_GRID_WG") ? atoi(getenv("MI3D_FLUX_GRID_WG")) : 0;   // (measurements: workgroups of the flux loop per CU, 1 ... 4)
-    const uint64_t cap = (uint64_t)h->num_cu * (use_fl ? (flux_wg_env > 0 && flux_wg_env <= MI3D_FLUX_WAVES(false) ? flux_wg_env : MI3D_FLUX_WAVES(h->counting != 0)) : use_col ? MI3D_LEAN_WAVES(h->counting != 0, march) : MI3D_BLOCKS_PER_CU(march, h->counting != 0));
-
-    // Entry records (k_entry, mi3d_kernel_lean.hip): the lean loop's builds without rays inside them take new photons where their
-    // first voxel walk begins.  48 bytes per photon of a launch, never more than half of the memory that is free: without them
-    // (no room, "entry_records" 0) the photons are launched inside the loop as before.
-    bool use_entry = false;
-#if MI3D_LEAN_FAST
-    if ((use_col || use_fl) && h->entry_records && h->nx < 65536 && h->ny < 65536 && h->nz < 32768) {
-        const size_t need = entry_f4((size_t)std::min<uint64_t>(nphoton, h->batch));
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = (size_t)8 << 30; }
-        free_b += h->d_entry.cap * sizeof(float4);
-        if (need <= h->d_entry.cap || need * sizeof(float4) <= free_b / 2) {
-            if (h->d_entry.alloc(need) == MI3D_OK) use_entry = true;
-            else (void)hipGetLastError();
-        }
-    }
-#endif
-    h->cold_host.entry = use_entry ? h->d_entry.p : nullptr;
-    // The pre-pass of a launch (photon order, entry records) on a stream of its own beside the photon loop of the launch before: a second set
-    // of what it writes.  (Not together with the second set of event lists of "overlap_rays": one spare DevCold.)
-    // Where the loop leaves room on a CU: the flux loop (four waves per SIMD) and the event-writing loop of jobs with marched views (+4 % for a flux
-    // run alone, +2.6 % with nine views).  The column / tally-window loop holds six waves per SIMD and most of the LDS: there the pre-pass only finds
-    // room in the loop's tail, and what runs beside it costs the loop more than it saves (-4 % on the 480 x 480 nadir bench, -3 % on 128 x 128:
-    // profiles/r05/ab_overlap_pre.log).
-    // A run of a few million photons that is read before the next one has no loop before it to hide behind and pays for the hop between the streams.
-    static const int pre_nadir = getenv("MI3D_PRE_NADIR") ? atoi(getenv("MI3D_PRE_NADIR")) : 0;     // (measurements: the pre-pass beside the column-view loop too; 2: on a stream of the lowest priority)
-    bool pre_two = h->overlap_pre && !two_sets && (sorted || use_entry) && (use_fl || (use_col && split) || (use_col && pre_nadir > 0)) && (h->overlap_pre > 1 || nphoton >= ((uint64_t)1 << 22) || h->runs_unread > 0);   // ("overlap_pre" 2: whatever the run)
+    if (plan.loop == Loop::Flux && (rc = flux_lists(h, plan, nphoton, TL, tl_two, lds_fl))) return rc;
+    if (h->rad_kind == 1 && plan.loop != Loop::ColumnRays && (rc = cam_fallback(h, plan.why))) return rc;
+    if ((rc = event_lists(h, plan, nphoton, ev_cap, two_sets))) return rc;
+    name_route(h, plan, TL[0].cap != 0, nphoton);
+    const uint64_t cap = (uint64_t)h->num_cu * (plan.loop == Loop::Flux ? MI3D_FLUX_WAVES(h->counting != 0)
+                                                : plan.loop == Loop::General ? MI3D_BLOCKS_PER_CU(plan.march, h->counting != 0)
+                                                                             : MI3D_LEAN_WAVES(h->counting != 0, plan.march));
+    const bool use_entry = use_entry_records(h, plan, nphoton);   // (fill_scene has cleared cold_host.entry)
+    const bool pre_two = pre_second_set(h, plan, use_entry, two_sets, nphoton);
     // (a launch of a kind that MAY be followed by a two-stream launch on this handle leaves the events the latter waits for, also when it runs on one stream itself)
-    const bool pre_track = h->overlap_pre && (sorted || use_entry);
+    const bool pre_track = h->overlap_pre && (plan.sorted || use_entry);
     h->runs_unread++;
-    if (pre_two && !h->pre_stream) {
-        int pr_least = 0, pr_greatest = 0;
-        (void)hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest);
-        const hipError_t ec = pre_nadir > 1 ? hipStreamCreateWithPriority(&h->pre_stream, hipStreamNonBlocking, pr_least) : hipStreamCreateWithFlags(&h->pre_stream, hipStreamNonBlocking);
-        if (ec != hipSuccess) { (void)hipGetLastError(); pre_two = false; }
-    }
-    for (int q = 0; q < 2 && pre_two; ++q) {
-        if (!h->pre_done[q] && hipEventCreateWithFlags(&h->pre_done[q], hipEventDisableTiming) != hipSuccess) pre_two = false;
-        if (pre_two && !h->pre_loop[q] && hipEventCreateWithFlags(&h->pre_loop[q], hipEventDisableTiming) != hipSuccess) pre_two = false;
-    }
-    if (pre_two && sorted && (h->d_order2.alloc(h->d_order.cap) != MI3D_OK || h->d_cursor2.alloc(kMaxTiles) != MI3D_OK)) { (void)hipGetLastError(); pre_two = false; }
-    if (pre_two && use_entry && h->d_entry2.cap < h->d_entry.cap) {   // (a second set of the same size, where half of the free memory holds it)
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
-        free_b += h->d_entry2.cap * sizeof(float4);
-        if (h->d_entry.cap * sizeof(float4) > free_b / 2 || h->d_entry2.alloc(h->d_entry.cap) != MI3D_OK) { (void)hipGetLastError(); pre_two = false; }
-    }
-    // (a job that does not use the second set gives back what is large: a hipFree waits for the device -- not for every small job)
-    if (!pre_two && (h->d_entry2.cap * sizeof(float4) + h->d_order2.cap * sizeof(uint32_t)) > ((size_t)256 << 20)) { h->d_order2.release(); h->d_entry2.release(); }
-    // The tally window of the lean loop (DevCold::tile_end ...): for the column view of a satellite image with one pixel per column,
-    // when the launch is worked through tile by tile.  Its place relative to a tile: where the direct beam that enters the top of
-    // the atmosphere above the tile reaches the height of the clouds, centred.
-    h->cold_host.tile_end = nullptr; h->cold_host.win_tc = 0; h->cold_host.win_ntx = 0; h->cold_host.win_ntile = 0; h->cold_host.win_off = 0u;
-    if (use_col && window_wanted(h) && sorted && h->nx < 32768 && h->ny < 32768 && h->nx >= kWin && h->ny >= kWin && h->z_cloud >= 0.0 && h->cold_host.sdz < 0.0f) {
-        const double ztoa = h->zgrd[h->nz];
-        // (under the independent-pixel approximation a photon never leaves the column it was launched above)
-        const double way = h->solver == MI3D_SOLVER_IPA ? 0.0 : (ztoa - h->z_cloud) / std::fabs((double)h->cold_host.sdz);
-        const int margin = (kWin - std::min(G.tcols, kWin)) / 2 - std::max(0, G.tcols - kWin) / 2;   // (a tile wider than the window: its middle)
-        auto wrap = [](long v, int n) { v %= n; if (v < 0) v += n; return (unsigned)v; };
-        // (the centring was checked by moving the window about: ±12 columns change the share of the tallies it catches by less than a
-        //  point, ±24 cost ten -- profiles/r04/win_offset_probe.log)
-        const unsigned ox = wrap(std::lround(h->cold_host.sdx * way / h->dx) - margin, h->nx);
-        const unsigned oy = wrap(std::lround(h->cold_host.sdy * way / h->dy) - margin, h->ny);
-        h->cold_host.tile_end = h->d_cursor.p;
-        h->cold_host.win_tc = G.tcols; h->cold_host.win_ntx = G.ntx; h->cold_host.win_ntile = ntile;
-        h->cold_host.win_off = ox | (oy << 16);
-    }
-    // Radiance tallies go to an accumulation image with one pixel per 128-byte line and are folded into the tally buffer (the
-    // library's own or the caller's) after the last launch of this call -- where the tallies are atomics from the photon loop itself
-    // ("rad_spread" -1, the default).  Not where the ray kernel makes them (marched views, cameras): its tallies spread over the images
-    // of several views or a wide camera image, and the compact image (8 bytes per pixel: 1.8 MB per view on the 480 x 480 scene, at home
-    // in the L2s) serves them better than 29 MB per view -- nine views 2.83 -> 3.11e8 photons/s, the camera +1 %
-    // (profiles/r04/ab_rad_line_density.log).  With the tally window either image does (2.79 / 2.78e9): the accumulation image stays.
-    // Rows of the accumulation image an ODD number of 4 KiB pages apart (32 pixels of kRadLine * 8 bytes a page).  The atomics of an
-    // XCD go to the pixels of one tile of columns, a few rows of which are busy at any time; with rows a multiple of four pages
-    // apart they meet in a few of the L2's sixteen channels: 128 pixels per row (4 pages) 1.93e9 photons/s against 2.47e9 at 5 pages
-    // and 2.52 at 4.5; 256 (8 pages) 1.63 against 2.25 at 9; 64 pixels padded to 4 pages 1.19 against 2.5; 512 (16) 2.11 against 2.25
-    // at 17.  Odd page counts came within 2 % of the best stride on every size tried (192 ... 512 pixels: 7, 9, 11, 13, 15, 17
-    // pages); half pages are good on some sizes and the worst choice on others (15.5 and 16.5 pages: 1.96 and 2.00 against 2.28).
-    // profiles/r04/stride_probe4.log ... stride_probe6.log, ab_rad_row_pad*.log; tools/stride_probe*.py
-    int rad_row = h->nxr + (h->rad_row_pad >= 0 ? h->rad_row_pad : 0);
-    if (h->rad_row_pad < 0) rad_row = 32 * (((h->nxr + 31) / 32) | 1);
-    const size_t acc_elems = (size_t)h->nview * h->nyr * rad_row;
-    const bool spread = (h->target & MI3D_TARGET_RADIANCE) && h->nview > 0 && h->rad_spread != 0 && !(h->rad_spread < 0 && use_col && split) &&
-                        (double)acc_elems * kRadLine * sizeof(tally_t) <= 1.0e9 && (double)acc_elems * kRadLine < 2147483647.0;
-    if (spread) {
-        const size_t need = acc_elems * kRadLine;
-        if (h->d_rad_acc.cap < need || !h->d_rad_acc.p) {
-            if ((rc = h->d_rad_acc.alloc(need))) return rc;
-            HIPCHK(hipMemsetAsync(h->d_rad_acc.p, 0, need * sizeof(tally_t), h->stream));
-        }
-        S.rad = h->d_rad_acc.p; S.rad_stride = kRadLine; S.rad_row = rad_row;
-    }
-    h->cold_host.cam_images = (unsigned)(split ? (h->cam_images < 0 ? 2 : h->cam_images) : 0);
-
+    set_tally_window(h, plan);
+    int rad_row = 0;
+    if ((rc = rad_acc_image(h, plan, S, rad_row))) return rc;
+    h->cold_host.cam_images = (unsigned)(plan.loop == Loop::ColumnRays ? (h->cam_images < 0 ? 2 : h->cam_images) : 0);
     HIPCHK(upload_cold(h, two_sets, pre_two));
-    // With two sets the time of a run is the span from its first launch to the end of its last ray kernel (one pair of events on the
-    // main stream, which joins the rays' stream at the end); launches that overlap cannot be timed one by one
+
+    // ---- the launches.  With two sets the time of a run is the span from its first launch to the end of its last ray kernel (one pair of
+    // events on the main stream, which joins the rays' stream at the end); launches that overlap cannot be timed one by one
     hipEvent_t run_e0 = nullptr;
     // (every way out of this function that still owns run_e0 is an error exit of a run on two streams: the event goes, and what is queued on
     //  the sort / pre-pass / rays streams is waited for -- ADVICE r5: several early returns left both behind)
     struct RunGuard { hipEvent_t &e; mi3d_solver *h; ~RunGuard() { if (e) { (void)hipEventDestroy(e); e = nullptr; (void)sync_streams(h); } } } run_guard{run_e0, h};
-    if (!use_fl) tl_two = false;
     const bool run_timed = two_sets || tl_two;   // (kernels on two streams: the run is timed as a whole, not launch by launch)
     if (run_timed) { HIPCHK(hipEventCreate(&run_e0)); HIPCHK(hipEventRecord(run_e0, h->stream)); }
     uint64_t ilaunch = 0;
-
-    // equal launches (a short last one would be mostly tail).  With k_rays a launch is as many photons as the event lists hold
-    // at the number of events per photon seen so far (twice the room: the lists fill unevenly); the first launch of a handle is a
-    // pilot of 65 536 photons.
     const uint64_t nlaunch = (nphoton + h->batch - 1) / h->batch;
     uint64_t per = (nphoton + nlaunch - 1) / nlaunch;
     for (uint64_t done = 0; done < nphoton; done += per) {
-        if (split) {
-            if ((rc = ev_collect(h, ev_cap, false))) { return rc; }
-            const uint64_t room = photons_that_fit(ev_cap, h->ev_per_photon, h->n_xcd);
-            const uint64_t left = nphoton - done, want_n = std::max<uint64_t>(std::min<uint64_t>(room, h->batch), 64);
-            const uint64_t nl = (left + want_n - 1) / want_n;
-            per = (left + nl - 1) / nl;
-        }
-        if (TL.cap) {
-            // as many photons as the record list holds at the records per photon seen so far
-            if ((rc = tl_collect(h, false))) return rc;
-            const uint64_t waves = (uint64_t)h->num_cu * MI3D_FLUX_WAVES(h->counting != 0) * 4;
-            // (what each of the three lists holds at its rate per photon seen so far: the loop's records, the sorted copy, the run records)
-            auto room_of = [&](uint64_t cap_, uint64_t chunk, double pp_) -> uint64_t {
-                return (uint64_t)((double)(cap_ > 2 * waves * chunk ? cap_ - waves * chunk : cap_ / 2) / pp_);
-            };
-            const double tpp = h->tl_total_pp > 0.0 ? 1.15 * h->tl_total_pp : (h->tl_per_photon > 0.0 && !TL.run_cap ? 1.15 * h->tl_per_photon : 1.5 * (h->nz + 1));
-            uint64_t room = room_of(TL.cap, kTlChunk, h->tl_per_photon > 0.0 ? 1.15 * h->tl_per_photon : tpp);
-            room = std::min(room, room_of(TL.bcap, kTlChunk, tpp));
-            if (TL.run_cap) room = std::min(room, room_of(TL.run_cap, kRunChunk, h->tl_runs_pp > 0.0 ? 1.15 * h->tl_runs_pp + 0.05 : tpp / kRunMin));
-            const uint64_t left = nphoton - done, want_n = std::max<uint64_t>(std::min<uint64_t>(room, h->batch), 4096);
-            uint64_t nl = (left + want_n - 1) / want_n;
-            // (the sort beside the next photon loop: a run in tl_split launches at least, of eight million photons or more -- all but the last sort are hidden)
-            if (tl_two && done == 0) nl = std::max<uint64_t>(nl, std::min<uint64_t>((uint64_t)h->tl_split, nphoton >> 23));
-            else if (tl_two) nl = std::max<uint64_t>(nl, std::min<uint64_t>((left + per - 1) / std::max<uint64_t>(per, 1), (uint64_t)h->tl_split));
-            nl = std::max<uint64_t>(nl, 1);
-            per = (left + nl - 1) / nl;
-            static const bool tl_verbose2 = getenv("MI3D_TL_VERBOSE") != nullptr;
-            if (tl_verbose2) fprintf(stderr, "[mi3d launch] left %.4g room %.4g (rec %.4g sorted %.4g runs %.4g) caps %u %u %u pp %.3f %.3f %.4f two %d -> %llu launches\n", (double)left, (double)room,
-                                     (double)room_of(TL.cap, kTlChunk, h->tl_per_photon > 0.0 ? 1.15 * h->tl_per_photon : tpp), (double)room_of(TL.bcap, kTlChunk, tpp),
-                                     TL.run_cap ? (double)room_of(TL.run_cap, kRunChunk, h->tl_runs_pp > 0.0 ? 1.15 * h->tl_runs_pp + 0.05 : tpp / kRunMin) : 0.0, TL.cap, TL.bcap, TL.run_cap,
-                                     h->tl_per_photon, h->tl_total_pp, h->tl_runs_pp, (int)tl_two, (unsigned long long)nl);
-        }
+        if ((rc = launch_photons(h, plan, ev_cap, TL[0], tl_two, nphoton, done, per))) return rc;
         const uint64_t nb = std::min<uint64_t>(per, nphoton - done), off = photon_offset + done;
         if (h->pending.size() >= 64 && (rc = drain_events(h))) return rc;
         HIPCHK(hipMemsetAsync(h->d_next.p, 0, 8 * kCtrStride * sizeof(unsigned long long), h->stream));
-        // ---- the pre-pass: photon order and entry records of this launch (set pset; with two sets on their own stream, behind the photon loop
-        //      that read the set last and beside the one that is running)
         const int pset = pre_two ? (int)(h->pre_no & 1) : 0;
-        hipStream_t const ps = pre_two ? h->pre_stream : h->stream;
-        uint32_t *const ord = pset ? h->d_order2.p : h->d_order.p;
-        float4 *const ent = pset ? h->d_entry2.p : h->d_entry.p;
-        {
-            hipError_t eb = hipSuccess;
-            // (set pset is free once the photon loop of the launch that read it last is through -- whichever stream arrangement that launch
-            //  had: a one-stream launch records pre_loop[0] too, below -- and the histogram / tile scratch the two sets share once the last
-            //  pre-pass on the main stream is: ADVICE r5, a two-stream run queued straight behind a one-stream run)
-            if (pre_two && h->pre_used[pset]) eb = hipStreamWaitEvent(ps, h->pre_loop[pset], 0);
-            if (eb == hipSuccess && pre_two && h->pre_main_used) { eb = hipStreamWaitEvent(ps, h->pre_main, 0); h->pre_main_used = false; }
-            if (eb == hipSuccess && sorted) eb = launch_bins(h, ps, G, ntile, seed, off, nb, ord, pset ? h->d_cursor2.p : h->d_cursor.p);
-            if (eb == hipSuccess && use_entry)   // the photons of this launch up to their first voxel walk
-                eb = launch_entry(h, ps, S, nb, seed, off, sorted ? (const uint32_t *)ord : (const uint32_t *)nullptr, ent);
-            if (eb == hipSuccess && pre_two) eb = hipEventRecord(h->pre_done[pset], ps);
-            if (eb == hipSuccess && pre_track && !pre_two) {
-                if (!h->pre_main) eb = hipEventCreateWithFlags(&h->pre_main, hipEventDisableTiming);
-                if (eb == hipSuccess) { eb = hipEventRecord(h->pre_main, h->stream); h->pre_main_used = true; }
-            }
-            if (eb == hipSuccess && pre_two) eb = hipStreamWaitEvent(h->stream, h->pre_done[pset], 0);
-            if (eb != hipSuccess) { (void)sync_streams(h); return fail(MI3D_EDEVICE, "photon order / entry records: %s", hipGetErrorString(eb)); }
-        }
+        mi3d_solver::PreSet &PS = h->pre[pset];
+        const hipError_t eb = launch_pre(h, plan, pset, pre_two, pre_track, use_entry, S, nb, seed, off);
+        if (eb != hipSuccess) { (void)sync_streams(h); return fail(MI3D_EDEVICE, "photon order / entry records: %s", hipGetErrorString(eb)); }
         DevScene Sl = S;
         if (pset) Sl.cold = h->d_cold.p + 1;   // (this launch's set of pre-pass buffers)
-        const uint64_t want = (nb + tb - 1) / tb;
+        const uint64_t want = (nb + 255) / 256;
         const unsigned grid = (unsigned)(want < cap ? want : cap);
         hipEvent_t e0 = nullptr, e1 = nullptr;
-        hipError_t err = hipSuccess;
-        if (!run_timed) {
-            err = hipEventCreate(&e0);
-            if (err == hipSuccess) err = hipEventCreate(&e1);
-            if (err == hipSuccess) err = hipEventRecord(e0, h->stream);
-        }
+        hipError_t err = run_timed ? hipSuccess : hipEventCreate(&e0);
+        if (err == hipSuccess && !run_timed && (err = hipEventCreate(&e1)) == hipSuccess) err = hipEventRecord(e0, h->stream);
         const int set = two_sets ? (int)(ilaunch & 1) : 0;
         const int tset = tl_two ? (int)(h->tl_launch_no & 1) : 0;
-        const TallyList &TLs = tset ? TL2 : TL;
-        unsigned long long *const set_ctr = set ? h->d_evctr2.p : h->d_evctr.p;
         hipStream_t const rs = two_sets ? h->rays_stream : h->stream;
-        if (err == hipSuccess && use_fl) {
-            if (err == hipSuccess) err = launch_flux(h, tset, h->stream, tl_two ? h->tl_stream : h->stream, h->tl_filled[tset], h->tl_scattered[tset], tl_two && h->tl_set_used[tset], Sl, TLs, mix, grid, lds_fl, nb, seed, off);
-            if (err == hipSuccess && tl_two) { err = hipEventRecord(h->tl_sorted[tset], h->tl_stream); h->tl_set_used[tset] = true; h->tl_unjoined = true; }
-        } else if (err == hipSuccess && use_col) {
-            const int emit_wg = h->counting ? 4 : (h->emit_wg > 0 ? std::min(h->emit_wg, MI3D_LEAN_EMIT_GRID) : MI3D_LEAN_EMIT_GRID);
-            const unsigned gridp = split ? (unsigned)std::min<uint64_t>(want, (uint64_t)h->num_cu * emit_wg) : grid;
-            DevScene Sx = Sl;
-            if (set) Sx.cold = h->d_cold.p + 1;       // (this launch's set of event lists)
-            // (the set is free once the ray kernels of the launch that used it last are through it)
-            if (two_sets && h->set_used[set]) err = hipStreamWaitEvent(h->stream, h->set_rays[set], 0);
-            if (err == hipSuccess && split) err = hipMemsetAsync(set_ctr, 0, kCtrWords * kCtrStride * sizeof(unsigned long long), h->stream);
-            if (err == hipSuccess) {
-                // (the general mixture with staged tables AND a tally window: three workgroups of 512 threads keep six waves per SIMD where
-                //  six of 256 would not find the LDS)
-                const size_t lds_lean = lds_col + (h->cold_host.tile_end ? kWinLds : 0) + lds_tab;
-                static const int wide_env = getenv("MI3D_LEAN_WIDE") ? atoi(getenv("MI3D_LEAN_WIDE")) : -1;     // (measurements: 0 never, 1 whenever three fit)
-                const bool wide = mix >= 2 && !split && !h->counting && lds_lean * 3 <= (size_t)160 * 1024 && (wide_env < 0 ? lds_lean * 6 > (size_t)160 * 1024 : wide_env != 0);
-                unsigned gridw = wide ? (unsigned)std::min<uint64_t>((nb + 511) / 512, (uint64_t)h->num_cu * 3) : gridp;
-                // (the general mixture in workgroups of 256: as many as its registers -- five waves per SIMD -- and its LDS let a CU hold)
-                if (mix >= 2 && !wide && !split && !h->counting) gridw = std::min<unsigned>(gridw, (unsigned)h->num_cu * (unsigned)std::max<size_t>(1, std::min<size_t>(MI3D_GEN_NARROW_WAVES, ((size_t)160 * 1024) / lds_lean)));
-                err = launch_lean(h, h->stream, Sx, split, mix_lean, wide ? 512 : 256, gridw, lds_lean, nb, seed, off);
-            }
-            if (err == hipSuccess && split) {  // the rays of the events just written: on their own stream beside the next launch's photon loop
-                if (two_sets) {
-                    err = hipEventRecord(h->set_emit[set], h->stream);
-                    if (err == hipSuccess) err = hipStreamWaitEvent(rs, h->set_emit[set], 0);
-                }
-                const bool plain_scene = (S.target & kTargetPlainPhase) != 0;
-                if (err == hipSuccess) err = launch_rays(h, rs, Sx, false, lds_col + rays_lds_extra(h->nz, h->rad_kind == 1) + (plain_scene && h->rad_kind != 1 ? 0 : lds_tab), seed);
-                if (err == hipSuccess && !h->sfc_lambert_only && h->rad_kind != 1)   // the reflections off LSRT / DSM surfaces it left aside
-                    err = launch_rays(h, rs, Sx, true, lds_col + rays_lds_extra(h->nz) + lds_tab, seed);
-            }
-        } else if (err == hipSuccess) {
-            const DevThermal *th = thermal ? h->d_th.p : nullptr;
-#define MI3D_LAUNCH_T(C, M, F, T)                                                                                          \
-    do {                                                                                                                 \
-        if (h->solver == MI3D_SOLVER_P3D)                                                                                \
-            hipLaunchKernelGGL((k_transport<C, M, F, true, T>), dim3(grid), dim3(tb), lds, h->stream, S, nb, seed, off, th);    \
-        else                                                                                                                     \
-            hipLaunchKernelGGL((k_transport<C, M, F, false, T>), dim3(grid), dim3(tb), lds, h->stream, S, nb, seed, off, th);   \
-    } while (0)
-#define MI3D_LAUNCH(C, M, F) do { if (thermal) MI3D_LAUNCH_T(C, M, F, true); else MI3D_LAUNCH_T(C, M, F, false); } while (0)
-            switch (variant) {
-                case 0: MI3D_LAUNCH(false, false, false); break;
-                case 1: MI3D_LAUNCH(false, false, true); break;
-                case 2: MI3D_LAUNCH(false, true, false); break;
-                case 3: MI3D_LAUNCH(false, true, true); break;
-                case 4: MI3D_LAUNCH(true, false, false); break;
-                case 5: MI3D_LAUNCH(true, false, true); break;
-                case 6: MI3D_LAUNCH(true, true, false); break;
-                default: MI3D_LAUNCH(true, true, true); break;
-            }
-#undef MI3D_LAUNCH
-#undef MI3D_LAUNCH_T
-            err = hipGetLastError();
-        }
+        if (err == hipSuccess && plan.loop == Loop::Flux) {
+            err = launch_flux(h, tset, tl_two, Sl, TL[tset], plan.mix, grid, lds_fl, nb, seed, off);
+            if (err == hipSuccess && tl_two) { err = hipEventRecord(h->tl[tset].sorted, h->tl_stream); h->tl[tset].used = true; h->tl_unjoined = true; }
+        } else if (err == hipSuccess && plan.loop == Loop::General) err = launch_general(h, Sl, plan.march, plan.flux, grid, nb, seed, off);
+        else if (err == hipSuccess) err = launch_column(h, plan, Sl, set, two_sets, rs, grid, nb, seed, off);
         if (err == hipSuccess && !run_timed) err = hipEventRecord(e1, h->stream);
         h->pre_last = pset;
         if (err == hipSuccess && (pre_two || pre_track)) {   // (the set may be written again once this launch's photon loop is through it)
-            if (!h->pre_loop[pset]) err = hipEventCreateWithFlags(&h->pre_loop[pset], hipEventDisableTiming);
-            if (err == hipSuccess) err = hipEventRecord(h->pre_loop[pset], h->stream);
-            h->pre_used[pset] = true;
+            if (!PS.loop) err = hipEventCreateWithFlags(&PS.loop, hipEventDisableTiming);
+            if (err == hipSuccess) err = hipEventRecord(PS.loop, h->stream);
+            PS.used = true;
             if (pre_two) h->pre_no++;
         }
         if (err != hipSuccess) {   // (no event is left behind on the error path)
@@ -2221,9 +2231,9 @@ int mi3d_run(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_of
         }
         if (!run_timed) h->pending.emplace_back(e0, e1);
         h->launches++; ilaunch++;
-        if (TL.cap) {
+        if (TL[0].cap) {
             const bool first = !(h->tl_total_pp > 0.0);
-            if ((rc = tl_note(h, TL.cap, TL.bcap, TL.run_cap, nb, h->d_tl_stats.p + 4 * ((h->launches - 1) % 64), tl_two ? h->tl_stream : h->stream))) return rc;
+            if ((rc = tl_note(h, TL[0].cap, TL[0].bcap, TL[0].run_cap, nb, h->d_tl_stats.p + 4 * ((h->launches - 1) % 64), tl_two ? h->tl_stream : h->stream))) return rc;
             h->tl_launch_no++;
             // (nothing known about the scene's records per photon yet: the first launch is waited for -- the ones to come are then
             //  sized by what it needed instead of by a guess twice too large)
@@ -2231,24 +2241,24 @@ int mi3d_run(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_of
                 if ((rc = tl_collect(h, true))) return rc;
                 // the pilot is through: lists for the rest of the run at the rates it has shown (every stream joined: the lists may move)
                 HIPCHK(sync_streams(h));
-                const unsigned cap_before = TL.cap;
-                if (!size_tally_lists(std::min<uint64_t>(nphoton - done - nb, h->batch)) && cap_before) return fail(MI3D_EDEVICE, "no device memory to grow the tally-record lists after the pilot launch");
+                if (!size_tally_lists(h, std::min<uint64_t>(nphoton - done - nb, h->batch), tl_two ? 2 : 1, TL)) return fail(MI3D_EDEVICE, "no device memory to grow the tally-record lists after the pilot launch");
             }
         }
-        if (split) {
+        if (plan.loop == Loop::ColumnRays) {
             // how full the lists got sizes the launches to come; read while they run (only a pilot is waited for)
-            rc = ev_note(h, ev_cap, nb, rs, set_ctr);
+            mi3d_solver::EvSet &E = h->ev[set];
+            rc = ev_note(h, ev_cap, nb, rs, E.evctr.p);
             if (!rc && two_sets) {            // (after the copy of its fill counters: the set may be zeroed and filled again)
-                if (hipEventRecord(h->set_rays[set], rs) != hipSuccess) rc = fail(MI3D_EDEVICE, "event record failed");
-                h->set_used[set] = true;
+                if (hipEventRecord(E.rays, rs) != hipSuccess) rc = fail(MI3D_EDEVICE, "event record failed");
+                E.used = true;
             }
             if (rc) { (void)sync_streams(h); return rc; }
             if (!(h->ev_per_photon > 0.0)) {
                 // a pilot: wait for it, then give the lists the size the rest of the run needs
-                if ((rc = ev_collect(h, ev_cap, true))) { return rc; }
+                if ((rc = ev_collect(h, true))) return rc;
                 if (done + nb < nphoton) {
                     HIPCHK(sync_streams(h));
-                    if (size_lists() != MI3D_OK) return fail(MI3D_EDEVICE, "no device memory to grow the event lists of the marched views after the pilot launch");
+                    if (!(ev_cap = size_ev_lists(h, nphoton, two_sets))) return fail(MI3D_EDEVICE, "no device memory to grow the event lists of the marched views after the pilot launch");
                     HIPCHK(upload_cold(h, two_sets, pre_two));
                 }
             }
@@ -2256,9 +2266,6 @@ int mi3d_run(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_of
     }
     // (the last launches' fill counters are looked at by whoever reads the tallies next -- ev_settle -- or by the next run: the
     //  host does not wait here, so that the next run's launches queue up behind this one's)
-    // (tallies in the handle's own buffers are read through calls that join the sort stream first -- tl_join --: the next run's photon
-    //  loops may start beside this run's last sort.  Buffers or a stream of the caller's: work the caller queues after this call must
-    //  find the tallies complete, the main stream waits here)
     // ONE completion rule (round 6): when mi3d_run returns, everything it has started is queued on the handle's main stream or joined to it --
     // whatever the caller queues on that stream next, and every mi3d call, finds the tallies complete in stream order.  (Round 5 returned before
     // the last sort had joined where the tallies lived in the handle's own buffers, so that the next run's loops started beside it: worth 1-2 %
@@ -2271,15 +2278,15 @@ int mi3d_run(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_of
         if (tl_two && !tl_lazy) HIPCHK(tl_join(h));   // (... or the sort's)
         // the main stream joins the rays' stream: whatever follows on it -- the fold below, the next run, a read-out after mi3d_sync -- comes
         // after the last ray kernel; the run's time is the span up to here
-        for (int q = 0; q < 2 && two_sets; ++q) if (h->set_used[q]) HIPCHK(hipStreamWaitEvent(h->stream, h->set_rays[q], 0));
+        for (const auto &E : h->ev) if (two_sets && E.used) HIPCHK(hipStreamWaitEvent(h->stream, E.rays, 0));
         hipEvent_t run_e1 = nullptr;
         HIPCHK(hipEventCreate(&run_e1)); HIPCHK(hipEventRecord(run_e1, tl_two && tl_lazy ? h->tl_stream : h->stream));
         h->pending.emplace_back(run_e0, run_e1);
         run_e0 = nullptr;   // (owned by the pending list from here on)
     }
-    if (split && (rc = ev_collect(h, ev_cap, false))) { (void)sync_streams(h); return rc; }
-    if (TL.cap && (rc = tl_collect(h, false))) return rc;
-    if (spread) {
+    if (plan.loop == Loop::ColumnRays && (rc = ev_collect(h, false))) { (void)sync_streams(h); return rc; }
+    if (TL[0].cap && (rc = tl_collect(h, false))) return rc;
+    if (rad_row) {
         const int n = (int)h->rad_elems();
         hipLaunchKernelGGL(k_fold_rad, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d_rad_acc.p, h->rad_ptr(), kRadLine, n, h->nxr, rad_row);
         HIPCHK(hipGetLastError());
@@ -2314,7 +2321,7 @@ int mi3d_set_tuning(mi3d_solver *h, const char *key, int value) {
         if (value < 10 || value > 28) return fail(MI3D_EINVAL, "evcap_log2=%d outside [10,28]", value);
         HIPCHK(sync_streams(h));
         h->ev_cap_log2 = value; ev_forget(h);
-        h->d_events.release(); h->d_hvlist.release(); h->d_events2.release(); h->d_hvlist2.release();   // (lists only grow otherwise)
+        for (auto &E : h->ev) E.release();   // (lists only grow otherwise)
     }
     else if (k == "rad_spread") h->rad_spread = value < 0 ? -1 : (value ? 1 : 0);   // (-1: the default choice by route, mi3d_run)
     else if (k == "tally_window") h->tally_window = value ? 1 : 0;
@@ -2323,8 +2330,8 @@ int mi3d_set_tuning(mi3d_solver *h, const char *key, int value) {
         if (value < 16 || value > 31) return fail(MI3D_EINVAL, "tlcap_log2=%d outside [16,31]", value);
         HIPCHK(sync_main(h));
         h->tl_cap_log2 = value; h->tl_per_photon = 0.0; h->tl_total_pp = 0.0; h->tl_runs_pp = 0.0;
-        for (bool &b : h->tl_busy) b = false;
-        h->d_tl_rec.release(); h->d_tl_binned.release(); h->d_tl_rec2.release(); h->d_tl_runs.release(); h->d_tl_runs2.release(); h->d_tl_binned2.release();
+        for (auto &S : h->tl_slot) S.busy = false;
+        for (auto &T : h->tl) T.release();
     }
     else if (k == "vpad_col" || k == "vpad_row") {
         // padding of the voxel records' strides, in records of 16 bytes (DevScene::vcol_f4, vrow_f4): where a grid's strides alias in
@@ -2334,22 +2341,14 @@ int mi3d_set_tuning(mi3d_solver *h, const char *key, int value) {
         h->dirty_grid = true;
     }
     else if (k == "overlap_rays") { HIPCHK(sync_streams(h)); h->overlap_rays = value ? 1 : 0; }
-    else if (k == "overlap_pre") { if (value < 0 || value > 2) return fail(MI3D_EINVAL, "overlap_pre=%d outside [0,2]", value); HIPCHK(sync_streams(h)); h->overlap_pre = value; if (!value) { h->d_order2.release(); h->d_entry2.release(); h->pre_last = 0; } }
-    else if (k == "overlap_sort") { if (value < 0 || value > 2) return fail(MI3D_EINVAL, "overlap_sort=%d outside [0,2]", value); HIPCHK(sync_streams(h)); h->overlap_sort = value; if (!value) { h->d_tl_rec2.release(); h->d_tl_words2.release(); h->d_tl_binned2.release(); h->d_tl_runs2.release(); } }
+    else if (k == "overlap_pre") { if (value < 0 || value > 2) return fail(MI3D_EINVAL, "overlap_pre=%d outside [0,2]", value); HIPCHK(sync_streams(h)); h->overlap_pre = value; if (!value) { h->pre[1].release(); h->pre_last = 0; } }
+    else if (k == "overlap_sort") { if (value < 0 || value > 2) return fail(MI3D_EINVAL, "overlap_sort=%d outside [0,2]", value); HIPCHK(sync_streams(h)); h->overlap_sort = value; if (!value) h->tl[1].release(); }
     else if (k == "tl_split") { if (value < 1 || value > 64) return fail(MI3D_EINVAL, "tl_split=%d outside [1,64]", value); h->tl_split = value; }
     else if (k == "rays_wg" || k == "emit_wg") { if (value < 0 || value > 8) return fail(MI3D_EINVAL, "%s=%d outside [0,8]", key, value); (k == "rays_wg" ? h->rays_wg : h->emit_wg) = value; }
     else if (k == "cam_images") { if (value < -1 || value > 8) return fail(MI3D_EINVAL, "cam_images=%d outside [-1,8]", value); h->cam_images = value; }
-    else if (k == "entry_records") {
-        HIPCHK(sync_main(h));
-        h->entry_records = value ? 1 : 0;
-        if (!value) h->d_entry.release();
-    }
-    else if (k == "tally_runs") { HIPCHK(sync_main(h)); h->tally_runs = value ? 1 : 0; h->tl_per_photon = 0.0; h->tl_total_pp = 0.0; h->tl_runs_pp = 0.0; if (!value) { h->d_tl_runs.release(); h->d_tl_runs2.release(); } }
-    else if (k == "tally_lists") {
-        HIPCHK(sync_main(h));
-        h->tally_lists = value ? 1 : 0;
-        if (!value) { h->d_tl_rec.release(); h->d_tl_binned.release(); h->d_tl_rec2.release(); h->d_tl_binned2.release(); h->d_tl_runs.release(); h->d_tl_runs2.release(); }
-    }
+    else if (k == "entry_records") { HIPCHK(sync_main(h)); h->entry_records = value ? 1 : 0; if (!value) h->pre[0].entry.release(); }
+    else if (k == "tally_runs") { HIPCHK(sync_main(h)); h->tally_runs = value ? 1 : 0; h->tl_per_photon = 0.0; h->tl_total_pp = 0.0; h->tl_runs_pp = 0.0; if (!value) for (auto &T : h->tl) T.runs.release(); }
+    else if (k == "tally_lists") { HIPCHK(sync_main(h)); h->tally_lists = value ? 1 : 0; if (!value) for (auto &T : h->tl) T.release(); }
     else if (k == "own_stream") {
         // a stream of the handle's own (non-blocking) wherever the caller binds none; the caller orders its own work with mi3d_sync
         HIPCHK(sync_main(h));
@@ -2668,11 +2667,11 @@ int mi3d_debug_order(mi3d_solver *h, uint64_t n, uint32_t *order_out, uint32_t *
     int rc = check_handle(h);
     if (rc) return rc;
     if (n == 0 || !order_out) return fail(MI3D_EINVAL, "bad arguments to mi3d_debug_order");
-    if (!h->d_order.p || h->d_order.cap < n) return fail(MI3D_ESTATE, "no photon order of that length (the last launch ran in id order, or was shorter)");
+    if (!h->pre[0].order.p || h->pre[0].order.cap < n) return fail(MI3D_ESTATE, "no photon order of that length (the last launch ran in id order, or was shorter)");
     HIPCHK(sync_main(h));
-    HIPCHK(hipMemcpy(order_out, h->pre_last ? h->d_order2.p : h->d_order.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(order_out, h->pre[h->pre_last].order.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (tile_end_out && ntile_max > 0)
-        HIPCHK(hipMemcpy(tile_end_out, h->pre_last ? h->d_cursor2.p : h->d_cursor.p, (size_t)std::min(ntile_max, kMaxTiles) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(tile_end_out, h->pre[h->pre_last].cursor.p, (size_t)std::min(ntile_max, kMaxTiles) * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return MI3D_OK;
 }
 
