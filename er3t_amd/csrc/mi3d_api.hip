@@ -105,6 +105,7 @@ struct mi3d_solver {
     double th_wlen = 0.0, th_ptot = 0.0, th_ms = 0.0;
     std::vector<float> th_tlev;
     size_t th_ntmpa = 0, th_ntmps = 0;   // elements of the anomalies handed over (0: none)
+    size_t th_ncell = 0;                 // cells of the CDF build_thermal made last (mi3d_debug_thermal)
     DevBuf<float> d_th_tlev, d_th_tmpa, d_th_tmps;
     DevBuf<double> d_th_cdf, d_th_bsum;
     DevBuf<DevThermal> d_th;
@@ -701,6 +702,7 @@ int build_thermal(mi3d_solver *h) {
     h->th_ms = ms;
     if (!(ptot >= 0.0) || !std::isfinite(ptot)) return fail(MI3D_EINVAL, "thermal source: total emitted power %g", ptot);
     h->th_ptot = ptot;
+    h->th_ncell = ncell;
     DevThermal T;
     T.cdf = h->d_th_cdf.p; T.ptot = ptot; T.ncell = (unsigned)ncell; T.nvox = (unsigned)nvox;
     T.nxb = sfc2d ? h->nxb : 1; T.nyb = sfc2d ? h->nyb : 1;
@@ -2672,6 +2674,19 @@ int mi3d_debug_order(mi3d_solver *h, uint64_t n, uint32_t *order_out, uint32_t *
     HIPCHK(hipMemcpy(order_out, h->pre[h->pre_last].order.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (tile_end_out && ntile_max > 0)
         HIPCHK(hipMemcpy(tile_end_out, h->pre[h->pre_last].cursor.p, (size_t)std::min(ntile_max, kMaxTiles) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return MI3D_OK;
+}
+
+int mi3d_debug_thermal(mi3d_solver *h, double *ptot, double *cdf_out, uint64_t n) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (h->src_mtype != 3) return fail(MI3D_ESTATE, "mi3d_debug_thermal: the job is not thermal (Src_mtype=%d)", h->src_mtype);
+    if (h->dirty_thermal || !h->d_th_cdf.p) return fail(MI3D_ESTATE, "mi3d_debug_thermal: the thermal source is not built (call mi3d_prepare)");
+    if (cdf_out && n != h->th_ncell)
+        return fail(MI3D_EINVAL, "mi3d_debug_thermal: the CDF has %zu cells, not %llu", h->th_ncell, (unsigned long long)n);
+    HIPCHK(sync_main(h));
+    if (ptot) *ptot = h->th_ptot;
+    if (cdf_out) HIPCHK(hipMemcpy(cdf_out, h->d_th_cdf.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     return MI3D_OK;
 }
 

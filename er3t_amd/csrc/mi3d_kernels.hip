@@ -1338,7 +1338,7 @@ k_transport(const DevScene S, const uint64_t nphoton, const uint64_t seed, const
                 const double target = u01_pair(q[0], q[1]) * th->ptot;
                 unsigned lo = 0, hi = th->ncell - 1;   // the first cell whose cumulative power exceeds the target (it emits)
                 while (lo < hi) {
-                    const unsigned mid = (lo + hi) >> 1;
+                    const unsigned mid = lo + ((hi - lo) >> 1);   // (lo + hi wraps beyond 2^31 cells)
                     if (cdf[mid] > target) hi = mid; else lo = mid + 1;
                 }
                 const unsigned nvox = th->nvox;

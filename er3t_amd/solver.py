@@ -74,6 +74,7 @@ _SIGNATURES = [
     ('mi3d_stats_get'          , C.c_int   , [C.c_void_p, C.c_int, _fp, _fp, C.POINTER(C.c_int)]),
     ('mi3d_debug_philox'       , C.c_int   , [C.c_void_p, _u64, _u64, C.c_uint32, C.c_int, C.POINTER(C.c_uint32)]),
     ('mi3d_debug_order'        , C.c_int   , [C.c_void_p, _u64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int]),
+    ('mi3d_debug_thermal'      , C.c_int   , [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), _u64]),
 ]
 
 
@@ -419,6 +420,12 @@ class Mi3dSolver:
         order = np.zeros(n, dtype=np.uint32); tend = np.zeros(ntile_max, dtype=np.uint32)
         self._chk(self.lib.mi3d_debug_order(self._h, int(n), order.ctypes.data_as(C.POINTER(C.c_uint32)), tend.ctypes.data_as(C.POINTER(C.c_uint32)), int(ntile_max)))
         return order, tend
+
+    def debug_thermal(self, ncell):
+        """test hook: (P_tot, the device CDF [ncell] float64) of the thermal source the last mi3d_prepare built"""
+        ptot = C.c_double(0.0); cdf = np.zeros(int(ncell), dtype=np.float64)
+        self._chk(self.lib.mi3d_debug_thermal(self._h, C.byref(ptot), cdf.ctypes.data_as(C.POINTER(C.c_double)), int(ncell)))
+        return float(ptot.value), cdf
 
     def philox(self, seed, id0, draw, n):
         out = np.zeros((n, 4), dtype=np.uint32)

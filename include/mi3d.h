@@ -419,6 +419,10 @@ int mi3d_debug_philox(mi3d_solver *h, uint64_t seed, uint64_t id0, uint32_t draw
  * k_bin_scatter leaves behind, which the lean loop's tally window reads; up to ntile_max words, 1024 at most).  MI3D_ESTATE when the
  * launch ran in id order (a small domain, fewer than 4096 photons, "tile_cols" 0). */
 int mi3d_debug_order(mi3d_solver *h, uint64_t n, uint32_t *order_out, uint32_t *tile_end_out, int ntile_max);
+/* Test hook: the thermal source as mi3d_prepare built it.  *ptot (if not NULL) = P_tot; cdf_out (if not NULL) [n] = the device's
+ * inclusive CDF of the cells' emitted power in float64, n = its number of cells (voxels, 1-D layers, surface cells: otherwise
+ * MI3D_EINVAL).  MI3D_ESTATE when the job is not thermal or its source is not built yet. */
+int mi3d_debug_thermal(mi3d_solver *h, double *ptot, double *cdf_out, uint64_t n);
 
 #ifdef __cplusplus
 }

@@ -34,6 +34,14 @@
  *                      u2 -> cos(scattering angle) or surface cos^2(zenith); u3 -> azimuth
  *   roulette         : consumes one extra draw (its u0) only when weight < wmin; survival probability
  *                      weight/wfac, survivors continue with weight wfac (Pho_wmin = 0.2, Pho_wfac = 1)
+ *
+ * Thermal source (src_mtype = 3): the launch takes two blocks, the flights start at draw 2.
+ *   draw 0           : u0,u1 -> x,y inside the emitting cell (a 1-D layer: inside the domain); u2 -> height inside the cell
+ *                      (a surface cell: on the surface); u3 -> polar cosine of the emission, 2 u3 - 1 (volume) or sqrt(u3) (surface)
+ *   draw 1 (raw)     : words w0,w1 -> u = ((w0 >> 9) + ((w1 >> 9) + 0.5) 2^-23) 2^-23 (46 bits); the cell is the first one whose
+ *                      cumulative power exceeds u P_tot; w2 -> azimuth 2 pi ((w2 >> 9) + 0.5) 2^-23; w3 unused
+ *   The emission is an event of weight 1 with local estimates 1/4pi (volume) or cos/pi (surface, down-looking sensors only);
+ *   a surface photon then tallies its upward crossing of level 0.  No photon is direct: the direct-down plane stays 0.
  */
 #include <math.h>
 #include <stdint.h>
@@ -94,6 +102,16 @@ typedef struct {
                         * carries le_cmin (unbiased; the decision is a hash of seed, photon id, Philox block index and view) */
     int cam_images;    /* cameras in the cyclic domain: an event contributes to the periodic images of the camera within this many
                         * domain lengths of the nearest one, (2 cam_images + 1)^2 images in all (0: the nearest image only) */
+    /* source type (Src_mtype): 1 solar, 3 thermal (include/mi3d.h: mi3d_set_thermal).  Thermal: Planck's law at the
+     * band-centre wavelength src_wlen [um]; tmp1d [nz+1] the INTERFACE temperatures [K] (a layer emits at the mean of its two),
+     * tmpa3d [nz3][ny][nx] voxel anomalies and tmps2d [nyb][nxb] surface anomalies [K] (each may be NULL); the surface emits at
+     * tmp1d[0] + its anomaly. */
+    int src_mtype;
+    double src_wlen;
+    const float *tmp1d, *tmpa3d, *tmps2d;
+    /* cameras' pixel map (Rad_mpmap): 1 polar, 2 rectangular (U = theta in [0, umax] over nxr columns, V = phi in [-vmax, vmax] over
+     * nyr rows); and weighting (Rad_mrproj): 1 multiplies every contribution by cos theta */
+    int cam_mpmap, cam_mrproj;
 } orc_config;
 
 /* ------------------------------------------------------------------------------------------ */
@@ -153,6 +171,11 @@ typedef struct {
     double *rad;  /* [nview][nyr][nxr] */
     double *flux; /* [3][nz+1][ny][nx] */
     double *heat; /* [nz][ny][nx] weight absorbed in every cell (target & 4: heating rates, Flx_mhrt = 1), or NULL */
+    /* thermal source: CDF of the cells' emitted power (voxels, 1-D layers, surface cells), P_tot */
+    double *th_cdf;
+    long th_ncell, th_nvox;
+    int th_nxb, th_nyb;
+    double th_ptot;
 } scene_t;
 
 static inline long vox(const scene_t *s, int ix, int iy, int k3) {
@@ -631,6 +654,16 @@ static void cam_image(const orc_config *c, int img, int *ii, int *jj) {
     *ii = t % n - c->cam_images; *jj = t / n - c->cam_images;
 }
 
+/* rectangular map: the weighted solid angle of a pixel of column ir of camera iv, int w dOmega over theta_ir .. theta_ir+1 and
+ * one row's dphi, w = 1 (mrproj 0) or cos theta (mrproj 1) */
+static double rect_W(const orc_config *c, int iv, int ir) {
+    double dth = c->cam_umax[iv] * PI / 180.0 / c->nxr, dph = 2.0 * c->cam_vmax[iv] * PI / 180.0 / c->nyr;
+    double t0 = ir * dth, t1 = (ir + 1) * dth;
+    return c->cam_mrproj == 1 ? 0.5 * (sin(t1) * sin(t1) - sin(t0) * sin(t0)) * dph : (cos(t0) - cos(t1)) * dph;
+}
+
+double orc_rect_pixel_W(const orc_config *c, int iv, int ir) { return rect_W(c, iv, ir); }
+
 /* camera: the ray from the event reaches the camera at distance r; tally into the pixel its direction falls in */
 static void camera_tally(const scene_t *s, const photon_t *ph, double contrib_no_T, int iv, int img, const double v[3], double r, uint64_t *cnt) {
     const orc_config *c = s->c;
@@ -652,6 +685,25 @@ static void camera_tally(const scene_t *s, const photon_t *ph, double contrib_no
     double dyc = -(v[0] * s->cam_ax[iv][1][0] + v[1] * s->cam_ax[iv][1][1] + v[2] * s->cam_ax[iv][1][2]);
     double dzc = -(v[0] * s->cam_ax[iv][2][0] + v[1] * s->cam_ax[iv][2][1] + v[2] * s->cam_ax[iv][2][2]);
     if (dzc > 1.0) dzc = 1.0;
+    if (c->cam_mpmap == 2) {
+        /* rectangular map: column by theta in [0, umax], row by phi in [-vmax, vmax] (phi = +-180 is one direction: with vmax = 180
+         * the row past the last is the first); the value is w c / W with W the pixel's weighted solid angle, w = cos theta under
+         * mrproj 1 */
+        if (dzc < -1.0) dzc = -1.0;
+        double th = acos(dzc), rho2 = dxc * dxc + dyc * dyc;
+        double ph_ = rho2 > 1e-24 ? atan2(dyc, dxc) : 0.0;
+        double umax = c->cam_umax[iv] * PI / 180.0, vmax = c->cam_vmax[iv] * PI / 180.0;
+        double dth = umax / c->nxr, dph = 2.0 * vmax / c->nyr;
+        int ir = (int)floor(th / dth), jr = (int)floor((ph_ + vmax) / dph);
+        if (c->cam_vmax[iv] >= 180.0 && jr == c->nyr) jr = 0;
+        if (ir < 0 || ir >= c->nxr || jr < 0 || jr >= c->nyr) return;
+        double W = rect_W(c, iv, ir);
+        if (!(W > 0.0)) return;
+        double a = c->cam_apsize[iv], r2 = r * r > a * a ? r * r : a * a;
+        double wgt = c->cam_mrproj == 1 ? dzc : 1.0;
+        add_atomic(&s->rad[((long)iv * c->nyr + jr) * c->nxr + ir], wgt * contrib_no_T * T / (r2 * W));
+        return;
+    }
     double theta = acos(dzc), rho = sqrt(dxc * dxc + dyc * dyc);
     double U = rho > 1e-12 ? theta * dxc / rho : 0.0, V = rho > 1e-12 ? theta * dyc / rho : 0.0;
     double du = c->cam_umax[iv] * PI / 180.0 / c->nxr, dv = c->cam_vmax[iv] * PI / 180.0 / c->nyr;
@@ -718,11 +770,151 @@ static void radiance_tally(const scene_t *s, const photon_t *ph, double contrib_
 }
 
 /* ------------------------------------------------------------------------------------------ */
+/* thermal source (src_mtype = 3)                                                              */
+/* ------------------------------------------------------------------------------------------ */
+/* Planck's law, W m-2 sr-1 um-1 at wl_um [um] and T [K] (CODATA 2018 h, c, k) */
+static double planck_B(double wl_um, double T) {
+    if (!(T > 0.0) || !(wl_um > 0.0)) return 0.0;
+    const double hP = 6.62607015e-34, cL = 299792458.0, kB = 1.380649e-23;
+    double lam = wl_um * 1.0e-6;
+    double x = hP * cL / (lam * kB * T);
+    return 2.0 * hP * cL * cL / (lam * lam * lam * lam * lam) / expm1(x) * 1.0e-6;
+}
+
+/* cells of the thermal source, in CDF order: voxels (file order), the nz layers of the 1-D grid, the surface cells (nxb x nyb of a
+ * 2-D surface, else one).  Returns their number. */
+static long thermal_cells(const orc_config *c, long *nvox, int *nxb, int *nyb) {
+    int two_d = c->jsfc && c->nxb > 0 && c->nyb > 0;
+    *nxb = two_d ? c->nxb : 1; *nyb = two_d ? c->nyb : 1;
+    *nvox = (long)c->nx * c->ny * c->nz3;
+    return *nvox + c->nz + (long)(*nxb) * (*nyb);
+}
+
+/* Emitted power of every cell [W um-1 per unit Src_flx], double precision from the float32 inputs:
+ *   voxel   4 pi ka B(T) dx dy dz, ka = abs1d + abst + sum ext (1 - omega) over the 1-D and 3-D constituents,
+ *           T = mean of the layer's interface temperatures + the voxel's anomaly
+ *   layer   4 pi ka B(T) Lx Ly dz (ka of the 1-D constituents and gas); a layer of the 3-D region emits through its voxels: 0
+ *   surface pi (1 - albedo) B(Ts) Lx Ly / (nxb nyb), Ts = tmp1d[0] + the cell's anomaly (Lambertian surfaces)
+ * The library takes ka as float32 total extinction minus float32 scattering; where ka is a small difference of two large
+ * numbers the two disagree by float32 rounding of beta.  This is deliberately not imitated: test scenes keep ka / beta >= 1e-3
+ * in every emitting cell, which holds the disagreement below 1e-4 of the cell's power. */
+static void thermal_powers(const orc_config *c, double *pw) {
+    long nvox; int nxb, nyb;
+    long ncell = thermal_cells(c, &nvox, &nxb, &nyb);
+    int k3lo = c->nz3 > 0 ? c->iz3l - 1 : 0;
+    double Lx = c->nx * c->dx, Ly = c->ny * c->dy;
+    for (long i = 0; i < ncell; ++i) pw[i] = 0.0;
+    /* absorption of the 1-D part of every layer */
+    for (int k = 0; k < c->nz; ++k) {
+        double ka = c->abs1d ? (double)c->abs1d[k] : 0.0;
+        for (int ip = 0; ip < c->np1d; ++ip)
+            ka += (double)c->ext1d[(long)ip * c->nz + k] * (1.0 - (double)c->omg1d[(long)ip * c->nz + k]);
+        double dz = c->zgrd[k + 1] - c->zgrd[k];
+        double T = 0.5 * ((double)c->tmp1d[k] + (double)c->tmp1d[k + 1]);
+        int in3d = c->nz3 > 0 && k >= k3lo && k < k3lo + c->nz3;
+        if (!in3d) {
+            pw[nvox + k] = ka > 0.0 ? 4.0 * PI * ka * planck_B(c->src_wlen, T) * Lx * Ly * dz : 0.0;
+            continue;
+        }
+        for (int iy = 0; iy < c->ny; ++iy)
+            for (int ix = 0; ix < c->nx; ++ix) {
+                long v = ((long)(k - k3lo) * c->ny + iy) * c->nx + ix;
+                double kv = ka + (c->abst ? (double)c->abst[v] : 0.0);
+                for (int ip = 0; ip < c->np3d; ++ip)
+                    kv += (double)c->extp[ip * nvox + v] * (1.0 - (double)c->omgp[ip * nvox + v]);
+                double Tv = T + (c->tmpa3d ? (double)c->tmpa3d[v] : 0.0);
+                pw[v] = kv > 0.0 ? 4.0 * PI * kv * planck_B(c->src_wlen, Tv) * c->dx * c->dy * dz : 0.0;
+            }
+    }
+    long nsfc = (long)nxb * nyb;
+    for (long i = 0; i < nsfc; ++i) {
+        double alb = (c->jsfc && c->nxb > 0 && c->nyb > 0) ? (double)c->psfc[i] : (double)c->sfc_param[0];
+        if (alb < 0.0) alb = 0.0;
+        if (alb > 1.0) alb = 1.0;
+        double Ts = (double)c->tmp1d[0] + (c->tmps2d ? (double)c->tmps2d[i] : 0.0);
+        pw[nvox + c->nz + i] = PI * (1.0 - alb) * planck_B(c->src_wlen, Ts) * Lx * Ly / (double)nsfc;
+    }
+}
+
+/* The CDF of the thermal source: cdf[i] = sum of the powers of cells 0 .. i (serial sum in double), its last element P_tot.
+ * Returns the number of cells (cdf may be NULL to ask for it), or -1 when the configuration is not thermal. */
+int64_t orc_thermal_cdf(const orc_config *c, double *cdf) {
+    if (c->src_mtype != 3 || !c->tmp1d) return -1;
+    long nvox; int nxb, nyb;
+    long ncell = thermal_cells(c, &nvox, &nxb, &nyb);
+    if (!cdf) return ncell;
+    thermal_powers(c, cdf);
+    double acc = 0.0;
+    for (long i = 0; i < ncell; ++i) { acc += cdf[i]; cdf[i] = acc; }
+    return ncell;
+}
+
+/* Start a thermal photon (the protocol in the header): its cell, position and emission event -- local estimates and, from the
+ * surface, the upward crossing of level 0 -- and its direction.  The flights that follow take Philox blocks 2, 3, ... */
+static void thermal_launch(const scene_t *s, photon_t *ph, uint64_t *cnt) {
+    const orc_config *c = s->c;
+    double u[4];
+    uint32_t q[4];
+    draw4(ph->seed, ph->id, 0, u);
+    orc_philox(ph->seed, ph->id, 1, q);
+    double target = ((double)(q[0] >> 9) + ((double)(q[1] >> 9) + 0.5) / 8388608.0) / 8388608.0 * s->th_ptot;
+    double azim = 2.0 * PI * ((double)(q[2] >> 9) + 0.5) / 8388608.0;
+    /* the cell: the smallest i with cdf[i] > target */
+    long a = -1, b = s->th_ncell - 1;        /* invariant: cdf[a] <= target (a = -1: none), cdf[b] > target */
+    while (b - a > 1) {
+        long m = a + (b - a) / 2;
+        if (s->th_cdf[m] > target) b = m; else a = m;
+    }
+    long cell = b;
+    int sfc = 0, k;
+    if (cell < s->th_nvox) {
+        long ncol = (long)c->nx * c->ny, col = cell % ncol;
+        k = s->k3lo + (int)(cell / ncol);
+        ph->x = ((double)(col % c->nx) + u[0]) * c->dx;
+        ph->y = ((double)(col / c->nx) + u[1]) * c->dy;
+    } else if (cell < s->th_nvox + s->nz) {
+        k = (int)(cell - s->th_nvox);
+        ph->x = u[0] * s->Lx; ph->y = u[1] * s->Ly;
+    } else {
+        long sc = cell - s->th_nvox - s->nz;
+        sfc = 1; k = 0;
+        ph->x = ((double)(sc % s->th_nxb) + u[0]) * (s->Lx / s->th_nxb);
+        ph->y = ((double)(sc / s->th_nxb) + u[1]) * (s->Ly / s->th_nyb);
+    }
+    if (ph->x >= s->Lx) ph->x = 0.0;
+    if (ph->y >= s->Ly) ph->y = 0.0;
+    ph->ix = (int)floor(ph->x / c->dx); if (ph->ix >= c->nx) ph->ix = c->nx - 1;
+    ph->iy = (int)floor(ph->y / c->dy); if (ph->iy >= c->ny) ph->iy = c->ny - 1;
+    ph->k = k;
+    ph->z = sfc ? c->zgrd[0] : c->zgrd[k] + u[2] * (c->zgrd[k + 1] - c->zgrd[k]);
+    ph->w = 1.0;
+    ph->nscat = 1;                    /* emitted light is diffuse: nothing enters the direct-down plane */
+    ph->ipa = (c->solver != 0);       /* partial 3-D: no thermal photon is direct, all of them stay in their column */
+    ph->draw = 2;
+    if (c->target & 2) {
+        for (int iv = 0; iv < c->nview; ++iv) {
+            const double *v = s->vdir[iv];
+            if (sfc && v[2] <= 0.0) continue;   /* an up-looking sensor does not see the surface */
+            radiance_tally(s, ph, sfc ? v[2] / PI : 1.0 / (4.0 * PI), iv, cnt);
+        }
+    }
+    ph->d[0] = 0.0; ph->d[1] = 0.0; ph->d[2] = 1.0;
+    rotate_dir(ph->d, sfc ? sqrt(u[3]) : 2.0 * u[3] - 1.0, azim);
+    if (sfc) flux_tally(s, ph, 0, 1, cnt);
+}
+
+/* ------------------------------------------------------------------------------------------ */
 static void run_photon(const scene_t *s, uint64_t seed, uint64_t id, uint64_t *cnt) {
     const orc_config *c = s->c;
     uint32_t draw = 0;
     double u[4];
     photon_t ph;
+    ph.seed = seed; ph.id = id;
+    if (c->src_mtype == 3) {
+        thermal_launch(s, &ph, cnt);
+        draw = 2;
+        goto transport;
+    }
     draw4(seed, id, draw++, u);
     ph.x = u[0] * s->Lx; ph.y = u[1] * s->Ly;
     if (ph.x >= s->Lx) ph.x = 0.0;
@@ -738,7 +930,7 @@ static void run_photon(const scene_t *s, uint64_t seed, uint64_t id, uint64_t *c
     ph.w = 1.0; ph.nscat = 0; ph.ipa = (c->solver == 2);
     flux_tally(s, &ph, s->nz, 0, cnt);
 
-    ph.seed = seed; ph.id = id;
+transport:
     for (;;) {
         draw4(seed, id, draw++, u);
         ph.draw = draw;
@@ -918,11 +1110,25 @@ static int build_scene(scene_t *s, const orc_config *c, double *rad, double *flu
         }
     }
     s->rad = rad; s->flux = flux; s->heat = (c->target & 4) ? heat : NULL;
+    if (c->src_mtype == 3) {
+        /* thermal: no cameras, no heating rates (as the library: MI3D_EUNSUP) */
+        if ((c->target & 2) && c->rad_kind == 1) return -4;
+        if (c->target & 4) return -5;
+        if (!c->tmp1d || !(c->src_wlen > 0.0)) return -6;
+        long n = (long)orc_thermal_cdf(c, NULL);
+        s->th_cdf = (double *)malloc(sizeof(double) * n);
+        orc_thermal_cdf(c, s->th_cdf);
+        s->th_ncell = n;
+        thermal_cells(c, &s->th_nvox, &s->th_nxb, &s->th_nyb);
+        s->th_ptot = s->th_cdf[n - 1];
+    } else if (c->src_mtype != 1 && c->src_mtype != 0) {
+        return -7;
+    }
     return 0;
 }
 
 static void free_scene(scene_t *s) {
-    free(s->bt1d); free(s->ks1d); free(s->tmu); free(s->tp); free(s->tcdf);
+    free(s->bt1d); free(s->ks1d); free(s->tmu); free(s->tp); free(s->tcdf); free(s->th_cdf);
 }
 
 /* Raw tallies (sums of weights / local-estimate contributions), double precision:
@@ -940,7 +1146,8 @@ int orc_run_heat(const orc_config *c, uint64_t nphoton, uint64_t seed, uint64_t 
                  double *flux_sum, double *heat_sum, uint64_t *counters) {
     scene_t s;
     int rc = build_scene(&s, c, rad_sum, flux_sum, heat_sum);
-    if (rc) return rc;
+    if (rc) { free_scene(&s); return rc; }
+    if (c->src_mtype == 3 && !(s.th_ptot > 0.0)) { free_scene(&s); return 0; }   /* nothing emits: the tallies stay 0 */
     int nt = c->nthreads > 0 ? c->nthreads : 1;
 #ifdef _OPENMP
     omp_set_num_threads(nt);

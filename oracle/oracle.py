@@ -47,6 +47,8 @@ class _Config(C.Structure):
         ('cam_apsize', C.c_double*MAX_VIEW),
         ('le_cmin', C.c_double),
         ('cam_images', C.c_int),
+        ('src_mtype', C.c_int), ('src_wlen', C.c_double), ('tmp1d', _fp), ('tmpa3d', _fp), ('tmps2d', _fp),
+        ('cam_mpmap', C.c_int), ('cam_mrproj', C.c_int),
     ]
 
 
@@ -81,6 +83,10 @@ def lib():
         _LIB.orc_phase_sample.restype = C.c_double
         _LIB.orc_phase_sample.argtypes = [C.c_double, C.c_double]
         _LIB.orc_phase_table.argtypes = [C.POINTER(_Config), C.c_int, C.c_int, _dp, _dp, _dp, _dp]
+        _LIB.orc_rect_pixel_W.restype = C.c_double
+        _LIB.orc_rect_pixel_W.argtypes = [C.POINTER(_Config), C.c_int, C.c_int]
+        _LIB.orc_thermal_cdf.restype = C.c_int64
+        _LIB.orc_thermal_cdf.argtypes = [C.POINTER(_Config), _dp]
     return _LIB
 
 
@@ -134,6 +140,11 @@ def _config(scene, nthreads=1):
             cfg.cam_xpos[i] = s.cam_xpos[i]; cfg.cam_ypos[i] = s.cam_ypos[i]; cfg.cam_psi[i] = s.cam_psi[i]
             cfg.cam_qmax[i] = s.cam_qmax[i]; cfg.cam_umax[i] = s.cam_umax[i]; cfg.cam_vmax[i] = s.cam_vmax[i]
             cfg.cam_apsize[i] = s.cam_apsize[i]
+    cfg.cam_mpmap = int(getattr(s, 'cam_mpmap', 1)); cfg.cam_mrproj = int(getattr(s, 'cam_mrproj', 0))
+    cfg.src_mtype = int(getattr(s, 'src_mtype', 1))
+    if cfg.src_mtype == 3:
+        cfg.src_wlen = float(s.src_wlen)
+        cfg.tmp1d = _ptr(f32(s.tmp1d), _fp); cfg.tmpa3d = _ptr(f32(s.tmpa3d), _fp); cfg.tmps2d = _ptr(f32(s.tmps2d), _fp)
     return cfg, keep
 
 
@@ -150,14 +161,38 @@ def run_raw(scene, nphoton, seed=1, offset=0, nthreads=1, heat=None):
     return rad[:scene.nview], flux, cnt
 
 
+def thermal_cdf(scene):
+    """the thermal source's CDF of the cells' emitted power (voxels, 1-D layers, surface cells), float64; its last element is P_tot"""
+    cfg, keep = _config(scene, 1)
+    n = lib().orc_thermal_cdf(C.byref(cfg), None)
+    if n < 0:
+        raise ValueError('Error [oracle]: not a thermal scene (src_mtype=%s).' % getattr(scene, 'src_mtype', 1))
+    cdf = np.zeros(n, dtype=np.float64)
+    lib().orc_thermal_cdf(C.byref(cfg), _ptr(cdf, _dp))
+    return cdf
+
+
+def rect_pixel_w(scene, iv):
+    """the rectangular map's weighted solid angle of every column of camera iv's pixels (one row each)"""
+    cfg, keep = _config(scene, 1)
+    return np.array([lib().orc_rect_pixel_W(C.byref(cfg), int(iv), ir) for ir in range(scene.nxr)])
+
+
+def _amp(scene):
+    """power per unit domain area the photons stand for in all: Src_flx mu0 (solar), Src_flx P_tot / (Lx Ly) (thermal)"""
+    if getattr(scene, 'src_mtype', 1) == 3:
+        return scene.src_flx * thermal_cdf(scene)[-1] / (scene.nx * scene.dx * scene.ny * scene.dy)
+    return scene.src_flx * scene.mu0
+
+
 def normalise(scene, rad_sum, flux_sum, nphoton):
     """radiance per unit Src_flx... times Src_flx; flux likewise (see include/mi3d.h: mi3d_get_radiance)"""
-    mu0 = scene.mu0
+    amp = _amp(scene)
     if getattr(scene, 'rad_kind', 2) == 1:     # camera: the tally already holds the 1 / (r^2 dOmega) of every contribution
-        rad = rad_sum * (scene.src_flx * mu0 * scene.nx * scene.dx * scene.ny * scene.dy / float(nphoton))
+        rad = rad_sum * (amp * scene.nx * scene.dx * scene.ny * scene.dy / float(nphoton))
     else:
-        rad = rad_sum * (scene.src_flx * mu0 * scene.nxr * scene.nyr / float(nphoton))
-    flux = flux_sum * (scene.src_flx * mu0 * scene.nx * scene.ny / float(nphoton))
+        rad = rad_sum * (amp * scene.nxr * scene.nyr / float(nphoton))
+    flux = flux_sum * (amp * scene.nx * scene.ny / float(nphoton))
     return rad, flux
 
 
@@ -169,7 +204,7 @@ def run(scene, nphoton, seed=1, offset=0, nthreads=1):
            'rad_sum': rad_sum, 'flux_sum': flux_sum}
     if heat is not None:
         # absorbed power per unit volume, per unit Src_flx: weight absorbed in the cell x (Src_flx mu0 nx ny / N) / layer thickness
-        out['heat'] = heat*(scene.src_flx*scene.mu0*scene.nx*scene.ny/float(nphoton))/np.diff(scene.zgrd)[:, None, None]
+        out['heat'] = heat*(_amp(scene)*scene.nx*scene.ny/float(nphoton))/np.diff(scene.zgrd)[:, None, None]
     return out
 
 

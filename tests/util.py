@@ -73,3 +73,57 @@ def block_expectations(nx=8, d=100.0):
         xr = (xx + sign*zz) % L
         image[sign] = np.histogram(xr.ravel(), bins=nx, range=(0.0, L))[0]/xx.size
     return shadow, image
+
+
+def thermal_mixed_scene(nx=12, ny=10, nz=8, nz3=4, iz3l=3, nxb=5, nyb=4, seed=0, wl=11.0, target=TARGET_FLUX | TARGET_RADIANCE):
+    """a thermal scene with every source of emission: two 3-D constituents (absorbing, scattering) and gas absorption in the
+    voxels, two 1-D constituents with scattering (ks1d) and gas in the layers, voxel temperature anomalies and a 2-D Lambert
+    surface of nxb x nyb cells (not the voxel grid) with albedo and temperature anomalies.  Every emitting cell keeps
+    ka / beta >= 1e-3 (oracle/mi3d_oracle.c: thermal_powers)."""
+    rng = np.random.default_rng(seed)
+    dz = 500.0
+    zgrd = np.arange(nz+1)*dz
+    ext1d = np.stack([rng.uniform(0.2e-4, 1.0e-4, nz), rng.uniform(0.1e-4, 0.5e-4, nz)])
+    omg1d = np.stack([np.full(nz, 0.9), rng.uniform(0.3, 0.95, nz)])
+    apf1d = np.stack([np.full(nz, -1.0), np.full(nz, 0.6)])
+    abs1d = rng.uniform(0.5e-5, 2.0e-5, nz)
+    shape = (nz3, ny, nx)
+    extp = np.stack([rng.uniform(0.0, 3.0e-3, shape)*(rng.random(shape) < 0.6), rng.uniform(0.1e-4, 1.0e-4, shape)])
+    omgp = np.stack([rng.uniform(0.8, 0.99, shape), np.full(shape, 0.2)])
+    apfp = np.stack([np.full(shape, 0.85), np.full(shape, 0.3)])
+    abst = rng.uniform(0.0, 2.0e-5, shape)
+    tlev = np.linspace(292.0, 230.0, nz+1)
+    tmpa = rng.uniform(-8.0, 8.0, shape)
+    jsfc = np.ones((nyb, nxb)); psfc = np.zeros((5, nyb, nxb)); psfc[0] = rng.uniform(0.0, 0.4, (nyb, nxb))
+    tmps = rng.uniform(-10.0, 10.0, (nyb, nxb))
+    return Scene(zgrd=zgrd, ext1d=ext1d, omg1d=omg1d, apf1d=apf1d, abs1d=abs1d, nx=nx, ny=ny, dx=400.0, dy=300.0, nz3=nz3, iz3l=iz3l,
+                 abst=abst, extp=extp, omgp=omgp, apfp=apfp, sfc_mtype=1, sfc_param=[0.1, 0, 0, 0, 0], jsfc=jsfc, psfc=psfc,
+                 target=target, view_the=[180.0, 140.0], view_phi=[0.0, 30.0], view_zloc=[1.0e6, 1.0e6], nxr=nx, nyr=ny,
+                 src_mtype=3, src_wlen=wl, tmp1d=tlev, tmpa3d=tmpa, tmps2d=tmps, src_the=180.0, src_qmax=0.0)
+
+
+def thermal_powers_np(s):
+    """numpy float64 restatement of the thermal source's cell powers in CDF order: voxels, layers, surface cells"""
+    from er3t_amd.thermal import planck
+    f = lambda a: np.asarray(a, dtype=np.float32).astype(np.float64)
+    nz = s.nz
+    dz = np.diff(np.asarray(s.zgrd, dtype=np.float64))
+    t = f(s.tmp1d)
+    tl = 0.5*(t[:-1]+t[1:])
+    ka1 = (f(s.abs1d) if s.abs1d is not None else np.zeros(nz)) + (f(s.ext1d)*(1.0-f(s.omg1d))).sum(axis=0)
+    Lx, Ly = s.nx*s.dx, s.ny*s.dy
+    lay = 4.0*np.pi*ka1*planck(s.src_wlen, tl)*Lx*Ly*dz
+    vox = np.zeros(0)
+    if s.nz3 > 0:
+        k3 = np.arange(s.iz3l-1, s.iz3l-1+s.nz3)
+        lay[k3] = 0.0
+        kv = ka1[k3][:, None, None] + (f(s.extp)*(1.0-f(s.omgp))).sum(axis=0) + (f(s.abst) if s.abst is not None else 0.0)
+        tv = tl[k3][:, None, None] + (f(s.tmpa3d) if s.tmpa3d is not None else 0.0)
+        vox = (4.0*np.pi*kv*planck(s.src_wlen, tv)*s.dx*s.dy*dz[k3][:, None, None]).ravel()
+    if s.jsfc is not None:
+        alb = np.clip(f(s.psfc)[0], 0.0, 1.0)
+        ts = t[0] + (f(s.tmps2d) if s.tmps2d is not None else 0.0)
+        sfc = (np.pi*(1.0-alb)*planck(s.src_wlen, ts)*Lx*Ly/alb.size).ravel()
+    else:
+        sfc = np.array([np.pi*(1.0-np.clip(float(np.float32(s.sfc_param[0])), 0.0, 1.0))*planck(s.src_wlen, t[0])*Lx*Ly])
+    return np.concatenate([vox, lay, sfc])
