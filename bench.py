@@ -15,7 +15,12 @@ HBM before the timed region.  Rank 0 prints ONE JSON line.  `--dump-outputs DIR`
 computed (the normalised field and the raw tally) as DIR/<name>.npy; the inputs and photon ids depend on the arguments alone, so two
 builds run with the same arguments can be compared output for output.
 
-Extra objects on the line
+A plain run does only what the headline figure needs: it sets up, warms up, times the steps, writes the outputs (--dump-outputs)
+and prints the line: `metric`, `value`, `unit`, `ms_per_step`, `dtype`, ... and `config`.  Everything else it can measure or check
+comes with `--full` alone, after the timed steps (les480 at N=1: some 80 s more; the one exception, a reading of the shader clock
+half way through the timed steps, is a child process beside the queued launches):
+
+Extra objects on the line (--full)
   roofline     : algorithmic bytes per launch (measured with the instrumented kernel build on a sub-sample of the
                  timed photon ids, formula in DESIGN.md §6) / average launch duration (HIP events on the launch
                  stream, inside libmi3drt) against the 8 TB/s HBM3E peak; `traffic` = HBM bytes per launch from PMC passes
@@ -31,6 +36,9 @@ Extra objects on the line
                  just transported, eight batches on either side: difference of the domain means in sigma of two independent estimates
                  of that size, the same difference paired (relative), z-scores of 16 x 16 block means (`parity_stats`; the
                  full-size tests of tests/test_gpu_fullsize.py assert on the same numbers)
+  secondary    : short legs of the other BASELINE configurations and of the general photon loop (les480, N=1)
+  published_case : the reference's one published wall-clock case, end to end through the drop-in classes (les480, N=1)
+  strong       : N > 1, --scaling weak: BASELINE config 4 as written, --photons in all sharded over the ranks
 """
 
 import argparse
@@ -573,9 +581,13 @@ def main():
     ap.add_argument('--photons', type=float, default=1.0e9, help='photon histories per step: per GPU (weak) or in all (strong)')
     ap.add_argument('--scaling', default='weak', choices=['weak', 'strong'])
     ap.add_argument('--workload', default='les480', choices=["les480", "les128", "les480_mv9", "les128_flux", "les128_aer", "les480_mv9_lambert", "les480_flux", "les128_cam", "les128_mie"])
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-secondary', action='store_true', help='headline workload only: no short legs of the other BASELINE configurations')
-    ap.add_argument('--no-pmc', action='store_true', help='no live rocprofv3 --pmc passes after the timed region: traffic figures replayed from profiles/traffic.json')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check what lies beyond the headline figure: roofline (instrumented sub-sample, rocprofv3 '
+                         '--pmc passes, stream copy, the shader clock half way through the timed steps and after them), CPU baseline and '
+                         'parity, the other BASELINE configurations, the published case, the strong-scaling line for N > 1')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: no CPU baseline and parity')
+    ap.add_argument('--no-secondary', action='store_true', help='with --full: headline workload only: no short legs of the other BASELINE configurations, no strong-scaling line')
+    ap.add_argument('--no-pmc', action='store_true', help='with --full: no live rocprofv3 --pmc passes after the timed region: traffic figures replayed from profiles/traffic.json')
     ap.add_argument('--march-le', action='store_true', help='march every local-estimate ray (no column table)')
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'], help='gloo: rehearsal of the N-rank plumbing')
     ap.add_argument('--dry-run', action='store_true',
@@ -665,7 +677,7 @@ def main():
     t0 = time.perf_counter()
     for i in range(args.steps):
         step(args.warmup + i)
-        if i == args.steps//2 and rank == 0 and world == 1 and args.steps >= 4:
+        if args.full and i == args.steps//2 and rank == 0 and world == 1 and args.steps >= 4:
             sclk_mid = sclk_mhz()      # (the shader clock UNDER the timed load: a child process beside the queued launches, the host does not wait for the device here)
     torch.cuda.synchronize(dev)
     if use_dist:
@@ -688,10 +700,15 @@ def main():
                                                    'tally': tally.reshape(field.shape) if tally.size == field.size else tally})
         print('bench.py: last timed step written to %s: %s' % (args.dump_outputs, written), file=sys.stderr)
 
+    # sanity: the tally of the last timed step is finite and positive
+    mean_rad = float(rad.sum().item())*scene.src_flx*scene.mu0/Ptot
+    if not (mean_rad > 0.0 and np.isfinite(mean_rad)):
+        raise SystemExit('bench.py: radiance tally is not finite/positive (%r)' % mean_rad)
+
     # ---- N > 1: BASELINE config 4 as it is written -- `--photons` IN ALL, sharded over the ranks -- timed beside the weak-scaling headline
     #      (the driver runs `--scaling weak`; the strong line is the config's own wording).  Same barrier / max-over-ranks bracket.
     strong = None
-    if world > 1 and args.scaling == 'weak' and not args.no_secondary:
+    if args.full and world > 1 and args.scaling == 'weak' and not args.no_secondary:
         Pst = P
         ks = max(2, args.steps//2)
 
@@ -718,12 +735,35 @@ def main():
                   'what': 'BASELINE config 4 as written: %g photons in all, sharded over %d GPUs, one all-reduce per step' % (Pst, world)}
         sol.timing()
 
-    # sanity: the tally of the last step is finite and positive
-    mean_rad = float(rad.sum().item())*scene.src_flx*scene.mu0/Ptot
-    if not (mean_rad > 0.0 and np.isfinite(mean_rad)):
-        raise SystemExit('bench.py: radiance tally is not finite/positive (%r)' % mean_rad)
-
     if rank == 0:
+        n_rank = photon_shard(Ptot, world, rank)[1]
+        out = {
+            'metric': 'photons/sec', 'value': Ptot*args.steps/elapsed, 'unit': 'photons/s',
+            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': 1.0e3*elapsed/args.steps,
+            'higher_is_better': True, 'scaling': args.scaling, 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
+            'rccl_ranks': dist.get_world_size() if use_dist else 1, 'backend': args.backend if use_dist else None,
+            'config': {'workload': '%s: %dx%dx%d-voxel LES cloud domain (Atm_nz=%d), %s, HG g=0.85 + Rayleigh%s'
+                                   % (args.workload, scene.nx, scene.ny, scene.nz3, scene.nz,
+                                      {'les480': 'nadir radiance', 'les128': 'nadir radiance', 'les480_mv9': 'nine view zenith angles',
+                                       'les128_flux': 'flux + 3-D aerosol', 'les128_aer': 'nadir radiance + 3-D aerosol',
+                                       'les480_mv9_lambert': 'nine view zenith angles', 'les480_flux': 'flux', 'les128_cam': 'all-sky camera on the ground, 500 x 500 pixels',
+                                       'les128_mie': 'nadir radiance, tabulated (Mie-like) phase functions in the cloud'}[args.workload],
+                                      ', LSRT surface' if args.workload == 'les480_mv9' else ', Lambert 0.03'),
+                       'photons_per_step': Ptot, 'photons_per_gpu_per_step': n_rank, 'views': scene.nview, 'target': 'flux' if is_flux else 'radiance',
+                       'local_estimate': ('none (flux job)' if is_flux else 'marched' if args.march_le else
+                                          'marched to the camera (event lists + ray kernel)' if args.workload == 'les128_cam' else
+                                          'column table for the nadir view, the eight slant views marched (event lists + ray kernel)' if args.workload.startswith('les480_mv9') else
+                                          'column-table (exact for nadir)'),
+                       'parallelism': 'photon-sharded x%d, 1 all-reduce/step' % world if world > 1 else 'single GPU',
+                       'tallies': ('float64 sums of 8-byte level-crossing records, sorted and summed in LDS after every launch' if 'k_tl_scatter' in kernel_name
+                                   else 'float32 sums per workgroup in LDS around the photons\' tile (tally window), added to the float64 image by atomics; tallies outside the window: float64 atomics'
+                                   if args.workload in ('les480', 'les128', 'les128_aer', 'les128_mie') and not args.march_le else 'float64 atomics') + ' (arithmetic of the path: float32)', 'mean_radiance': mean_rad,
+                       'le_roulette': {'tau1': getattr(scene, 'le_tau1', 0.0), 'cmin': getattr(scene, 'le_cmin', 0.0),
+                                       'note': 'unbiased Russian roulettes on marched local-estimate rays (none on column-table views)'}},
+            'full': args.full,
+        }
+
+    if rank == 0 and args.full:
         # ---- algorithmic bytes per photon: instrumented build on a sub-sample of the timed ids
         nsub = min(P, 2000000)
         sol.bind(rad_ptr=None, flux_ptr=None, stream=stream.cuda_stream)
@@ -736,7 +776,6 @@ def main():
         # a step is transported in launches of at most 2^30 photons (the photon order of a launch is sorted by start tile):
         # the roofline figure is per launch of the transport kernel, averaged over the timed launches of this rank
         avg_ms = kernel_ms/max(launches, 1)
-        n_rank = photon_shard(Ptot, world, rank)[1]
         per_launch = n_rank*args.steps/max(launches, 1)
         achieved = bpp*per_launch/(avg_ms*1.0e-3)/1.0e9
         traffic = None
@@ -783,29 +822,7 @@ def main():
                         'issue_frac': v*per_launch/(avg_ms*1.0e-3)/VALU_MIX_CEILING, 'wave_cycles': t.get('sq_active_inst_valu'), 'source': source}
         peak_meas, peak_why_not = stream_peak() if world == 1 else (None, 'measured at N=1 only')
 
-        out = {
-            'metric': 'photons/sec', 'value': Ptot*args.steps/elapsed, 'unit': 'photons/s',
-            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': 1.0e3*elapsed/args.steps,
-            'higher_is_better': True, 'scaling': args.scaling, 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
-            'rccl_ranks': dist.get_world_size() if use_dist else 1, 'backend': args.backend if use_dist else None,
-            'config': {'workload': '%s: %dx%dx%d-voxel LES cloud domain (Atm_nz=%d), %s, HG g=0.85 + Rayleigh%s'
-                                   % (args.workload, scene.nx, scene.ny, scene.nz3, scene.nz,
-                                      {'les480': 'nadir radiance', 'les128': 'nadir radiance', 'les480_mv9': 'nine view zenith angles',
-                                       'les128_flux': 'flux + 3-D aerosol', 'les128_aer': 'nadir radiance + 3-D aerosol',
-                                       'les480_mv9_lambert': 'nine view zenith angles', 'les480_flux': 'flux', 'les128_cam': 'all-sky camera on the ground, 500 x 500 pixels',
-                                       'les128_mie': 'nadir radiance, tabulated (Mie-like) phase functions in the cloud'}[args.workload],
-                                      ', LSRT surface' if args.workload == 'les480_mv9' else ', Lambert 0.03'),
-                       'photons_per_step': Ptot, 'photons_per_gpu_per_step': n_rank, 'views': scene.nview, 'target': 'flux' if is_flux else 'radiance',
-                       'local_estimate': ('none (flux job)' if is_flux else 'marched' if args.march_le else
-                                          'marched to the camera (event lists + ray kernel)' if args.workload == 'les128_cam' else
-                                          'column table for the nadir view, the eight slant views marched (event lists + ray kernel)' if args.workload.startswith('les480_mv9') else
-                                          'column-table (exact for nadir)'),
-                       'parallelism': 'photon-sharded x%d, 1 all-reduce/step' % world if world > 1 else 'single GPU',
-                       'tallies': ('float64 sums of 8-byte level-crossing records, sorted and summed in LDS after every launch' if 'k_tl_scatter' in kernel_name
-                                   else 'float32 sums per workgroup in LDS around the photons\' tile (tally window), added to the float64 image by atomics; tallies outside the window: float64 atomics'
-                                   if args.workload in ('les480', 'les128', 'les128_aer', 'les128_mie') and not args.march_le else 'float64 atomics') + ' (arithmetic of the path: float32)', 'mean_radiance': mean_rad,
-                       'le_roulette': {'tau1': getattr(scene, 'le_tau1', 0.0), 'cmin': getattr(scene, 'le_cmin', 0.0),
-                                       'note': 'unbiased Russian roulettes on marched local-estimate rays (none on column-table views)'}},
+        out.update({
             # `bound` / `frac`: the HBM roofline SURVEY.md §8(d) prescribes for this path.  `bound_actual`: what the dominant kernel of
             # the workload runs into on this chip: the voxel reads are L2 hits, so none of them is HBM-bound
             'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
@@ -839,7 +856,7 @@ def main():
                                                                  'a higher clock under this loop, which waits on memory half of the time -- the ceiling scales with the clock, the fraction with its inverse: the 0.90 by rate and the '
                                                                  '0.77 per busy cycle of VERDICT r5 (SQ_ACTIVE_INST_VALU x 4 / SQ_BUSY_CYCLES: 35.0 against 45.6) are one number once both sides are counted in cycles') if valu else None),
                          'per_photon': {k: cnt[k]/nsub for k in ('steps3d', 'le_steps3d', 'le_column', 'scatter', 'surface', 'le_rays', 'flux_tally')}},
-        }
+        })
 
         if world == 1 and not args.no_cpu_baseline:
             from oracle import oracle
@@ -927,6 +944,7 @@ def main():
                 out['published_case'] = {'error': repr(e)[:300]}
         if strong is not None:
             out['strong'] = strong
+    if rank == 0:
         print(json.dumps(out))
 
     if use_dist:

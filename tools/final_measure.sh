@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/$R; mkdir -p $O
 if [[ $PART == *A* ]]; then
 # 1. kernel trace + stats of the bench command (5 steps of 1e9 photons)
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/kt -o bench --output-format csv -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-pmc > $O/bench_under_rocprof.log 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/kt -o bench --output-format csv -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-pmc > $O/bench_under_rocprof.log 2>&1
 echo kt done
 # 2. PMC passes of one full-size launch (5e8 photons: what one launch of a bench step of 1e9 is)
 N=500000000
@@ -37,22 +37,22 @@ python3 tools/pmc_parse.py $O/pmcf/* > $O/pmc_summary_les128_flux.txt
 python3 tools/make_traffic.py $O/pmcf les128_flux $NF $O/traffic.json "round ${R}, $(date -u +%Y-%m-%dT%H:%MZ), tools/final_measure.sh"
 cp $O/traffic.json profiles/traffic.json
 # 3. the bench lines (with the traffic figures just measured)
-timeout -k 10 600 python bench.py > $O/bench_les480_n1.json.log 2> $O/bench_err.log
+timeout -k 10 600 python bench.py --full > $O/bench_les480_n1.json.log 2> $O/bench_err.log
 tail -1 $O/bench_les480_n1.json.log
-timeout -k 10 400 python bench.py --workload les480_mv9 --photons 2e8 --steps 8 --no-cpu-baseline --no-pmc > $O/bench_les480_mv9_n1.json.log 2>> $O/bench_err.log
+timeout -k 10 400 python bench.py --full --workload les480_mv9 --photons 2e8 --steps 8 --no-cpu-baseline --no-pmc > $O/bench_les480_mv9_n1.json.log 2>> $O/bench_err.log
 tail -1 $O/bench_les480_mv9_n1.json.log
-timeout -k 10 400 python bench.py --workload les128 --photons 1e9 --steps 5 --no-cpu-baseline --no-pmc > $O/bench_les128_n1.json.log 2>> $O/bench_err.log
-timeout -k 10 400 python bench.py --workload les128_flux --photons 1e8 --steps 5 --no-cpu-baseline --no-pmc > $O/bench_les128_flux_n1.json.log 2>> $O/bench_err.log || true
-timeout -k 10 400 python bench.py --workload les128_aer --photons 1e9 --steps 5 --no-cpu-baseline --no-pmc > $O/bench_les128_aer_n1.json.log 2>> $O/bench_err.log || true
-timeout -k 10 300 python bench.py --workload les480_flux --photons 1e8 --steps 5 --no-cpu-baseline --no-pmc > $O/bench_les480_flux_n1.json.log 2>> $O/bench_err.log || true
-timeout -k 10 300 python bench.py --workload les128_cam --photons 5e7 --steps 5 --no-cpu-baseline --no-pmc > $O/bench_les128_cam_n1.json.log 2>> $O/bench_err.log || true
+timeout -k 10 400 python bench.py --full --workload les128 --photons 1e9 --steps 5 --no-cpu-baseline --no-pmc > $O/bench_les128_n1.json.log 2>> $O/bench_err.log
+timeout -k 10 400 python bench.py --full --workload les128_flux --photons 1e8 --steps 5 --no-cpu-baseline --no-pmc > $O/bench_les128_flux_n1.json.log 2>> $O/bench_err.log || true
+timeout -k 10 400 python bench.py --full --workload les128_aer --photons 1e9 --steps 5 --no-cpu-baseline --no-pmc > $O/bench_les128_aer_n1.json.log 2>> $O/bench_err.log || true
+timeout -k 10 300 python bench.py --full --workload les480_flux --photons 1e8 --steps 5 --no-cpu-baseline --no-pmc > $O/bench_les480_flux_n1.json.log 2>> $O/bench_err.log || true
+timeout -k 10 300 python bench.py --full --workload les128_cam --photons 5e7 --steps 5 --no-cpu-baseline --no-pmc > $O/bench_les128_cam_n1.json.log 2>> $O/bench_err.log || true
 echo part A done
 fi
 if [[ $PART == *B* ]]; then
 # strong scaling rehearsal on one GPU: the per-GPU share of config 4 / 5 on eight GPUs (1.25e8 photons per step): what the
 # fixed cost of a step (sort, launch tail, fold, zeroing) does to the rate
-timeout -k 10 300 python bench.py --gpus 1 --scaling strong --photons 1.25e8 --steps 20 --warmup 2 --no-cpu-baseline > $O/bench_les480_strong_share_of_8.json.log 2>> $O/bench_err.log || true
-timeout -k 10 300 python bench.py --gpus 1 --scaling strong --photons 1.25e8 --steps 10 --warmup 2 --workload les480_mv9 --no-cpu-baseline > $O/bench_les480_mv9_strong_share_of_8.json.log 2>> $O/bench_err.log || true
+timeout -k 10 300 python bench.py --full --gpus 1 --scaling strong --photons 1.25e8 --steps 20 --warmup 2 --no-cpu-baseline > $O/bench_les480_strong_share_of_8.json.log 2>> $O/bench_err.log || true
+timeout -k 10 300 python bench.py --full --gpus 1 --scaling strong --photons 1.25e8 --steps 10 --warmup 2 --workload les480_mv9 --no-cpu-baseline > $O/bench_les480_mv9_strong_share_of_8.json.log 2>> $O/bench_err.log || true
 # K16: the HIP path against the deterministic plane-parallel answer, the table behind the assertions
 rm -f $O/k16_gpu_matrix.log; K16_LOG=$O/k16_gpu_matrix.log timeout -k 10 600 python -m pytest tests/test_k16.py -m gpu -q > $O/k16_pytest.log 2>&1 || true
 # 4. scheduler diagnostics and microbenchmarks whose logs are kept

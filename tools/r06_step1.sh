@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/r06/c1; rm -rf $O; mkdir -p $O
 timeout -k 10 400 python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "pre_pass_beside or record_sort_beside or flux_tally_routes or flux_parity_les" > $O/pytest_subset.log 2>&1; echo "pytest rc $?"; tail -3 $O/pytest_subset.log
 for w in les128_flux les480_flux; do
-  timeout -k 10 300 python bench.py --workload $w --steps 8 --no-pmc --no-cpu-baseline > $O/bench_$w.log 2>&1; echo "bench $w rc $?"
+  timeout -k 10 300 python bench.py --full --workload $w --steps 8 --no-pmc --no-cpu-baseline > $O/bench_$w.log 2>&1; echo "bench $w rc $?"
   python - $O/bench_$w.log <<'PY'
 import json,sys
 for ln in open(sys.argv[1]):

@@ -2,7 +2,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/r06/c30; rm -rf $O; mkdir -p $O
 timeout -k 10 600 python -m pytest tests/test_gpu_fullsize.py -x -q -m gpu -s -k "les128_mie" > $O/pytest_mie.log 2>&1; echo "pytest mie rc $?"; grep "les128_mie\|passed\|failed" $O/pytest_mie.log | tail -12
-timeout -k 10 900 python bench.py > $O/bench.log 2> $O/bench.err; echo "bench rc $?"; tail -3 $O/bench.err
+timeout -k 10 900 python bench.py --full > $O/bench.log 2> $O/bench.err; echo "bench rc $?"; tail -3 $O/bench.err
 python - $O/bench.log <<'PY'
 import json,sys
 for ln in open(sys.argv[1]):
