@@ -156,6 +156,7 @@ struct mi3d_solver {
     tally_t *rad_ext = nullptr, *flux_ext = nullptr;
     DevBuf<double> d_heat_own;       // heating rates (MI3D_TARGET_HEAT): weight absorbed per cell [nz][ny][nx]
     double *heat_ext = nullptr;
+    int heat_estimator = 0;          // mi3d_set_heating_estimator: 0 collision, 1 path length
     size_t heat_elems() const { return (size_t)nz * nx * ny; }
     double *heat_ptr() { return heat_ext ? heat_ext : d_heat_own.p; }
     DevBuf<unsigned long long> d_counters, d_next;
@@ -516,6 +517,7 @@ int fill_scene(mi3d_solver *h, DevScene &S) {
     // er3t's default mixture (mca_atm.py:95-102,299-303): Rayleigh as the one 1-D constituent, Henyey-Greenstein in every voxel:
     // the lean kernels then evaluate the two phase functions without looking at their selectors (bit 8 of the target word)
     if (rayleigh_1d(h)) S.target |= kTargetRayleigh1d | (h->hg3d ? kTargetPlainPhase : 0);
+    if ((h->target & MI3D_TARGET_HEAT) && h->heat_estimator == 1) S.target |= kTargetHeatPath;
     S.rad = h->rad_ptr(); S.flux = h->flux_ptr(); S.rad_stride = 1;
     C.next_photon = h->d_next.p;
     C.le_tau1 = (float)h->le_tau1;
@@ -1101,6 +1103,20 @@ int mi3d_bind_device_buffers(mi3d_solver *h, void *rad_sum, void *flux_sum, void
     return MI3D_OK;
 }
 
+int mi3d_set_heating_estimator(mi3d_solver *h, int estimator) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (estimator != 0 && estimator != 1) return fail(MI3D_EINVAL, "heating estimator %d (0: collision, 1: path length)", estimator);
+    if (estimator == h->heat_estimator) return MI3D_OK;
+    HIPCHK(sync_main(h));   // (as every call that changes what the kernels work on)
+    h->heat_estimator = estimator;
+    // (another estimator, other records per photon: the lists are sized anew; its sums and the other one's do not mix in one tally)
+    h->tl_per_photon = 0.0; h->tl_total_pp = 0.0; h->tl_runs_pp = 0.0;
+    for (auto &S : h->tl_slot) S.busy = false;
+    if (h->target & MI3D_TARGET_HEAT) h->dirty_tally = true;
+    return MI3D_OK;
+}
+
 int mi3d_bind_heating_buffer(mi3d_solver *h, void *heat_sum) {
     int rc = check_handle(h);
     if (rc) return rc;
@@ -1462,14 +1478,16 @@ static hipError_t launch_flux(mi3d_solver *h, int tset, bool two_streams, const 
     if (T.pend.on && (e0 = launch_sum(h, tset, st)) != hipSuccess) return e0;
     // (the set's cursors: behind the wait -- the sort of the launch that used the set last writes one of them and copies them out on its stream)
     if (TL.cap && (e0 = hipMemsetAsync(TL.cursor, 0, 3 * sizeof(unsigned long long), st)) != hipSuccess) return e0;
-#define MI3D_FLUX_LAUNCH(C, P)                                                                                              \
+#define MI3D_FLUX_LAUNCH_H(C, P, H)                                                                                         \
     do {                                                                                                                    \
         if (mix == 2) {                                                                                                     \
-            if (lds > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_transport_flux<C, P, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            hipLaunchKernelGGL((k_transport_flux<C, P, 2>), dim3(grid), dim3(256), lds, st, S, TLd, nb, seed, off);          \
-        } else if (mix == 1) hipLaunchKernelGGL((k_transport_flux<C, P, 1>), dim3(grid), dim3(256), lds, st, S, TLd, nb, seed, off);  \
-        else hipLaunchKernelGGL((k_transport_flux<C, P, 0>), dim3(grid), dim3(256), lds, st, S, TLd, nb, seed, off);         \
+            if (lds > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_transport_flux<C, P, 2, H>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+            hipLaunchKernelGGL((k_transport_flux<C, P, 2, H>), dim3(grid), dim3(256), lds, st, S, TLd, nb, seed, off);       \
+        } else if (mix == 1) hipLaunchKernelGGL((k_transport_flux<C, P, 1, H>), dim3(grid), dim3(256), lds, st, S, TLd, nb, seed, off);  \
+        else hipLaunchKernelGGL((k_transport_flux<C, P, 0, H>), dim3(grid), dim3(256), lds, st, S, TLd, nb, seed, off);      \
     } while (0)
+    // (the path-length estimator of the heating rates: builds of their own)
+#define MI3D_FLUX_LAUNCH(C, P) do { if (S.target & kTargetHeatPath) MI3D_FLUX_LAUNCH_H(C, P, true); else MI3D_FLUX_LAUNCH_H(C, P, false); } while (0)
     switch ((h->counting ? 2 : 0) | (h->solver == MI3D_SOLVER_P3D ? 1 : 0)) {
         case 0: MI3D_FLUX_LAUNCH(false, false); break;
         case 1: MI3D_FLUX_LAUNCH(false, true); break;
@@ -1477,6 +1495,7 @@ static hipError_t launch_flux(mi3d_solver *h, int tset, bool two_streams, const 
         default: MI3D_FLUX_LAUNCH(true, true); break;
     }
 #undef MI3D_FLUX_LAUNCH
+#undef MI3D_FLUX_LAUNCH_H
     hipError_t err = hipGetLastError();
     if (err == hipSuccess) {
         if (!h->tldesc_ev[slot]) err = hipEventCreateWithFlags(&h->tldesc_ev[slot], hipEventDisableTiming);
@@ -1704,10 +1723,12 @@ static int cam_fallback(mi3d_solver *h, const char *why) {
 static void name_route(mi3d_solver *h, const RunPlan &plan, bool lists, uint64_t nphoton) {
     const int c = h->counting ? 1 : 0, p3d = h->solver == MI3D_SOLVER_P3D ? 1 : 0;
     char nm[96];
-    if (plan.loop == Loop::Flux) snprintf(nm, sizeof(nm), lists ? "k_transport_flux<%d,%d,%d> + k_tl_scatter + k_tl_sum" : "k_transport_flux<%d,%d,%d>", c, p3d, plan.mix);
+    const bool hpath = (h->target & MI3D_TARGET_HEAT) && h->heat_estimator == 1;
+    if (plan.loop == Loop::Flux && hpath) snprintf(nm, sizeof(nm), lists ? "k_transport_flux<%d,%d,%d,1> + k_tl_scatter + k_tl_sum" : "k_transport_flux<%d,%d,%d,1>", c, p3d, plan.mix);
+    else if (plan.loop == Loop::Flux) snprintf(nm, sizeof(nm), lists ? "k_transport_flux<%d,%d,%d> + k_tl_scatter + k_tl_sum" : "k_transport_flux<%d,%d,%d>", c, p3d, plan.mix);
     else if (plan.loop == Loop::ColumnRays) snprintf(nm, sizeof(nm), "k_transport_lean<%d,%d,2,%d> + k_rays", c, p3d, plan.mix_lean);
     else if (plan.loop == Loop::Column) snprintf(nm, sizeof(nm), "k_transport_lean<%d,%d,0,%d>", c, p3d, plan.mix_lean);
-    else snprintf(nm, sizeof(nm), plan.thermal ? "k_transport<%d,%d,%d,%d> [thermal]" : "k_transport<%d,%d,%d,%d>", c, plan.march ? 1 : 0, plan.flux ? 1 : 0, p3d);
+    else snprintf(nm, sizeof(nm), plan.thermal ? "k_transport<%d,%d,%d,%d> [thermal]" : hpath ? "k_transport<%d,%d,%d,%d> [heating: path length]" : "k_transport<%d,%d,%d,%d>", c, plan.march ? 1 : 0, plan.flux ? 1 : 0, p3d);
     h->last_kernel = nm;
     if (plan.loop == Loop::General && h->kernel_choice == 0 && !h->general_warned && nphoton >= 4096 && !plan.thermal) {
         fprintf(stderr, "Warning [mi3d_run]: this job runs on the general photon loop (k_transport), not on a lean one: %s.  Same results, a third to a half of the speed.\n", plan.why);
@@ -1722,7 +1743,9 @@ static size_t free_bytes(size_t unknown) { size_t f = 0, t = 0; if (hipMemGetInf
 // Nothing known yet: a record per level and a half, every one of them written by the loop, a run for every kRunMin of them.
 struct TlRates { double tpp, dpp, rpp; };
 static TlRates tl_rates(const mi3d_solver *h, bool runs) {
-    const double tpp = h->tl_total_pp > 0.0 ? 1.15 * h->tl_total_pp : (h->tl_per_photon > 0.0 && !runs ? 1.15 * h->tl_per_photon : 1.5 * (h->nz + 1));
+    // (the path-length estimator of the heating rates: a record per cell and layer flown through beside the one per level -- twice the guess)
+    const double guess = ((h->target & MI3D_TARGET_HEAT) && h->heat_estimator == 1 ? 3.0 : 1.5) * (h->nz + 1);
+    const double tpp = h->tl_total_pp > 0.0 ? 1.15 * h->tl_total_pp : (h->tl_per_photon > 0.0 && !runs ? 1.15 * h->tl_per_photon : guess);
     return {tpp, h->tl_per_photon > 0.0 ? 1.15 * h->tl_per_photon : tpp, !runs ? 0.0 : h->tl_runs_pp > 0.0 ? 1.15 * h->tl_runs_pp + 0.05 : tpp / kRunMin};
 }
 
@@ -1739,7 +1762,9 @@ static void tl_compact_hist(const mi3d_solver *h, TallyList &T) {
     const size_t ncol_ = (size_t)h->nx * h->ny, nlev_ = (size_t)h->nz + 1, nflux_ = 3 * nlev_ * ncol_;
     std::vector<std::pair<int, int>> rg;
     for (size_t pl = 0; pl < 3; ++pl) rg.emplace_back((int)(((pl * nlev_ + ks_lo) * ncol_) >> shift), (int)((((pl * nlev_ + ks_hi + 2) * ncol_) - 1) >> shift));
-    if (h->target & MI3D_TARGET_HEAT) rg.emplace_back((int)((nflux_ + (size_t)ks_lo * ncol_) >> shift), (int)((nflux_ + ((size_t)ks_hi + 1) * ncol_ - 1) >> shift));
+    // (the path-length estimator leaves records in the heating cells of EVERY layer, the uniform ones too: all of their bins)
+    if ((h->target & MI3D_TARGET_HEAT) && h->heat_estimator == 1) rg.emplace_back((int)(nflux_ >> shift), nbins - 1);
+    else if (h->target & MI3D_TARGET_HEAT) rg.emplace_back((int)((nflux_ + (size_t)ks_lo * ncol_) >> shift), (int)((nflux_ + ((size_t)ks_hi + 1) * ncol_ - 1) >> shift));
     std::sort(rg.begin(), rg.end());
     std::vector<std::pair<int, int>> mg;
     for (auto &q : rg) { if (!mg.empty() && q.first <= mg.back().second + 1) mg.back().second = std::max(mg.back().second, q.second); else mg.push_back(q); }
@@ -1889,6 +1914,8 @@ static uint64_t size_ev_lists(mi3d_solver *h, uint64_t nphoton, bool two_sets) {
 // (no room, "entry_records" 0) the photons are launched inside the loop as before.  Points cold_host at the records.
 static bool use_entry_records(mi3d_solver *h, const RunPlan &plan, uint64_t nphoton) {
 #if MI3D_LEAN_FAST
+    // (the path-length estimator of the heating rates tallies the first flight too: its photons are launched inside the loop)
+    if ((h->target & MI3D_TARGET_HEAT) && h->heat_estimator == 1) return false;
     if (plan.loop == Loop::General || !h->entry_records || h->nx >= 65536 || h->ny >= 65536 || h->nz >= 32768) return false;
     DevBuf<float4> &E = h->pre[0].entry;
     const size_t need = entry_f4((size_t)std::min<uint64_t>(nphoton, h->batch));

@@ -92,7 +92,13 @@ __host__ __device__ inline int tl_nrow(const TallyList &TL) { return (TL.hist_wg
 
 // MIX: as in k_transport_lean: 0 one 1-D and one 3-D constituent, 1 a second 3-D constituent, 2 the general mixture (several 1-D
 //      constituents, tabulated phase functions: the tables staged in LDS behind the waves' stages)
-template <bool COUNT, bool P3D, int MIX>
+// HEST: the heating-rate tally's estimator (mi3d_set_heating_estimator; builds of their own, so that the default's carry none of it).
+//      false: a collision leaves w (bt - sum ks) / bt in its cell.  true: the PATH-LENGTH estimator -- every flight segment inside one
+//      cell leaves w kappa_a l, kappa_a = max(bt - sum ks, 0) from the records and the sum of scattering coefficients a collision in
+//      that cell would use (kabs_of below), and a collision leaves nothing: a record per voxel step with kappa_a > 0 (phase A), one for the
+//      piece up to a collision (blocks C, B0), and one per layer a flight through uniform layers touches (block B0, cut at the levels only;
+//      the column is the one of the piece's midpoint).  It draws no random number: same photon id, same history, same flux records.
+template <bool COUNT, bool P3D, int MIX, bool HEST>
 __global__ void __launch_bounds__(256, MI3D_FLUX_WAVES(COUNT))
 k_transport_flux(const DevScene S, const TallyList *__restrict__ TLp, const uint64_t nphoton, const uint64_t seed, const uint64_t offset) {
     constexpr bool TWO = (MIX == 1), GEN = (MIX == 2);
@@ -167,6 +173,9 @@ k_transport_flux(const DevScene S, const TallyList *__restrict__ TLp, const uint
     // the tally a lane has made in the step just taken, written out by the whole wave at once (TL_FLUSH)
     unsigned pidx = kTlNone;
     float pw = 0.0f;
+    // (HEST: a voxel step that crosses a level leaves two records, the level's and the cell's: the second one waits here for a flush of its own)
+    unsigned hidx = kTlNone;
+    float hw = 0.0f;
     unsigned long long tl_pos = 0, tl_end = 0;   // wave-uniform: the part of this wave's chunk that is still free
     bool tl_off = (tl_cap == 0u);                 // wave-uniform: tallies go out as atomics (no lists, or the list has run full)
 
@@ -240,6 +249,7 @@ k_transport_flux(const DevScene S, const TallyList *__restrict__ TLp, const uint
                 if (!tl_off) stage[st_n + __builtin_amdgcn_mbcnt_hi((unsigned)(m_ >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m_, 0u))] = make_uint2(pidx, __float_as_uint(pw)); \
                 else { TL_ATOMIC(pidx, pw); if (COUNT) cnt.le_column++; /* (instrumented build: tallies that went out as atomics) */ } \
                 if (COUNT && pidx < nflux) cnt.flux_tally++;                                                                    \
+                if (COUNT && HEST && pidx >= nflux) cnt.le_steps3d++;   /* (instrumented path-length build: its heating records, in a counter the flux loop does not use) */ \
                 MI3D_RUNLEN_DIAG();                                                                                             \
                 pidx = kTlNone;                                                                                                 \
             }                                                                                                                   \
@@ -258,6 +268,19 @@ k_transport_flux(const DevScene S, const TallyList *__restrict__ TLp, const uint
     // collisions the walk finds, the rarer events in full passes, new photons from entry records.
     constexpr int M_COLLU = 12, M_UNIFW = 13, M_SETUP = 14;   // (as in mi3d_kernel_lean.hip)
 #define VREC(ix_, iy_, k_) (*reinterpret_cast<const float4 *>(vbase + ((unsigned)(iy_) * sy_b + (unsigned)(ix_) * sx_b + (unsigned)(k_) * 16u)))
+    // HEST: the absorption coefficient of cell (ix_, iy_, k_) whose total extinction is bt_ and whose first 3-D constituent scatters with ks3_
+    // (0 outside the 3-D region): bt less the sum of scattering coefficients blocks C and B2 form for a collision there, operand for operand
+    auto kabs_of = [&](const float bt_, const float ks3_, const int ix_, const int iy_, const int k_, const bool in3d_) -> float {
+        const LayerRec &Lq = lay[k_];
+        float kst = Lq.ks1d[0] + ks3_;
+        if (GEN) for (int ip = 1; ip < np1d; ++ip) kst += Lq.ks1d[ip];
+        if (two3 && in3d_) kst += cold->csca[((unsigned)(iy_ * S.nx + ix_) * (unsigned)S.nz3 + (unsigned)(k_ - S.k3lo)) * 2u + 1u].x;
+        return fmaxf(bt_ - kst, 0.0f);
+    };
+    (void)kabs_of;
+#define HEAT_CELL(ix_, iy_, k_) (nflux + (unsigned)((k_) * S.ny + (iy_)) * (unsigned)S.nx + (unsigned)(ix_))
+    // (the cell's record of a step: after the level's)
+#define HEAT_FLUSH() do { if (HEST) { pidx = hidx; pw = hw; hidx = kTlNone; TL_FLUSH(); } } while (0)
     for (;;) {
         // =================================== phase A: voxel steps ===================================
         MI3D_MARK("FA");
@@ -273,6 +296,10 @@ k_transport_flux(const DevScene S, const TallyList *__restrict__ TLp, const uint
                 if (COUNT) { cnt.steps++; cnt.steps3d++; }
                 if (dtau >= rem) mode = M_COLL;
                 else {
+                    if (HEST) {   // the segment through this cell: w kappa_a (tn - t), from the record the step has read
+                        const float ka = kabs_of(rec.x, rec.z, ix, iy, k, true);
+                        if (ka > 0.0f) { hidx = HEAT_CELL(ix, iy, k); hw = w * ka * (tn - t); }
+                    }
                     rem -= dtau;
                     t = tn;
                     const bool zf = (tz == tn), xf = !zf && (tx == tn), yf = !zf && !xf;
@@ -296,6 +323,7 @@ k_transport_flux(const DevScene S, const TallyList *__restrict__ TLp, const uint
                 }
             }
             TL_FLUSH();
+            HEAT_FLUSH();
         }
 
         // =================================== phase B ===================================
@@ -330,7 +358,8 @@ k_transport_flux(const DevScene S, const TallyList *__restrict__ TLp, const uint
             const float w_in = w;
             w *= (kstot >= rec.x) ? 1.0f : kstot * ibt;
             // heating rates (Flx_mhrt = 1): what the collision takes from the weight stays in this cell -- one more tally record
-            if (cold->heat && kstot < rec.x) { pidx = nflux + (unsigned)(k * S.ny + iy) * (unsigned)S.nx + (unsigned)ix; pw = w_in * (rec.x - kstot) * ibt; }
+            // (HEST: the piece of the flight from the last face to the collision, rem / bt long, instead)
+            if (cold->heat && kstot < rec.x) { pidx = HEAT_CELL(ix, iy, k); pw = HEST ? w_in * (rec.x - kstot) * (rem * ibt) : w_in * (rec.x - kstot) * ibt; }
             if (!(w > 0.0f)) { if (COUNT) cnt.absorbed++; mode = M_NEED; }
             else {
                 float mu_rot;
@@ -391,6 +420,8 @@ k_transport_flux(const DevScene S, const TallyList *__restrict__ TLp, const uint
         const bool inrun = mode == M_UNIF;
         int knew = 0, next = M_SETUP, la = 1, lb = 0;
         float pzn = 0.0f, s = 0.0f, iuzl = 0.0f;
+        int hk_last = 0;       // HEST: the last layer the flight touches, and the height it ends at
+        float hz_end = 0.0f;
         if (inrun) {
             const bool up = uz > 0.0f;
             const LayerRec &Lk = lay[k];
@@ -406,6 +437,7 @@ k_transport_flux(const DevScene S, const TallyList *__restrict__ TLp, const uint
                 rem -= tpath;
                 s = hv * iuzl;
                 kraw = knew = up ? kend + 1 : kend - 1;
+                if (HEST) { hk_last = kend; hz_end = up ? Le.zlo + Le.dz : Le.zlo; }
                 next = M_SETUP;
                 if (knew >= S.nz) { if (COUNT) cnt.escaped++; next = M_NEED; }
                 else if (knew < 0) { knew = 0; next = M_SURF; }
@@ -421,6 +453,7 @@ k_transport_flux(const DevScene S, const TallyList *__restrict__ TLp, const uint
                 pzn = fminf(fmaxf((T - lay[lo].tauz) * frcp(fmaxf(Lj.y, 1e-30f)), 0.0f), Lj.x);
                 s = fabsf((Lj.z + pzn) - (Lk.zlo + pz)) * iuzl;
                 kraw = knew = lo;
+                if (HEST) { hk_last = lo; hz_end = Lj.z + pzn; }
                 bt_ev = Lj.y;
                 next = M_COLLU;
             }
@@ -512,6 +545,37 @@ k_transport_flux(const DevScene S, const TallyList *__restrict__ TLp, const uint
                 __builtin_amdgcn_wave_barrier();
             }
         }
+        // HEST: what the flight leaves in the layers it touches, one record per layer: the piece of it between the layer's levels (the
+        // first and the last layer: from where it starts, up to where it ends), in the column of the piece's midpoint -- placed from where
+        // the flight started by the multiply-add and fold that places its level crossings.  (A loop of every lane over its own layers,
+        // the wave as long as its longest flight: run records know nothing of layers yet.)
+        if (HEST && cold->heat) {
+            const float z0 = inrun ? lay4[k * kL4].z + pz : 0.0f;
+            const float zlo_f = fminf(z0, hz_end), zhi_f = fmaxf(z0, hz_end);
+            const int nlay = inrun ? abs(hk_last - k) + 1 : 0, dk = hk_last >= k ? 1 : -1;
+            const bool ipa = IPA_NOW();
+            for (int it = 0; __ballot(it < nlay) != 0ull; ++it) {
+                if (it < nlay) {
+                    const int j = k + it * dk;
+                    const float4 Lj = lay4[j * kL4];     // {dz, bt, zlo, flags}
+                    const float za = fmaxf(Lj.z, zlo_f), zb = fminf(Lj.z + Lj.x, zhi_f);
+                    int jx = ix, jy = iy;
+                    if (!ipa) {
+                        const float sl = fabsf(0.5f * (za + zb) - z0) * iuzl;
+                        const float fx = floorf(fmaf(ux, sl, px) * cold->inv_dx), fy = floorf(fmaf(uy, sl, py) * cold->inv_dy);
+                        jx += (int)fx; jy += (int)fy;
+                        if ((unsigned)jx >= (unsigned)S.nx) jx = wrapi(jx, S.nx, cold->inv_nx);
+                        if ((unsigned)jy >= (unsigned)S.ny) jy = wrapi(jy, S.ny, cold->inv_ny);
+                        jx = min(max(jx, 0), S.nx - 1); jy = min(max(jy, 0), S.ny - 1);     // (a flight along the horizon: whatever its fold gives, a cell of the tally)
+                    }
+                    const bool in3d = (__float_as_int(Lj.w) & kLayIn3d) != 0;
+                    const float ks3 = in3d ? VREC(jx, jy, j).z : 0.0f;
+                    const float ka = kabs_of(Lj.y, ks3, jx, jy, j, in3d);
+                    if (ka > 0.0f && zb > za) { pidx = HEAT_CELL(jx, jy, j); pw = w * ka * (zb - za) * iuzl; }
+                }
+                TL_FLUSH();
+            }
+        }
         if (inrun) {
             px += ux * s; py += uy * s;
             k = knew; pz = pzn;
@@ -551,7 +615,7 @@ k_transport_flux(const DevScene S, const TallyList *__restrict__ TLp, const uint
                 }
                 const float w_in = w;
                 w *= (kstot >= bt_ev) ? 1.0f : kstot * frcp(bt_ev);
-                if (cold->heat && kstot < bt_ev) { pidx = nflux + (unsigned)(k * S.ny + iy) * (unsigned)S.nx + (unsigned)ix; pw = w_in * (bt_ev - kstot) * frcp(bt_ev); }
+                if (!HEST && cold->heat && kstot < bt_ev) { pidx = nflux + (unsigned)(k * S.ny + iy) * (unsigned)S.nx + (unsigned)ix; pw = w_in * (bt_ev - kstot) * frcp(bt_ev); }
                 if (!(w > 0.0f)) { if (COUNT) cnt.absorbed++; dead = true; }
                 kind = E_SCATTER;
             }
@@ -728,6 +792,8 @@ k_transport_flux(const DevScene S, const TallyList *__restrict__ TLp, const uint
         MI3D_MARK("FEND");
         if (__ballot(mode != M_DONE) == 0ull) break;
     }
+#undef HEAT_FLUSH
+#undef HEAT_CELL
 #undef VREC
 #undef MI3D_TICK
 #undef IPA_NOW
@@ -1279,10 +1345,11 @@ k_tl_sum(const TallyList TL, tally_t *__restrict__ flux, const unsigned nflux, d
     }
 }
 
-#define MI3D_FLUX_INST(C, P) template __global__ void k_transport_flux<C, P, 0>(const DevScene, const TallyList *, const uint64_t, const uint64_t, const uint64_t); \
-                             template __global__ void k_transport_flux<C, P, 1>(const DevScene, const TallyList *, const uint64_t, const uint64_t, const uint64_t); \
-                             template __global__ void k_transport_flux<C, P, 2>(const DevScene, const TallyList *, const uint64_t, const uint64_t, const uint64_t);
+#define MI3D_FLUX_INST1(C, P, M) template __global__ void k_transport_flux<C, P, M, false>(const DevScene, const TallyList *, const uint64_t, const uint64_t, const uint64_t); \
+                                 template __global__ void k_transport_flux<C, P, M, true>(const DevScene, const TallyList *, const uint64_t, const uint64_t, const uint64_t);
+#define MI3D_FLUX_INST(C, P) MI3D_FLUX_INST1(C, P, 0) MI3D_FLUX_INST1(C, P, 1) MI3D_FLUX_INST1(C, P, 2)
 MI3D_FLUX_INST(false, false) MI3D_FLUX_INST(false, true) MI3D_FLUX_INST(true, false) MI3D_FLUX_INST(true, true)
+#undef MI3D_FLUX_INST1
 #undef MI3D_FLUX_INST
 
 } // namespace mi3d

@@ -738,6 +738,22 @@ k_transport(const DevScene S, const uint64_t nphoton, const uint64_t seed, const
     const bool do_rad = (S.target & MI3D_TARGET_RADIANCE) != 0 && S.nview > 0;
 #endif
     const bool jump = !FLUX; // flux needs every level crossing
+    // Heating rates by the path-length estimator (mi3d_set_heating_estimator 1, kTargetHeatPath): every piece of a photon's flight inside one
+    // cell leaves w kappa_a l there -- kappa_a = max(bt - sum ks, 0), the sum block B2 forms for a collision in that cell -- and a collision
+    // leaves nothing.  Uniform layers are cut at the levels only: a layer's piece goes to the column of its midpoint.
+    const bool hest = FLUX && cold->heat != nullptr && (S.target & kTargetHeatPath) != 0;
+    auto heat_path = [&](const int jx_, const int jy_, const int kk, const float bt, const float ks3, const bool in3d, const float wl) {
+        const int jx = min(max(jx_, 0), S.nx - 1), jy = min(max(jy_, 0), S.ny - 1);     // (whatever a fold along the horizon gives: a cell of the tally)
+        const LayerRec &Lq = lay[kk];
+        float kst = 0.0f;
+        for (int ip = 0; ip < S.np1d; ++ip) kst += Lq.ks1d[ip];
+        if (in3d) {
+            kst += ks3;
+            const unsigned vox = (unsigned)(jy * S.nx + jx) * (unsigned)S.nz3 + (unsigned)(kk - S.k3lo);
+            for (int ip = 1; ip < S.np3d; ++ip) kst += cold->csca[vox * (unsigned)S.np3d + (unsigned)ip].x;
+        }
+        if (kst < bt && wl > 0.0f) atomicAdd(&cold->heat[(unsigned)(kk * S.ny + jy) * (unsigned)S.nx + (unsigned)jx], (double)(wl * (bt - kst)));
+    };
     Counters cnt = {};
 
     // ---- lane state
@@ -805,6 +821,7 @@ k_transport(const DevScene S, const uint64_t nphoton, const uint64_t seed, const
                 if (!is_le && dtau >= rem) {
                     // ---- the collision lies inside this voxel
                     const float sc = rem * frcp(bt);
+                    if (FLUX && hest) heat_path(ix, iy, k, bt, r4.z, true, w * sc);
                     // (no clamping of x and y: a position a rounding error outside its voxel gives a negative face distance,
                     //  which the max(s, 0) above turns into a zero-length step across that face)
                     px += ux * sc; py += uy * sc;
@@ -817,6 +834,7 @@ k_transport(const DevScene S, const uint64_t nphoton, const uint64_t seed, const
                     mode = M_LEEND;
                 } else {
                     if (is_le) acc += dtau; else rem -= dtau;
+                    if (FLUX && hest && !is_le) heat_path(ix, iy, k, bt, r4.z, true, w * s);
                     // ---- move onto the face and into the neighbour voxel
                     px += ux * s; py += uy * s;
                     pz = fminf(fmaxf(pz + uz * s, 0.0f), dz);
@@ -884,7 +902,8 @@ k_transport(const DevScene S, const uint64_t nphoton, const uint64_t seed, const
             // and added when the result is read (S.kdir, mi3d_get_flux).  A sensor plane inside the atmosphere ends the ray
             // somewhere in the run: layer by layer.
             const LayerRec &Lk = lay[k];
-            const bool can_jump = is_le ? !(zstop < INFINITY) : (jump || (direct && !up && Lk.run_lo >= S.kdir));
+            // (the path-length estimator of the heating rates tallies every layer flown through: no jump for a photon)
+            const bool can_jump = is_le ? !(zstop < INFINITY) : (jump || (direct && !up && Lk.run_lo >= S.kdir && !(FLUX && hest)));
             if (can_jump) {
                 // from the prefix sums of the layer table
                 const int kend = up ? Lk.run_hi : Lk.run_lo;
@@ -940,6 +959,15 @@ k_transport(const DevScene S, const uint64_t nphoton, const uint64_t seed, const
                     const float s = fmaxf((up ? dz - pz : pz) * iuz, 0.0f);
                     const float dtau = bt * s;
                     if (COUNT) { if (is_le) cnt.le_steps++; else cnt.steps++; }
+                    if (FLUX && hest && !is_le) {   // this layer's piece (up to the collision, if it lies here), in the column of its midpoint
+                        const float sl = dtau >= rem ? rem * frcp(bt) : s;
+                        float qx = px + ux * (0.5f * sl), qy = py + uy * (0.5f * sl);
+                        int jx = ix, jy = iy;
+                        fold_xy(S, cold, qx, qy, jx, jy, IPA_NOW(false));
+                        const bool in3d_l = (__float_as_int(L.w) & kLayIn3d) != 0;
+                        const float ks3 = in3d_l ? S.vrec[(unsigned)jy * S.vrow_f4 + (unsigned)jx * S.vcol_f4 + (unsigned)(k - S.k3lo)].z : 0.0f;
+                        heat_path(jx, jy, k, bt, ks3, in3d_l, w * sl);
+                    }
                     if (!is_le && dtau >= rem) {
                         const float sc = rem * frcp(bt);
                         px += ux * sc; py += uy * sc;
@@ -1054,7 +1082,7 @@ k_transport(const DevScene S, const uint64_t nphoton, const uint64_t seed, const
                 const float w_in = w;
                 w *= (kstot >= bt_ev) ? 1.0f : kstot * frcp(bt_ev);
                 // heating rates (Flx_mhrt = 1): what the collision takes from the weight stays in this cell
-                if (FLUX && cold->heat && kstot < bt_ev)
+                if (FLUX && cold->heat && !hest && kstot < bt_ev)
                     atomicAdd(&cold->heat[(unsigned)(k * S.ny + iy) * (unsigned)S.nx + (unsigned)ix], (double)(w_in * (bt_ev - kstot) * frcp(bt_ev)));
                 if (!(w > 0.0f)) { if (COUNT) cnt.absorbed++; dead = true; }
             }

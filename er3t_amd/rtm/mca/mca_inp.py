@@ -50,6 +50,7 @@ _CATALOGUE = [
     ('mcarSrc_nml_init', [('Src_nsrc', 'number of sources')]),
     ('mcarFlx_nml_init', [
         ('Flx_mflx', 'flux density calculation flag'), ('Flx_mhrt', 'heating rate calculation flag'),
+        ('Flx_mhest', 'heating rate estimator: 0 collision, 1 path length (a key of this project)'),
         ('Flx_nxf', 'flux cells along X'), ('Flx_nyf', 'flux cells along Y'), ('Flx_diff0', 'numerical diffusion parameter'),
         ('Flx_diff1', 'numerical diffusion parameter'), ('Flx_cf_dtau', 'layer optical thickness for collision forcing')]),
     ('mcarRad_nml_init', [

@@ -272,11 +272,13 @@ def read_heating_mca_out(mca_obj, abs_obj, mode='mean', squeeze=True):
             run += np.squeeze(scaled) if squeeze else scaled
         hr[..., ir] = run
     dims_info = dims_info+['Nr']
+    # (the same variable under both estimators of the tally, mcarats_ng's <heating_estimator>: the default's names are what they were)
+    est = ', path-length estimator' if getattr(mca_obj, 'heating_estimator', 'collision') == 'path' else ''
     if mode.lower() == 'all':
-        data['heating_rate'] = {'data': hr, 'name': 'Absorbed power per unit volume', 'units': 'W/m^3/nm', 'dims_info': dims_info}
+        data['heating_rate'] = {'data': hr, 'name': 'Absorbed power per unit volume'+est, 'units': 'W/m^3/nm', 'dims_info': dims_info}
     else:
-        data['heating_rate'] = {'data': np.mean(hr, axis=-1), 'name': 'Absorbed power per unit volume (mean)', 'units': 'W/m^3/nm', 'dims_info': dims_info[:-1]}
-        data['heating_rate_std'] = {'data': np.std(hr, axis=-1), 'name': 'Absorbed power per unit volume (standard deviation)', 'units': 'W/m^3/nm', 'dims_info': dims_info[:-1]}
+        data['heating_rate'] = {'data': np.mean(hr, axis=-1), 'name': 'Absorbed power per unit volume (mean%s)' % est, 'units': 'W/m^3/nm', 'dims_info': dims_info[:-1]}
+        data['heating_rate_std'] = {'data': np.std(hr, axis=-1), 'name': 'Absorbed power per unit volume (standard deviation%s)' % est, 'units': 'W/m^3/nm', 'dims_info': dims_info[:-1]}
     return data
 
 

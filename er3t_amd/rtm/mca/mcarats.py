@@ -88,6 +88,9 @@ class mcarats_ng:
                            atm_1ds[0]'s atmosphere (atm_obj.lev['temperature']); the solar-only arguments are ignored
         wavelength [None] : thermal: Src_wlen in nm (default: the wavelength of atm_1ds[0]'s absorption object)
         surface_temperature [None]: thermal: replaces the lowest interface temperature (the surface's) [K]
+        heating_estimator ['collision']: target='heating rate' only: 'path' tallies w kappa_a l along every flight segment instead of
+                           w kappa_a / beta_t at every collision (Flx_mhest=1, a key of this project written only then:
+                           include/mi3d.h, mi3d_set_heating_estimator) -- same variable, same units, far less noise in optically thin cells
 
     Afterwards: input and output files under <fdir>; attributes Ng, Nrun, Nx, Ny, dx, dy, date, target, solver,
     photons (Nrun*Ng,), photons_per_set, fnames_inp[ir][ig], fnames_out[ir][ig], nml (list of Ng dictionaries).
@@ -100,7 +103,8 @@ class mcarats_ng:
                  surface_albedo=0.03, solar_zenith_angle=30.0, solar_azimuth_angle=0.0, sensor_zenith_angle=0.0,
                  sensor_azimuth_angle=0.0, sensor_altitude=705000.0, sensor_type='satellite', sensor_xpos=0.5,
                  sensor_ypos=0.5, solver='3d', photons=1e7, base_ratio=0.05, verbose=False, quiet=False,
-                 abs_obj=None, keep_files=True, source='solar', wavelength=None, surface_temperature=None):
+                 abs_obj=None, keep_files=True, source='solar', wavelength=None, surface_temperature=None,
+                 heating_estimator='collision'):
 
         # one process per GPU (torch.distributed): rank 0 writes the job files, all ranks transport their share of every job
         from er3t_amd.dist import world_info, barrier
@@ -130,6 +134,11 @@ class mcarats_ng:
         if self.source not in ('solar', 'thermal'):
             raise OSError('Error [mcarats_ng]: <source=%s> must be \'solar\' or \'thermal\'.' % source)
         self.wavelength, self.surface_temperature = wavelength, surface_temperature
+        self.heating_estimator = str(heating_estimator).lower()
+        if self.heating_estimator not in ('collision', 'path'):
+            raise OSError('Error [mcarats_ng]: <heating_estimator=%s> must be \'collision\' or \'path\'.' % heating_estimator)
+        if self.heating_estimator == 'path' and str(target).lower() not in ('heating rate', 'hr'):
+            raise OSError('Error [mcarats_ng]: <heating_estimator=\'path\'> is an estimator of the heating rates: use <target=\'heating rate\'>.')
         if self.source == 'thermal' and not quiet and (solar_zenith_angle != 30.0 or solar_azimuth_angle != 0.0):
             print('Message [mcarats_ng]: <source=\'thermal\'>: <solar_zenith_angle> and <solar_azimuth_angle> are ignored.')
         self.solver  = _match(solver, _SOLVERS, 'solver')
@@ -196,6 +205,8 @@ class mcarats_ng:
         if self.target != 'radiance':
             mflx, mhrt = _FLX_FLAGS[self.target]
             self._all({'Wld_mtarget': 1, 'Flx_mflx': mflx, 'Flx_mhrt': mhrt})
+            if self.heating_estimator == 'path':       # (written only then: every other job file stays what it was, byte for byte)
+                self._all({'Flx_mhest': 1})
             return
 
         if sensor_type.lower() in _SENSOR_MRPROJ:

@@ -115,6 +115,8 @@ class Scene:
     solver: int = SOLVER_3D
     wmin  : float = 0.2                   # Pho_wmin: Russian roulette below this weight ...
     wfac  : float = 1.0                   # Pho_wfac: ... survivors continue with this weight
+    heat_estimator: int = 0               # Flx_mhest (a key of this project; include/mi3d.h: mi3d_set_heating_estimator): the heating-rate
+                                          # tally's estimator, 0 collision, 1 path length (w kappa_a l per flight segment and cell)
     le_tau1: float = 2.0                  # Russian roulette on marched local-estimate rays beyond this optical depth (unbiased;
                                           # +64 % results per second on the nine-view configuration at 0.5 % more noise per photon); 0 = off
 
@@ -339,6 +341,10 @@ class Scene:
                 raise OSError('Error [Scene]: <Rad_mrkind=%d> is not supported (1: camera, 2: satellite).' % mrkind)
         elif mtarget == 1:
             kw.update(target=TARGET_FLUX | (TARGET_HEAT if int(get('Flx_mhrt', 0) or 0) == 1 else 0))
+            mhest = int(get('Flx_mhest', 0) or 0)
+            if mhest not in (0, 1):
+                raise OSError('Error [Scene]: <Flx_mhest=%d> is not supported (0: collision estimator, 1: path-length estimator).' % mhest)
+            kw.update(heat_estimator=mhest)
         else:
             raise OSError('Error [Scene]: <Wld_mtarget=%d> is not supported.' % mtarget)
 

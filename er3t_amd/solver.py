@@ -51,6 +51,7 @@ _SIGNATURES = [
     ('mi3d_set_counting'       , C.c_int   , [C.c_void_p, C.c_int]),
     ('mi3d_bind_device_buffers', C.c_int   , [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ('mi3d_bind_heating_buffer', C.c_int   , [C.c_void_p, C.c_void_p]),
+    ('mi3d_set_heating_estimator', C.c_int , [C.c_void_p, C.c_int]),
     ('mi3d_prepare'            , C.c_int   , [C.c_void_p]),
     ('mi3d_reset'              , C.c_int   , [C.c_void_p]),
     ('mi3d_run'                , C.c_int   , [C.c_void_p, _u64, _u64, _u64]),
@@ -258,6 +259,10 @@ class Mi3dSolver:
     def set_le_weight_roulette(self, cmin=0.0):
         self._chk(self.lib.mi3d_set_le_weight_roulette(self._h, float(cmin)))
 
+    def set_heating_estimator(self, estimator=0):
+        """the heating-rate tally's estimator (include/mi3d.h: mi3d_set_heating_estimator): 0 collision, 1 path length"""
+        self._chk(self.lib.mi3d_set_heating_estimator(self._h, int(estimator)))
+
     def set_counting(self, on=True):
         self._chk(self.lib.mi3d_set_counting(self._h, 1 if on else 0))
 
@@ -283,6 +288,7 @@ class Mi3dSolver:
         else:
             self.set_views(s.view_the, s.view_phi, s.view_zloc, zref=s.zref, nxr=s.nxr, nyr=s.nyr)
         self.set_options(s.target, s.solver, s.wmin, s.wfac, column_le)
+        self.set_heating_estimator(int(getattr(s, 'heat_estimator', 0)))
         self.set_le_roulette(getattr(s, 'le_tau1', 0.0))
         self.set_le_weight_roulette(getattr(s, 'le_cmin', 0.0))
         self.scene = s

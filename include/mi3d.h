@@ -260,6 +260,24 @@ int mi3d_bind_device_buffers(mi3d_solver *h, void *rad_sum, void *flux_sum, void
  * library's own buffer. */
 int mi3d_bind_heating_buffer(mi3d_solver *h, void *heat_sum);
 
+/* The estimator of the heating-rate tally (MI3D_TARGET_HEAT; a key of this project, Flx_mhest).  Same tally, same normalisation
+ * (mi3d_get_heating), same output variable and units under both:
+ *   0 (default)  collision: a collision leaves w (bt - sum ks) / bt in its cell.
+ *   1            path length: every flight segment inside ONE cell -- it ends at a cell face, a level, the collision site, the surface
+ *                or the top -- leaves w kappa_a l there, w the weight the photon flies with, kappa_a = max(bt - sum ks, 0) from the
+ *                float32 records and the sum of scattering coefficients a collision in that cell uses: both estimators mean the same
+ *                absorber and have the same expectation segment by segment.  The collision itself leaves nothing; cells with
+ *                kappa_a = 0 get nothing.  The cell is the one the walk is in (independent columns, partial 3-D: the photon's
+ *                column).  Layers the walk crosses without x / y faces (the 1-D layers outside the 3-D region, horizontally
+ *                uniform layers inside it) are cut at the LEVELS only: a layer's piece goes to the column of the piece's midpoint,
+ *                folded cyclically -- layer means stay unbiased; within such a layer the columns are smoothed over the piece's
+ *                horizontal extent, where the optical properties do not vary.
+ * The estimator draws no random number: (seed, photon id) -> history is what it is, and the flux planes of a job do not depend on the
+ * choice beyond the order of their float64 sums.  The weight roulette is unchanged.  Thermal jobs refuse heating rates whichever
+ * estimator.  Anything but 0 / 1: MI3D_EINVAL.  A change marks the tallies dirty (the handle's own buffers are cleared by the next
+ * mi3d_prepare: sums of two estimators do not mix). */
+int mi3d_set_heating_estimator(mi3d_solver *h, int estimator);
+
 /* Build the device-side scene (layout transform, total extinction, column optical depth,
  * phase-function CDFs).  Called implicitly by mi3d_run when inputs changed; exposed so that
  * set-up can be excluded from the timed region. */
