@@ -660,6 +660,18 @@ double src_amp(const mi3d_solver *h) {
     return h->src_flx * std::fabs(std::cos(h->src_the * 3.14159265358979323846 / 180.0));
 }
 
+// The atmosphere as cell_emission reads it (k_thermal_power, k_get_net_heating): valid once build_thermal has uploaded the temperatures
+static ThermalGrid thermal_grid(const mi3d_solver *h) {
+    ThermalGrid G;
+    G.nx = h->nx; G.ny = h->ny; G.nz = h->nz; G.nz3 = h->nz3; G.k3lo = h->nz3 > 0 ? h->iz3l - 1 : 0; G.np1d = h->np1d; G.np3d = h->np3d;
+    G.wl_um = h->th_wlen;
+    G.lay = (const LayerRec *)h->d_lay.p;
+    G.vrec = (const float4 *)(h->nz3 > 0 ? h->d_vrec.p : nullptr); G.vcol_f4 = h->vcol_f4; G.vrow_f4 = h->vrow_f4;
+    G.csca = (const float2 *)h->d_csca.p;
+    G.tlev = (const float *)h->d_th_tlev.p; G.tmpa3d = (const float *)(h->th_ntmpa ? h->d_th_tmpa.p : nullptr);
+    return G;
+}
+
 // Thermal source: emitted power of every cell (k_thermal_power), its CDF and P_tot (k_scan_*), the photon loop's DevThermal.
 int build_thermal(mi3d_solver *h) {
     if ((int)h->th_tlev.size() != h->nz + 1)
@@ -681,10 +693,7 @@ int build_thermal(mi3d_solver *h) {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
     HIPCHK(hipEventRecord(e0, h->stream));
-    const int k3lo = h->nz3 > 0 ? h->iz3l - 1 : 0;
-    hipLaunchKernelGGL(k_thermal_power, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, h->stream, h->nx, h->ny, h->nz, h->nz3, k3lo, h->np1d,
-                       h->np3d, h->dx, h->dy, h->th_wlen, (const LayerRec *)h->d_lay.p, (const float4 *)(h->nz3 > 0 ? h->d_vrec.p : nullptr), h->vcol_f4, h->vrow_f4,
-                       (const float2 *)h->d_csca.p, (const float *)h->d_th_tlev.p, (const float *)(h->th_ntmpa ? h->d_th_tmpa.p : nullptr),
+    hipLaunchKernelGGL(k_thermal_power, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, h->stream, thermal_grid(h), h->dx, h->dy,
                        sfc2d ? h->nxb : 1, sfc2d ? h->nyb : 1, (const float *)(sfc2d ? h->d_sfc2d.p : nullptr), h->sfc_param[0],
                        (const float *)(h->th_ntmps ? h->d_th_tmps.p : nullptr), h->d_th_cdf.p);
     HIPCHK(hipGetLastError());
@@ -1728,7 +1737,7 @@ static void name_route(mi3d_solver *h, const RunPlan &plan, bool lists, uint64_t
     else if (plan.loop == Loop::Flux) snprintf(nm, sizeof(nm), lists ? "k_transport_flux<%d,%d,%d> + k_tl_scatter + k_tl_sum" : "k_transport_flux<%d,%d,%d>", c, p3d, plan.mix);
     else if (plan.loop == Loop::ColumnRays) snprintf(nm, sizeof(nm), "k_transport_lean<%d,%d,2,%d> + k_rays", c, p3d, plan.mix_lean);
     else if (plan.loop == Loop::Column) snprintf(nm, sizeof(nm), "k_transport_lean<%d,%d,0,%d>", c, p3d, plan.mix_lean);
-    else snprintf(nm, sizeof(nm), plan.thermal ? "k_transport<%d,%d,%d,%d> [thermal]" : hpath ? "k_transport<%d,%d,%d,%d> [heating: path length]" : "k_transport<%d,%d,%d,%d>", c, plan.march ? 1 : 0, plan.flux ? 1 : 0, p3d);
+    else snprintf(nm, sizeof(nm), plan.thermal ? (hpath ? "k_transport<%d,%d,%d,%d> [thermal] [heating: path length]" : "k_transport<%d,%d,%d,%d> [thermal]") : hpath ? "k_transport<%d,%d,%d,%d> [heating: path length]" : "k_transport<%d,%d,%d,%d>", c, plan.march ? 1 : 0, plan.flux ? 1 : 0, p3d);
     h->last_kernel = nm;
     if (plan.loop == Loop::General && h->kernel_choice == 0 && !h->general_warned && nphoton >= 4096 && !plan.thermal) {
         fprintf(stderr, "Warning [mi3d_run]: this job runs on the general photon loop (k_transport), not on a lean one: %s.  Same results, a third to a half of the speed.\n", plan.why);
@@ -2167,8 +2176,6 @@ int mi3d_run(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_of
     const bool thermal = h->src_mtype == 3;
     if (thermal && (h->target & MI3D_TARGET_RADIANCE) && h->rad_kind == 1)
         return fail(MI3D_EUNSUP, "thermal source: all-sky cameras (Rad_mrkind=1) are not supported");
-    if (thermal && (h->target & MI3D_TARGET_HEAT))
-        return fail(MI3D_EUNSUP, "thermal source: heating rates are not supported");
     if (nphoton == 0) return MI3D_OK;
     if (thermal && !(h->th_ptot > 0.0)) { h->last_kernel = "k_transport [thermal: nothing emits]"; return MI3D_OK; }   // (the tallies stay 0)
     {   // the kernels index every table with 32-bit arithmetic
@@ -2488,9 +2495,20 @@ int mi3d_get_heating(mi3d_solver *h, uint64_t nphoton_total, float *out) {
     if (!(h->target & MI3D_TARGET_HEAT) || !h->heat_ptr()) return fail(MI3D_ESTATE, "no heating-rate tally (the job's target does not include MI3D_TARGET_HEAT, or nothing has run)");
     HIPCHK(sync_main(h));
     const size_t n = h->heat_elems();
-    const double pi = 3.14159265358979323846;
-    const double mu0 = std::fabs(std::cos(h->src_the * pi / 180.0));
-    const double fac = h->src_flx * mu0 * (double)h->nx * (double)h->ny / (double)nphoton_total;
+    // a photon stands for Src_flx mu0 Lx Ly / N of power (thermal: Src_flx P_tot / N)
+    const double fac = src_amp(h) * (double)h->nx * (double)h->ny / (double)nphoton_total;
+    if (h->src_mtype == 3) {
+        // thermal job: the NET, absorbed - emitted.  The emission is known, not tallied: taken off here, once, in float64 on the device
+        if (h->dirty_thermal || !h->d_th_tlev.p) return fail(MI3D_ESTATE, "thermal source: not built (nothing has run since the scene changed)");
+        if (n == 0) return MI3D_OK;
+        if ((rc = h->d_get_out.alloc(n))) return rc;
+        hipLaunchKernelGGL(k_get_net_heating, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, thermal_grid(h), (const double *)h->heat_ptr(),
+                           fac, h->src_flx, h->d_get_out.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out, h->d_get_out.p, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        return MI3D_OK;
+    }
     // (on the device as the flux: tally * fac / layer thickness, float32 to the host)
     std::vector<double> dz((size_t)h->nz);
     for (int k = 0; k < h->nz; ++k) dz[k] = h->zgrd[k + 1] - h->zgrd[k];
@@ -2499,6 +2517,24 @@ int mi3d_get_heating(mi3d_solver *h, uint64_t nphoton_total, float *out) {
     if ((rc = h->d_get_out.alloc(n))) return rc;
     hipLaunchKernelGGL(k_get_field, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const tally_t *)h->heat_ptr(), h->d_get_out.p, fac,
                        (unsigned)((size_t)h->nx * h->ny), (unsigned)h->nz, -1L, (const double *)h->d_get_add.p, n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, h->d_get_out.p, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MI3D_OK;
+}
+
+int mi3d_get_emission(mi3d_solver *h, float *out) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (!out) return fail(MI3D_EINVAL, "out is NULL");
+    if (h->src_mtype != 3) return fail(MI3D_ESTATE, "mi3d_get_emission: the job is not thermal (Src_mtype=%d): nothing emits", h->src_mtype);
+    if ((rc = mi3d_prepare(h))) return rc;
+    const size_t n = h->heat_elems();
+    if (n == 0) return MI3D_OK;
+    HIPCHK(sync_main(h));   // (d_get_out may still be on its way to the host for another getter's caller: one stream, in order)
+    if ((rc = h->d_get_out.alloc(n))) return rc;
+    hipLaunchKernelGGL(k_get_net_heating, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, thermal_grid(h), (const double *)nullptr,
+                       0.0, h->src_flx, h->d_get_out.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, h->d_get_out.p, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));

@@ -161,48 +161,84 @@ struct DevThermal {
     int nxb, nyb;          // surface cells (1 x 1: uniform surface)
 };
 
-// One thread per cell: emitted power in float64 from the scene as the transport kernel sees it.  Absorption coefficient of a
-// cell = total extinction - total scattering coefficient of the same float32 records the photon loop reads, so that what a cell
-// emits matches what it absorbs (Kirchhoff).  Volume: 4 pi ka B(T) V; surface: pi (1 - albedo) B(Ts) A (Lambertian only).
+// What one cell of the atmosphere emits: absorption coefficient, temperature and emitted power per unit volume, 4 pi ka B(T)
+// [W m-3 um-1], in float64 from the scene as the transport kernel sees it.  ka = total extinction - total scattering coefficient
+// of the same float32 records the photon loop reads, so that what a cell emits matches what it absorbs (Kirchhoff); T = the mean
+// of the layer's two interface temperatures plus the voxel's Atm_tmpa3d.  Layer k inside the 3-D region: the voxel (ix, iy) (`in3d`);
+// outside it: the layer of the 1-D grid, ix and iy ignored.  The ONE place this is worked out: the source's CDF (k_thermal_power)
+// and the emission that mi3d_get_heating subtracts (k_get_net_heating) both call it, so that what is subtracted is what is sampled.
+struct ThermalGrid {
+    int nx, ny, nz, nz3, k3lo, np1d, np3d;
+    double wl_um;
+    const LayerRec *lay;
+    const float4 *vrec;
+    unsigned vcol_f4, vrow_f4;
+    const float2 *csca;
+    const float *tlev, *tmpa3d;
+};
+struct CellEmission { double ka, T, e; };
+__device__ inline CellEmission cell_emission(const ThermalGrid &G, int k, int iy, int ix, bool in3d) {
+    const double four_pi = 4.0 * 3.14159265358979323846;
+    const LayerRec L = G.lay[k];
+    CellEmission c;
+    float ks = 0.0f;
+    if (in3d) {
+        const int k3 = k - G.k3lo, col = iy * G.nx + ix;
+        const float4 r = G.vrec[(size_t)iy * G.vrow_f4 + (size_t)ix * G.vcol_f4 + k3];
+        ks = r.z;
+        for (int ip = 0; ip < G.np1d; ++ip) ks += L.ks1d[ip];
+        for (int ip = 1; ip < G.np3d; ++ip) ks += G.csca[((size_t)col * G.nz3 + k3) * G.np3d + ip].x;
+        c.ka = fmax((double)r.x - (double)ks, 0.0);
+        c.T = 0.5 * ((double)G.tlev[k] + (double)G.tlev[k + 1]) + (G.tmpa3d ? (double)G.tmpa3d[((size_t)k3 * G.ny + iy) * G.nx + ix] : 0.0);
+    } else {
+        for (int ip = 0; ip < G.np1d; ++ip) ks += L.ks1d[ip];
+        c.ka = fmax((double)L.bt - (double)ks, 0.0);
+        c.T = 0.5 * ((double)G.tlev[k] + (double)G.tlev[k + 1]);
+    }
+    c.e = four_pi * c.ka * planck_um(G.wl_um, c.T);
+    return c;
+}
+
+// One thread per cell of the source: emitted power in float64.  Volume: 4 pi ka B(T) V (cell_emission);
+// surface: pi (1 - albedo) B(Ts) A (Lambertian only).
 __global__ void __launch_bounds__(256)
-k_thermal_power(int nx, int ny, int nz, int nz3, int k3lo, int np1d, int np3d, double dx, double dy, double wl_um,
-                const LayerRec *lay, const float4 *vrec, unsigned vcol_f4, unsigned vrow_f4, const float2 *csca,
-                const float *tlev, const float *tmpa3d, int nxb, int nyb, const float *sfc2d, float albedo, const float *tmps2d,
+k_thermal_power(const ThermalGrid G, double dx, double dy, int nxb, int nyb, const float *sfc2d, float albedo, const float *tmps2d,
                 double *pw) {
+    const int nx = G.nx, ny = G.ny, nz = G.nz, nz3 = G.nz3, k3lo = G.k3lo;
     const unsigned long nvox = (unsigned long)nx * ny * nz3, nsfc = (unsigned long)nxb * nyb;
     const unsigned long i = (unsigned long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nvox + nz + nsfc) return;
-    const double four_pi = 4.0 * 3.14159265358979323846;
     double p = 0.0;
     if (i < nvox) {
         const unsigned long ncol = (unsigned long)nx * ny;
         const int k3 = (int)(i / ncol), col = (int)(i % ncol), iy = col / nx, ix = col % nx, k = k3lo + k3;
-        const LayerRec L = lay[k];
-        const float4 r = vrec[(size_t)iy * vrow_f4 + (size_t)ix * vcol_f4 + k3];
-        float ks = r.z;
-        for (int ip = 0; ip < np1d; ++ip) ks += L.ks1d[ip];
-        for (int ip = 1; ip < np3d; ++ip) ks += csca[((size_t)col * nz3 + k3) * np3d + ip].x;
-        const double ka = fmax((double)r.x - (double)ks, 0.0);
-        const double T = 0.5 * ((double)tlev[k] + (double)tlev[k + 1]) + (tmpa3d ? (double)tmpa3d[i] : 0.0);
-        p = four_pi * ka * planck_um(wl_um, T) * dx * dy * (double)L.dz;
+        p = cell_emission(G, k, iy, ix, true).e * dx * dy * (double)G.lay[k].dz;
     } else if (i < nvox + nz) {
         const int k = (int)(i - nvox);
-        if (!(nz3 > 0 && k >= k3lo && k < k3lo + nz3)) {
-            const LayerRec L = lay[k];
-            float ks = 0.0f;
-            for (int ip = 0; ip < np1d; ++ip) ks += L.ks1d[ip];
-            const double ka = fmax((double)L.bt - (double)ks, 0.0);
-            const double T = 0.5 * ((double)tlev[k] + (double)tlev[k + 1]);
-            p = four_pi * ka * planck_um(wl_um, T) * dx * nx * dy * ny * (double)L.dz;
-        }
+        if (!(nz3 > 0 && k >= k3lo && k < k3lo + nz3)) p = cell_emission(G, k, 0, 0, false).e * dx * nx * dy * ny * (double)G.lay[k].dz;
     } else {
         const unsigned long s = i - nvox - nz;
         const double a = sfc2d ? (double)sfc2d[s * 8 + 1] : (double)albedo;
         const double eps = 1.0 - fmin(fmax(a, 0.0), 1.0);
-        const double T = (double)tlev[0] + (tmps2d ? (double)tmps2d[s] : 0.0);
-        p = 3.14159265358979323846 * eps * planck_um(wl_um, T) * (dx * nx / nxb) * (dy * ny / nyb);
+        const double T = (double)G.tlev[0] + (tmps2d ? (double)tmps2d[s] : 0.0);
+        p = 3.14159265358979323846 * eps * planck_um(G.wl_um, T) * (dx * nx / nxb) * (dy * ny / nyb);
     }
     pw[i] = p;
+}
+
+// mi3d_get_heating of a thermal job, mi3d_get_emission: one thread per cell of the heating grid [nz][ny][nx].  The emitted power per
+// unit volume is known, not tallied (cell_emission; in a layer outside the 3-D region every column gets the layer's value); the net is
+// absorbed - emitted = tally * norm / dz - src_flx * e in float64, rounded to float32 once.  tally == NULL: the emission alone.
+__global__ void __launch_bounds__(256)
+k_get_net_heating(const ThermalGrid G, const double *__restrict__ tally, double norm, double src_flx, float *__restrict__ out) {
+#pragma clang fp contract(off)
+    const size_t n = (size_t)G.nz * G.ny * G.nx;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int k = (int)(i / ((size_t)G.ny * G.nx)), col = (int)(i % ((size_t)G.ny * G.nx)), iy = col / G.nx, ix = col % G.nx;
+    const bool in3d = G.nz3 > 0 && k >= G.k3lo && k < G.k3lo + G.nz3;
+    const double emit = src_flx * cell_emission(G, k, iy, ix, in3d).e;
+    out[i] = tally ? (float)(tally[i] * norm / (double)G.lay[k].dz - emit) : (float)emit;
 }
 
 // Inclusive prefix sum of n doubles in place, in three passes: every block scans kScanChunk elements and leaves its total,

@@ -57,7 +57,8 @@ def _check_thermal(nml, fdir):
         raise OSError('Error [mca_exe]: a thermal job needs <Atm_tmp1d> at the %d layer INTERFACES (nz+1); %d values %s.'
                       % (nz+1, ntmp, 'are ambiguous (nz: the layer temperatures a solar job carries)' if ntmp == nz else 'do not fit'))
     if int(nml.get('Wld_mtarget', 1)) == 1 and int(nml.get('Flx_mhrt', 0) or 0) == 1:
-        raise OSError('Error [mca_exe]: <target=\'heating rate\'> (Flx_mhrt=1) is not supported for a thermal job.')
+        raise OSError('Error [mca_exe]: <target=\'heating rate\'> (Flx_mhrt=1) is not supported for a thermal job: absorbed or net is ambiguous there; '
+                      '<Flx_mhrt=2> is the NET heating rate (absorbed - emitted).')
     if int(nml.get('Wld_mtarget', 1)) == 2 and int(nml.get('Rad_mrkind', 2)) == 1:
         raise OSError('Error [mca_exe]: all-sky cameras (<Rad_mrkind=1>) are not supported for a thermal job.')
     if nml.get('Sfc_inpfile') and int(nml.get('Sfc_nxb', 0) or 0) > 0:
@@ -68,6 +69,12 @@ def _check_thermal(nml, fdir):
                 raise OSError('Error [mca_exe]: a thermal job needs a Lambertian surface (jsfc2d = 1 everywhere): non-Lambertian (BRDF) surfaces do not emit here.')
     elif int(nml.get('Sfc_mtype', 1)) != 1:
         raise OSError('Error [mca_exe]: a thermal job needs a Lambertian surface (<Sfc_mtype=1>): non-Lambertian (BRDF) surfaces do not emit here.')
+
+
+def thermal_heating(nml):
+    """is this the namelist of a thermal job with the NET heating rate (Src_mtype = 3, Flx_mhrt = 2)?  Its read-out subtracts the known
+    emission (include/mi3d.h: mi3d_get_heating), which JobRunner._normalise does not: several ranks take such jobs one by one"""
+    return int(nml.get('Src_mtype', 1) or 1) == 3 and int(nml.get('Wld_mtarget', 1)) == 1 and int(nml.get('Flx_mhrt', 0) or 0) == 2
 
 
 def wants_rdir(scene):
@@ -217,6 +224,7 @@ class JobRunner:
             out['flux'] = self.sol.flux(nphoton)
         if self.scene.target & TARGET_HEAT:
             out['heat'] = self.sol.heating(nphoton)
+            out['heat_net'] = getattr(self.scene, 'src_mtype', 1) == 3
         return out
 
     def collect(self, nphoton, slot=0):
@@ -233,6 +241,7 @@ class JobRunner:
             out['flux'] = sol.flux(int(nphoton))
         if scene.target & TARGET_HEAT:
             out['heat'] = sol.heating(int(nphoton))
+            out['heat_net'] = getattr(scene, 'src_mtype', 1) == 3
         return out
 
     # ---- several ranks, file route: one exchange per BATCH of jobs instead of one per job -------------------------------------
@@ -257,6 +266,9 @@ class JobRunner:
                 nml = mca_inp_read(fname_inp)
                 fdir = os.path.dirname(os.path.abspath(fname_inp))
                 sc = self.load(nml, fdir, int(solver), slot=slot)
+                if sc.target & TARGET_HEAT and getattr(sc, 'src_mtype', 1) == 3:
+                    raise OSError('Error [mca_exe]: the net heating rate of a thermal job (Flx_mhrt=2) is not served by the batched route (its read-out '
+                                  'subtracts the emission: include/mi3d.h, mi3d_get_heating); run such jobs one by one (run_job), as mca_run does.')
                 sizes = (max(sc.nview, 1)*sc.nyr*sc.nxr if sc.target & TARGET_RADIANCE else 0,
                          3*(sc.nz+1)*sc.ny*sc.nx if sc.target & TARGET_FLUX else 0,
                          sc.nz*sc.ny*sc.nx if sc.target & TARGET_HEAT else 0)
@@ -425,7 +437,10 @@ class JobRunner:
             names = [('fdnd', 'direct downward flux density'), ('fdn', 'total downward flux density'), ('fup', 'upward flux density')]
             variables = [(n, d, np.transpose(f[i], (2, 1, 0))) for i, (n, d) in enumerate(names)]
             if 'heat' in result:                                 # (nz, ny, nx) -> (nx, ny, nz): a fourth variable on the layer grid (Flx_mhrt = 1)
-                variables.append(('hrt', 'absorbed power per unit volume (heating rate x air density x c_p)', np.transpose(result['heat'], (2, 1, 0))))
+                desc = 'absorbed power per unit volume (heating rate x air density x c_p)'
+                if result.get('heat_net'):                       # thermal job (Flx_mhrt = 2)
+                    desc = 'net (absorbed - emitted) power per unit volume (heating rate x air density x c_p)'
+                variables.append(('hrt', desc, np.transpose(result['heat'], (2, 1, 0))))
             mca_out_write(fname_out, variables)
         else:
             r = result['rad']                                    # (nview, nyr, nxr) -> (nxr, nyr, nview)

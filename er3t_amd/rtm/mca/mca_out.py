@@ -252,6 +252,8 @@ def read_heating_mca_out(mca_obj, abs_obj, mode='mean', squeeze=True):
     grid (Nx, Ny, Nz layers), scaled per g like the fluxes (the factor of a layer is that of its lower level: the slit function is
     given per layer, mca_out.py:313-328) and summed over g.  Units: W/m^3/nm; divided by air density x c_p: K/s.
     (The reference's reader has no such branch, er3t/rtm/mca/mca_out.py:202-205: its `mca_out_ng` ends without data for this target.)
+    Thermal object (mcarats_ng(source='thermal'), Flx_mhrt = 2): the variable is the NET absorbed power per unit volume, absorbed - emitted
+    (negative: longwave cooling), combined with the thermal g-sum: sum_g weight[ig] x_g / 1000, no solar spectrum, no slit function.
     """
 
     data = read_flux_mca_out(mca_obj, abs_obj, mode=mode, squeeze=squeeze)
@@ -274,11 +276,12 @@ def read_heating_mca_out(mca_obj, abs_obj, mode='mean', squeeze=True):
     dims_info = dims_info+['Nr']
     # (the same variable under both estimators of the tally, mcarats_ng's <heating_estimator>: the default's names are what they were)
     est = ', path-length estimator' if getattr(mca_obj, 'heating_estimator', 'collision') == 'path' else ''
+    what = 'Net absorbed power per unit volume' if getattr(mca_obj, 'source', 'solar') == 'thermal' else 'Absorbed power per unit volume'
     if mode.lower() == 'all':
-        data['heating_rate'] = {'data': hr, 'name': 'Absorbed power per unit volume'+est, 'units': 'W/m^3/nm', 'dims_info': dims_info}
+        data['heating_rate'] = {'data': hr, 'name': what+est, 'units': 'W/m^3/nm', 'dims_info': dims_info}
     else:
-        data['heating_rate'] = {'data': np.mean(hr, axis=-1), 'name': 'Absorbed power per unit volume (mean%s)' % est, 'units': 'W/m^3/nm', 'dims_info': dims_info[:-1]}
-        data['heating_rate_std'] = {'data': np.std(hr, axis=-1), 'name': 'Absorbed power per unit volume (standard deviation%s)' % est, 'units': 'W/m^3/nm', 'dims_info': dims_info[:-1]}
+        data['heating_rate'] = {'data': np.mean(hr, axis=-1), 'name': '%s (mean%s)' % (what, est), 'units': 'W/m^3/nm', 'dims_info': dims_info[:-1]}
+        data['heating_rate_std'] = {'data': np.std(hr, axis=-1), 'name': '%s (standard deviation%s)' % (what, est), 'units': 'W/m^3/nm', 'dims_info': dims_info[:-1]}
     return data
 
 

@@ -85,13 +85,16 @@ class mca_run:
             self.save(fname=fname_sh)
 
     def run(self):
-        from er3t_amd.rtm.mca.mca_exe import get_runner, run_job, submit_job, collect_job
+        from er3t_amd.rtm.mca.mca_exe import get_runner, run_job, submit_job, collect_job, thermal_heating
+        from er3t_amd.rtm.mca.mca_inp import mca_inp_read
         runner = get_runner()
         ms0, n0 = runner.kernel_ms, runner.photons_done
         # One process: two solver handles take turns, job i+1 is launched before job i is read back and written, so that the
         # tail of a launch (as long as its longest history) and the writing of the output file run beside the next launch.
             # Under torchrun the jobs go through JobRunner.run_batched: one exchange per batch of jobs.
-        if runner.world > 1 and len(self.jobs) > 1:
+        # (not the net heating rates of a thermal source: run_batched normalises with Src_flx mu0 and knows no emission.  Such jobs go one by
+        #  one: run, all-reduce of the raw tallies, then mi3d_get_heating on every rank)
+        if runner.world > 1 and len(self.jobs) > 1 and not thermal_heating(mca_inp_read(self.jobs[0][0])):
             # several ranks: the raw tallies of a batch of jobs are exchanged with ONE all-reduce (JobRunner.run_batched)
             if self.verbose:
                 for command in self.commands:

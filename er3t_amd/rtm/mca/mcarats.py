@@ -85,7 +85,10 @@ class mcarats_ng:
                            (a flux job on 480 x 480 x 100 is 0.3 GB per file).
         source ['solar']  : 'thermal' writes Src_mtype=3 and Src_wlen (the band-centre wavelength in micrometres, a key of this
                            project: include/mi3d.h, mi3d_set_thermal) and Atm_tmp1d as the nz+1 INTERFACE temperatures of
-                           atm_1ds[0]'s atmosphere (atm_obj.lev['temperature']); the solar-only arguments are ignored
+                           atm_1ds[0]'s atmosphere (atm_obj.lev['temperature']); the solar-only arguments are ignored.  With
+                           target='heating rate' the job files carry Flx_mhrt=2, a value of this project: the NET heating rate,
+                           absorbed - emitted, negative where a cell cools (include/mi3d.h: mi3d_get_heating); the surface's net
+                           gain is f_down - f_up at level 0
         wavelength [None] : thermal: Src_wlen in nm (default: the wavelength of atm_1ds[0]'s absorption object)
         surface_temperature [None]: thermal: replaces the lowest interface temperature (the surface's) [K]
         heating_estimator ['collision']: target='heating rate' only: 'path' tallies w kappa_a l along every flight segment instead of
@@ -204,6 +207,8 @@ class mcarats_ng:
             raise OSError('Error [mcarats_ng]: <sensor_type=%r> is a radiance job: use <target=\'radiance\'>.' % sensor_type)
         if self.target != 'radiance':
             mflx, mhrt = _FLX_FLAGS[self.target]
+            if mhrt == 1 and self.source == 'thermal':
+                mhrt = 2                               # the NET heating rate of a thermal job (a value of this project: 1 would be ambiguous)
             self._all({'Wld_mtarget': 1, 'Flx_mflx': mflx, 'Flx_mhrt': mhrt})
             if self.heating_estimator == 'path':       # (written only then: every other job file stays what it was, byte for byte)
                 self._all({'Flx_mhest': 1})

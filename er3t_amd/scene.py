@@ -22,6 +22,7 @@ __all__ = ['Scene', 'TARGET_FLUX', 'TARGET_RADIANCE', 'TARGET_HEAT', 'SOLVER_3D'
 TARGET_FLUX     = 1
 TARGET_RADIANCE = 2
 TARGET_HEAT     = 4     # heating rates beside the fluxes (Flx_mhrt = 1, er3t/rtm/mca/mcarats.py:279-283): with TARGET_FLUX
+                        # (thermal job, Flx_mhrt = 2, a value of this project: the NET heating rate, absorbed - emitted)
 
 SOLVER_3D  = 0
 SOLVER_P3D = 1
@@ -340,7 +341,11 @@ class Scene:
             elif mrkind != 2:
                 raise OSError('Error [Scene]: <Rad_mrkind=%d> is not supported (1: camera, 2: satellite).' % mrkind)
         elif mtarget == 1:
-            kw.update(target=TARGET_FLUX | (TARGET_HEAT if int(get('Flx_mhrt', 0) or 0) == 1 else 0))
+            mhrt = int(get('Flx_mhrt', 0) or 0)
+            if mhrt == 2 and mtype != 3:
+                raise OSError('Error [Scene]: <Flx_mhrt=2> is the NET heating rate of a thermal job (Src_mtype=3); nothing emits in a solar job: use <Flx_mhrt=1>.')
+            # (Flx_mhrt = 1 with the thermal source stays refused by mca_exe: absorbed or net is what is ambiguous about it)
+            kw.update(target=TARGET_FLUX | (TARGET_HEAT if (mhrt == 1 or (mhrt == 2 and mtype == 3)) else 0))
             mhest = int(get('Flx_mhest', 0) or 0)
             if mhest not in (0, 1):
                 raise OSError('Error [Scene]: <Flx_mhest=%d> is not supported (0: collision estimator, 1: path-length estimator).' % mhest)

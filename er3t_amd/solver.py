@@ -65,6 +65,7 @@ _SIGNATURES = [
     ('mi3d_get_direct_levels'  , C.c_int   , [C.c_void_p, _dp]),
     ('mi3d_get_camera_direct'  , C.c_int   , [C.c_void_p, _dp]),
     ('mi3d_get_heating'        , C.c_int   , [C.c_void_p, _u64, _fp]),
+    ('mi3d_get_emission'       , C.c_int   , [C.c_void_p, _fp]),
     ('mi3d_get_counters'       , C.c_int   , [C.c_void_p, C.POINTER(_u64)]),
     ('mi3d_stats_begin'        , C.c_int   , [C.c_void_p, C.c_void_p, C.c_void_p]),
     ('mi3d_stats_set_analytic_share', C.c_int, [C.c_void_p, C.c_double]),
@@ -365,10 +366,21 @@ class Mi3dSolver:
         return out
 
     def heating(self, nphoton_total):
-        """absorbed power per unit volume and unit Src_flx, (nz, ny, nx): jobs whose target includes TARGET_HEAT (Flx_mhrt = 1)"""
+        """absorbed power per unit volume and unit Src_flx, (nz, ny, nx): jobs whose target includes TARGET_HEAT (Flx_mhrt = 1).
+        Thermal job (Flx_mhrt = 2): the NET, absorbed - emitted [W m-3 um-1 per unit Src_flx], negative where the cell cools; the
+        emitted part is emission(), known and not tallied.  The surface is not part of the grid: its net gain is fdn - fup at level 0
+        of flux()"""
         s = self.scene
         out = np.zeros((s.nz, s.ny, s.nx), dtype=np.float32)
         self._chk(self.lib.mi3d_get_heating(self._h, int(nphoton_total), _ptr(out)))
+        return out
+
+    def emission(self):
+        """(nz, ny, nx) float32: what every cell of a thermal job emits per unit volume, Src_flx 4 pi ka B(T), in the units of heating()
+        (include/mi3d.h: mi3d_get_emission); absorbed = heating() + emission().  A solar job raises OSError"""
+        s = self.scene
+        out = np.zeros((s.nz, s.ny, s.nx), dtype=np.float32)
+        self._chk(self.lib.mi3d_get_emission(self._h, _ptr(out)))
         return out
 
     # ---- run statistics on the device (sum over g per run, mean / std over runs) ---------------

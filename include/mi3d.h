@@ -51,7 +51,8 @@ extern "C" {
 /* target (Wld_mtarget, er3t/rtm/mca/mcarats.py:267-287) */
 #define MI3D_TARGET_FLUX 1
 #define MI3D_TARGET_RADIANCE 2
-#define MI3D_TARGET_HEAT 4 /* heating rates beside the fluxes: Flx_mhrt = 1 (mcarats.py:279-283; mca_inp.py:124); with MI3D_TARGET_FLUX */
+#define MI3D_TARGET_HEAT 4 /* heating rates beside the fluxes: Flx_mhrt = 1 (mcarats.py:279-283; mca_inp.py:124); with MI3D_TARGET_FLUX
+                            * (a thermal job: the NET heating rate, Flx_mhrt = 2, see mi3d_get_heating) */
 
 /* solver (2nd CLI argument of the reference's command line, mcarats.py:450-454) */
 #define MI3D_SOLVER_3D 0
@@ -167,8 +168,12 @@ int mi3d_set_source(mi3d_solver *h, double flx, double qmax_deg, double the_deg,
  *   Results: radiance (Rad_mrkind = 2) in W m-2 sr-1 um-1, fluxes in W m-2 um-1 (mi3d_get_radiance / mi3d_get_flux /
  *   mi3d_stats_add: the normalisation is Src_flx P_tot / N in place of Src_flx mu0 Lx Ly / N).  No direct beam: the direct-down
  *   plane is 0 and the analytic direct-beam levels are off.  A thermal job always runs on the general photon loop
- *   (mi3d_last_kernel: "k_transport<...> [thermal]"); cameras (Rad_mrkind = 1) and heating rates: MI3D_EUNSUP.  Under
- *   MI3D_SOLVER_P3D every thermal photon stays in its column (no photon is direct). */
+ *   (mi3d_last_kernel: "k_transport<...> [thermal]", followed by " [heating: path length]" under that estimator); cameras
+ *   (Rad_mrkind = 1): MI3D_EUNSUP.  Under MI3D_SOLVER_P3D every thermal photon stays in its column (no photon is direct).
+ *   Heating rates (MI3D_TARGET_FLUX | MI3D_TARGET_HEAT, the project's key Flx_mhrt = 2): the NET, absorbed minus emitted --
+ *   longwave cooling where negative; see mi3d_get_heating and mi3d_get_emission.  The emission event deposits nothing; the first
+ *   flight is tallied from the emission point (path-length estimator: the part of the cell from that point to the first face or
+ *   collision).  A source that emits nothing (P_tot = 0) runs no photon: every result is 0. */
 int mi3d_set_thermal(mi3d_solver *h, int mtype, double wlen_um, int nlev, const float *tmp1d, const float *tmpa3d,
                      const float *tmps2d);
 
@@ -273,8 +278,8 @@ int mi3d_bind_heating_buffer(mi3d_solver *h, void *heat_sum);
  *                folded cyclically -- layer means stay unbiased; within such a layer the columns are smoothed over the piece's
  *                horizontal extent, where the optical properties do not vary.
  * The estimator draws no random number: (seed, photon id) -> history is what it is, and the flux planes of a job do not depend on the
- * choice beyond the order of their float64 sums.  The weight roulette is unchanged.  Thermal jobs refuse heating rates whichever
- * estimator.  Anything but 0 / 1: MI3D_EINVAL.  A change marks the tallies dirty (the handle's own buffers are cleared by the next
+ * choice beyond the order of their float64 sums.  The weight roulette is unchanged.  Thermal jobs take either estimator for the
+ * absorbed part of their net heating rate.  Anything but 0 / 1: MI3D_EINVAL.  A change marks the tallies dirty (the handle's own buffers are cleared by the next
  * mi3d_prepare: sums of two estimators do not mix). */
 int mi3d_set_heating_estimator(mi3d_solver *h, int estimator);
 
@@ -389,8 +394,22 @@ int mi3d_get_camera_direct(mi3d_solver *h, double *out);
  *                                    Src_flx]: (weight absorbed in the cell) x Src_flx mu0 nx ny / N / layer thickness.  The
  *                                    fourth variable ("hrt", nz layers) of the flux out.bin of a job with Flx_mhrt = 1; divided by
  *                                    (air density x c_p) it is the heating rate in K/s.  (The reference's reader has no branch for
- *                                    it, er3t/rtm/mca/mca_out.py:202-205; MCARaTS' own unit for the variable is not in the tree.) */
+ *                                    it, er3t/rtm/mca/mca_out.py:202-205; MCARaTS' own unit for the variable is not in the tree.)
+ *   THERMAL job (mi3d_set_thermal 3; Flx_mhrt = 2): the NET absorbed power per unit volume, absorbed - emitted, same array, same "hrt"
+ *   variable, W m-3 um-1 per unit Src_flx; negative values are cooling.
+ *     absorbed  the same float64 tally under either estimator, normalised with the thermal photon power Src_flx P_tot / N:
+ *               (weight absorbed in the cell) x Src_flx P_tot / (N dx dy dz).
+ *     emitted   known, not tallied (as the analytic direct beam of mi3d_get_flux): Src_flx 4 pi ka B(T), with exactly the ka and
+ *               T the source's CDF was built from (ka = total extinction - total scattering of the float32 records, T = mean of the
+ *               two interface temperatures + Atm_tmpa3d); in a 1-D layer outside the 3-D region every column gets the layer's value.
+ *               Subtracted here, in float64 on the device, rounded to float32 once.  The raw tally (mi3d_bind_heating_buffer) stays
+ *               a pure sum over photons: photon-id ranges add and ranks all-reduce as for a solar job, and the emission comes off once.
+ *   The surface is not part of the heating grid: its net gain is fdn - fup at level 0 of the same job's mi3d_get_flux. */
 int mi3d_get_heating(mi3d_solver *h, uint64_t nphoton_total, float *out);
+/* The emitted power per unit volume of a thermal job, out[nz][ny][nx], in the units of mi3d_get_heating: Src_flx 4 pi ka B(T), the term
+ * mi3d_get_heating subtracts, so that absorbed = net + emitted.  Builds the source first if needed (mi3d_prepare); needs no run and
+ * no MI3D_TARGET_HEAT.  MI3D_ESTATE for a solar job, where nothing emits. */
+int mi3d_get_emission(mi3d_solver *h, float *out);
 int mi3d_get_counters(mi3d_solver *h, uint64_t out[MI3D_NCOUNTER]);
 
 /* ---- Run statistics on the device -------------------------------------------------------------

@@ -1,9 +1,10 @@
 """
 Thermal source (Src_mtype = 3): photons per second of the general photon loop on the synthetic cloud scenes of BASELINE
-configs 2 (128 x 128 x 50) and 4 (480 x 480 x 100), nadir radiance and flux, and what building the source costs per job
+configs 2 (128 x 128 x 50) and 4 (480 x 480 x 100), nadir radiance, flux and net heating rates under both estimators (legs
+'heat': collision, 'heat_path': path length; float64 atomics into the heating cells), and what building the source costs per job
 (k_thermal_power + the prefix scan + reading P_tot back: the wall time of mi3d_prepare after mi3d_set_thermal).
 
-    python tools/thermal_rate.py [--photons 5e7] [--reps 3]
+    python tools/thermal_rate.py [--photons 5e7] [--reps 3] [--legs radiance,flux,heat,heat_path]
 """
 
 import argparse
@@ -17,7 +18,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from er3t_amd.scene import TARGET_FLUX, TARGET_RADIANCE      # noqa: E402
+from er3t_amd.scene import TARGET_FLUX, TARGET_RADIANCE, TARGET_HEAT      # noqa: E402
 from er3t_amd.solver import Mi3dSolver                        # noqa: E402
 from er3t_amd.synth import les_scene, z_levels_config4, atm_synth   # noqa: E402
 
@@ -32,6 +33,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--photons', type=float, default=5e7)
     ap.add_argument('--reps', type=int, default=3)
+    ap.add_argument('--legs', default='radiance,flux,heat,heat_path')
     a = ap.parse_args()
     sol = Mi3dSolver(0)
     n = int(a.photons)
@@ -40,8 +42,12 @@ def main():
                              ('les480', dict(nx=480, ny=480, nz3=100, levels=z_levels_config4(), z_top=1.6, seed=20251004), z_levels_config4())):
         from er3t_amd.synth import z_levels_config2
         lev = levels if levels is not None else z_levels_config2()
-        for target in ('radiance', 'flux'):
-            s = thermal(les_scene(target=target, **kw), lev)
+        for target in a.legs.split(','):
+            if target in ('heat', 'heat_path'):            # net heating rates beside the fluxes (Flx_mhrt = 2), either estimator
+                s = thermal(les_scene(target='flux', **kw), lev)
+                s = dataclasses.replace(s, target=TARGET_FLUX | TARGET_HEAT, heat_estimator=int(target == 'heat_path'))
+            else:
+                s = thermal(les_scene(target=target, **kw), lev)
             sol.load_scene(s)
             # the per-job cost of the source: set again (dirty), then prepare
             build = []
@@ -56,7 +62,10 @@ def main():
                 ms, _ = sol.timing()
                 rates.append(n/(ms*1e-3))
             row = dict(scene=name, target=target, kernel=sol.kernel_name(), photons=n, photons_per_s=float(np.median(rates)),
-                       thermal_build_ms=float(np.median(build)))
+                       photons_per_s_min=float(np.min(rates)), photons_per_s_max=float(np.max(rates)), thermal_build_ms=float(np.median(build)))
+            if s.target & TARGET_HEAT:                     # (read once: the emission is taken off on the device)
+                h = sol.heating(n)
+                row['net_heating_domain_mean'] = float(h.astype(np.float64).mean())
             rows.append(row)
             print(json.dumps(row), flush=True)
     return rows
