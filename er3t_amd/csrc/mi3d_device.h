@@ -220,8 +220,25 @@ __device__ inline float4 nt_load(const float4 *p) { const vf4_t v = __builtin_no
 __device__ inline void nt_store(float4 *p, const float4 v) { __builtin_nontemporal_store((vf4_t){v.x, v.y, v.z, v.w}, reinterpret_cast<vf4_t *>(p)); }
 __device__ inline uint2 nt_load(const uint2 *p) { const vu2_t v = __builtin_nontemporal_load(reinterpret_cast<const vu2_t *>(p)); return make_uint2(v.x, v.y); }
 __device__ inline void nt_store(uint2 *p, const uint2 v) { __builtin_nontemporal_store((vu2_t){v.x, v.y}, reinterpret_cast<vu2_t *>(p)); }
+// Reads through a wave-uniform base pointer and a per-lane 32-bit byte offset (round 7).  A pointer read from the LDS copy of DevCold is a
+// per-lane value of no known address space to the compiler: every access through it is a FLAT instruction on a 64-bit per-lane address,
+// which also counts as an LDS access when the wave next waits for one.  sgpr_ptr puts the pointer into scalar registers; glb_load /
+// glb_nt_load say that it points to global memory: one global_load with the base in scalar registers and a 32-bit lane offset.
+#define MI3D_GLOBAL_AS __attribute__((address_space(1)))
+template <class T> __device__ __forceinline__ const T *sgpr_ptr(const T *p) {
+    const unsigned long long v = (unsigned long long)p;
+    return reinterpret_cast<const T *>(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)v));
+}
+__device__ __forceinline__ uint32_t glb_load_u32(const void *ubase, const unsigned byte_off) {
+    return *reinterpret_cast<const MI3D_GLOBAL_AS uint32_t *>((const MI3D_GLOBAL_AS char *)ubase + byte_off);
+}
+template <bool NTL> __device__ __forceinline__ float4 glb_load_f4(const void *ubase, const unsigned byte_off) {
+    const MI3D_GLOBAL_AS vf4_t *p = reinterpret_cast<const MI3D_GLOBAL_AS vf4_t *>((const MI3D_GLOBAL_AS char *)ubase + byte_off);
+    const vf4_t v = NTL ? __builtin_nontemporal_load(p) : *p;
+    return make_float4(v.x, v.y, v.z, v.w);
+}
 #ifndef MI3D_ENTRY_NT_LOAD
-#define MI3D_ENTRY_NT_LOAD 1   // 1: the photon loops read their entry records with non-temporal loads (+1.1 % on the 480 x 480 nadir bench, profiles/r05/ab_nt_entry_tally_records.log)
+#define MI3D_ENTRY_NT_LOAD 1  // 1: the photon loops read their entry records with non-temporal loads (+1.1 % on the 480 x 480 nadir bench, profiles/r05/ab_nt_entry_tally_records.log)
 #endif
 #ifndef MI3D_TL_NT
 #define MI3D_TL_NT 9           // bit 0: the flux loop writes its tally records with non-temporal stores; bit 1: the sort reads them so and writes the binned

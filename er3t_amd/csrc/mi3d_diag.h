@@ -22,6 +22,21 @@
 #define MI3D_DIAG_TICK(COUNT_, cnt_, tick_, slot) do { if (COUNT_) { const long long t_ = clock64(); (cnt_).cyc[slot] += (uint32_t)((t_ - (tick_)) >> 6); (tick_) = t_; } } while (0)
 #endif
 
+// -DMI3D_FULL_CENSUS=1 / 2 (round 7, tools/full_pass_census.py, profiles/r07/full_pass_census_*.log): what the full passes of the lean photon
+// loop serve and what they park, in counters the column-view build leaves at zero (le_steps, le_steps3d, flux_tally) and in the six clock
+// counters, whose split becomes A | B0 + B5 + B6 + B7 | C | B4 until its reads are issued | B2 | B4 from there until the records are unpacked.
+//   1: le_steps   lanes in a rare mode (not flying, not done, no collision found by the walk) when phase B of a pass that is NOT full begins
+//      le_steps3d lanes x full passes (64 per full pass of a wave)
+//      flux_tally lanes a later block hands to an earlier one (B6 -> M_UNIF, roulette survivor -> M_DRAW): they wait for a second full pass
+//   2: le_steps / le_steps3d / flux_tally  lanes served by B0 / B2 / B4 (B5 serves what B2 leaves alive, B6 those and the roulette, B7 the rest)
+#ifdef MI3D_FULL_CENSUS
+#define MI3D_FPC(COUNT_, cnt_, set_, field_, cond_) do { if ((COUNT_) && MI3D_FULL_CENSUS == (set_) && (cond_)) (cnt_).field_++; } while (0)
+#define MI3D_FPC_TICK(COUNT_, cnt_, tick_, slot_old, slot_census) MI3D_DIAG_TICK(COUNT_, cnt_, tick_, slot_census)
+#else
+#define MI3D_FPC(COUNT_, cnt_, set_, field_, cond_) do { } while (0)
+#define MI3D_FPC_TICK(COUNT_, cnt_, tick_, slot_old, slot_census) do { if ((slot_old) >= 0) MI3D_DIAG_TICK(COUNT_, cnt_, tick_, (slot_old) < 0 ? 0 : (slot_old)); } while (0)
+#endif
+
 // -DMI3D_WIN_DIAG: le_steps3d counts the column-view tallies that stayed in the LDS tally window, le_steps all of them (82-90 %,
 // profiles/r04/win_offset_probe.log)
 #ifdef MI3D_WIN_DIAG

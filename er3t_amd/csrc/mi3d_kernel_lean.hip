@@ -66,6 +66,9 @@ namespace mi3d {
 #ifndef MI3D_EV_NT_STORE
 #define MI3D_EV_NT_STORE 1   // 1: the event records leave through non-temporal stores (0 / 1: 3.37 / 3.68e8 photons/s with nine views, profiles/r05/ab_nt_event_records.log)
 #endif
+#ifndef MI3D_LEAN_B4_DEFER
+#define MI3D_LEAN_B4_DEFER 1   // 1: B4 unpacks the entry records after the window logic, not before it (0: at once, as rounds 4-6 did)
+#endif
 #ifndef MI3D_LEAN_PEND
 #define MI3D_LEAN_PEND 1   // 1: consecutive tallies of one history into the same pixel are summed in a register before they leave
 #endif
@@ -153,6 +156,7 @@ constexpr int M_UNIFW = 13;   // the walk has crossed a level into a uniform lay
 constexpr int M_SETUP = 14;   // about to walk voxels: B7 sets up the face parameters and asks for the first record
 constexpr int M_DRAWR = 15;   // needs a Philox block for its roulette (M_DRAW here: for its next flight)
 constexpr int M_DRAWL = 16;   // ... for its launch (no entry records)
+constexpr int M_ENTRY = 17;   // inside B4 only: the lane has asked for its entry record; ix and k hold the record's two packed words
 
 template <bool COUNT, bool P3D, int MARCH, int MIX, int NT = 256>
 #ifndef MI3D_LEAN_REG_WAVES
@@ -187,6 +191,8 @@ k_transport_lean(const DevScene S, const uint64_t nphoton, const uint64_t seed, 
     //  through a volatile pointer the compiler loses the address space and every access becomes a FLAT instruction on a 64-bit address)
     unsigned *wctl = reinterpret_cast<unsigned *>(wbuf + kWin * kWin);
 #define WLD(i_) __hip_atomic_load(wctl + (i_), __ATOMIC_SEQ_CST, __HIP_MEMORY_SCOPE_WORKGROUP)
+    // (the same word in every lane: into a scalar register, so that what is decided on it is decided on the scalar unit)
+#define WLDS(i_) ((unsigned)__builtin_amdgcn_readfirstlane((int)WLD(i_)))
 #define WST(i_, v_) __hip_atomic_store(wctl + (i_), (unsigned)(v_), __ATOMIC_SEQ_CST, __HIP_MEMORY_SCOPE_WORKGROUP)
     // (not in the build that writes event records: it has no registers to spare -- 93 hold five waves per SIMD, 105 would hold four --
     //  and its column view is one view in nine)
@@ -245,7 +251,7 @@ k_transport_lean(const DevScene S, const uint64_t nphoton, const uint64_t seed, 
     uint32_t draw = 0;
     int mode = M_NEED, kind = E_LAUNCH;
     bool direct = false;
-    unsigned long long pool_next = 0, pool_end = 0;
+    unsigned pool_next = 0, pool_left = 0;   // wave-uniform: the next place of the launch's order this wave hands out, and how many it still holds (32 bits, as lid)
     const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 7u;   // HW_REG_XCC_ID (speed only)
     unsigned victim = 0;
     unsigned nphot_wave = 0;   // wave-uniform: histories this wave has ended
@@ -307,7 +313,17 @@ k_transport_lean(const DevScene S, const uint64_t nphoton, const uint64_t seed, 
     bool emit = false;   // EMIT: this lane's event of the current pass is to be written to the event list
     unsigned long long ev_lo = 0, ev_hi = 0;   // EMIT, wave-uniform: slots of this XCD's list reserved by this wave and not yet used
 
+    // the cell, the layer and the mode out of an entry record's packed words (block B4)
+#define MI3D_ENTRY_UNPACK()                                                                                          \
+    do {                                                                                                             \
+        const unsigned cell_ = (unsigned)ix, km_ = (unsigned)k;                                                      \
+        ix = (int)(cell_ & 0xffffu); iy = (int)(cell_ >> 16);                                                        \
+        k = (int)(km_ & 0xffffu);                                                                                    \
+        mode = ((km_ >> 16) & 0x7fffu) == (unsigned)M_FLY ? M_SETUP : M_UNIF;                                        \
+        if (COUNT && (km_ >> 31)) cnt.steps++;      /* (the run of uniform layers k_entry has crossed) */            \
+    } while (0)
 #define MI3D_TICK(slot) MI3D_DIAG_TICK(COUNT, cnt, tick, slot)     // (mi3d_diag.h: instrumented build only)
+#define MI3D_TICKC(slot, census_slot) MI3D_FPC_TICK(COUNT, cnt, tick, slot, census_slot)   // (-DMI3D_FULL_CENSUS: another split; slot -1: that build only)
     long long tick = COUNT ? clock64() : 0; (void)tick;   // instrumented build: wave clock ticks / 64 spent in A, walk end + B0, C + B2, B4, B5, B6 + B7
     unsigned pass_ctr = 0;
     for (;;) {
@@ -372,6 +388,8 @@ k_transport_lean(const DevScene S, const uint64_t nphoton, const uint64_t seed, 
         bool full_ = MI3D_LEAN_FAST_PASS <= 1 || ((pass_ctr++ % (unsigned)(MI3D_LEAN_FAST_PASS)) == 0u) || __ballot(mode == M_COLL) == 0ull;
         if (MI3D_LEAN_RARE_T > 0 && !full_) full_ = __popcll(__ballot(mode != M_FLY && mode != M_DONE && mode != M_COLL)) >= MI3D_LEAN_RARE_T;
         const bool full = full_;
+        MI3D_FPC(COUNT, cnt, 1, le_steps, !full && mode != M_FLY && mode != M_DONE && mode != M_COLL);
+        MI3D_FPC(COUNT, cnt, 1, le_steps3d, full);
 
         // =================================== block C ===================================
         // The same formulas in the same order as the shared blocks below (B2, B5, B6, B7), which serve the rarer events: one lane in a
@@ -511,6 +529,7 @@ k_transport_lean(const DevScene S, const uint64_t nphoton, const uint64_t seed, 
         // =================================== the rarer events: full passes ===================================
         if (full) {
         MI3D_MARK("B0");
+        MI3D_FPC(COUNT, cnt, 2, le_steps, mode == M_UNIFW || mode == M_UNIF);
         // ---- where a walk has ended on a level, in front of a horizontally uniform layer (or out of the atmosphere)
         if (mode == M_UNIFW) {
             const float4 L = lay4[k * kL4];
@@ -574,6 +593,7 @@ k_transport_lean(const DevScene S, const uint64_t nphoton, const uint64_t seed, 
 
         MI3D_TICK(1);
         MI3D_MARK("B2");
+        MI3D_FPC(COUNT, cnt, 2, le_steps3d, mode == M_COLLU || mode == M_SURF);
         // ---- B2: a collision inside uniform layers, or the surface: weight, local estimates answered from the column table
         if (mode == M_COLLU || mode == M_SURF) {
             const float4 L = lay4[k * kL4];              // {dz, bt, zlo, flags}
@@ -665,7 +685,7 @@ k_transport_lean(const DevScene S, const uint64_t nphoton, const uint64_t seed, 
         }
         if (EMIT) emit_events(cold, xcc, emit, ev_lo, ev_hi, px, py, pz, w, ux, uy, uz, ev_ks0, ev_apf0, ev_sfc, ix, iy, k, kind, seed, PHOTON_ID(), draw);
 
-        MI3D_TICK(2);
+        MI3D_TICKC(2, 4);
         MI3D_MARK("B5");
         // ---- B5: finish the event (scattering inside uniform layers, surface reflection, or a launch without entry record)
         if (mode == M_FINISH) {
@@ -708,7 +728,7 @@ k_transport_lean(const DevScene S, const uint64_t nphoton, const uint64_t seed, 
             }
         }
 
-        MI3D_TICK(4);
+        MI3D_TICKC(4, 1);
         MI3D_MARK("B6");
         // ---- B6: the Philox block of the rarer events
         if (mode == M_DRAW || mode == M_DRAWR || mode == M_DRAWL) {
@@ -718,7 +738,9 @@ k_transport_lean(const DevScene S, const uint64_t nphoton, const uint64_t seed, 
                 rem = -0.69314718f * __builtin_amdgcn_logf(r0);
                 u1 = r1; u2 = r2; u3 = r3;
                 mode = (lay[k].flags & kLayStep3d) ? M_SETUP : M_UNIF;
+                MI3D_FPC(COUNT, cnt, 1, flux_tally, mode == M_UNIF);
             } else if (mode == M_DRAWR) {
+                MI3D_FPC(COUNT, cnt, 1, flux_tally, r0 * S.wfac < w);
                 if (r0 * S.wfac < w) { w = S.wfac; mode = M_DRAW; }    // (survived: its flight is drawn in the next full pass)
                 else { if (COUNT) cnt.killed++; mode = M_NEED; }
             } else { // the launch of a photon without entry record
@@ -740,40 +762,41 @@ k_transport_lean(const DevScene S, const uint64_t nphoton, const uint64_t seed, 
                 mode = M_FINISH;
             }
         }
-        MI3D_TICK(5);
+        MI3D_TICKC(5, 1);
 
         // ---- B4: next photon
         MI3D_MARK("B4");
-        // A history that has just ended hands in its pending tally; then the lanes without a photon take the next ids of the launch's
+        MI3D_FPC(COUNT, cnt, 2, flux_tally, mode == M_NEED);
+        // The lanes without a photon take the next ids of the launch's
         // order -- a wave takes kChunk places at a time from the cursor of the XCD it runs on (speed only: an XCD then works on one
         // tile of the domain at a time, whose records stay in its L2) and, once that piece is used up, from the next XCD's -- and with
         // them their entry records (k_entry): launch, cone jitter, first free path and the uniform layers above the clouds are behind
-        // such a photon, and B7 sets up its first voxel walk in this very pass.
-        {
-            const bool ended = mode == M_NEED && draw != 0;   // a history just ended (a lane that has had a photon has drawn for it)
-            nphot_wave += (unsigned)__popcll(__ballot(ended));            // (counted per wave, in a scalar register)
-            if (ended) {
-                draw = 0;
-                if (pend_pix >= 0) { RAD_TALLY(pend_pix, pend_val); pend_pix = -1; }
-            }
-        }
+        // such a photon, and B7 sets up its first voxel walk in this very pass.  While the records are on their way from HBM a history
+        // that has just ended hands in its pending tally and the window is looked after; only then are the records unpacked.
+        const bool ended = mode == M_NEED && draw != 0;   // a history just ended (a lane that has had a photon has drawn for it)
+        nphot_wave += (unsigned)__popcll(__ballot(ended));            // (counted per wave, in a scalar register)
+        if (ended) draw = 0;
+        // (round 7: what is the same in every lane lives in scalar registers and is compared there -- 32-bit places inside the launch, as
+        //  lid; the scalar unit has no ordered 64-bit compare, so 64-bit cursors were compared on the vector unit -- and the lanes read
+        //  through scalar base pointers with 32-bit lane offsets: global_load, not FLAT)
         bool took = false;   // wave-uniform: this pass has taken photons off the launch's order
         for (;;) {
             const unsigned long long need = __ballot(mode == M_NEED);
             if (need == 0ull) break;
-            if (pool_next >= pool_end) {
+            if (pool_left == 0u) {
                 const int leader = __ffsll((long long)need) - 1;
                 bool got = false;
                 while (victim < 8u) {
                     const unsigned x = (xcc + victim) & 7u;
                     const unsigned long long lo = (nphoton * x) >> 3, hi = (nphoton * (x + 1u)) >> 3;
+                    const unsigned piece = (unsigned)(hi - lo);   // (a launch is at most 2^32 places: a piece at most 2^29)
                     unsigned long long b = 0;
                     if ((int)(threadIdx.x & 63) == leader) b = atomicAdd(cold->next_photon + x * kCtrStride, (unsigned long long)kChunk);
-                    // (through scalar registers: the cursors are the same in every lane, and as per-lane values they cost five registers)
-                    b = ((unsigned long long)__builtin_amdgcn_readlane((int)(b >> 32), leader) << 32) | (unsigned)__builtin_amdgcn_readlane((int)b, leader);
-                    if (lo + b < hi) {
-                        pool_next = lo + b;
-                        pool_end = lo + b + kChunk < hi ? lo + b + kChunk : hi;
+                    // (the cursor of a piece starts at 0 with the launch and every wave overshoots its end once at most: 32 bits hold it)
+                    const unsigned b32 = (unsigned)__builtin_amdgcn_readlane((int)b, leader);
+                    if (b32 < piece) {
+                        pool_next = (unsigned)lo + b32;
+                        pool_left = min(piece - b32, (unsigned)kChunk);
                         got = true;
                         break;
                     }
@@ -784,53 +807,57 @@ k_transport_lean(const DevScene S, const uint64_t nphoton, const uint64_t seed, 
                     break;
                 }
             }
-            const unsigned long long avail = pool_end - pool_next;
             const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(need >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)need, 0u));
-            const unsigned long long nn = (unsigned long long)__popcll(need);
-            if (mode == M_NEED && rank < avail) {
-                const uint32_t *order = cold->order;
-                lid = order ? order[pool_next + rank] : (uint32_t)(pool_next + rank);
-                if (cold->entry) {
-                    const float4 *e = cold->entry + entry_index((unsigned)(pool_next + rank));
-#if MI3D_ENTRY_NT_LOAD
-                    const float4 q0 = nt_load(e), q1 = nt_load(e + 64), q2 = nt_load(e + 128);
-#else
-                    const float4 q0 = e[0], q1 = e[64], q2 = e[128];
-#endif
+            const unsigned take = min((unsigned)__popcll(need), pool_left);
+            if (mode == M_NEED && rank < pool_left) {
+                const uint32_t *order = sgpr_ptr(cold->order);
+                const float4 *entry = sgpr_ptr(cold->entry);
+                lid = order ? glb_load_u32(order + pool_next, rank * 4u) : pool_next + rank;
+                if (entry) {
+                    // entry_index(pool_next + rank): the 64-lane block pool_next lies in from the scalar unit, the rest per lane
+                    const unsigned j = (pool_next & 63u) + rank;
+                    const float4 *eb = entry + (size_t)(pool_next >> 6) * (size_t)(64 * kEntryF4);
+                    const unsigned eo = ((j >> 6) * (unsigned)(64 * kEntryF4) + (j & 63u)) * 16u;
+                    const float4 q0 = glb_load_f4<MI3D_ENTRY_NT_LOAD != 0>(eb, eo), q1 = glb_load_f4<MI3D_ENTRY_NT_LOAD != 0>(eb, eo + 1024u), q2 = glb_load_f4<MI3D_ENTRY_NT_LOAD != 0>(eb, eo + 2048u);
                     px = q0.x; py = q0.y; pz = q0.z; rem = q0.w;
                     ux = q1.x; uy = q1.y; uz = q1.z; u1 = q1.w;
                     u2 = q2.x; u3 = q2.y;
-                    const unsigned cell = __float_as_uint(q2.z), km = __float_as_uint(q2.w);
-                    ix = (int)(cell & 0xffffu); iy = (int)(cell >> 16);
-                    k = (int)(km & 0xffffu);
-                    mode = ((km >> 16) & 0x7fffu) == (unsigned)M_FLY ? M_SETUP : M_UNIF;
-                    if (COUNT && (km >> 31)) cnt.steps++;      // (the run of uniform layers k_entry has crossed)
+                    // (the two packed words wait in ix and k until the window has been looked after: unpacking them here would make the
+                    //  wave wait for the record at once, and it comes from HBM)
+                    ix = __float_as_int(q2.z); k = __float_as_int(q2.w);
+                    mode = M_ENTRY;
                     w = 1.0f; direct = true; draw = 2;
                     kind = E_LAUNCH;
+#if !MI3D_LEAN_B4_DEFER
+                    MI3D_ENTRY_UNPACK();
+#endif
                 } else {   // (no entry records: launched by B6 and B5 in the full passes to come)
                     draw = 0;
                     mode = M_DRAWL;
                 }
             }
-            took = took || avail != 0ull;
-            pool_next += nn < avail ? nn : avail;
+            took = true;
+            pool_next += take; pool_left -= take;
         }
+        MI3D_TICKC(-1, 3);   // (the reads of the entry records are on their way)
+        // (the pending tally of a history that has ended: handed in while the next photon's record is on its way)
+        if (ended && pend_pix >= 0) { RAD_TALLY(pend_pix, pend_val); pend_pix = -1; }
         // ---- the tally window follows the photons (see RAD_TALLY above)
         if (win_on) {
             const bool lane0 = (threadIdx.x & 63) == 0;
-            if (WLD(2) == wave_w + 1u) {
+            if (WLDS(2) == wave_w + 1u) {
                 // this wave has closed the window: has every other wave begun a pass since (or left)?
                 bool clear = true;
                 for (unsigned q = 0; q < NW; ++q) {
-                    const unsigned c = WLD(8 + q);
-                    if (q != wave_w && !(c != WLD(8 + NW + q) || c == kWinNone)) clear = false;
+                    const unsigned c = WLDS(8 + q);
+                    if (q != wave_w && !(c != WLDS(8 + NW + q) || c == kWinNone)) clear = false;
                 }
                 if (clear) {
                     win_flush();
                     // the tile the wanted place of the order lies in: tiles whose pieces end at or before it
-                    const unsigned pos = WLD(6);
-                    const uint32_t *tend = cold->tile_end;
-                    const int ntile = cold->win_ntile;
+                    const unsigned pos = WLDS(6);
+                    const uint32_t *tend = sgpr_ptr(cold->tile_end);
+                    const int ntile = __builtin_amdgcn_readfirstlane(cold->win_ntile);
                     int t = 0;
                     for (int j = 0; j < ntile; j += 64) {
                         const int q = j + (int)(threadIdx.x & 63);
@@ -851,8 +878,8 @@ k_transport_lean(const DevScene S, const uint64_t nphoton, const uint64_t seed, 
                     }
                 }
             } else if (took) {
-                const unsigned pos = (unsigned)(pool_next - 1ull);
-                if ((pos < WLD(4) || pos >= WLD(5)) && WLD(2) == 0u) {
+                const unsigned pos = pool_next - 1u;
+                if ((pos < WLDS(4) || pos >= WLDS(5)) && WLDS(2) == 0u) {
                     unsigned won = 0u;
                     if (lane0) won = atomicCAS(wctl + 2, 0u, wave_w + 1u) == 0u ? 1u : 0u;
                     won = (unsigned)__builtin_amdgcn_readfirstlane((int)won);
@@ -866,7 +893,9 @@ k_transport_lean(const DevScene S, const uint64_t nphoton, const uint64_t seed, 
                 }
             }
         }
-        MI3D_TICK(3);
+        // ---- the new photons' cell and mode, out of the words their records brought
+        if (mode == M_ENTRY) MI3D_ENTRY_UNPACK();
+        MI3D_TICKC(3, 5);
 
         MI3D_MARK("B7");
         // ---- B7: a lane about to walk: the parameters of the walk's first three faces, seen from where it is; the first record
@@ -884,13 +913,15 @@ k_transport_lean(const DevScene S, const uint64_t nphoton, const uint64_t seed, 
             rec = VREC(ix, iy, k);
             mode = M_FLY;
         }
-        MI3D_TICK(5);
+        MI3D_TICKC(5, 1);
         }   // full
 
         MI3D_MARK("END");
         if (__ballot(mode != M_DONE) == 0ull) break;
     }
 #undef MI3D_TICK
+#undef MI3D_TICKC
+#undef MI3D_ENTRY_UNPACK
     if (win_on) {
         // this wave adds to the window no more; the last one to leave empties it (a wave that leaves in the middle of a move leaves
         // the window closed: the sums wait for the last one)
