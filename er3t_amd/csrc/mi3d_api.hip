@@ -103,6 +103,10 @@ struct mi3d_solver {
     // emitted power of every cell as a CDF on the device (k_thermal_power, k_scan_*), rebuilt by mi3d_prepare when dirty
     int src_mtype = 1;
     double th_wlen = 0.0, th_ptot = 0.0, th_ms = 0.0;
+    // solar+thermal source (Src_mtype 2): the thermal source plus the sun's irradiance Src_fsol (mi3d_set_solar_irradiance; < 0: not set);
+    // th_psol = Src_fsol mu0 Lx Ly is worked out with P_tot by build_thermal
+    double src_fsol = -1.0, th_psol = 0.0;
+    bool thermal() const { return src_mtype == 3 || src_mtype == 2; }   // does the job emit (either of the two sources with a CDF)?
     std::vector<float> th_tlev;
     size_t th_ntmpa = 0, th_ntmps = 0;   // elements of the anomalies handed over (0: none)
     size_t th_ncell = 0;                 // cells of the CDF build_thermal made last (mi3d_debug_thermal)
@@ -534,7 +538,9 @@ int fill_scene(mi3d_solver *h, DevScene &S) {
         // (a source cone much wider than the solar disc -- er3t hard-wires 0.533 deg, mcarats.py:378 -- spreads the path
         //  lengths of the direct beam: then every crossing is tallied like anywhere else)
         if (h->src_qmax > 1.0) h->kdir = nz + 1;
-        if (h->src_mtype == 3) h->kdir = nz + 1;   // (thermal: there is no direct beam)
+        // (thermal: there is no direct beam.  Solar+thermal: dir_level is per unit Src_flx mu0, a mixed job's amplitude is another: its
+        //  solar photons tally the direct-down plane at every level, the top included)
+        if (h->thermal()) h->kdir = nz + 1;
         S.kdir = h->kdir;
         h->dir_level.assign(nz + 1, 0.0);
         const double mu0 = std::fabs(std::cos(th));
@@ -654,9 +660,11 @@ int check_handle(mi3d_solver *h) {
     return MI3D_OK;
 }
 
-// The power per unit domain area a job's photons stand for in all: Src_flx mu0 (solar), Src_flx P_tot / (Lx Ly) (thermal)
+// The power per unit domain area a job's photons stand for in all: Src_flx mu0 (solar), Src_flx P_tot / (Lx Ly) (thermal),
+// Src_flx (P_tot + P_sol) / (Lx Ly) (solar+thermal)
 double src_amp(const mi3d_solver *h) {
     if (h->src_mtype == 3) return h->src_flx * h->th_ptot / ((h->dx * h->nx) * (h->dy * h->ny));
+    if (h->src_mtype == 2) return h->src_flx * (h->th_ptot + h->th_psol) / ((h->dx * h->nx) * (h->dy * h->ny));
     return h->src_flx * std::fabs(std::cos(h->src_the * 3.14159265358979323846 / 180.0));
 }
 
@@ -674,6 +682,8 @@ static ThermalGrid thermal_grid(const mi3d_solver *h) {
 
 // Thermal source: emitted power of every cell (k_thermal_power), its CDF and P_tot (k_scan_*), the photon loop's DevThermal.
 int build_thermal(mi3d_solver *h) {
+    if (h->src_mtype == 2 && !(h->src_fsol >= 0.0))
+        return fail(MI3D_ESTATE, "solar+thermal source (Src_mtype=2): no solar irradiance set (mi3d_set_solar_irradiance)");
     if ((int)h->th_tlev.size() != h->nz + 1)
         return fail(MI3D_ESTATE, "thermal source: %d interface temperatures for Atm_nz=%d (call mi3d_set_thermal again)", (int)h->th_tlev.size(), h->nz);
     const size_t nvox = (size_t)h->nx * h->ny * h->nz3;
@@ -714,8 +724,11 @@ int build_thermal(mi3d_solver *h) {
     if (!(ptot >= 0.0) || !std::isfinite(ptot)) return fail(MI3D_EINVAL, "thermal source: total emitted power %g", ptot);
     h->th_ptot = ptot;
     h->th_ncell = ncell;
+    h->th_psol = 0.0;
+    if (h->src_mtype == 2)
+        h->th_psol = h->src_fsol * std::fabs(std::cos(h->src_the * 3.14159265358979323846 / 180.0)) * (h->dx * h->nx) * (h->dy * h->ny);
     DevThermal T;
-    T.cdf = h->d_th_cdf.p; T.ptot = ptot; T.ncell = (unsigned)ncell; T.nvox = (unsigned)nvox;
+    T.cdf = h->d_th_cdf.p; T.ptot = ptot; T.psol = h->th_psol; T.ncell = (unsigned)ncell; T.nvox = (unsigned)nvox;
     T.nxb = sfc2d ? h->nxb : 1; T.nyb = sfc2d ? h->nyb : 1;
     if ((rc = h->d_th.upload(&T, 1))) return rc;
     return MI3D_OK;
@@ -962,6 +975,7 @@ int mi3d_set_source(mi3d_solver *h, double flx, double qmax_deg, double the_deg,
     if (h->src_the != the_deg || h->src_phi != phi_deg || h->src_qmax != qmax_deg) ev_forget(h);
     h->src_flx = flx; h->src_qmax = qmax_deg; h->src_the = the_deg; h->src_phi = phi_deg;
     h->dirty_camdir = true;
+    if (h->src_mtype == 2) h->dirty_thermal = true;   // (P_sol holds mu0)
     return MI3D_OK;
 }
 
@@ -975,8 +989,8 @@ int mi3d_set_thermal(mi3d_solver *h, int mtype, double wlen_um, int nlev, const 
         h->src_mtype = 1; h->th_ptot = 0.0; h->dirty_thermal = false;
         return MI3D_OK;
     }
-    if (mtype == 0 || mtype == 2) return fail(MI3D_EUNSUP, "Src_mtype=%d: only the solar (1) and the thermal (3) source are supported", mtype);
-    if (mtype != 3) return fail(MI3D_EINVAL, "unknown Src_mtype=%d", mtype);
+    if (mtype == 0) return fail(MI3D_EUNSUP, "Src_mtype=0: only the solar (1), the solar+thermal (2) and the thermal (3) source are supported");
+    if (mtype != 3 && mtype != 2) return fail(MI3D_EINVAL, "unknown Src_mtype=%d", mtype);
     if (!h->have_1d) return fail(MI3D_ESTATE, "mi3d_set_atm1d has not been called");
     if (!(wlen_um > 0.0) || !std::isfinite(wlen_um)) return fail(MI3D_EINVAL, "Src_wlen=%g um must be positive", wlen_um);
     if (nlev != h->nz + 1) return fail(MI3D_EINVAL, "Atm_tmp1d: %d values for Atm_nz=%d -- the thermal source needs the nz+1 INTERFACE temperatures", nlev, h->nz);
@@ -997,10 +1011,29 @@ int mi3d_set_thermal(mi3d_solver *h, int mtype, double wlen_um, int nlev, const 
         if ((rc = h->d_th_tmps.upload(tmps2d, nsfc))) return rc;
         h->th_ntmps = nsfc;
     }
-    if (h->src_mtype != 3) ev_forget(h);
-    h->src_mtype = 3; h->th_wlen = wlen_um;
+    if (h->src_mtype != mtype) ev_forget(h);
+    h->src_mtype = mtype; h->th_wlen = wlen_um;
     h->th_tlev.assign(tmp1d, tmp1d + nlev);
     h->dirty_thermal = true;
+    return MI3D_OK;
+}
+
+int mi3d_set_solar_irradiance(mi3d_solver *h, double fsol) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (!(fsol >= 0.0) || !std::isfinite(fsol)) return fail(MI3D_EINVAL, "Src_fsol=%g W m-2 um-1 must be finite and >= 0", fsol);
+    h->src_fsol = fsol;
+    if (h->src_mtype == 2) h->dirty_thermal = true;
+    return MI3D_OK;
+}
+
+int mi3d_get_source_power(mi3d_solver *h, double *ptot, double *psol) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (!h->thermal()) return fail(MI3D_ESTATE, "mi3d_get_source_power: the job is solar (Src_mtype=1): its photons stand for Src_flx mu0 Lx Ly");
+    if ((rc = mi3d_prepare(h))) return rc;
+    if (ptot) *ptot = h->th_ptot;
+    if (psol) *psol = h->th_psol;
     return MI3D_OK;
 }
 
@@ -1243,7 +1276,7 @@ int mi3d_prepare(mi3d_solver *h) {
         }
         h->dirty_tally = false;
     }
-    if (h->src_mtype == 3 && h->dirty_thermal) {
+    if (h->thermal() && h->dirty_thermal) {
         if ((rc = build_thermal(h))) return rc;
         h->dirty_thermal = false;
     }
@@ -1383,12 +1416,12 @@ static hipError_t launch_general(mi3d_solver *h, const DevScene &S, bool march, 
     const int tb = 256;
     const size_t lds = (size_t)h->nz * sizeof(LayerRec) + MI3D_MAX_VIEW * sizeof(ViewRec) + sizeof(DevCold) + (size_t)9 * tb * sizeof(float) +
                        (size_t)(h->tab_n > 0 ? (1 + 2 * h->tab_n) * h->nang * sizeof(float) : 0);
-    const bool thermal = h->src_mtype == 3;
-    const DevThermal *th = thermal ? h->d_th.p : nullptr;
+    const int src = h->src_mtype == 3 ? 1 : h->src_mtype == 2 ? 2 : 0;   // k_transport's SRC
+    const DevThermal *th = src ? h->d_th.p : nullptr;
 #define MI3D_LAUNCH_T(C, M, F, T)                                                                                                      \
     do { if (h->solver == MI3D_SOLVER_P3D) hipLaunchKernelGGL((k_transport<C, M, F, true, T>), dim3(grid), dim3(tb), lds, h->stream, S, nb, seed, off, th); \
          else hipLaunchKernelGGL((k_transport<C, M, F, false, T>), dim3(grid), dim3(tb), lds, h->stream, S, nb, seed, off, th); } while (0)
-#define MI3D_LAUNCH(C, M, F) do { if (thermal) MI3D_LAUNCH_T(C, M, F, true); else MI3D_LAUNCH_T(C, M, F, false); } while (0)
+#define MI3D_LAUNCH(C, M, F) do { if (src == 2) MI3D_LAUNCH_T(C, M, F, 2); else if (src == 1) MI3D_LAUNCH_T(C, M, F, 1); else MI3D_LAUNCH_T(C, M, F, 0); } while (0)
     switch ((h->counting ? 4 : 0) | (march ? 2 : 0) | (flux ? 1 : 0)) {
         case 0: MI3D_LAUNCH(false, false, false); break;
         case 1: MI3D_LAUNCH(false, false, true); break;
@@ -1672,7 +1705,7 @@ struct RunPlan {
 
 static RunPlan plan_run(const mi3d_solver *h, uint64_t nphoton) {
     RunPlan plan;
-    plan.thermal = h->src_mtype == 3;
+    plan.thermal = h->thermal();   // (a mixed job's photons start anywhere too: id order, the general loop)
     plan.march = (h->target & MI3D_TARGET_RADIANCE) && h->nmarch > 0;
     plan.flux = (h->target & MI3D_TARGET_FLUX) != 0;
     int tc = plan.thermal ? 0 : choose_tile_cols(h);   // (a thermal photon does not start at the top: id order)
@@ -1737,6 +1770,7 @@ static void name_route(mi3d_solver *h, const RunPlan &plan, bool lists, uint64_t
     else if (plan.loop == Loop::Flux) snprintf(nm, sizeof(nm), lists ? "k_transport_flux<%d,%d,%d> + k_tl_scatter + k_tl_sum" : "k_transport_flux<%d,%d,%d>", c, p3d, plan.mix);
     else if (plan.loop == Loop::ColumnRays) snprintf(nm, sizeof(nm), "k_transport_lean<%d,%d,2,%d> + k_rays", c, p3d, plan.mix_lean);
     else if (plan.loop == Loop::Column) snprintf(nm, sizeof(nm), "k_transport_lean<%d,%d,0,%d>", c, p3d, plan.mix_lean);
+    else if (h->src_mtype == 2) snprintf(nm, sizeof(nm), hpath ? "k_transport<%d,%d,%d,%d> [solar+thermal] [heating: path length]" : "k_transport<%d,%d,%d,%d> [solar+thermal]", c, plan.march ? 1 : 0, plan.flux ? 1 : 0, p3d);
     else snprintf(nm, sizeof(nm), plan.thermal ? (hpath ? "k_transport<%d,%d,%d,%d> [thermal] [heating: path length]" : "k_transport<%d,%d,%d,%d> [thermal]") : hpath ? "k_transport<%d,%d,%d,%d> [heating: path length]" : "k_transport<%d,%d,%d,%d>", c, plan.march ? 1 : 0, plan.flux ? 1 : 0, p3d);
     h->last_kernel = nm;
     if (plan.loop == Loop::General && h->kernel_choice == 0 && !h->general_warned && nphoton >= 4096 && !plan.thermal) {
@@ -2173,11 +2207,14 @@ int mi3d_run(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_of
         return fail(MI3D_ESTATE, "radiance requested but no view is set (mi3d_set_views)");
     if ((h->target & MI3D_TARGET_RADIANCE) && h->rad_kind == 1 && h->solver != MI3D_SOLVER_3D)
         return fail(MI3D_EUNSUP, "cameras (Rad_mrkind=1) need the 3-D solver");
-    const bool thermal = h->src_mtype == 3;
+    const bool thermal = h->thermal();
     if (thermal && (h->target & MI3D_TARGET_RADIANCE) && h->rad_kind == 1)
         return fail(MI3D_EUNSUP, "thermal source: all-sky cameras (Rad_mrkind=1) are not supported");
     if (nphoton == 0) return MI3D_OK;
-    if (thermal && !(h->th_ptot > 0.0)) { h->last_kernel = "k_transport [thermal: nothing emits]"; return MI3D_OK; }   // (the tallies stay 0)
+    if (thermal && !(h->th_ptot + h->th_psol > 0.0)) {   // (the tallies stay 0)
+        h->last_kernel = h->src_mtype == 2 ? "k_transport [solar+thermal: nothing emits, no sunlight]" : "k_transport [thermal: nothing emits]";
+        return MI3D_OK;
+    }
     {   // the kernels index every table with 32-bit arithmetic
         const double lim = 2147483647.0;
         const double nvox = (double)h->nx * h->ny * (h->nz3 + 1) * (h->np3d > 0 ? h->np3d : 1);
@@ -2495,10 +2532,10 @@ int mi3d_get_heating(mi3d_solver *h, uint64_t nphoton_total, float *out) {
     if (!(h->target & MI3D_TARGET_HEAT) || !h->heat_ptr()) return fail(MI3D_ESTATE, "no heating-rate tally (the job's target does not include MI3D_TARGET_HEAT, or nothing has run)");
     HIPCHK(sync_main(h));
     const size_t n = h->heat_elems();
-    // a photon stands for Src_flx mu0 Lx Ly / N of power (thermal: Src_flx P_tot / N)
+    // a photon stands for Src_flx mu0 Lx Ly / N of power (thermal: Src_flx P_tot / N; solar+thermal: Src_flx (P_tot + P_sol) / N)
     const double fac = src_amp(h) * (double)h->nx * (double)h->ny / (double)nphoton_total;
-    if (h->src_mtype == 3) {
-        // thermal job: the NET, absorbed - emitted.  The emission is known, not tallied: taken off here, once, in float64 on the device
+    if (h->thermal()) {
+        // thermal or solar+thermal job: the NET, absorbed (from either source) - emitted.  The emission is known, not tallied: taken off here, once, in float64 on the device
         if (h->dirty_thermal || !h->d_th_tlev.p) return fail(MI3D_ESTATE, "thermal source: not built (nothing has run since the scene changed)");
         if (n == 0) return MI3D_OK;
         if ((rc = h->d_get_out.alloc(n))) return rc;
@@ -2527,7 +2564,7 @@ int mi3d_get_emission(mi3d_solver *h, float *out) {
     int rc = check_handle(h);
     if (rc) return rc;
     if (!out) return fail(MI3D_EINVAL, "out is NULL");
-    if (h->src_mtype != 3) return fail(MI3D_ESTATE, "mi3d_get_emission: the job is not thermal (Src_mtype=%d): nothing emits", h->src_mtype);
+    if (!h->thermal()) return fail(MI3D_ESTATE, "mi3d_get_emission: the job is not thermal (Src_mtype=%d): nothing emits", h->src_mtype);
     if ((rc = mi3d_prepare(h))) return rc;
     const size_t n = h->heat_elems();
     if (n == 0) return MI3D_OK;
@@ -2743,7 +2780,7 @@ int mi3d_debug_order(mi3d_solver *h, uint64_t n, uint32_t *order_out, uint32_t *
 int mi3d_debug_thermal(mi3d_solver *h, double *ptot, double *cdf_out, uint64_t n) {
     int rc = check_handle(h);
     if (rc) return rc;
-    if (h->src_mtype != 3) return fail(MI3D_ESTATE, "mi3d_debug_thermal: the job is not thermal (Src_mtype=%d)", h->src_mtype);
+    if (!h->thermal()) return fail(MI3D_ESTATE, "mi3d_debug_thermal: the job is not thermal (Src_mtype=%d)", h->src_mtype);
     if (h->dirty_thermal || !h->d_th_cdf.p) return fail(MI3D_ESTATE, "mi3d_debug_thermal: the thermal source is not built (call mi3d_prepare)");
     if (cdf_out && n != h->th_ncell)
         return fail(MI3D_EINVAL, "mi3d_debug_thermal: the CDF has %zu cells, not %llu", h->th_ncell, (unsigned long long)n);

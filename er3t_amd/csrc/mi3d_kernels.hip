@@ -11,7 +11,7 @@
 //                    flown through like 1-D layers: no voxel walk, no extinction reads)
 //   k_build_column   per-column optical depth from every 3-D level up to the top of atmosphere
 //   k_transport      persistent photon loop (see the comment on the kernel)
-//   k_thermal_power  thermal source (Src_mtype = 3): emitted power of every cell, float64; k_scan_* make its CDF
+//   k_thermal_power  thermal source (Src_mtype = 3, and the thermal half of 2): emitted power of every cell, float64; k_scan_* make its CDF
 //   k_stats_*        per-run g-sum and sum / sum of squares over runs of the result fields
 //   k_philox         test hook
 //
@@ -157,6 +157,7 @@ __host__ __device__ inline double planck_um(double wl_um, double T) {
 struct DevThermal {
     const double *cdf;     // [ncell] inclusive prefix sums of the cells' emitted power [W um-1]
     double ptot;           // cdf[ncell - 1]
+    double psol;           // solar+thermal source (Src_mtype = 2): the sun's power on the domain, Src_fsol mu0 Lx Ly [W um-1]; the thermal builds never read it
     unsigned ncell, nvox;
     int nxb, nyb;          // surface cells (1 x 1: uniform surface)
 };
@@ -729,10 +730,16 @@ __device__ inline void flux_add(const DevScene &S, int ix, int iy, float w, bool
 // THERM (th != nullptr): thermal source (Src_mtype = 3); the solar builds carry none of its code.  A new photon starts in a cell drawn from the CDF of emitted power (block B6,
 // D_LAUNCH), at a uniform position in it, with weight 1 (the normalisation applies P_tot / N); its emission is served by block
 // B2 as an event (M_EMIT) whose local estimates carry 1 / 4 pi (volume) or cos / pi (surface), then block B5 gives it an
-// isotropic (volume) or cosine-weighted (surface) direction.  No photon is direct: under P3D everything stays in its column.
-template <bool COUNT, bool MARCH, bool FLUX, bool P3D, bool THERM>
+// isotropic (volume) or cosine-weighted (surface) direction.  In the thermal builds (SRC == 1) no photon is direct: under P3D everything
+// stays in its column; in the mixed builds that holds for the thermal photons only.
+// SRC: 0 solar, 1 thermal, 2 solar+thermal (Src_mtype = 2).  A mixed build is a thermal build whose launch sends the
+// photon to the sun instead when the number that picks the emitting cell falls beyond the emitted power, target >= P_tot of
+// P_tot + P_sol: then it starts like a solar build's, direct until its first event (the host switches the analytic direct beam off,
+// S.kdir = nz + 1: every level's direct-down plane is tallied).  Builds 0 and 1 carry none of this.
+template <bool COUNT, bool MARCH, bool FLUX, bool P3D, int SRC>
 __global__ void __launch_bounds__(256, MI3D_WAVES(MARCH, COUNT))
 k_transport(const DevScene S, const uint64_t nphoton, const uint64_t seed, const uint64_t offset, const DevThermal *th) {
+    constexpr bool THERM = SRC != 0, MIX = SRC == 2;
     extern __shared__ float4 smem[];
     const LayerRec *lay = reinterpret_cast<const LayerRec *>(smem);
     const float4 *lay4 = smem;
@@ -1386,6 +1393,16 @@ k_transport(const DevScene S, const uint64_t nphoton, const uint64_t seed, const
         if (EVT && mode == M_DRAW && (full || dkind == D_FLIGHT)) {
             float r0, r1, r2, r3;
             draw4(seed, id, draw++, r0, r1, r2, r3);
+            // D_LAUNCH of a mixed build: the second block a thermal launch draws, whose 46-bit number picks the emitting cell, picks the source
+            // first: the thermal source owns [0, P_tot) of P_tot + P_sol, the sun the rest (P_sol = 0: the thermal job's histories, id for id)
+            uint32_t q[4];
+            double target = 0.0;
+            bool emits = false;
+            if (MIX && dkind == D_LAUNCH) {
+                philox4x32_10((uint32_t)id, (uint32_t)(id >> 32), draw++, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), q);
+                target = u01_pair(q[0], q[1]) * (th->ptot + th->psol);
+                emits = target < th->ptot;
+            }
             if (dkind == D_FLIGHT) {
                 rem = -0.69314718f * __builtin_amdgcn_logf(r0); // u >= 2^-24: never denormal, the bare v_log_f32 will do
                 u1 = r1; u2 = r2; u3 = r3;
@@ -1395,11 +1412,12 @@ k_transport(const DevScene S, const uint64_t nphoton, const uint64_t seed, const
             } else if (dkind == D_ROULETTE) {
                 if (r0 * S.wfac < w) { w = S.wfac; dkind = D_FLIGHT; }
                 else { if (COUNT) cnt.killed++; mode = M_NEED; }
-            } else if (THERM) { // D_LAUNCH of a thermal photon: a cell by its share of the emitted power, a position in it
-                uint32_t q[4];
-                philox4x32_10((uint32_t)id, (uint32_t)(id >> 32), draw++, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), q);
+            } else if (THERM && (!MIX || emits)) { // D_LAUNCH of a thermal photon: a cell by its share of the emitted power, a position in it
+                if (!MIX) {
+                    philox4x32_10((uint32_t)id, (uint32_t)(id >> 32), draw++, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), q);
+                    target = u01_pair(q[0], q[1]) * th->ptot;
+                }
                 const double *cdf = th->cdf;
-                const double target = u01_pair(q[0], q[1]) * th->ptot;
                 unsigned lo = 0, hi = th->ncell - 1;   // the first cell whose cumulative power exceeds the target (it emits)
                 while (lo < hi) {
                     const unsigned mid = lo + ((hi - lo) >> 1);   // (lo + hi wraps beyond 2^31 cells)
@@ -1460,7 +1478,7 @@ k_transport(const DevScene S, const uint64_t nphoton, const uint64_t seed, const
                                                 // tests/test_gpu_parity.py::test_single_histories_follow_the_oracle)
                 w = 1.0f;
                 direct = true;
-                if (do_flux && S.nz < S.kdir) flux_add<COUNT>(S, ix, iy, w, true, S.nz, false, cnt);   // (never: the top level is analytic)
+                if (do_flux && S.nz < S.kdir) flux_add<COUNT>(S, ix, iy, w, true, S.nz, false, cnt);   // (solar builds: never, the top level is analytic; mixed builds, kdir = nz + 1: this tallies the direct-down plane at the top)
                 kind = E_LAUNCH;
                 mode = M_FINISH;
             }
@@ -1489,12 +1507,12 @@ k_transport(const DevScene S, const uint64_t nphoton, const uint64_t seed, const
 }
 
 #undef IPA_NOW
-#define MI3D_INST(C, M, F) template __global__ void k_transport<C, M, F, false, false>(const DevScene, const uint64_t, const uint64_t, const uint64_t, const DevThermal *); \
-                           template __global__ void k_transport<C, M, F, true, false>(const DevScene, const uint64_t, const uint64_t, const uint64_t, const DevThermal *); \
-                           template __global__ void k_transport<C, M, F, false, true>(const DevScene, const uint64_t, const uint64_t, const uint64_t, const DevThermal *); \
-                           template __global__ void k_transport<C, M, F, true, true>(const DevScene, const uint64_t, const uint64_t, const uint64_t, const DevThermal *);
+#define MI3D_INST_S(C, M, F, SRC) template __global__ void k_transport<C, M, F, false, SRC>(const DevScene, const uint64_t, const uint64_t, const uint64_t, const DevThermal *); \
+                                  template __global__ void k_transport<C, M, F, true, SRC>(const DevScene, const uint64_t, const uint64_t, const uint64_t, const DevThermal *);
+#define MI3D_INST(C, M, F) MI3D_INST_S(C, M, F, 0) MI3D_INST_S(C, M, F, 1) MI3D_INST_S(C, M, F, 2)
 MI3D_INST(false, false, false) MI3D_INST(false, false, true) MI3D_INST(false, true, false) MI3D_INST(false, true, true)
 MI3D_INST(true, false, false) MI3D_INST(true, false, true) MI3D_INST(true, true, false) MI3D_INST(true, true, true)
 #undef MI3D_INST
+#undef MI3D_INST_S
 
 } // namespace mi3d

@@ -38,19 +38,26 @@ def _check_supported(nml, fdir=None):
     if int(nml.get('Wld_mtarget', 1)) == 2 and int(nml.get('Rad_mrkind', 2)) not in (1, 2):
         raise OSError('Error [mca_exe]: <Rad_mrkind=%s> is not supported (1: all-sky camera, 2: satellite sensor).' % nml.get('Rad_mrkind'))
     mtype = int(nml.get('Src_mtype', 1))
-    if mtype in (0, 2):
-        raise OSError('Error [mca_exe]: <Src_mtype=%d> (%s) is not supported: only the solar (1) or the thermal (3) source; '
-                      'solar+thermal in one job is out of scope (er3t splits the spectrum: thermal from 5 um on).' % (mtype, 'local' if mtype == 0 else 'solar+thermal'))
-    if mtype not in (1, 3):
+    if mtype == 0:
+        raise OSError('Error [mca_exe]: <Src_mtype=0> (local) is not supported: only the solar (1), the solar+thermal (2) or the thermal (3) source.')
+    if mtype not in (1, 2, 3):
         raise OSError('Error [mca_exe]: unknown <Src_mtype=%d>.' % mtype)
-    if mtype == 3:
+    if mtype == 2:
+        fsol = nml.get('Src_fsol')
+        if fsol is None:
+            raise OSError('Error [mca_exe]: a solar+thermal job (<Src_mtype=2>) needs <Src_fsol>, the solar spectral irradiance on a plane normal '
+                          'to the beam at the top of the atmosphere in W m-2 um-1 (a key of this project: mcarats_ng(source=\'solar+thermal\') writes it).')
+        fsol = float(np.ravel(fsol)[0])
+        if not (fsol >= 0.0) or not np.isfinite(fsol):
+            raise OSError('Error [mca_exe]: <Src_fsol=%g> of a solar+thermal job (<Src_mtype=2>) must be finite and >= 0.' % fsol)
+    if mtype in (2, 3):
         _check_thermal(nml, fdir)
 
 
 def _check_thermal(nml, fdir):
-    """what a thermal job (Src_mtype = 3) needs and what it cannot have (include/mi3d.h: mi3d_set_thermal)"""
+    """what a thermal or solar+thermal job (Src_mtype = 3, 2) needs and what it cannot have (include/mi3d.h: mi3d_set_thermal)"""
     if nml.get('Src_wlen') is None:
-        raise OSError('Error [mca_exe]: a thermal job (<Src_mtype=3>) needs <Src_wlen>, the band-centre wavelength in micrometres.')
+        raise OSError('Error [mca_exe]: a thermal job (<Src_mtype=%d>) needs <Src_wlen>, the band-centre wavelength in micrometres.' % int(nml.get('Src_mtype', 3)))
     nz = int(nml.get('Atm_nz', np.size(nml.get('Atm_zgrd0', [])) - 1))
     ntmp = np.size(nml.get('Atm_tmp1d', []))
     if ntmp != nz + 1:
@@ -72,9 +79,12 @@ def _check_thermal(nml, fdir):
 
 
 def thermal_heating(nml):
-    """is this the namelist of a thermal job with the NET heating rate (Src_mtype = 3, Flx_mhrt = 2)?  Its read-out subtracts the known
-    emission (include/mi3d.h: mi3d_get_heating), which JobRunner._normalise does not: several ranks take such jobs one by one"""
-    return int(nml.get('Src_mtype', 1) or 1) == 3 and int(nml.get('Wld_mtarget', 1)) == 1 and int(nml.get('Flx_mhrt', 0) or 0) == 2
+    """is this the namelist of a job that several ranks take one by one (run -> all-reduce -> the mi3d_get_* calls) instead of through
+    JobRunner.run_batched?  A thermal job with the NET heating rate (Src_mtype = 3, Flx_mhrt = 2): its read-out subtracts the known emission
+    (include/mi3d.h: mi3d_get_heating), which JobRunner._normalise does not.  EVERY solar+thermal job (Src_mtype = 2): _normalise scales with
+    Src_flx mu0, a mixed job's photons stand for Src_flx (P_tot + P_sol) / (Lx Ly)"""
+    mtype = int(nml.get('Src_mtype', 1) or 1)
+    return mtype == 2 or (mtype == 3 and int(nml.get('Wld_mtarget', 1)) == 1 and int(nml.get('Flx_mhrt', 0) or 0) == 2)
 
 
 def wants_rdir(scene):
@@ -139,8 +149,8 @@ class JobRunner:
         return n
 
     # What consecutive jobs may share: the side files (identified by path, size and time stamp) and EVERY namelist entry
-    # except the per-g 1-D profiles and the seed.  On a hit only the 1-D profiles are replaced on the device.
-    _PER_JOB = ('Atm_ext1d', 'Atm_omg1d', 'Atm_apf1d', 'Atm_abs1d', 'Atm_tmp1d', 'Wld_jseed')
+    # except the per-g 1-D profiles, the per-g sunlight of a solar+thermal job and the seed.  On a hit only the 1-D profiles are replaced on the device.
+    _PER_JOB = ('Atm_ext1d', 'Atm_omg1d', 'Atm_apf1d', 'Atm_abs1d', 'Atm_tmp1d', 'Src_fsol', 'Wld_jseed')
 
     @classmethod
     def _file_key(cls, nml, fdir):
@@ -168,9 +178,9 @@ class JobRunner:
             s1 = Scene.from_nml(nml1, fdir, solver=solver)
             if s1.nz != scene.nz or s1.np1d != scene.np1d:      # (the key holds Atm_nz and Atm_np1d: cannot happen)
                 raise OSError('Error [mca_exe]: the 1-D grid changed shape between two jobs that share their 3-D inputs.')
-            if scene.src_mtype == 3:      # (the interface temperatures are per-job keys; the anomalies stay those of the side files)
-                scene.tmp1d = s1.tmp1d
-                sol.set_thermal(3, scene.src_wlen, scene.tmp1d, scene.tmpa3d, scene.tmps2d)
+            if scene.src_mtype in (2, 3):      # (the interface temperatures are per-job keys; the anomalies stay those of the side files)
+                scene.tmp1d, scene.src_fsol = s1.tmp1d, s1.src_fsol
+                sol.set_thermal(scene.src_mtype, scene.src_wlen, scene.tmp1d, scene.tmpa3d, scene.tmps2d, fsol=scene.src_fsol)
             sol.update_atm1d(s1)
             scene.zgrd, scene.ext1d, scene.omg1d, scene.apf1d, scene.abs1d = s1.zgrd, s1.ext1d, s1.omg1d, s1.apf1d, s1.abs1d
         else:
@@ -224,7 +234,7 @@ class JobRunner:
             out['flux'] = self.sol.flux(nphoton)
         if self.scene.target & TARGET_HEAT:
             out['heat'] = self.sol.heating(nphoton)
-            out['heat_net'] = getattr(self.scene, 'src_mtype', 1) == 3
+            out['heat_net'] = getattr(self.scene, 'src_mtype', 1) in (2, 3)
         return out
 
     def collect(self, nphoton, slot=0):
@@ -241,7 +251,7 @@ class JobRunner:
             out['flux'] = sol.flux(int(nphoton))
         if scene.target & TARGET_HEAT:
             out['heat'] = sol.heating(int(nphoton))
-            out['heat_net'] = getattr(scene, 'src_mtype', 1) == 3
+            out['heat_net'] = getattr(scene, 'src_mtype', 1) in (2, 3)
         return out
 
     # ---- several ranks, file route: one exchange per BATCH of jobs instead of one per job -------------------------------------
@@ -266,6 +276,9 @@ class JobRunner:
                 nml = mca_inp_read(fname_inp)
                 fdir = os.path.dirname(os.path.abspath(fname_inp))
                 sc = self.load(nml, fdir, int(solver), slot=slot)
+                if getattr(sc, 'src_mtype', 1) == 2:
+                    raise OSError('Error [mca_exe]: a solar+thermal job (Src_mtype=2) is not served by the batched route (its photons stand for '
+                                  'Src_flx (P_tot + P_sol) / (Lx Ly), not Src_flx mu0); run such jobs one by one (run_job), as mca_run does.')
                 if sc.target & TARGET_HEAT and getattr(sc, 'src_mtype', 1) == 3:
                     raise OSError('Error [mca_exe]: the net heating rate of a thermal job (Flx_mhrt=2) is not served by the batched route (its read-out '
                                   'subtracts the emission: include/mi3d.h, mi3d_get_heating); run such jobs one by one (run_job), as mca_run does.')

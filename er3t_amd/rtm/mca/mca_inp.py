@@ -84,6 +84,7 @@ _CATALOGUE = [
     ('mcarSrc_nml_job', [
         ('Src_mtype', 'source type: 0 local, 1 solar, 2 solar+thermal, 3 thermal'), ('Src_dwlen', 'band width [micron]'),
         ('Src_wlen', 'band-centre wavelength [micron] (thermal source; a key of this project)'),
+        ('Src_fsol', 'solar irradiance normal to the beam at the top [W/m^2/micron] (solar+thermal source; a key of this project)'),
         ('Src_mphi', 'random azimuth flag'), ('Src_flx', 'source flux density'), ('Src_qmax', 'full cone angle [deg]'),
         ('Src_the', 'zenith angle of photon travel [deg]'), ('Src_phi', 'azimuth angle of photon travel [deg]')]),
     ('mcarRad_nml_job', [

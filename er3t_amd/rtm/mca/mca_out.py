@@ -114,13 +114,17 @@ def g_factors(mca_obj, abs_obj, Nz):
     """
 
     weight = abs_obj.coef['weight']['data']
-    if getattr(mca_obj, 'source', 'solar') == 'thermal':
+    source = getattr(mca_obj, 'source', 'solar')
+    if source in ('thermal', 'solar+thermal'):
         # thermal source (Src_mtype = 3): every job's result is in W m-2 (sr-1) um-1 already -- no solar spectrum, no Earth-Sun
-        # distance, no slit function: sum_g weight[ig] x_g, per nm like the solar output
+        # distance, no slit function: sum_g weight[ig] x_g, per nm like the solar output.  Solar+thermal (Src_mtype = 2): the same
+        # float32 factors -- the job's own Src_fsol carries the solar spectrum and the Earth-Sun distance (mcarats_ng.init_src), so the
+        # sunlight is NOT weighted with the slit function as a solar job's is; `toa` is the solar route's
         factors = np.zeros((Nz, mca_obj.Ng), dtype=np.float32)
         for ig in range(mca_obj.Ng):
             factors[:, ig] = np.float32(weight[ig]*1.0e-3)
-        return factors, 0.0
+        toa = np.sum(cal_sol_fac(mca_obj.date)*abs_obj.coef['solar']['data']*weight) if source == 'solar+thermal' else 0.0
+        return factors, toa
     zz = np.arange(Nz)
     if Nz > 1:
         zz[-1] = zz[-2]
@@ -254,6 +258,7 @@ def read_heating_mca_out(mca_obj, abs_obj, mode='mean', squeeze=True):
     (The reference's reader has no such branch, er3t/rtm/mca/mca_out.py:202-205: its `mca_out_ng` ends without data for this target.)
     Thermal object (mcarats_ng(source='thermal'), Flx_mhrt = 2): the variable is the NET absorbed power per unit volume, absorbed - emitted
     (negative: longwave cooling), combined with the thermal g-sum: sum_g weight[ig] x_g / 1000, no solar spectrum, no slit function.
+    Solar+thermal object (source='solar+thermal'): the same variable and the same g-sum, the absorbed sunlight included.
     """
 
     data = read_flux_mca_out(mca_obj, abs_obj, mode=mode, squeeze=squeeze)
@@ -276,7 +281,7 @@ def read_heating_mca_out(mca_obj, abs_obj, mode='mean', squeeze=True):
     dims_info = dims_info+['Nr']
     # (the same variable under both estimators of the tally, mcarats_ng's <heating_estimator>: the default's names are what they were)
     est = ', path-length estimator' if getattr(mca_obj, 'heating_estimator', 'collision') == 'path' else ''
-    what = 'Net absorbed power per unit volume' if getattr(mca_obj, 'source', 'solar') == 'thermal' else 'Absorbed power per unit volume'
+    what = 'Net absorbed power per unit volume' if getattr(mca_obj, 'source', 'solar') in ('thermal', 'solar+thermal') else 'Absorbed power per unit volume'
     if mode.lower() == 'all':
         data['heating_rate'] = {'data': hr, 'name': what+est, 'units': 'W/m^3/nm', 'dims_info': dims_info}
     else:
@@ -290,6 +295,9 @@ def read_radiance_mca_out(mca_obj, abs_obj, mode='mean', squeeze=True):
     """
     Radiance summed over g, per run ('all') or mean and population standard deviation over runs ('mean').
     keys: rad (+ rad_std for 'mean'), toa, N_photon, N_run      (reference: mca_out.py:412-505)
+    Thermal and solar+thermal objects add `bt`, the brightness temperature of the g-combined radiance at the band centre.  Solar+thermal:
+    the g-sum is the thermal route's, sum_g weight[ig] x_g / 1000 with NO slit function (every job is absolute already: its Src_fsol holds
+    the solar spectrum); `toa` is the solar route's; `bt` includes the reflected sunlight, as a 3.9 um channel measures it.
     """
 
     mode = mode.lower()
@@ -303,12 +311,15 @@ def read_radiance_mca_out(mca_obj, abs_obj, mode='mean', squeeze=True):
         data['rad_std'] = {'data': np.std(rad, axis=-1), 'name': 'Radiance (standard deviation)', 'units': 'W/m^2/nm/sr', 'dims_info': dims_info[:-1]}
     else:
         raise OSError('Error [read_radiance_mca_out]: Do not support <mode=%s>.' % mode)
-    if getattr(mca_obj, 'source', 'solar') == 'thermal':
+    source = getattr(mca_obj, 'source', 'solar')
+    if source in ('thermal', 'solar+thermal'):
         # brightness temperature of the g-combined radiance at the band centre (W m-2 sr-1 nm-1 -> um-1)
         from er3t_amd.thermal import brightness_temperature
-        data['toa']['name'] = 'TOA without SZA (none: thermal source)'
+        if source == 'thermal':
+            data['toa']['name'] = 'TOA without SZA (none: thermal source)'
         data['bt'] = {'data': brightness_temperature(mca_obj.wlen_um, data['rad']['data'].astype(np.float64)*1.0e3).astype(np.float32),
-                      'name': 'Brightness temperature' + (' (of the mean radiance)' if mode == 'mean' else ''), 'units': 'K',
+                      'name': 'Brightness temperature' + (', reflected sunlight included' if source == 'solar+thermal' else '')
+                              + (' (of the mean radiance)' if mode == 'mean' else ''), 'units': 'K',
                       'dims_info': data['rad']['dims_info']}
     data['N_photon'] = {'data': mca_obj.photons, 'name': 'Number of photons', 'units': 'N/A'}
     data['N_run']    = {'data': mca_obj.Nrun, 'name': 'Number of runs', 'units': 'N/A'}

@@ -89,6 +89,12 @@ class mcarats_ng:
                            target='heating rate' the job files carry Flx_mhrt=2, a value of this project: the NET heating rate,
                            absorbed - emitted, negative where a cell cools (include/mi3d.h: mi3d_get_heating); the surface's net
                            gain is f_down - f_up at level 0
+                           'solar+thermal' writes Src_mtype=2: both sources in one job, for the 3-5 um channels where reflected sunlight and
+                           emission are the same size.  The job files carry what a thermal job's do, the sun's direction (Src_the, Src_phi from
+                           the solar angles) and per g Src_fsol = 1000 * cal_sol_fac(date) * solar[ig] (a key of this project: the solar spectral
+                           irradiance on a plane normal to the beam at the top of the atmosphere, W m-2 um-1; include/mi3d.h,
+                           mi3d_set_solar_irradiance).  Every result is absolute, as a thermal job's; `mca_out_ng` combines the g as it does a
+                           thermal object's and its `bt` includes the sunlight
         wavelength [None] : thermal: Src_wlen in nm (default: the wavelength of atm_1ds[0]'s absorption object)
         surface_temperature [None]: thermal: replaces the lowest interface temperature (the surface's) [K]
         heating_estimator ['collision']: target='heating rate' only: 'path' tallies w kappa_a l along every flight segment instead of
@@ -134,8 +140,8 @@ class mcarats_ng:
             self.Nview = max(int(np.size(a)) for a in (sensor_zenith_angle, sensor_azimuth_angle, sensor_altitude, sensor_xpos, sensor_ypos))
         self.abs_obj, self.keep_files, self.fused = abs_obj, keep_files, None
         self.source = str(source).lower()
-        if self.source not in ('solar', 'thermal'):
-            raise OSError('Error [mcarats_ng]: <source=%s> must be \'solar\' or \'thermal\'.' % source)
+        if self.source not in ('solar', 'thermal', 'solar+thermal'):
+            raise OSError('Error [mcarats_ng]: <source=%s> must be \'solar\', \'thermal\' or \'solar+thermal\'.' % source)
         self.wavelength, self.surface_temperature = wavelength, surface_temperature
         self.heating_estimator = str(heating_estimator).lower()
         if self.heating_estimator not in ('collision', 'path'):
@@ -207,7 +213,7 @@ class mcarats_ng:
             raise OSError('Error [mcarats_ng]: <sensor_type=%r> is a radiance job: use <target=\'radiance\'>.' % sensor_type)
         if self.target != 'radiance':
             mflx, mhrt = _FLX_FLAGS[self.target]
-            if mhrt == 1 and self.source == 'thermal':
+            if mhrt == 1 and self.source in ('thermal', 'solar+thermal'):
                 mhrt = 2                               # the NET heating rate of a thermal job (a value of this project: 1 would be ambiguous)
             self._all({'Wld_mtarget': 1, 'Flx_mflx': mflx, 'Flx_mhrt': mhrt})
             if self.heating_estimator == 'path':       # (written only then: every other job file stays what it was, byte for byte)
@@ -280,7 +286,7 @@ class mcarats_ng:
             for atm_1d in atm_1ds:
                 nml.update({key: item['data'] for key, item in atm_1d.nml[ig].items()})
 
-        if self.source == 'thermal':
+        if self.source in ('thermal', 'solar+thermal'):
             # the thermal source needs the temperatures at the nz+1 layer INTERFACES (MCARaTS: Atm_tmp1d(KNZ+1)); what a solar job
             # carries are er3t's nz layer temperatures
             atm0 = atm_1ds[0]
@@ -290,6 +296,10 @@ class mcarats_ng:
             wvl_nm = self.wavelength if self.wavelength is not None else atm0.abs.wvl
             self.wlen_um = float(wvl_nm)*1.0e-3
             self._all({'Atm_tmp1d': tlev})
+            if self.source == 'solar+thermal':
+                # the sunlight of every g, absolute: W m-2 nm-1 of the absorption object's solar spectrum -> W m-2 um-1 at today's Earth-Sun distance
+                from er3t_amd.util import cal_sol_fac
+                self.fsol = 1000.0*cal_sol_fac(self.date)*np.array(atm0.abs.coef['solar']['data'], dtype=np.float64)[:self.Ng]
 
         for atm_3d in atm_3ds:
             _relative_side_file(atm_3d.nml, 'Atm_inpfile', self.fdir)
@@ -306,6 +316,12 @@ class mcarats_ng:
     def init_src(self, solar_zenith_angle=0.0, solar_azimuth_angle=0.0):
         if self.source == 'thermal':
             self._all(dict(_SRC_FIXED, Src_mtype=3, Src_wlen=float(self.wlen_um), Src_the=180.0, Src_phi=0.0))
+            return
+        if self.source == 'solar+thermal':
+            self._all(dict(_SRC_FIXED, Src_mtype=2, Src_wlen=float(self.wlen_um), Src_the=180.0-solar_zenith_angle,
+                           Src_phi=cal_mca_azimuth(solar_azimuth_angle)))
+            for ig, nml in enumerate(self.nml):
+                nml['Src_fsol'] = float(self.fsol[ig])
             return
         self._all(dict(_SRC_FIXED, Src_the=180.0-solar_zenith_angle, Src_phi=cal_mca_azimuth(solar_azimuth_angle)))
 

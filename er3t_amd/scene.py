@@ -79,6 +79,9 @@ class Scene:
     tmp1d : np.ndarray = None
     tmpa3d: np.ndarray = None
     tmps2d: np.ndarray = None
+    # solar+thermal source (Src_mtype = 2): the inputs of the thermal source plus Src_fsol (a key of this project), the solar spectral
+    # irradiance on a plane normal to the beam at the top of the atmosphere [W m-2 um-1]; the sun stands where src_the, src_phi say
+    src_fsol : float = None
 
     # radiance views (Rad_the, Rad_phi, Rad_zloc, Rad_zref, Rad_nxr, Rad_nyr)
     view_the : list = field(default_factory=list)
@@ -174,9 +177,14 @@ class Scene:
                                  % (self.cam_mpmap, self.cam_mrproj))
         elif self.rad_kind != 2:
             raise ValueError('Error [Scene]: <rad_kind=%s> (Rad_mrkind) must be 1 or 2.' % self.rad_kind)
-        if self.src_mtype == 3:
+        if self.src_mtype in (2, 3):
+            if self.src_mtype == 2:
+                if self.src_fsol is None or not (float(self.src_fsol) >= 0.0) or not np.isfinite(float(self.src_fsol)):
+                    raise ValueError('Error [Scene]: a solar+thermal source (Src_mtype=2) needs the solar irradiance <Src_fsol> >= 0 [W m-2 um-1], got %s.'
+                                     % self.src_fsol)
+                self.src_fsol = float(self.src_fsol)
             if self.src_wlen is None or not (float(self.src_wlen) > 0.0):
-                raise ValueError('Error [Scene]: a thermal source (Src_mtype=3) needs the band-centre wavelength <Src_wlen> [um].')
+                raise ValueError('Error [Scene]: a thermal source (Src_mtype=%d) needs the band-centre wavelength <Src_wlen> [um].' % self.src_mtype)
             self.tmp1d = _f32(np.ravel(self.tmp1d)) if self.tmp1d is not None else None
             if self.tmp1d is None or self.tmp1d.size != nz + 1:
                 raise ValueError('Error [Scene]: a thermal source needs the %d interface temperatures <Atm_tmp1d> (nz+1), got %s.'
@@ -190,7 +198,7 @@ class Scene:
                 if self.jsfc is None or self.tmps2d.shape != self.jsfc.shape:
                     raise ValueError('Error [Scene]: <tmps2d> must have the (nyb, nxb) shape of a 2-D surface.')
         elif self.src_mtype != 1:
-            raise ValueError('Error [Scene]: <Src_mtype=%s> is not supported (1: solar, 3: thermal).' % self.src_mtype)
+            raise ValueError('Error [Scene]: <Src_mtype=%s> is not supported (1: solar, 2: solar+thermal, 3: thermal).' % self.src_mtype)
 
     # convenient sizes
     @property
@@ -305,16 +313,21 @@ class Scene:
                   src_the=float(get('Src_the', 120.0)), src_phi=float(get('Src_phi', 0.0)))
 
         mtype = int(get('Src_mtype', 1))
-        if mtype == 3:
+        if mtype in (2, 3):
+            if mtype == 2:
+                if get('Src_fsol') is None:
+                    raise OSError('Error [Scene]: a solar+thermal job (<Src_mtype=2>) needs <Src_fsol>, the solar irradiance at the top of the '
+                                  'atmosphere in W m-2 um-1.')
+                kw.update(src_fsol=float(np.ravel(get('Src_fsol'))[0]))
             if get('Src_wlen') is None:
-                raise OSError('Error [Scene]: a thermal job (Src_mtype=3) needs <Src_wlen>, the band-centre wavelength in micrometres.')
+                raise OSError('Error [Scene]: a thermal job (Src_mtype=%d) needs <Src_wlen>, the band-centre wavelength in micrometres.' % mtype)
             tmp = np.ravel(np.asarray(get('Atm_tmp1d', []), dtype=np.float64))
             if tmp.size != nz + 1:
                 raise OSError('Error [Scene]: a thermal job needs the %d INTERFACE temperatures <Atm_tmp1d> (nz+1); %d values (%s) are ambiguous.'
                               % (nz+1, tmp.size, 'nz: layer temperatures' if tmp.size == nz else 'neither nz nor nz+1'))
-            kw.update(src_mtype=3, src_wlen=float(np.ravel(get('Src_wlen'))[0]), tmp1d=tmp)
+            kw.update(src_mtype=mtype, src_wlen=float(np.ravel(get('Src_wlen'))[0]), tmp1d=tmp)
         elif mtype != 1:
-            raise OSError('Error [Scene]: <Src_mtype=%d> is not supported (1: solar, 3: thermal).' % mtype)
+            raise OSError('Error [Scene]: <Src_mtype=%d> is not supported (1: solar, 2: solar+thermal, 3: thermal).' % mtype)
         else:
             kw.pop('tmpa3d', None); kw.pop('tmps2d', None)
 
@@ -342,10 +355,10 @@ class Scene:
                 raise OSError('Error [Scene]: <Rad_mrkind=%d> is not supported (1: camera, 2: satellite).' % mrkind)
         elif mtarget == 1:
             mhrt = int(get('Flx_mhrt', 0) or 0)
-            if mhrt == 2 and mtype != 3:
+            if mhrt == 2 and mtype not in (2, 3):
                 raise OSError('Error [Scene]: <Flx_mhrt=2> is the NET heating rate of a thermal job (Src_mtype=3); nothing emits in a solar job: use <Flx_mhrt=1>.')
             # (Flx_mhrt = 1 with the thermal source stays refused by mca_exe: absorbed or net is what is ambiguous about it)
-            kw.update(target=TARGET_FLUX | (TARGET_HEAT if (mhrt == 1 or (mhrt == 2 and mtype == 3)) else 0))
+            kw.update(target=TARGET_FLUX | (TARGET_HEAT if (mhrt == 1 or (mhrt == 2 and mtype in (2, 3))) else 0))
             mhest = int(get('Flx_mhest', 0) or 0)
             if mhest not in (0, 1):
                 raise OSError('Error [Scene]: <Flx_mhest=%d> is not supported (0: collision estimator, 1: path-length estimator).' % mhest)

@@ -42,6 +42,8 @@ _SIGNATURES = [
     ('mi3d_set_surface2d'      , C.c_int   , [C.c_void_p, C.c_int, C.c_int, _fp, _fp, _fp]),
     ('mi3d_set_source'         , C.c_int   , [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double]),
     ('mi3d_set_thermal'        , C.c_int   , [C.c_void_p, C.c_int, C.c_double, C.c_int, _fp, _fp, _fp]),
+    ('mi3d_set_solar_irradiance', C.c_int  , [C.c_void_p, C.c_double]),
+    ('mi3d_get_source_power'   , C.c_int   , [C.c_void_p, _dp, _dp]),
     ('mi3d_set_views'          , C.c_int   , [C.c_void_p, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int, C.c_int]),
     ('mi3d_set_cameras'        , C.c_int   , [C.c_void_p, C.c_int] + [_dp]*10 + [C.c_int, C.c_int]),
     ('mi3d_set_camera_map'     , C.c_int   , [C.c_void_p, C.c_int, C.c_int]),
@@ -217,9 +219,11 @@ class Mi3dSolver:
     def set_source(self, flx=1.0, qmax=0.533133, the=150.0, phi=270.0):
         self._chk(self.lib.mi3d_set_source(self._h, float(flx), float(qmax), float(the), float(phi)))
 
-    def set_thermal(self, mtype=3, wlen=None, tmp1d=None, tmpa3d=None, tmps2d=None):
+    def set_thermal(self, mtype=3, wlen=None, tmp1d=None, tmpa3d=None, tmps2d=None, fsol=None):
         """thermal source (Src_mtype = 3): band-centre wavelength <wlen> [um], (nz+1,) interface temperatures <tmp1d> [K], optional
-        voxel anomalies <tmpa3d> (nz3, ny, nx) and surface anomalies <tmps2d> (nyb, nxb) [K]; mtype=1 switches back to the sun"""
+        voxel anomalies <tmpa3d> (nz3, ny, nx) and surface anomalies <tmps2d> (nyb, nxb) [K]; mtype=1 switches back to the sun.
+        mtype=2, solar+thermal: the same arguments plus <fsol>, the solar irradiance normal to the beam at the top of the atmosphere
+        [W m-2 um-1] (include/mi3d.h: mi3d_set_solar_irradiance); the sun stands where set_source says"""
         if int(mtype) == 1:
             self._chk(self.lib.mi3d_set_thermal(self._h, 1, 0.0, 0, None, None, None))
             return
@@ -230,6 +234,16 @@ class Mi3dSolver:
             tmps2d = np.ascontiguousarray(tmps2d, dtype=np.float32)
         self._chk(self.lib.mi3d_set_thermal(self._h, int(mtype), float(wlen if wlen is not None else 0.0), tmp1d.size, _ptr(tmp1d),
                                             _ptr(tmpa3d), _ptr(tmps2d)))
+        if fsol is not None:
+            self._chk(self.lib.mi3d_set_solar_irradiance(self._h, float(fsol)))
+
+    def source_power(self):
+        """(P_tot, P_sol) [W um-1 per unit Src_flx] of a thermal or solar+thermal job: what its cells emit in all, and Src_fsol mu0 Lx Ly
+        (0 for a thermal job); a photon is thermal with probability P_tot / (P_tot + P_sol).  Builds the source if needed, needs no run
+        (include/mi3d.h: mi3d_get_source_power).  A solar job raises OSError"""
+        ptot, psol = C.c_double(0.0), C.c_double(0.0)
+        self._chk(self.lib.mi3d_get_source_power(self._h, C.byref(ptot), C.byref(psol)))
+        return float(ptot.value), float(psol.value)
 
     def set_views(self, the, phi, zloc, zref=0.0, nxr=1, nyr=1):
         the = np.ascontiguousarray(np.atleast_1d(the), dtype=np.float64)
@@ -277,8 +291,8 @@ class Mi3dSolver:
         else:
             self.set_surface(s.sfc_mtype, s.sfc_param)
         self.set_source(s.src_flx, s.src_qmax, s.src_the, s.src_phi)
-        if getattr(s, 'src_mtype', 1) == 3:
-            self.set_thermal(3, s.src_wlen, s.tmp1d, s.tmpa3d, s.tmps2d)
+        if getattr(s, 'src_mtype', 1) in (2, 3):
+            self.set_thermal(s.src_mtype, s.src_wlen, s.tmp1d, s.tmpa3d, s.tmps2d, fsol=s.src_fsol if s.src_mtype == 2 else None)
         else:
             self.set_thermal(1)
         if getattr(s, 'rad_kind', 2) == 1 and s.nview > 0:

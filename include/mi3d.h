@@ -151,8 +151,8 @@ int mi3d_set_source(mi3d_solver *h, double flx, double qmax_deg, double the_deg,
  * Sfc_inpfile (er3t/rtm/mca/mca_inp.py:287 "0:local 1:solar 2:solar+thermal 3:thermal"; mca_atm.py:73,175-214; mca_sfc.py:74).
  * Src_wlen, the band-centre wavelength in micrometres, is a key of THIS project in the Src group: MCARaTS' own thermal inputs cannot
  * be confirmed, its source is not in the reference.  Src_dwlen is accepted and ignored: the source is monochromatic at Src_wlen.
- *   mtype    3 thermal; 1 switches the handle back to the solar source (the other arguments are then ignored); 0 and 2
- *            (local, solar+thermal): MI3D_EUNSUP
+ *   mtype    3 thermal; 2 solar+thermal, with the arguments of 3 (see mi3d_set_solar_irradiance below); 1 switches the handle back
+ *            to the solar source (the other arguments are then ignored); 0 (local): MI3D_EUNSUP
  *   wlen_um  Src_wlen [um], > 0
  *   nlev     must be nz+1: tmp1d[nz+1] holds the INTERFACE temperatures [K] from the surface up (MCARaTS: Atm_tmp1d(KNZ+1))
  *   tmpa3d   [nz3][ny][nx] voxel temperature anomalies [K] in the file layout of mi3d_set_atm3d, or NULL (0)
@@ -176,6 +176,36 @@ int mi3d_set_source(mi3d_solver *h, double flx, double qmax_deg, double the_deg,
  *   collision).  A source that emits nothing (P_tot = 0) runs no photon: every result is 0. */
 int mi3d_set_thermal(mi3d_solver *h, int mtype, double wlen_um, int nlev, const float *tmp1d, const float *tmpa3d,
                      const float *tmps2d);
+
+/* Solar+thermal source (Src_mtype = 2, mi3d_set_thermal 2) = the keys of the thermal source, the sun's direction Src_the, Src_phi, Src_qmax
+ * of mi3d_set_source, and Src_fsol: the solar spectral irradiance on a plane normal to the beam at the top of the atmosphere in
+ * W m-2 um-1, >= 0.  Src_fsol is a key of THIS project in the Src group (as Src_wlen), written only when Src_mtype = 2.  For the
+ * 3-5 um channels, where reflected sunlight and emission are the same size.
+ *   fsol     negative or not finite: MI3D_EINVAL.  The handle keeps the value; it is ignored under mtype 1 and 3.  With mtype 2 and no
+ *            irradiance set, mi3d_prepare and mi3d_run return MI3D_ESTATE.
+ * Contract: one job, two sources, equal-weight photons.
+ *   P_tot    the emitted power of the thermal source [W um-1]; P_sol = Src_fsol mu0 Lx Ly, mu0 = |cos Src_the|, in float64.
+ *   A photon is thermal with probability P_tot / (P_tot + P_sol), otherwise solar; every photon starts with weight 1 and stands for
+ *   Src_flx (P_tot + P_sol) / N.  mi3d_get_radiance, _flux, _heating and mi3d_stats_add normalise with that amplitude, so a result is
+ *   Src_flx x (thermal result + Src_fsol x solar result per unit irradiance): absolute W m-2 (sr-1) um-1 for Src_flx = 1.
+ *   Sampling: (seed, id) -> history stays a function.  Draw 0 is the launch block; the 46-bit number u of draw 1 (the block a
+ *   thermal launch draws for its cell) gives target = u (P_tot + P_sol).  target < P_tot: a thermal photon, launched as
+ *   mi3d_set_thermal 3 launches it for that very target -- with Src_fsol = 0 a mixed job walks the thermal job's histories id for
+ *   id.  Otherwise a solar photon, launched from draw 0 as a solar job launches it (position at the top, cone jitter); it has spent
+ *   one more block than a solar job's and agrees with it statistically, not id by id.  No stratification by id: id ranges add
+ *   and ranks shard as for every other job.
+ *   Direct beam: the analytic direct-beam levels are off (they are per unit Src_flx mu0): the solar photons tally the direct-down
+ *   plane at every level, the top included.  Under MI3D_SOLVER_P3D a solar photon is direct (3-D) until its first event, a
+ *   thermal photon never is.
+ *   Heating rates (Flx_mhrt = 2): the net, absorbed from both sources under either estimator minus emitted; mi3d_get_emission works.
+ *   As for the thermal source: Lambertian surfaces only, cameras MI3D_EUNSUP, the general photon loop in id order
+ *   (mi3d_last_kernel: "k_transport<...> [solar+thermal]", followed by " [heating: path length]" under that estimator).
+ *   P_tot = 0 and P_sol = 0: no photon runs, every result is 0 and mi3d_last_kernel says so.  P_tot = 0, Src_fsol > 0: every
+ *   photon is solar. */
+int mi3d_set_solar_irradiance(mi3d_solver *h, double fsol);
+/* The two powers of a thermal or solar+thermal job [W um-1, per unit Src_flx]: *ptot = P_tot, *psol = P_sol (0 for a thermal job);
+ * either pointer may be NULL.  Builds the source first if needed (mi3d_prepare); needs no run.  MI3D_ESTATE for a solar job. */
+int mi3d_get_source_power(mi3d_solver *h, double *ptot, double *psol);
 
 /* Radiance views = keys Rad_nrad, Rad_the, Rad_phi, Rad_zloc, Rad_zref, Rad_nxr, Rad_nyr for
  * Rad_mrkind = 2 (pixel-averaged radiance; er3t/rtm/mca/mcarats.py:285-307,360-367).  The
@@ -395,7 +425,7 @@ int mi3d_get_camera_direct(mi3d_solver *h, double *out);
  *                                    fourth variable ("hrt", nz layers) of the flux out.bin of a job with Flx_mhrt = 1; divided by
  *                                    (air density x c_p) it is the heating rate in K/s.  (The reference's reader has no branch for
  *                                    it, er3t/rtm/mca/mca_out.py:202-205; MCARaTS' own unit for the variable is not in the tree.)
- *   THERMAL job (mi3d_set_thermal 3; Flx_mhrt = 2): the NET absorbed power per unit volume, absorbed - emitted, same array, same "hrt"
+ *   THERMAL or SOLAR+THERMAL job (mi3d_set_thermal 3 or 2; Flx_mhrt = 2; for 2 read P_tot + P_sol where P_tot scales the tally): the NET absorbed power per unit volume, absorbed - emitted, same array, same "hrt"
  *   variable, W m-3 um-1 per unit Src_flx; negative values are cooling.
  *     absorbed  the same float64 tally under either estimator, normalised with the thermal photon power Src_flx P_tot / N:
  *               (weight absorbed in the cell) x Src_flx P_tot / (N dx dy dz).
@@ -406,7 +436,7 @@ int mi3d_get_camera_direct(mi3d_solver *h, double *out);
  *               a pure sum over photons: photon-id ranges add and ranks all-reduce as for a solar job, and the emission comes off once.
  *   The surface is not part of the heating grid: its net gain is fdn - fup at level 0 of the same job's mi3d_get_flux. */
 int mi3d_get_heating(mi3d_solver *h, uint64_t nphoton_total, float *out);
-/* The emitted power per unit volume of a thermal job, out[nz][ny][nx], in the units of mi3d_get_heating: Src_flx 4 pi ka B(T), the term
+/* The emitted power per unit volume of a thermal or solar+thermal job, out[nz][ny][nx], in the units of mi3d_get_heating: Src_flx 4 pi ka B(T), the term
  * mi3d_get_heating subtracts, so that absorbed = net + emitted.  Builds the source first if needed (mi3d_prepare); needs no run and
  * no MI3D_TARGET_HEAT.  MI3D_ESTATE for a solar job, where nothing emits. */
 int mi3d_get_emission(mi3d_solver *h, float *out);

@@ -1,0 +1,47 @@
+"""
+Compare two register reports of the library (`make -C er3t_amd/csrc report 2> report.log`, -Rpass-analysis=kernel-resource-usage):
+every kernel of the first report must be in the second with every printed figure identical; the kernels only the second one has are
+listed with VGPR / scratch / waves per SIMD / SGPR spill.  (The fifth template argument of k_transport was a bool before the
+solar+thermal source: Lb0E / Lb1E of an older report are read as Li0E / Li1E.)
+
+    python tools/resource_usage_diff.py parent_report.log new_report.log
+"""
+import re
+import sys
+
+
+def parse(fn):
+    out, cur = {}, None
+    for line in open(fn):
+        m = re.search(r'remark: Function Name: (\S+)', line)
+        if m:
+            cur = m.group(1); out[cur] = []
+            continue
+        m = re.search(r'remark:\s+([A-Za-z \[\]/]+): (\S+) \[-Rpass', line)
+        if m and cur:
+            out[cur].append((m.group(1).strip(), m.group(2)))
+    return out
+
+
+def norm(name):
+    return re.sub(r'(k_transportILb\dELb\dELb\dELb\dE)Lb(\d)E', r'\1Li\2E', name)
+
+
+def main(parent, new):
+    a = {norm(k): v for k, v in parse(parent).items()}
+    b = parse(new)
+    bad = 0
+    for k, v in a.items():
+        if k not in b:
+            print('MISSING', k); bad += 1
+        elif b[k] != v:
+            print('DIFF', k, [x for x in zip(v, b[k]) if x[0] != x[1]]); bad += 1
+    print('%d kernels of the parent, %d differ; %d new kernels' % (len(a), bad, len(set(b) - set(a))))
+    for k in sorted(set(b) - set(a)):
+        d = dict(b[k])
+        print(k, 'VGPR', d['VGPRs'], 'scratch', d['ScratchSize [bytes/lane]'], 'waves/SIMD', d['Occupancy [waves/SIMD]'], 'SGPR spill', d['SGPRs Spill'])
+    return 1 if bad else 0
+
+
+if __name__ == '__main__':
+    sys.exit(main(*sys.argv[1:3]))

@@ -4,7 +4,13 @@ configs 2 (128 x 128 x 50) and 4 (480 x 480 x 100), nadir radiance, flux and net
 'heat': collision, 'heat_path': path length; float64 atomics into the heating cells), and what building the source costs per job
 (k_thermal_power + the prefix scan + reading P_tot back: the wall time of mi3d_prepare after mi3d_set_thermal).
 
+Leg 'mix': the solar+thermal source (Src_mtype = 2) at 3.75 um, nadir radiance, sun at 40 degrees, Src_fsol = 10 W m-2 um-1; its row
+carries the solar share p = P_sol / (P_tot + P_sol).  Legs 'mix_thermal' and 'mix_solar' are its two halves as jobs of their own on
+the same scene -- the thermal job at 3.75 um, and the solar job sent to the general loop (set_kernel(general=True)) --: with their
+times per photon t_thermal and t_solar a mixed photon should cost p t_solar + (1 - p) t_thermal.
+
     python tools/thermal_rate.py [--photons 5e7] [--reps 3] [--legs radiance,flux,heat,heat_path]
+    python tools/thermal_rate.py --legs mix,mix_thermal,mix_solar
 """
 
 import argparse
@@ -43,16 +49,29 @@ def main():
         from er3t_amd.synth import z_levels_config2
         lev = levels if levels is not None else z_levels_config2()
         for target in a.legs.split(','):
-            if target in ('heat', 'heat_path'):            # net heating rates beside the fluxes (Flx_mhrt = 2), either estimator
+            general = False
+            if target in ('mix', 'mix_thermal', 'mix_solar'):
+                s = thermal(les_scene(target='radiance', **kw), lev, wl=3.75)
+                s = dataclasses.replace(s, src_the=140.0, src_phi=0.0)
+                if target == 'mix':
+                    s = dataclasses.replace(s, src_mtype=2, src_fsol=10.0)
+                elif target == 'mix_solar':
+                    s = dataclasses.replace(s, src_mtype=1)
+                    general = True
+            elif target in ('heat', 'heat_path'):            # net heating rates beside the fluxes (Flx_mhrt = 2), either estimator
                 s = thermal(les_scene(target='flux', **kw), lev)
                 s = dataclasses.replace(s, target=TARGET_FLUX | TARGET_HEAT, heat_estimator=int(target == 'heat_path'))
             else:
                 s = thermal(les_scene(target=target, **kw), lev)
+            sol.set_kernel(general=general)
             sol.load_scene(s)
             # the per-job cost of the source: set again (dirty), then prepare
             build = []
             for _ in range(a.reps):
-                sol.set_thermal(3, s.src_wlen, s.tmp1d, s.tmpa3d, s.tmps2d)
+                if s.src_mtype == 3:
+                    sol.set_thermal(3, s.src_wlen, s.tmp1d, s.tmpa3d, s.tmps2d)
+                elif s.src_mtype == 2:
+                    sol.set_thermal(2, s.src_wlen, s.tmp1d, s.tmpa3d, s.tmps2d, fsol=s.src_fsol)
                 t0 = time.perf_counter(); sol.prepare(); build.append((time.perf_counter()-t0)*1e3)
             sol.reset(); sol.run(min(n, 2000000), seed=1); sol.sync()        # warm-up
             rates = []
@@ -63,11 +82,15 @@ def main():
                 rates.append(n/(ms*1e-3))
             row = dict(scene=name, target=target, kernel=sol.kernel_name(), photons=n, photons_per_s=float(np.median(rates)),
                        photons_per_s_min=float(np.min(rates)), photons_per_s_max=float(np.max(rates)), thermal_build_ms=float(np.median(build)))
+            if s.src_mtype == 2:
+                ptot, psol = sol.source_power()
+                row['solar_share'] = psol/(ptot+psol)
             if s.target & TARGET_HEAT:                     # (read once: the emission is taken off on the device)
                 h = sol.heating(n)
                 row['net_heating_domain_mean'] = float(h.astype(np.float64).mean())
             rows.append(row)
             print(json.dumps(row), flush=True)
+    sol.set_kernel(general=False)
     return rows
 
 
