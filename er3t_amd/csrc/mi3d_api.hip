@@ -2790,4 +2790,71 @@ int mi3d_debug_thermal(mi3d_solver *h, double *ptot, double *cdf_out, uint64_t n
     return MI3D_OK;
 }
 
+static_assert(MI3D_TAB_IDX_N == kTabIdxN, "include/mi3d.h states the length of a bucket index");
+
+int mi3d_debug_phase_tables(mi3d_solver *h, int nang, int npf, float *mu, float *p, float *cdf, uint16_t *mu_idx, uint16_t *cdf_idx) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (h->npf <= 0 || h->dirty_phase || !h->d_tmu.p) return fail(MI3D_ESTATE, "mi3d_debug_phase_tables: no phase table is built (mi3d_set_phase, mi3d_prepare)");
+    if (nang != h->nang || npf != h->npf) return fail(MI3D_EINVAL, "mi3d_debug_phase_tables: the tables are %d x %d, not %d x %d", h->npf, h->nang, npf, nang);
+    HIPCHK(sync_main(h));
+    const size_t n = (size_t)nang, nt = n * (size_t)npf;
+    if (mu) HIPCHK(hipMemcpy(mu, h->d_tmu.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (p) HIPCHK(hipMemcpy(p, h->d_tp.p, nt * sizeof(float), hipMemcpyDeviceToHost));
+    if (cdf) HIPCHK(hipMemcpy(cdf, h->d_tcdf.p, nt * sizeof(float), hipMemcpyDeviceToHost));
+    if (mu_idx) HIPCHK(hipMemcpy(mu_idx, h->d_tmuidx.p, (size_t)kTabIdxN * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    if (cdf_idx) HIPCHK(hipMemcpy(cdf_idx, h->d_tcdfidx.p, (size_t)npf * kTabIdxN * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return MI3D_OK;
+}
+
+int mi3d_debug_phase(mi3d_solver *h, int path, int tab_lo, int tab_n, int n, const float *apf, const float *x, const float *usel,
+                     float *p_out, float *mu_out) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (path < 0 || path > 3 || n <= 0 || !apf || !x || !usel || !p_out || !mu_out) return fail(MI3D_EINVAL, "bad arguments to mi3d_debug_phase");
+    const bool tables = h->npf > 0;
+    if (tables && (h->dirty_phase || !h->d_tmu.p)) return fail(MI3D_ESTATE, "mi3d_debug_phase: the phase tables are not built (call mi3d_prepare)");
+    const bool staged = tables && (path == 1 || path == 2);
+    size_t lds = sizeof(DevCold);
+    if (staged) {
+        if (tab_lo < 0 || tab_n < 1 || tab_n > h->npf - tab_lo)
+            return fail(MI3D_EINVAL, "mi3d_debug_phase: tables %d .. %d are not among the %d loaded", tab_lo, tab_lo + tab_n - 1, h->npf);
+        lds += lean_tab_floats(h->nang, tab_n) * sizeof(float);
+        if (lds > 64 * 1024) return fail(MI3D_EINVAL, "mi3d_debug_phase: %d tables of %d angles do not fit the LDS (%zu bytes)", tab_n, h->nang, lds);
+    }
+    for (int i = 0; i < n; ++i) {
+        if (path == 3 && !(apf[i] < 1.0f)) return fail(MI3D_EINVAL, "mi3d_debug_phase: path 3 takes analytic selectors only (apf[%d] = %g)", i, (double)apf[i]);
+        if (staged && apf[i] >= 1.0f) {   // (the tables the routines will touch: table_pick's arithmetic)
+            const float t = apf[i] - 1.0f;
+            int i0 = (int)std::floor(t), i1 = t > (float)i0 ? i0 + 1 : i0;
+            if (i0 >= h->npf - 1) i0 = i1 = h->npf - 1;
+            if (i0 < tab_lo || i1 > tab_lo + tab_n - 1)
+                return fail(MI3D_EINVAL, "mi3d_debug_phase: apf[%d] = %g refers to a table outside the staged %d .. %d", i, (double)apf[i], tab_lo, tab_lo + tab_n - 1);
+        }
+    }
+    DevCold C;
+    memset(&C, 0, sizeof(C));
+    if (tables) {
+        C.nang = h->nang; C.npf = h->npf; C.tmu = h->d_tmu.p; C.tp = h->d_tp.p; C.tcdf = h->d_tcdf.p;
+        C.tmu_idx = h->d_tmuidx.p; C.tcdf_idx = h->d_tcdfidx.p;
+        if (staged) { C.tab_lo = tab_lo; C.tab_n = tab_n; }
+    }
+    DevBuf<DevCold> d_cold;
+    DevBuf<float> d_in, d_out;
+    const size_t m = (size_t)n;
+    auto done = [&](int code) { d_cold.release(); d_in.release(); d_out.release(); return code; };
+    if ((rc = d_cold.upload(&C, 1)) || (rc = d_in.alloc(3 * m)) || (rc = d_out.alloc(2 * m))) return done(rc);
+    if (hipMemcpy(d_in.p, apf, m * sizeof(float), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_in.p + m, x, m * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_in.p + 2 * m, usel, m * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+        return done(fail(MI3D_EDEVICE, "mi3d_debug_phase: copy to the device failed"));
+    const unsigned nblk = (unsigned)std::min<size_t>((m + 255) / 256, 1024);
+    hipLaunchKernelGGL(k_debug_phase, dim3(nblk), dim3(256), lds, h->stream, d_cold.p, path, n, d_in.p, d_in.p + m, d_in.p + 2 * m, d_out.p, d_out.p + m);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = sync_main(h);
+    if (e == hipSuccess) e = hipMemcpy(p_out, d_out.p, m * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(mu_out, d_out.p + m, m * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return done(fail(MI3D_EDEVICE, "mi3d_debug_phase: %s", hipGetErrorString(e)));
+    return done(MI3D_OK);
+}
+
 } // extern "C"

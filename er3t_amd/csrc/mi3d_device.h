@@ -523,7 +523,7 @@ __device__ inline void stage_tables(const DevCold *C, float *dst) {
     for (int i = threadIdx.x; i < C->tab_n * kTabIdxN; i += blockDim.x) ib[kTabIdxN + i] = C->tcdf_idx[(long)C->tab_lo * kTabIdxN + i];
 }
 
-// largest node lo in [0, n - 2] with a[lo] <= x, for a[0] <= x < a[n - 1]; b: the bucket of x.  The nodes of the lower buckets lie below x:
+// largest node lo in [0, n - 2] with a[lo] <= x, for a[0] <= x (x >= a[n - 1]: n - 2); b: the bucket of x.  The nodes of the lower buckets lie below x:
 // the search starts at the last of them and looks at the nodes of x's own bucket -- at most two in nearly every bucket of er3t's angle
 // grids (two reads at fixed offsets, no loop); the crowded buckets (the diffraction peak's hundred nodes per bucket of mu) finish by bisection.
 __device__ inline int lean_tab_find(const float *a, const uint16_t *idx, const int n, const float x, const int b) {
@@ -554,11 +554,14 @@ __device__ inline float lean_phase_eval(const LeanTab &T, const float apf, const
         float fr = t - (float)i;
         if (i >= T.npf - 1) { i = T.npf - 1; fr = 0.0f; }
         const float *m = T.mu, *p = T.p(i);
-        // (the grid's ends are -1 and 1 exactly, build_tables: a cosine clamped just inside them needs no branch for the ends -- at -1
-        //  the search ends on node 0 with f = 0, just below 1 on the last interval with f = 1 to seven digits)
-        const float mc = fminf(fmaxf(mu, -1.0f), 0.99999994f);
+        // (the grid's ends are -1 and 1 exactly, build_tables: a cosine clamped onto them needs no branch for the ends -- at -1 the search ends
+        //  on node 0 with f = 0, at 1 on the last interval with f = 1.  Where the last nodes are equal in float32 -- er3t's grid: cos 0.01 deg
+        //  rounds to 1 -- that interval has no width and f is 0 x inf: the minimum turns the NaN into 1, the value of the last node, as
+        //  table_eval returns it.  A clamp at 1 - 2^-24, which keeps the search off that interval, gives mu = 1 the value of the last node
+        //  BELOW 1 -- 0.02 deg away on er3t's grid, 0.6 % of the last interval short on a 0.25-degree grid: tests/test_gpu_phase_functions.py)
+        const float mc = fminf(fmaxf(mu, -1.0f), 1.0f);
         const int lo = lean_tab_find(m, T.mu_idx(), T.nang, mc, tab_bucket_mu(mc));
-        const float f = (mc - m[lo]) * frcp(m[lo + 1] - m[lo]);
+        const float f = fminf((mc - m[lo]) * frcp(m[lo + 1] - m[lo]), 1.0f);
         float pv = fmaf(f, p[lo + 1] - p[lo], p[lo]);
         if (fr > 0.0f) { const float *q = p + T.nang; pv = (1.0f - fr) * pv + fr * fmaf(f, q[lo + 1] - q[lo], q[lo]); }
         return pv;

@@ -138,6 +138,43 @@ __global__ void k_philox(uint64_t seed, uint64_t id0, uint32_t draw, int n, uint
     out[4 * i + 0] = w[0]; out[4 * i + 1] = w[1]; out[4 * i + 2] = w[2]; out[4 * i + 3] = w[3];
 }
 
+// Test hook (mi3d_debug_phase): the phase-function routines of mi3d_device.h themselves on the caller's points, one point per lane in a
+// grid-stride loop.  The cold block is the hook's own copy (only the table fields are set, tab_lo / tab_n the caller's) and is read from
+// LDS as in the photon loops; the tables are staged behind it as the photon loops stage them: path 1 in the layout phase_tab expects
+// (k_transport's copy loop), path 2 by stage_tables.  LDS: sizeof(DevCold) + lean_tab_floats(nang, tab_n) floats (paths 1, 2).
+__global__ void __launch_bounds__(256)
+k_debug_phase(const DevCold *gcold, const int path, const int n, const float *__restrict__ apf, const float *__restrict__ x,
+              const float *__restrict__ usel, float *__restrict__ p_out, float *__restrict__ mu_out) {
+    extern __shared__ float4 smem[];
+    const DevCold *cold = reinterpret_cast<const DevCold *>(smem);
+    float *dst = reinterpret_cast<float *>(smem + kColdF4);
+    if (threadIdx.x < kColdF4) smem[threadIdx.x] = reinterpret_cast<const float4 *>(gcold)[threadIdx.x];
+    const float *ltab = nullptr;
+    if (path == 1 && gcold->tab_n > 0) {
+        const int nang = gcold->nang, nt = gcold->tab_n * nang;
+        for (int i = threadIdx.x; i < nang; i += blockDim.x) dst[i] = gcold->tmu[i];
+        for (int i = threadIdx.x; i < nt; i += blockDim.x) {
+            dst[nang + i] = gcold->tp[(long)gcold->tab_lo * nang + i];
+            dst[nang + nt + i] = gcold->tcdf[(long)gcold->tab_lo * nang + i];
+        }
+        ltab = dst;
+    }
+    if (path == 2 && gcold->tab_n > 0) {
+        stage_tables(gcold, dst);
+        ltab = dst;
+    }
+    __syncthreads();
+    const LeanTab T = path == 2 ? lean_tab(cold, ltab) : LeanTab{};
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const float a = apf[i], v = x[i], us = usel[i];
+        float p, m;
+        if (path == 2) { p = lean_phase_eval(T, a, v); m = lean_phase_sample(T, a, v, us); }
+        else if (path == 3) { p = phase_eval_analytic(a, v); m = phase_sample_analytic(a, v); }
+        else { p = phase_eval(cold, ltab, a, v); m = phase_sample(cold, ltab, a, v, us); }
+        p_out[i] = p; mu_out[i] = m;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // thermal source (Src_mtype = 3, include/mi3d.h: mi3d_set_thermal)
 // ---------------------------------------------------------------------------------------------

@@ -79,7 +79,11 @@ _SIGNATURES = [
     ('mi3d_debug_philox'       , C.c_int   , [C.c_void_p, _u64, _u64, C.c_uint32, C.c_int, C.POINTER(C.c_uint32)]),
     ('mi3d_debug_order'        , C.c_int   , [C.c_void_p, _u64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int]),
     ('mi3d_debug_thermal'      , C.c_int   , [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), _u64]),
+    ('mi3d_debug_phase_tables' , C.c_int   , [C.c_void_p, C.c_int, C.c_int, _fp, _fp, _fp, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]),
+    ('mi3d_debug_phase'        , C.c_int   , [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp]),
 ]
+
+TAB_IDX_N = 514     # entries of a bucket index into the phase tables (include/mi3d.h: MI3D_TAB_IDX_N)
 
 
 def library_path():
@@ -458,6 +462,26 @@ class Mi3dSolver:
         ptot = C.c_double(0.0); cdf = np.zeros(int(ncell), dtype=np.float64)
         self._chk(self.lib.mi3d_debug_thermal(self._h, C.byref(ptot), cdf.ctypes.data_as(C.POINTER(C.c_double)), int(ncell)))
         return float(ptot.value), cdf
+
+    def debug_phase_tables(self, nang, npf):
+        """test hook: the device's phase tables after set_phase + prepare: (mu [nang], p [npf, nang], cdf [npf, nang]) float32 and the
+        bucket indices (mu_idx [TAB_IDX_N], cdf_idx [npf, TAB_IDX_N]) uint16"""
+        mu = np.zeros(nang, dtype=np.float32); p = np.zeros((npf, nang), dtype=np.float32); cdf = np.zeros((npf, nang), dtype=np.float32)
+        mi = np.zeros(TAB_IDX_N, dtype=np.uint16); ci = np.zeros((npf, TAB_IDX_N), dtype=np.uint16)
+        u16 = C.POINTER(C.c_uint16)
+        self._chk(self.lib.mi3d_debug_phase_tables(self._h, int(nang), int(npf), _ptr(mu), _ptr(p), _ptr(cdf), _ptr(mi, u16), _ptr(ci, u16)))
+        return mu, p, cdf, mi, ci
+
+    def debug_phase(self, path, apf, x, usel=None, tab_lo=0, tab_n=0):
+        """test hook: (P(apf, mu = x), mu(apf, u = x, usel)) float32 per point from the device's own routines; path 0: phase_eval /
+        phase_sample on the tables in global memory, 1: through an LDS copy of tables tab_lo .. tab_lo + tab_n - 1, 2: the lean kernels'
+        lean_phase_eval / lean_phase_sample on the staged tables, 3: the analytic copies (include/mi3d.h: mi3d_debug_phase)"""
+        x = np.ascontiguousarray(np.ravel(x), dtype=np.float32)
+        apf = np.ascontiguousarray(np.broadcast_to(np.asarray(apf, dtype=np.float32), x.shape))
+        usel = np.ascontiguousarray(np.broadcast_to(np.asarray(0.0 if usel is None else usel, dtype=np.float32), x.shape))
+        p = np.zeros(x.size, dtype=np.float32); m = np.zeros(x.size, dtype=np.float32)
+        self._chk(self.lib.mi3d_debug_phase(self._h, int(path), int(tab_lo), int(tab_n), x.size, _ptr(apf), _ptr(x), _ptr(usel), _ptr(p), _ptr(m)))
+        return p, m
 
     def philox(self, seed, id0, draw, n):
         out = np.zeros((n, 4), dtype=np.uint32)

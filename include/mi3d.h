@@ -490,6 +490,20 @@ int mi3d_debug_order(mi3d_solver *h, uint64_t n, uint32_t *order_out, uint32_t *
  * inclusive CDF of the cells' emitted power in float64, n = its number of cells (voxels, 1-D layers, surface cells: otherwise
  * MI3D_EINVAL).  MI3D_ESTATE when the job is not thermal or its source is not built yet. */
 int mi3d_debug_thermal(mi3d_solver *h, double *ptot, double *cdf_out, uint64_t n);
+/* Test hook: the phase tables as they stand on the device after mi3d_set_phase + mi3d_prepare (each pointer may be NULL): mu [nang]
+ * ascending, p and cdf [npf][nang] (float32, normalised), the bucket index of mu [MI3D_TAB_IDX_N] and those of the CDFs
+ * [npf][MI3D_TAB_IDX_N] (uint16).  nang / npf must be the loaded ones (otherwise MI3D_EINVAL); MI3D_ESTATE when no table is loaded or
+ * mi3d_prepare has not built it. */
+#define MI3D_TAB_IDX_N 514
+int mi3d_debug_phase_tables(mi3d_solver *h, int nang, int npf, float *mu, float *p, float *cdf, uint16_t *mu_idx, uint16_t *cdf_idx);
+/* Test hook: the device's own phase-function routines (er3t_amd/csrc/mi3d_device.h) on n points: p_out[i] = P(apf[i], mu = x[i]) and
+ * mu_out[i] = the cosine drawn from apf[i] with the uniform number x[i] (usel[i]: which of two mixed tables).  path:
+ *   0  phase_eval / phase_sample, tables in global memory          1  the same through an LDS copy of tables tab_lo .. tab_lo + tab_n - 1
+ *   2  lean_phase_eval / lean_phase_sample on the staged tables    3  phase_eval_analytic / phase_sample_analytic (apf < 1 only)
+ * Paths 1 and 2 take the staged range from the caller (1 <= tab_n, tab_lo + tab_n <= npf; it must fit the LDS of a launch, and every
+ * selector >= 1 must refer to staged tables only: otherwise MI3D_EINVAL); paths 0 and 3 ignore it.  No photon kernel is involved. */
+int mi3d_debug_phase(mi3d_solver *h, int path, int tab_lo, int tab_n, int n, const float *apf, const float *x, const float *usel,
+                     float *p_out, float *mu_out);
 
 #ifdef __cplusplus
 }
