@@ -1370,6 +1370,15 @@ static hipError_t launch_lean(mi3d_solver *h, hipStream_t st, const DevScene &S,
 static hipError_t launch_rays(mi3d_solver *h, hipStream_t st, const DevScene &S, bool heavy, size_t lds, uint64_t seed) {
     if (h->rad_kind == 1) {   // cameras: the build whose rays carry their own direction (3-D solver: mi3d_run has checked)
         const unsigned gridc = (unsigned)h->num_cu * 4u;
+        if (h->src_mtype == 3) {   // (a thermal job's events: emissions among them)
+            if (lds > 65536) {
+                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_rays<true, false, false, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_rays<false, false, false, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            }
+            if (h->counting) hipLaunchKernelGGL((k_rays<true, false, false, true, false, true>), dim3(gridc), dim3(256), lds, st, S, seed);
+            else hipLaunchKernelGGL((k_rays<false, false, false, true, false, true>), dim3(gridc), dim3(256), lds, st, S, seed);
+            return hipGetLastError();
+        }
         if (lds > 65536) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_rays<true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_rays<false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1412,12 +1421,18 @@ static hipError_t launch_rays(mi3d_solver *h, hipStream_t st, const DevScene &S,
 #endif
 
 // The general photon loop (mi3d_kernels.hip): every job the lean loops do not serve, the thermal source's among them
-static hipError_t launch_general(mi3d_solver *h, const DevScene &S, bool march, bool flux, unsigned grid, uint64_t nb, uint64_t seed, uint64_t off) {
+// (emit: the thermal builds that write event records for k_rays instead of marching the rays of the cameras themselves, k_transport<.,2,...>)
+static hipError_t launch_general(mi3d_solver *h, const DevScene &S, bool march, bool flux, unsigned grid, uint64_t nb, uint64_t seed, uint64_t off, bool emit = false) {
     const int tb = 256;
     const size_t lds = (size_t)h->nz * sizeof(LayerRec) + MI3D_MAX_VIEW * sizeof(ViewRec) + sizeof(DevCold) + (size_t)9 * tb * sizeof(float) +
                        (size_t)(h->tab_n > 0 ? (1 + 2 * h->tab_n) * h->nang * sizeof(float) : 0);
     const int src = h->src_mtype == 3 ? 1 : h->src_mtype == 2 ? 2 : 0;   // k_transport's SRC
     const DevThermal *th = src ? h->d_th.p : nullptr;
+    if (emit) {
+        if (h->counting) hipLaunchKernelGGL((k_transport<true, 2, false, false, 1>), dim3(grid), dim3(tb), lds, h->stream, S, nb, seed, off, th);
+        else hipLaunchKernelGGL((k_transport<false, 2, false, false, 1>), dim3(grid), dim3(tb), lds, h->stream, S, nb, seed, off, th);
+        return hipGetLastError();
+    }
 #define MI3D_LAUNCH_T(C, M, F, T)                                                                                                      \
     do { if (h->solver == MI3D_SOLVER_P3D) hipLaunchKernelGGL((k_transport<C, M, F, true, T>), dim3(grid), dim3(tb), lds, h->stream, S, nb, seed, off, th); \
          else hipLaunchKernelGGL((k_transport<C, M, F, false, T>), dim3(grid), dim3(tb), lds, h->stream, S, nb, seed, off, th); } while (0)
@@ -1732,6 +1747,11 @@ static RunPlan plan_run(const mi3d_solver *h, uint64_t nphoton) {
     if (lean && plan.flux && !rad_job && h->nx < 65536 && h->ny < 65536 && h->nz < 65535) plan.loop = Loop::Flux;
     else if (lean && !plan.flux && h->nview > 0 && (plan.march ? cells16 && (h->rad_kind == 2 || h->solver == MI3D_SOLVER_3D) : h->rad_kind == 2))
         plan.loop = plan.march ? Loop::ColumnRays : Loop::Column;
+    // Thermal cameras (Src_mtype = 3, Rad_mrkind = 1): where the lean loops' limits hold, the general loop's builds that write
+    // event records, and k_rays' thermal camera build behind them -- the ColumnRays machinery with another photon loop in front
+    if (h->src_mtype == 3 && h->kernel_choice == 0 && h->np3d <= 2 && tabs_ok && vox32 && !plan.flux && h->nview > 0 && plan.march && cells16 &&
+        h->rad_kind == 1 && h->solver == MI3D_SOLVER_3D)
+        plan.loop = Loop::ColumnRays;
     plan.mix_lean = (plan.mix == 2 && plan.loop != Loop::ColumnRays && rayleigh_1d(h) && h->np3d == 1) ? 3 : plan.mix;
     if (plan.loop == Loop::General || (h->rad_kind == 1 && plan.loop != Loop::ColumnRays))
         plan.why = h->kernel_choice != 0 ? "kernel choice 1"
@@ -1768,6 +1788,7 @@ static void name_route(mi3d_solver *h, const RunPlan &plan, bool lists, uint64_t
     const bool hpath = (h->target & MI3D_TARGET_HEAT) && h->heat_estimator == 1;
     if (plan.loop == Loop::Flux && hpath) snprintf(nm, sizeof(nm), lists ? "k_transport_flux<%d,%d,%d,1> + k_tl_scatter + k_tl_sum" : "k_transport_flux<%d,%d,%d,1>", c, p3d, plan.mix);
     else if (plan.loop == Loop::Flux) snprintf(nm, sizeof(nm), lists ? "k_transport_flux<%d,%d,%d> + k_tl_scatter + k_tl_sum" : "k_transport_flux<%d,%d,%d>", c, p3d, plan.mix);
+    else if (plan.loop == Loop::ColumnRays && plan.thermal) snprintf(nm, sizeof(nm), "k_transport<%d,2,0,0> [thermal] + k_rays", c);
     else if (plan.loop == Loop::ColumnRays) snprintf(nm, sizeof(nm), "k_transport_lean<%d,%d,2,%d> + k_rays", c, p3d, plan.mix_lean);
     else if (plan.loop == Loop::Column) snprintf(nm, sizeof(nm), "k_transport_lean<%d,%d,0,%d>", c, p3d, plan.mix_lean);
     else if (h->src_mtype == 2) snprintf(nm, sizeof(nm), hpath ? "k_transport<%d,%d,%d,%d> [solar+thermal] [heating: path length]" : "k_transport<%d,%d,%d,%d> [solar+thermal]", c, plan.march ? 1 : 0, plan.flux ? 1 : 0, p3d);
@@ -1959,7 +1980,7 @@ static bool use_entry_records(mi3d_solver *h, const RunPlan &plan, uint64_t npho
 #if MI3D_LEAN_FAST
     // (the path-length estimator of the heating rates tallies the first flight too: its photons are launched inside the loop)
     if ((h->target & MI3D_TARGET_HEAT) && h->heat_estimator == 1) return false;
-    if (plan.loop == Loop::General || !h->entry_records || h->nx >= 65536 || h->ny >= 65536 || h->nz >= 32768) return false;
+    if (plan.loop == Loop::General || plan.thermal || !h->entry_records || h->nx >= 65536 || h->ny >= 65536 || h->nz >= 32768) return false;
     DevBuf<float4> &E = h->pre[0].entry;
     const size_t need = entry_f4((size_t)std::min<uint64_t>(nphoton, h->batch));
     size_t free_b = free_bytes((size_t)8 << 30);
@@ -2037,7 +2058,11 @@ static int rad_acc_image(mi3d_solver *h, const RunPlan &plan, DevScene &S, int &
     rad_row = 0;
     const int row = h->rad_row_pad >= 0 ? h->nxr + h->rad_row_pad : 32 * (((h->nxr + 31) / 32) | 1);
     const size_t acc_elems = (size_t)h->nview * h->nyr * row;
-    const bool spread = (h->target & MI3D_TARGET_RADIANCE) && h->nview > 0 && h->rad_spread != 0 && !(h->rad_spread < 0 && plan.loop == Loop::ColumnRays) &&
+    // (the point radiometers of a thermal job, DESIGN.md §5.10: sixteen one-pixel images are ONE 128-byte line of the compact image, and the ray
+    //  kernel's atomics to it run one after the other -- spread they are sixteen lines: 1.87 -> 6.63e7 photons/s for sixteen sensors on 128 x 128,
+    //  profiles/r10/spread_probe.log)
+    const bool few_pixels = plan.thermal && h->rad_kind == 1 && (size_t)h->nview * h->nyr * h->nxr <= 1024;
+    const bool spread = (h->target & MI3D_TARGET_RADIANCE) && h->nview > 0 && h->rad_spread != 0 && !(h->rad_spread < 0 && plan.loop == Loop::ColumnRays && !few_pixels) &&
                         (double)acc_elems * kRadLine * sizeof(tally_t) <= 1.0e9 && (double)acc_elems * kRadLine < 2147483647.0;
     if (!spread) return MI3D_OK;
     const size_t need = acc_elems * kRadLine;
@@ -2099,7 +2124,8 @@ static hipError_t launch_column(mi3d_solver *h, const RunPlan &plan, const DevSc
     // (the set is free once the ray kernels of the launch that used it last are through it)
     if (two_sets && E.used) err = hipStreamWaitEvent(h->stream, E.rays, 0);
     if (err == hipSuccess && split) err = hipMemsetAsync(E.evctr.p, 0, kCtrWords * kCtrStride * sizeof(unsigned long long), h->stream);
-    if (err == hipSuccess) {
+    if (err == hipSuccess && plan.thermal) err = launch_general(h, Sx, false, false, gridp, nb, seed, off, true);   // (thermal cameras: the general loop writes the records)
+    else if (err == hipSuccess) {
         // (the general mixture with staged tables AND a tally window: three workgroups of 512 threads keep six waves per SIMD where
         //  six of 256 would not find the LDS)
         const size_t lds_lean = lds_col + (h->cold_host.tile_end ? kWinLds : 0) + plan.lds_tab;
@@ -2208,8 +2234,9 @@ int mi3d_run(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_of
     if ((h->target & MI3D_TARGET_RADIANCE) && h->rad_kind == 1 && h->solver != MI3D_SOLVER_3D)
         return fail(MI3D_EUNSUP, "cameras (Rad_mrkind=1) need the 3-D solver");
     const bool thermal = h->thermal();
-    if (thermal && (h->target & MI3D_TARGET_RADIANCE) && h->rad_kind == 1)
-        return fail(MI3D_EUNSUP, "thermal source: all-sky cameras (Rad_mrkind=1) are not supported");
+    // (thermal cameras, Src_mtype = 3: served; the direct sun of a mixed job's cameras would need a normalisation of its own)
+    if (h->src_mtype == 2 && (h->target & MI3D_TARGET_RADIANCE) && h->rad_kind == 1)
+        return fail(MI3D_EUNSUP, "solar+thermal source (Src_mtype=2): all-sky cameras (Rad_mrkind=1) are not supported");
     if (nphoton == 0) return MI3D_OK;
     if (thermal && !(h->th_ptot + h->th_psol > 0.0)) {   // (the tallies stay 0)
         h->last_kernel = h->src_mtype == 2 ? "k_transport [solar+thermal: nothing emits, no sunlight]" : "k_transport [thermal: nothing emits]";

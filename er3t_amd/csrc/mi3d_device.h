@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "../../include/mi3d.h"
+#include "mi3d_diag.h"
 
 namespace mi3d {
 
@@ -351,6 +352,61 @@ __device__ inline float le_weight_roulette_base(float c, float cmin, uint32_t ba
 }
 __device__ inline float le_weight_roulette(float c, float cmin, uint64_t seed, uint64_t id, uint32_t draw, int iv) {
     return le_weight_roulette_base(c, cmin, le_hash_base(seed, id, draw), iv);
+}
+
+#ifndef MI3D_EV_NT_STORE
+#define MI3D_EV_NT_STORE 1   // 1: the event records leave through non-temporal stores (0 / 1: 3.37 / 3.68e8 photons/s with nine views, profiles/r05/ab_nt_event_records.log)
+#endif
+// The photon loops that write event records (k_transport_lean<.,.,2>, k_transport<.,2,...>): the events of this pass go to this XCD's list for k_rays; the photons carry on at once.  A wave reserves
+// room for kEvBlock records at a time (one returning atomic per block instead of one per pass: the wave waits for it) and hands the
+// slots out itself; what it leaves unused is marked empty (weight 0) before it reserves again or ends.  Wave-level: to be called
+// where the whole wave passes (ev_lo, ev_hi are wave-uniform).
+__device__ __forceinline__ void emit_events(const DevCold *cold, const unsigned xcc, bool &emit, unsigned long long &ev_lo, unsigned long long &ev_hi,
+                                            const float px, const float py, const float pz, const float w, const float ux, const float uy, const float uz,
+                                            const float ev_ks0, const float ev_apf0, const float ev_sfc, const int ix, const int iy, const int k, const int kind,
+                                            const uint64_t seed, const uint64_t id, const uint32_t draw) {
+    const unsigned long long em = __ballot(emit);
+    if (em != 0ull) {
+        const unsigned n = (unsigned)__popcll(em);
+        if (ev_lo + n > ev_hi) {
+            for (unsigned long long q = ev_lo + (threadIdx.x & 63); q < ev_hi; q += 64)
+                if (q < (unsigned long long)cold->ev_cap) cold->ev_list[ev_list_f4(cold->ev_cap) * xcc + ev_index((unsigned)q)] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            const int leader = __ffsll((long long)em) - 1;
+            unsigned long long base = 0;
+            if ((int)(threadIdx.x & 63) == leader) base = atomicAdd(cold->ev_ctr + xcc * kCtrStride, (unsigned long long)kEvBlock);
+            // (through scalar registers: the reservation is the same in every lane, and as per-lane values ev_lo / ev_hi cost four registers)
+            base = ((unsigned long long)__builtin_amdgcn_readlane((int)(base >> 32), leader) << 32) | (unsigned)__builtin_amdgcn_readlane((int)base, leader);
+            ev_lo = base; ev_hi = base + kEvBlock;
+        }
+        if (emit) {
+            const unsigned long long slot = ev_lo + __builtin_amdgcn_mbcnt_hi((unsigned)(em >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)em, 0u));
+            if (slot < (unsigned long long)cold->ev_cap) {
+                // (plain stores: write-through ones that bypass the XCD's L2, `sc1`, were 10 % slower -- the four 16-byte
+                //  pieces of a record then leave one by one, profiles/r02/mv9_event_stores.log)
+                float4 *lbase = cold->ev_list + ev_list_f4(cold->ev_cap) * xcc;       // (this XCD's list: wave-uniform)
+                float4 *e = lbase + ev_index((unsigned)slot);
+#if MI3D_DIAG_NOEMITSTORE   // (mi3d_diag.h: ablation build, results wrong)
+                MI3D_DIAG_KEEP11(px, py, pz, w, ux, uy, uz, ev_ks0, ev_apf0, ev_sfc, e);
+#elif MI3D_EV_NT_STORE
+                // (written once, read once by another kernel: non-temporal stores, so that 1.1 KB of records per photon do not push the
+                //  voxel records out of the XCD's L2)
+                typedef float vf4 __attribute__((ext_vector_type(4)));
+                vf4 *en = reinterpret_cast<vf4 *>(e);
+                __builtin_nontemporal_store((vf4){px, py, pz, w}, en);
+                __builtin_nontemporal_store((vf4){ux, uy, uz, ev_ks0}, en + kEvStride);
+                __builtin_nontemporal_store((vf4){ev_apf0, ev_sfc, __int_as_float(ix | (iy << 16)), __int_as_float(k | (kind << 16))}, en + 2 * kEvStride);
+                __builtin_nontemporal_store(le_hash_base(seed, id, draw), reinterpret_cast<uint32_t *>(lbase) + ev_word((unsigned)slot));
+#else
+                e[0] = make_float4(px, py, pz, w);
+                e[kEvStride] = make_float4(ux, uy, uz, ev_ks0);
+                e[2 * kEvStride] = make_float4(ev_apf0, ev_sfc, __int_as_float(ix | (iy << 16)), __int_as_float(k | (kind << 16)));
+                reinterpret_cast<uint32_t *>(lbase)[ev_word((unsigned)slot)] = le_hash_base(seed, id, draw);
+#endif
+            } else cold->ev_ctr[8 * kCtrStride] = 1ull;   // list full: the launch is reported as failed (mi3d_run), never silently short
+            emit = false;
+        }
+        ev_lo += n;
+    }
 }
 
 struct PhaseTab {

@@ -80,9 +80,12 @@ __host__ __device__ inline size_t rays_lds_extra(int nz, bool cam = false) {
 // periodic image of the camera --, which travels in a third float4 of its pool record; its value carries 1 / r^2 and the solid angle
 // of its pixel of the polar map, both known where the ray starts.  Every surface model in the one build (four waves per SIMD).
 // PLAIN: the 1-D constituent is Rayleigh, every 3-D one Henyey-Greenstein (kTargetPlainPhase, checked on the host): no selector is looked at
-template <bool COUNT, bool P3D, bool HEAVY, bool CAM = false, bool PLAIN = false>
+// THERM: the camera build of a thermal job (Src_mtype = 3), fed by k_transport<.,2,...>: two more kinds of event, the
+// emission of a volume cell (w / 4 pi, isotropic) and of the surface (w cos / pi, never seen from below); thermal scenes are Lambertian
+template <bool COUNT, bool P3D, bool HEAVY, bool CAM = false, bool PLAIN = false, bool THERM = false>
 __global__ void __launch_bounds__(256, CAM ? 4 : MI3D_RAYS_WAVES(COUNT, HEAVY))
 k_rays(const DevScene S, const uint64_t seed) {
+    static_assert(!THERM || (CAM && !P3D && !HEAVY && !PLAIN), "the thermal build is a camera build");
     constexpr unsigned PF4 = CAM ? 3u : kPoolF4;   // float4 per pool record
     extern __shared__ float4 smem[];
     // (layer table with an end record below the surface and above the top, as in k_transport_lean: no bounds check per level crossing)
@@ -380,7 +383,7 @@ k_rays(const DevScene S, const uint64_t seed) {
                         if (!PLAIN) for (int ip = 1; ip < S.np1d; ++ip) eks1 += Lk.ks1d[ip];     // (every 1-D constituent: the mixture's total)
                         eks3 = (Lk.flags & kLayIn3d) ? E1.w : 0.0f;
                         eksb = 0.0f; eapfb = 0.0f;
-                        if (S.np3d > 1 && (Lk.flags & kLayIn3d) && ((ekk >> 16) & 15) != E_SURFACE) {   // the voxel's second 3-D constituent
+                        if (S.np3d > 1 && (Lk.flags & kLayIn3d) && ((ekk >> 16) & 15) != E_SURFACE && (!THERM || ((ekk >> 16) & 15) == E_SCATTER)) {   // the voxel's second 3-D constituent (THERM: an emission scatters nothing)
                             const float2 cs = cold->csca[((unsigned)((ecell >> 16) * S.nx + (ecell & 0xffff)) * (unsigned)S.nz3 + (unsigned)((ekk & 0xffff) - S.k3lo)) * 2u + 1u];
                             eksb = cs.x; eapfb = cs.y;
                         }
@@ -443,11 +446,13 @@ k_rays(const DevScene S, const uint64_t seed) {
                     const float inv_r2 = frcp(fmaxf(r2, Cm.r2min));
                     // outside the cone of view, a line of sight within 0.06 degrees of the horizontal, the surface seen from below: nothing to carry
                     const bool visible = fimg > 0.0f && r2 > 0.0f && fabsf(vz) >= 1e-3f && -(vx * Cm.zx + vy * Cm.zy + vz * Cm.zz) >= Cm.cos_half &&
-                                         !((kind & 15) == E_SURFACE && vz <= 0.0f);
+                                         !((kind & 15) == E_SURFACE && vz <= 0.0f) && !(THERM && kind == E_EMIT_SFC && vz <= 0.0f);
                     if (visible) {
                         float c;
-                        if ((kind & 15) == E_SURFACE) {
-                            if ((kind >> 4) == MI3D_SFC_LAMBERT) c = E0.w * fminf(fmaxf(E1.w, 0.0f), 1.0f) * vz * (1.0f / kPi);
+                        if (THERM && kind == E_EMIT) c = E0.w * (0.25f / kPi);
+                        else if (THERM && kind == E_EMIT_SFC) c = E0.w * vz * (1.0f / kPi);
+                        else if ((kind & 15) == E_SURFACE) {
+                            if (THERM || (kind >> 4) == MI3D_SFC_LAMBERT) c = E0.w * fminf(fmaxf(E1.w, 0.0f), 1.0f) * vz * (1.0f / kPi);
                             else {   // (LSRT, DSM: this build runs at four waves per SIMD anyway and has the registers)
                                 const Sfc sf = (kind >> 4) == MI3D_SFC_DSM ? load_sfc(S, cold, ecell & 0xffff, ecell >> 16, E0.x, E0.y) : Sfc{kind >> 4, E1.w, eapf, esfc, 0.0f, 0.0f};
                                 c = E0.w * surface_R(sf, E1.x, E1.y, E1.z, vx, vy, vz) * vz * (1.0f / kPi);
@@ -616,6 +621,8 @@ k_rays(const DevScene S, const uint64_t seed) {
 
 template __global__ void k_rays<false, false, false, true>(const DevScene, const uint64_t);
 template __global__ void k_rays<true, false, false, true>(const DevScene, const uint64_t);
+template __global__ void k_rays<false, false, false, true, false, true>(const DevScene, const uint64_t);
+template __global__ void k_rays<true, false, false, true, false, true>(const DevScene, const uint64_t);
 #define MI3D_RAYS_INST(C, P) template __global__ void k_rays<C, P, false, false, false>(const DevScene, const uint64_t); \
                              template __global__ void k_rays<C, P, false, false, true>(const DevScene, const uint64_t);  \
                              template __global__ void k_rays<C, P, true, false, false>(const DevScene, const uint64_t);

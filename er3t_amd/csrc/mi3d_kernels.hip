@@ -773,9 +773,15 @@ __device__ inline void flux_add(const DevScene &S, int ix, int iy, float w, bool
 // photon to the sun instead when the number that picks the emitting cell falls beyond the emitted power, target >= P_tot of
 // P_tot + P_sol: then it starts like a solar build's, direct until its first event (the host switches the analytic direct beam off,
 // S.kdir = nz + 1: every level's direct-down plane is tallied).  Builds 0 and 1 carry none of this.
-template <bool COUNT, bool MARCH, bool FLUX, bool P3D, int SRC>
-__global__ void __launch_bounds__(256, MI3D_WAVES(MARCH, COUNT))
+// MARCHK: 0 no marched view; 1 their local-estimate rays are marched in the photon's own lane (blocks B3, B1); 2 (thermal cameras,
+// DESIGN.md §5.10) block B2 writes an event record per emission, collision and reflection into this XCD's list instead (emit_events, the
+// records k_transport_lean<.,.,2> writes) and the photon goes straight on: k_rays' thermal camera build marches the rays, to every
+// periodic image of the sensors.  Thermal, radiance-only, 3-D solver builds only.
+template <bool COUNT, int MARCHK, bool FLUX, bool P3D, int SRC>
+__global__ void __launch_bounds__(256, MI3D_WAVES(MARCHK, COUNT))
 k_transport(const DevScene S, const uint64_t nphoton, const uint64_t seed, const uint64_t offset, const DevThermal *th) {
+    constexpr bool MARCH = MARCHK == 1, EMIT = MARCHK == 2;
+    static_assert(MARCHK >= 0 && MARCHK <= 2 && (!EMIT || (SRC == 1 && !FLUX && !P3D)), "event records: the thermal radiance builds");
     constexpr bool THERM = SRC != 0, MIX = SRC == 2;
     extern __shared__ float4 smem[];
     const LayerRec *lay = reinterpret_cast<const LayerRec *>(smem);
@@ -860,6 +866,8 @@ k_transport(const DevScene S, const uint64_t nphoton, const uint64_t seed, const
     // again by the marched views and the finish block: another read would queue behind the tally atomic, vmcnt being in order
     float ev_ks0 = 0.0f, ev_apf0 = 0.0f, ev_tab = 0.0f;
     float &ev_sfc = ev_tab; // third surface parameter of a surface event (ev_tab has been consumed when it is written)
+    bool ev_emit = false;                      // EMIT: this lane's event of the current pass is to be written to the event list
+    unsigned long long ev_lo = 0, ev_hi = 0;   // EMIT, wave-uniform: slots of this XCD's list reserved by this wave and not yet used
 
 #ifdef MI3D_CENSUS
 #define MI3D_TICK(slot) do { if (COUNT && (slot) < 3) { const long long t_ = clock64(); cnt.cyc[slot] += (uint32_t)((t_ - tick) >> 6); tick = t_; } } while (0)
@@ -1222,10 +1230,14 @@ k_transport(const DevScene S, const uint64_t nphoton, const uint64_t seed, const
                     iv = 0;
                     mode = M_VIEWS;
                 } else {
+                    if constexpr (EMIT) ev_emit = S.nmarch > 0;
                     mode = M_FINISH;
                 }
             }
         }
+        // (where the whole wave passes: the records of this pass's events, kind E_EMIT / E_EMIT_SFC in the kind bits of an emission, the
+        //  hash of the Philox block index block B3 would hand to the roulettes of the event's rays)
+        if constexpr (EMIT) emit_events(cold, xcc, ev_emit, ev_lo, ev_hi, px, py, pz, w, ux, uy, uz, ev_ks0, ev_apf0, ev_sfc, ix, iy, k, kind, seed, id, draw);
 
         MI3D_TICK(2);
         MI3D_MARK("B3");
@@ -1528,6 +1540,10 @@ k_transport(const DevScene S, const uint64_t nphoton, const uint64_t seed, const
 #undef MI3D_TICK
 #undef EVT
 
+    if constexpr (EMIT) {   // the records this wave reserved and did not use: empty
+        for (unsigned long long q = ev_lo + (threadIdx.x & 63); q < ev_hi; q += 64)
+            if (q < (unsigned long long)S.cold->ev_cap) S.cold->ev_list[ev_list_f4(S.cold->ev_cap) * xcc + ev_index((unsigned)q)] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
     // ---- counters: wave reduction, one atomic per wave and counter
     {
         uint32_t vals[24] = {cnt.photons, cnt.steps, cnt.steps3d, cnt.scatter, cnt.surface, cnt.le_rays,
@@ -1551,5 +1567,8 @@ MI3D_INST(false, false, false) MI3D_INST(false, false, true) MI3D_INST(false, tr
 MI3D_INST(true, false, false) MI3D_INST(true, false, true) MI3D_INST(true, true, false) MI3D_INST(true, true, true)
 #undef MI3D_INST
 #undef MI3D_INST_S
+// the builds that write event records for k_rays' thermal camera build
+template __global__ void k_transport<false, 2, false, false, 1>(const DevScene, const uint64_t, const uint64_t, const uint64_t, const DevThermal *);
+template __global__ void k_transport<true, 2, false, false, 1>(const DevScene, const uint64_t, const uint64_t, const uint64_t, const DevThermal *);
 
 } // namespace mi3d

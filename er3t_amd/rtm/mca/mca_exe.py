@@ -37,6 +37,11 @@ def _check_supported(nml, fdir=None):
         raise OSError('Error [mca_exe]: <Wld_mtarget=%s> is not supported (1: flux, 2: radiance).' % nml.get('Wld_mtarget'))
     if int(nml.get('Wld_mtarget', 1)) == 2 and int(nml.get('Rad_mrkind', 2)) not in (1, 2):
         raise OSError('Error [mca_exe]: <Rad_mrkind=%s> is not supported (1: all-sky camera, 2: satellite sensor).' % nml.get('Rad_mrkind'))
+    if int(nml.get('Wld_mtarget', 1)) == 2 and int(nml.get('Rad_mrkind', 2)) == 1 and nml.get('Rad_nimg') is not None:
+        nimg = float(np.ravel(nml.get('Rad_nimg'))[0])
+        if nimg != int(nimg) or not 0 <= int(nimg) <= 8:
+            raise OSError('Error [mca_exe]: <Rad_nimg=%g> must be an integer from 0 to 8: the domain lengths around the nearest periodic image of a '
+                          'camera within which its images are served (a key of this project).' % nimg)
     mtype = int(nml.get('Src_mtype', 1))
     if mtype == 0:
         raise OSError('Error [mca_exe]: <Src_mtype=0> (local) is not supported: only the solar (1), the solar+thermal (2) or the thermal (3) source.')
@@ -67,7 +72,14 @@ def _check_thermal(nml, fdir):
         raise OSError('Error [mca_exe]: <target=\'heating rate\'> (Flx_mhrt=1) is not supported for a thermal job: absorbed or net is ambiguous there; '
                       '<Flx_mhrt=2> is the NET heating rate (absorbed - emitted).')
     if int(nml.get('Wld_mtarget', 1)) == 2 and int(nml.get('Rad_mrkind', 2)) == 1:
-        raise OSError('Error [mca_exe]: all-sky cameras (<Rad_mrkind=1>) are not supported for a thermal job.')
+        if int(nml.get('Src_mtype', 3)) == 2:       # (the direct sun of its cameras would need a normalisation of its own)
+            raise OSError('Error [mca_exe]: all-sky cameras (<Rad_mrkind=1>) are not supported for a thermal job.')
+        # a thermal all-sky camera or point radiometer: how much of the horizon the cyclic domain's images add decides a
+        # hemispheric longwave reading, so the job file has to say it
+        if nml.get('Rad_nimg') is None:
+            raise OSError('Error [mca_exe]: an all-sky camera or point radiometer (<Rad_mrkind=1>) of a thermal job needs <Rad_nimg>, the number of '
+                          'domain lengths (0 to 8) around the nearest periodic image of a sensor within which its images are served '
+                          '(a key of this project: mcarats_ng(source=\'thermal\', sensor_type=\'all-sky\' | \'irradiance\' | \'actinic\') writes it).')
     if nml.get('Sfc_inpfile') and int(nml.get('Sfc_nxb', 0) or 0) > 0:
         if fdir is not None:
             nxb, nyb = int(nml['Sfc_nxb']), int(nml['Sfc_nyb'])
@@ -82,9 +94,12 @@ def thermal_heating(nml):
     """is this the namelist of a job that several ranks take one by one (run -> all-reduce -> the mi3d_get_* calls) instead of through
     JobRunner.run_batched?  A thermal job with the NET heating rate (Src_mtype = 3, Flx_mhrt = 2): its read-out subtracts the known emission
     (include/mi3d.h: mi3d_get_heating), which JobRunner._normalise does not.  EVERY solar+thermal job (Src_mtype = 2): _normalise scales with
-    Src_flx mu0, a mixed job's photons stand for Src_flx (P_tot + P_sol) / (Lx Ly)"""
+    Src_flx mu0, a mixed job's photons stand for Src_flx (P_tot + P_sol) / (Lx Ly).  A thermal camera or point-radiometer job (Src_mtype = 3,
+    Rad_mrkind = 1): _normalise would scale a camera's tallies with Src_flx mu0 Lx Ly, a thermal photon stands for Src_flx P_tot / N
+    (include/mi3d.h: mi3d_get_radiance)"""
     mtype = int(nml.get('Src_mtype', 1) or 1)
-    return mtype == 2 or (mtype == 3 and int(nml.get('Wld_mtarget', 1)) == 1 and int(nml.get('Flx_mhrt', 0) or 0) == 2)
+    return mtype == 2 or (mtype == 3 and int(nml.get('Wld_mtarget', 1)) == 1 and int(nml.get('Flx_mhrt', 0) or 0) == 2) \
+        or (mtype == 3 and int(nml.get('Wld_mtarget', 1)) == 2 and int(nml.get('Rad_mrkind', 2)) == 1)
 
 
 def wants_rdir(scene):
@@ -282,6 +297,10 @@ class JobRunner:
                 if sc.target & TARGET_HEAT and getattr(sc, 'src_mtype', 1) == 3:
                     raise OSError('Error [mca_exe]: the net heating rate of a thermal job (Flx_mhrt=2) is not served by the batched route (its read-out '
                                   'subtracts the emission: include/mi3d.h, mi3d_get_heating); run such jobs one by one (run_job), as mca_run does.')
+                if sc.target & TARGET_RADIANCE and getattr(sc, 'rad_kind', 2) == 1 and getattr(sc, 'src_mtype', 1) == 3:
+                    raise OSError('Error [mca_exe]: the cameras and point radiometers of a thermal job (Rad_mrkind=1) are not served by the batched route '
+                                  '(a camera\'s tallies are scaled with the emitted power: include/mi3d.h, mi3d_get_radiance); run such jobs one by one '
+                                  '(run_job), as mca_run does.')
                 sizes = (max(sc.nview, 1)*sc.nyr*sc.nxr if sc.target & TARGET_RADIANCE else 0,
                          3*(sc.nz+1)*sc.ny*sc.nx if sc.target & TARGET_FLUX else 0,
                          sc.nz*sc.ny*sc.nx if sc.target & TARGET_HEAT else 0)

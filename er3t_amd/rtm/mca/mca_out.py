@@ -197,7 +197,9 @@ def _from_fused(fused, nvar, squeeze):
 
     """per-run fields gathered on the device by `mcarats_ng(abs_obj=...)`, brought to the file route's shapes"""
 
-    if nvar == 2:       # point radiometers: the run field holds diffuse + direct, the direct part is known per run -> (diffuse, direct)
+    if nvar == 2 and 'rdir' not in fused:      # point radiometers of a thermal job: no sun, the run field is the diffuse part and the direct part 0
+        runs = np.stack([fused['rad']['runs'], np.zeros_like(fused['rad']['runs'])])
+    elif nvar == 2:     # point radiometers: the run field holds diffuse + direct, the direct part is known per run -> (diffuse, direct)
         runs = np.stack([fused['rad']['runs']-fused['rdir']['runs'], fused['rdir']['runs']])
     else:
         runs = fused['flux']['runs'] if nvar == 3 else fused['rad']['runs'][None]      # (nvar, Nz, Ny, Nx, Nr)
@@ -333,7 +335,9 @@ def read_radiometer_mca_out(mca_obj, abs_obj, mode='mean', squeeze=True):
     (the view axis), summed over g, per run ('all') or mean and population standard deviation over runs ('mean').
     keys: f, f_diffuse, f_direct (+ *_std for 'mean'), toa, N_photon, N_run.  The files hold the cosine-weighted (irradiance) or
     plain (actinic) mean radiance over the hemisphere: scattered light as `rad`, the direct sun as `rdir`; the fluxes are pi (irradiance)
-    or 2 pi (actinic flux) times them.
+    or 2 pi (actinic flux) times them.  Thermal object (mcarats_ng(source='thermal'): a pyrgeometer, an IR radiometer): the thermal g-sum,
+    sum_g weight[ig] x_g / 1000 with no solar spectrum and no slit function; `rdir` is 0 -- a thermal job has no sun --, so f_direct = 0
+    and f = f_diffuse.
     """
 
     mode = mode.lower()
@@ -342,7 +346,8 @@ def read_radiometer_mca_out(mca_obj, abs_obj, mode='mean', squeeze=True):
     f_diffuse, f_direct = rad*solid, rdir*solid
     fields = [('f', f_diffuse+f_direct, 'Total'), ('f_diffuse', f_diffuse, 'Diffuse'), ('f_direct', f_direct, 'Direct')]
     what = 'irradiance' if str(mca_obj.sensor_type).lower() == 'irradiance' else 'actinic flux'
-    data = {'toa': {'data': toa, 'name': 'TOA without SZA', 'units': 'W/m^2/nm'}}
+    data = {'toa': {'data': toa, 'name': 'TOA without SZA' + (' (none: thermal source)' if getattr(mca_obj, 'source', 'solar') == 'thermal' else ''),
+                    'units': 'W/m^2/nm'}}
     for key, arr, name in fields:
         if mode == 'all':
             data[key] = {'data': arr, 'name': '%s %s' % (name, what), 'units': 'W/m^2/nm', 'dims_info': dims_info}

@@ -100,6 +100,11 @@ class mcarats_ng:
         heating_estimator ['collision']: target='heating rate' only: 'path' tallies w kappa_a l along every flight segment instead of
                            w kappa_a / beta_t at every collision (Flx_mhest=1, a key of this project written only then:
                            include/mi3d.h, mi3d_set_heating_estimator) -- same variable, same units, far less noise in optically thin cells
+        camera_images [None]: sensor_type 'all-sky' | 'irradiance' | 'actinic': the periodic images of a sensor in the cyclic domain are served
+                           within this many domain lengths of the nearest one, 0 ... 8 (Rad_nimg, a key of this project).  source='thermal'
+                           serves these sensors too (a pyrgeometer, an IR radiometer, a thermal sky imager: DESIGN.md §5.10) and always writes
+                           the key, 2 when None: the clear sky is limb-brightened in the window channels, and the images decide how much of
+                           the horizon a hemispheric sensor sees.  A solar job file carries the key only when a value is given
 
     Afterwards: input and output files under <fdir>; attributes Ng, Nrun, Nx, Ny, dx, dy, date, target, solver,
     photons (Nrun*Ng,), photons_per_set, fnames_inp[ir][ig], fnames_out[ir][ig], nml (list of Ng dictionaries).
@@ -113,7 +118,7 @@ class mcarats_ng:
                  sensor_azimuth_angle=0.0, sensor_altitude=705000.0, sensor_type='satellite', sensor_xpos=0.5,
                  sensor_ypos=0.5, solver='3d', photons=1e7, base_ratio=0.05, verbose=False, quiet=False,
                  abs_obj=None, keep_files=True, source='solar', wavelength=None, surface_temperature=None,
-                 heating_estimator='collision'):
+                 heating_estimator='collision', camera_images=None):
 
         # one process per GPU (torch.distributed): rank 0 writes the job files, all ranks transport their share of every job
         from er3t_amd.dist import world_info, barrier
@@ -143,6 +148,18 @@ class mcarats_ng:
         if self.source not in ('solar', 'thermal', 'solar+thermal'):
             raise OSError('Error [mcarats_ng]: <source=%s> must be \'solar\', \'thermal\' or \'solar+thermal\'.' % source)
         self.wavelength, self.surface_temperature = wavelength, surface_temperature
+        # cameras and point radiometers (sensor_type 'all-sky' | 'irradiance' | 'actinic'): the periodic images of a sensor within this many
+        # domain lengths of the nearest one are served (Rad_nimg, a key of this project)
+        self.point_sensor = str(target).lower() in _TARGETS['radiance'] and \
+            ('all-sky' in str(sensor_type).lower() or str(sensor_type).lower() in _SENSOR_MRPROJ)
+        if camera_images is not None and (isinstance(camera_images, bool) or int(camera_images) != camera_images or not 0 <= int(camera_images) <= 8):
+            raise OSError('Error [mcarats_ng]: <camera_images=%s> must be an integer from 0 to 8 (or None).' % camera_images)
+        if camera_images is not None and not self.point_sensor:
+            raise OSError('Error [mcarats_ng]: <camera_images> belongs to <target=\'radiance\'> with <sensor_type=\'all-sky\' | \'irradiance\' | \'actinic\'>.')
+        if self.point_sensor and self.source == 'solar+thermal':
+            raise OSError('Error [mcarats_ng]: <source=\'solar+thermal\'> with <sensor_type=%r> is not implemented: the direct sun in a camera of a mixed '
+                          'job would need a normalisation of its own; <source=\'thermal\'> and <source=\'solar\'> serve these sensors.' % sensor_type)
+        self.camera_images = None if camera_images is None else int(camera_images)
         self.heating_estimator = str(heating_estimator).lower()
         if self.heating_estimator not in ('collision', 'path'):
             raise OSError('Error [mcarats_ng]: <heating_estimator=%s> must be \'collision\' or \'path\'.' % heating_estimator)
@@ -220,6 +237,10 @@ class mcarats_ng:
                 self._all({'Flx_mhest': 1})
             return
 
+        # (Rad_nimg: a thermal sensor job always says how far its periodic images are served -- 2 unless told otherwise --; a solar job file
+        #  carries the key only when <camera_images> is given, and stays what it was, byte for byte, without)
+        if self.point_sensor and (self.camera_images is not None or self.source == 'thermal'):
+            self._all({'Rad_nimg': 2 if self.camera_images is None else self.camera_images})
         if sensor_type.lower() in _SENSOR_MRPROJ:
             self._init_radiometers(sensor_type.lower(), sensor_zenith_angle, sensor_azimuth_angle, sensor_altitude, sensor_xpos, sensor_ypos)
             return

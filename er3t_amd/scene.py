@@ -351,6 +351,12 @@ class Scene:
                 kw.update(rad_kind=1, cam_xpos=per_view('Rad_xpos', 0.5), cam_ypos=per_view('Rad_ypos', 0.5),
                           cam_psi=per_view('Rad_psi', 0.0), cam_qmax=per_view('Rad_qmax', 180.0), cam_umax=per_view('Rad_umax', 180.0),
                           cam_vmax=per_view('Rad_vmax', 180.0), cam_apsize=per_view('Rad_apsize', 0.0), cam_mpmap=mpmap, cam_mrproj=mrproj)
+                # (a key of this project: the periodic images of a sensor the job asks for; without it the route's default, cam_images = -1)
+                if get('Rad_nimg') is not None:
+                    nimg = float(np.ravel(get('Rad_nimg'))[0])
+                    if nimg != int(nimg) or not 0 <= int(nimg) <= 8:
+                        raise OSError('Error [Scene]: <Rad_nimg=%g> must be an integer from 0 to 8.' % nimg)
+                    kw.update(cam_images=int(nimg))
             elif mrkind != 2:
                 raise OSError('Error [Scene]: <Rad_mrkind=%d> is not supported (1: camera, 2: satellite).' % mrkind)
         elif mtarget == 1:

@@ -167,9 +167,10 @@ int mi3d_set_source(mi3d_solver *h, double flx, double qmax_deg, double the_deg,
  *   mi3d_prepare).  Volume emission is isotropic, surface emission follows the cosine law.
  *   Results: radiance (Rad_mrkind = 2) in W m-2 sr-1 um-1, fluxes in W m-2 um-1 (mi3d_get_radiance / mi3d_get_flux /
  *   mi3d_stats_add: the normalisation is Src_flx P_tot / N in place of Src_flx mu0 Lx Ly / N).  No direct beam: the direct-down
- *   plane is 0 and the analytic direct-beam levels are off.  A thermal job always runs on the general photon loop
- *   (mi3d_last_kernel: "k_transport<...> [thermal]", followed by " [heating: path length]" under that estimator); cameras
- *   (Rad_mrkind = 1): MI3D_EUNSUP.  Under MI3D_SOLVER_P3D every thermal photon stays in its column (no photon is direct).
+ *   plane is 0 and the analytic direct-beam levels are off.  A thermal job runs on the general photon loop
+ *   (mi3d_last_kernel: "k_transport<...> [thermal]", followed by " [heating: path length]" under that estimator); its cameras
+ *   (Rad_mrkind = 1) are served as stated at mi3d_set_cameras, "Thermal cameras".  Under MI3D_SOLVER_P3D every thermal photon stays
+ *   in its column (no photon is direct).
  *   Heating rates (MI3D_TARGET_FLUX | MI3D_TARGET_HEAT, the project's key Flx_mhrt = 2): the NET, absorbed minus emitted --
  *   longwave cooling where negative; see mi3d_get_heating and mi3d_get_emission.  The emission event deposits nothing; the first
  *   flight is tallied from the emission point (path-length estimator: the part of the cell from that point to the first face or
@@ -230,7 +231,31 @@ int mi3d_set_views(mi3d_solver *h, int nview, const double *the_deg, const doubl
  * V = theta sin(phi), the image spanning umax x vmax degrees (Rad_umax, Rad_vmax) in nxr x nyr pixels.  Estimator: every
  * collision and reflection sends w P / (4 pi) exp(-tau) / r^2 (surface: w R cos / pi ...) to the nearest periodic image of
  * the camera, r not counted below apsize metres (Rad_apsize); 3-D solver only.  MCARaTS' own regularisation of the 1/r^2
- * estimator (Rad_difr*, Rad_rmin0 ...) is not in the reference tree and not applied: see DESIGN.md. */
+ * estimator (Rad_difr*, Rad_rmin0 ...) is not in the reference tree and not applied: see DESIGN.md.
+ * Thermal cameras (mi3d_set_thermal 3 with cameras): a pyrgeometer, an up- or down-looking IR radiometer, a thermal
+ * sky imager.  Served: the 3-D solver over Lambertian surfaces (what a thermal job needs anyway), the polar map (all-sky images) and
+ * the rectangular map with Rad_mrproj 0 or 1 (actinic and irradiance radiometers), up to MI3D_MAX_VIEW sensors anywhere in the scene
+ * in any orientation.
+ *   Units      pixel values are absolute mean radiances over the pixel's (weighted) solid angle in W m-2 sr-1 um-1 per unit Src_flx,
+ *              the unit of a thermal satellite view's pixels: mi3d_get_radiance and mi3d_stats_add normalise the tallies with
+ *              src_amp Lx Ly / N, src_amp = Src_flx P_tot / (Lx Ly).
+ *   Estimator  every event of a thermal photon sends its local estimate to every image of every sensor within cam_images domain
+ *              lengths of the nearest one: its emission (a volume cell: w / (4 pi r^2); the surface: w cos(theta) / (pi r^2), never
+ *              seen from below) and every later scattering or Lambertian reflection.  The Russian roulettes on farther images, on
+ *              the optical depth and on the weight are the solar camera's, with the same hashes of (photon id, index of the
+ *              photon's Philox block, view, image): (seed, id) -> contributions is a function whichever kernels serve the job.
+ *   No direct term: a thermal job has no sun.  mi3d_get_camera_direct returns zeros (nothing is marched towards Src_the) and
+ *              mi3d_stats_add adds nothing.
+ *   Route      where the lean loops' limits hold (at most two 3-D constituents, phase tables that fit the LDS, 16-bit cell
+ *              numbers, voxel records below 4 GB, no mi3d_set_kernel 1): builds of the general loop that write an event record per
+ *              emission, collision and reflection, and the thermal camera build of the ray kernel behind them
+ *              (mi3d_last_kernel: "k_transport<C,2,0,0> [thermal] + k_rays"), cam_images -1 standing for 2.  Anything else: the
+ *              general loop with the rays in the photons' lanes ("k_transport<...> [thermal]") serves the NEAREST image alone, as
+ *              for a solar camera: cam_images > 0 is then refused (MI3D_EUNSUP), the default -1 warned about once per handle.
+ *   Solar+thermal jobs (mi3d_set_thermal 2) with cameras: MI3D_EUNSUP from mi3d_run -- their direct sun would need a second
+ *              normalisation.
+ *   The 1 / r^2 of an event inside the medium around a sensor is bounded by the Rad_apsize clamp alone: a sensor inside an
+ *              absorbing layer reads low by the order of ka x apsize x B (what the clamp removes) and its noise is heavy-tailed. */
 int mi3d_set_cameras(mi3d_solver *h, int ncam, const double *the_deg, const double *phi_deg, const double *psi_deg,
                      const double *xpos, const double *ypos, const double *zloc, const double *qmax_deg,
                      const double *umax_deg, const double *vmax_deg, const double *apsize, int nxr, int nyr);
@@ -408,7 +433,7 @@ int mi3d_get_flux(mi3d_solver *h, uint64_t nphoton_total, float *out);
  * mi3d_get_flux adds it by itself; a caller that normalises all-reduced RAW tallies of several jobs at once (one exchange per
  * batch of jobs instead of one per job) takes it from here, job by job. */
 int mi3d_get_direct_levels(mi3d_solver *h, double *out);
-/* The direct sun in the cameras (mi3d_set_cameras, solar source): out[nview][nyr][nxr] in the units of mi3d_get_radiance, known
+/* The direct sun in the cameras (mi3d_set_cameras, solar source; a thermal job has no sun: zeros): out[nview][nyr][nxr] in the units of mi3d_get_radiance, known
  * rather than tallied and so free of noise, for the scene and source set now (worked out once per job by mi3d_prepare, k_cam_direct).
  * The optical depth tau from the camera to the top of the atmosphere is integrated in float64 along the sun's CENTRAL direction
  * through the voxels (cyclic in x and y) and the 1-D layers; Src_qmax is ignored for this term.  Where that direction lies in a

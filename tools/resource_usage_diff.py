@@ -2,7 +2,8 @@
 Compare two register reports of the library (`make -C er3t_amd/csrc report 2> report.log`, -Rpass-analysis=kernel-resource-usage):
 every kernel of the first report must be in the second with every printed figure identical; the kernels only the second one has are
 listed with VGPR / scratch / waves per SIMD / SGPR spill.  (The fifth template argument of k_transport was a bool before the
-solar+thermal source: Lb0E / Lb1E of an older report are read as Li0E / Li1E.)
+solar+thermal source: Lb0E / Lb1E of an older report are read as Li0E / Li1E; the second one a bool and k_rays without its sixth argument
+before the thermal cameras.)
 
     python tools/resource_usage_diff.py parent_report.log new_report.log
 """
@@ -24,7 +25,9 @@ def parse(fn):
 
 
 def norm(name):
-    return re.sub(r'(k_transportILb\dELb\dELb\dELb\dE)Lb(\d)E', r'\1Li\2E', name)
+    name = re.sub(r'(k_transportILb\dELb\dELb\dELb\dE)Lb(\d)E', r'\1Li\2E', name)
+    name = re.sub(r'(k_transportILb\dE)Lb(\d)E', r'\1Li\2E', name)                    # MARCH: a bool before the thermal cameras
+    return re.sub(r'(k_raysILb\dELb\dELb\dELb\dELb\dE)(E)', r'\1Lb0E\2', name)      # THERM: a sixth argument since then
 
 
 def main(parent, new):

@@ -9,8 +9,13 @@ carries the solar share p = P_sol / (P_tot + P_sol).  Legs 'mix_thermal' and 'mi
 the same scene -- the thermal job at 3.75 um, and the solar job sent to the general loop (set_kernel(general=True)) --: with their
 times per photon t_thermal and t_solar a mixed photon should cost p t_solar + (1 - p) t_thermal.
 
+Leg 'cam' (DESIGN.md 5.10): sixteen up-looking irradiance sensors on the ground, a 4 x 4 grid, three rows: cam_images = 2 through the
+event lists and the ray kernel, and cam_images = 0 on that route and on the general loop with the rays in the photons' lanes -- the one
+like-for-like comparison of the two.  Its rows carry the mean reading of the sixteen sensors.
+
     python tools/thermal_rate.py [--photons 5e7] [--reps 3] [--legs radiance,flux,heat,heat_path]
     python tools/thermal_rate.py --legs mix,mix_thermal,mix_solar
+    python tools/thermal_rate.py --legs cam --photons 1e7
 """
 
 import argparse
@@ -35,6 +40,16 @@ def thermal(scene, levels, wl=11.0):
     return dataclasses.replace(scene, src_mtype=3, src_wlen=wl, tmp1d=atm.lev['temperature']['data'], omgp=omgp)
 
 
+def pyrgeometers(scene, images, n=4, z=1.0):
+    """n x n up-looking irradiance sensors z metres above the ground (cameras with the rectangular map, one pixel over the hemisphere)"""
+    g = (np.arange(n)+0.5)/n
+    xp, yp = [list(v.ravel()) for v in np.meshgrid(g, g)]
+    m = n*n
+    return dataclasses.replace(scene, target=TARGET_RADIANCE, rad_kind=1, view_the=[0.0]*m, view_phi=[0.0]*m, view_zloc=[z]*m, cam_xpos=xp,
+                               cam_ypos=yp, cam_psi=[0.0]*m, cam_qmax=[180.0]*m, cam_umax=[90.0]*m, cam_vmax=[180.0]*m, cam_apsize=[0.05]*m,
+                               nxr=1, nyr=1, cam_mpmap=2, cam_mrproj=1, cam_images=images)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--photons', type=float, default=5e7)
@@ -48,9 +63,13 @@ def main():
                              ('les480', dict(nx=480, ny=480, nz3=100, levels=z_levels_config4(), z_top=1.6, seed=20251004), z_levels_config4())):
         from er3t_amd.synth import z_levels_config2
         lev = levels if levels is not None else z_levels_config2()
-        for target in a.legs.split(','):
+        legs = sum([['cam', 'cam0', 'cam0_general'] if t == 'cam' else [t] for t in a.legs.split(',')], [])
+        for target in legs:
             general = False
-            if target in ('mix', 'mix_thermal', 'mix_solar'):
+            if target in ('cam', 'cam0', 'cam0_general'):
+                s = pyrgeometers(thermal(les_scene(target='radiance', **kw), lev), 2 if target == 'cam' else 0)
+                general = target == 'cam0_general'
+            elif target in ('mix', 'mix_thermal', 'mix_solar'):
                 s = thermal(les_scene(target='radiance', **kw), lev, wl=3.75)
                 s = dataclasses.replace(s, src_the=140.0, src_phi=0.0)
                 if target == 'mix':
@@ -85,6 +104,9 @@ def main():
             if s.src_mtype == 2:
                 ptot, psol = sol.source_power()
                 row['solar_share'] = psol/(ptot+psol)
+            if getattr(s, 'rad_kind', 2) == 1:
+                row['cam_images'] = s.cam_images
+                row['f_down_sensor_mean'] = float(np.pi*sol.radiance(n).astype(np.float64).mean())
             if s.target & TARGET_HEAT:                     # (read once: the emission is taken off on the device)
                 h = sol.heating(n)
                 row['net_heating_domain_mean'] = float(h.astype(np.float64).mean())
