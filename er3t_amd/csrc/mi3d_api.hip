@@ -167,8 +167,9 @@ struct mi3d_solver {
     // photon order of a launch (k_bin_*): indices sorted by start tile, the tile of every index (shared by both pre-pass sets), histogram
     DevBuf<uint32_t> d_hist;
     DevBuf<uint16_t> d_tile;
+    size_t bin_lds_set = 0;          // the dynamic LDS k_bin_scatter has been allowed on this handle's device (launch_bins; above 64 KB only)
     // What the pre-pass kernels of a launch write: photon order, tiles' ends (the cursors, which are also the tally window's tile_end) and
-    // entry records (k_entry -> k_transport_lean, 48 bytes per photon).  Set 1: the pre-pass of launch i + 1 runs on a stream of its own
+    // entry records (k_entry -> k_transport_lean, 48 or 32 bytes per photon: entry_form).  Set 1: the pre-pass of launch i + 1 runs on a stream of its own
     // beside the photon loop of launch i (28 registers against the loop's 80 x 6: one more wave per SIMD fits).  release(): the large
     // buffers (set 0's cursor is allocated by mi3d_create)
     struct PreSet {
@@ -188,7 +189,11 @@ struct mi3d_solver {
                                      // -1 (default): 2 where the ray kernel serves the job, the nearest image alone (with a warning) where it cannot
     bool cam_warned = false;         // the warning of that fall-back has been printed for this handle
     bool general_warned = false;     // ... and the one that says a job has landed on the general photon loop without having asked for it
-    int entry_records = 1;           // mi3d_set_tuning "entry_records": 0: new photons are launched inside the photon loop
+    int entry_records = 1;           // mi3d_set_tuning "entry_records": 0: new photons are launched inside the photon loop; 1: entry records, the short
+                                     // form where the launch and the build allow (entry_form); 2: entry records, always the long form
+    int entry_form_run = 0;          // the form of the current run's entry records (kEntryF4, kEntryF4Short; 0: none)
+    int entry_form_last = 0;         // ... of the last launch of the last mi3d_run, and that launch's photons (mi3d_debug_entry)
+    uint64_t entry_n_last = 0;
     // marched views served by k_rays: event lists (one per XCD), their counters and the list of reflections off LSRT / DSM surfaces.  Set 1
     // (round 5): the ray kernel of launch i works through set i & 1 on a stream of its own while the photon loop of launch i + 1 fills the
     // other set -- the tail of either kernel (a tenth of a launch) no longer leaves the chip half empty.  release(): the lists
@@ -258,7 +263,7 @@ struct mi3d_solver {
     int kernel_choice = 0;           // 0: the lean kernels where they apply (marched views through k_rays), 1: always k_transport
                                      // (MI3D_KERNEL=generic); A/B and tests
     int tile_cols = -1;              // tile edge in columns: -1 choose from the scene, 0 no sorting (MI3D_TILE_COLS overrides)
-    uint64_t batch = (uint64_t)1 << 30; // most photons per kernel launch (order and tile buffers hold one launch: 4 GB + 2 GB; entry records 48 B per photon, where half
+    uint64_t batch = (uint64_t)1 << 30; // most photons per kernel launch (order and tile buffers hold one launch: 4 GB + 2 GB; entry records 32 or 48 B per photon, where half
                                         // of the free memory holds them).  Every launch ends with a tail in which the chip runs empty: 2^27 -> 2^29 is worth 2.8 %
                                         // (profiles/r02/launch_batch_size.log), 2^29 -> 2^30 another 1.4 % (profiles/r05/ab_batch_2p30.log)
     DevCold cold_host;               // source of the asynchronous upload in fill_scene: must outlive the call
@@ -797,7 +802,7 @@ int mi3d_create(int device, mi3d_solver **out) {
     { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, device) == hipSuccess && v >= 32768) h->lds_max = v; else (void)hipGetLastError(); }
     int rc;
     if ((rc = h->d_counters.alloc(MI3D_NCOUNTER)) || (rc = h->d_next.alloc(8 * kCtrStride)) ||
-        (rc = h->d_hist.alloc(kMaxTiles)) || (rc = h->pre[0].cursor.alloc(kMaxTiles))) { delete h; return rc; }
+        (rc = h->pre[0].cursor.alloc(kMaxTiles))) { delete h; return rc; }
     HIPCHK(hipMemset(h->d_counters.p, 0, MI3D_NCOUNTER * sizeof(unsigned long long)));
     HIPCHK(hipMemset(h->d_next.p, 0, 8 * kCtrStride * sizeof(unsigned long long)));
     {   // XCDs in use (eight on an MI355X in SPX mode; fewer in CPX / QPX partitions)
@@ -820,7 +825,7 @@ int mi3d_create(int device, mi3d_solver **out) {
     if (const char *e = getenv("MI3D_TALLY_WINDOW")) h->tally_window = atoi(e) ? 1 : 0;
     if (const char *e = getenv("MI3D_TALLY_LISTS")) h->tally_lists = atoi(e) ? 1 : 0;
     if (const char *e = getenv("MI3D_TALLY_RUNS")) h->tally_runs = atoi(e) ? 1 : 0;
-    if (const char *e = getenv("MI3D_ENTRY_RECORDS")) h->entry_records = atoi(e) ? 1 : 0;
+    if (const char *e = getenv("MI3D_ENTRY_RECORDS")) { const int v = atoi(e); h->entry_records = v == 2 ? 2 : (v ? 1 : 0); }
     if (const char *e = getenv("MI3D_OVERLAP_RAYS")) h->overlap_rays = atoi(e) ? 1 : 0;
     if (const char *e = getenv("MI3D_OVERLAP_SORT")) h->overlap_sort = std::max(0, std::min(2, atoi(e)));
     if (const char *e = getenv("MI3D_OVERLAP_PRE")) h->overlap_pre = std::max(0, std::min(2, atoi(e)));
@@ -1309,32 +1314,44 @@ int mi3d_reset(mi3d_solver *h) {
 }
 
 // ---- launchers shared by mi3d_run and its pipelined form -------------------------------------------------------------------
+// The photon order of a launch (mi3d_kernels.hip: k_bin_count, k_bin_scan, k_bin_scatter).  The blocks of the first and the third kernel
+// own the same slabs of the indices; d_hist: [ntile][nblk] counts, then first slots, per tile and block, followed by the tiles' photons [ntile].
 static hipError_t launch_bins(mi3d_solver *h, hipStream_t st, const BinGeom &G, int ntile, uint64_t seed, uint64_t off, uint64_t nb, uint32_t *order, uint32_t *cursor) {
-    hipError_t err = hipMemsetAsync(h->d_hist.p, 0, kMaxTiles * sizeof(uint32_t), st);
-    if (err != hipSuccess) return err;
     const unsigned nblk = (unsigned)std::min<uint64_t>((nb + 4095) / 4096, 4096);
-    hipLaunchKernelGGL(k_bin_count, dim3(nblk), dim3(256), 0, st, G, seed, off, (uint32_t)nb, h->d_tile.p, h->d_hist.p);
-    hipLaunchKernelGGL(k_bin_scan, dim3(1), dim3(256), 0, st, ntile, h->d_hist.p, cursor);
-    const uint32_t slab = (uint32_t)((nb + nblk - 1) / nblk);
-    hipLaunchKernelGGL(k_bin_scatter, dim3(nblk), dim3(256), 0, st, ntile, (uint32_t)nb, slab, h->d_tile.p, cursor, order);
+    const uint32_t slab = (uint32_t)(((nb + nblk - 1) / nblk + 7) / 8 * 8);     // (a multiple of 8: the scatter reads tile[] 16 bytes at a time)
+    uint32_t *bhist = h->d_hist.p, *hist = h->d_hist.p + (size_t)ntile * nblk;
+    const size_t lds = bin_scatter_lds(ntile);
+    if (lds > 65536 && lds > h->bin_lds_set) {     // (above 819 tiles; once per handle and size, not per launch)
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_bin_scatter), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return hipGetLastError();
+        h->bin_lds_set = lds;
+    }
+    hipLaunchKernelGGL(k_bin_count, dim3(nblk), dim3(256), 0, st, G, seed, off, (uint32_t)nb, slab, h->d_tile.p, bhist);
+    hipLaunchKernelGGL(k_bin_scan, dim3((unsigned)ntile), dim3(256), 0, st, (int)nblk, bhist, hist);
+    hipLaunchKernelGGL(k_bin_scatter, dim3(nblk), dim3(256), lds, st, ntile, (uint32_t)nb, slab, h->d_tile.p, bhist, hist, cursor, order);
     return hipGetLastError();
 }
 
 // The photons of a launch up to their first voxel walk (k_entry, mi3d_kernel_lean.hip); one photon per thread: the stream of records
-// leaves at the rate a plain copy reaches.
-static hipError_t launch_entry(mi3d_solver *h, hipStream_t st, const DevScene &S, uint64_t nb, uint64_t seed, uint64_t off, const uint32_t *order, float4 *entry) {
+// leaves at the rate a plain copy reaches.  form: the build that writes long records or the one that writes short ones (entry_form).
+static hipError_t launch_entry(mi3d_solver *h, hipStream_t st, const DevScene &S, int form, uint64_t nb, uint64_t seed, uint64_t off, const uint32_t *order, float4 *entry) {
     const DevCold &C = h->cold_host;
     EntryArgs A;
     A.lay = C.lay;
     A.Lx = C.Lx; A.Ly = C.Ly; A.dx = S.dx; A.dy = S.dy; A.inv_dx = C.inv_dx; A.inv_dy = C.inv_dy; A.inv_nx = C.inv_nx; A.inv_ny = C.inv_ny;
     A.sdx = C.sdx; A.sdy = C.sdy; A.sdz = C.sdz; A.cos_cone = C.cos_cone;
     A.nx = S.nx; A.ny = S.ny; A.nz = S.nz; A.solver = S.solver; A.target = S.target; A.kdir = S.kdir;
-    hipLaunchKernelGGL(k_entry, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, A, nb, seed, off, order, entry);
+    if (form == kEntryF4Short) hipLaunchKernelGGL(k_entry<kEntryF4Short>, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, A, nb, seed, off, order, entry);
+    else hipLaunchKernelGGL(k_entry<kEntryF4>, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, A, nb, seed, off, order, entry);
     return hipGetLastError();
 }
 
+// The builds of the lean loop that read short entry records (mi3d_kernel_lean.hip: k_transport_lean<., ., 0, 0, 256, kEntryF4Short>)
+static bool lean_short_build(bool emit, int mix, int nt) { return !emit && mix == 0 && nt == 256; }
+
 static hipError_t launch_lean(mi3d_solver *h, hipStream_t st, const DevScene &S, bool emit, int mix, int nt, unsigned grid, size_t lds, uint64_t nb, uint64_t seed, uint64_t off) {
     // mix: 0 er3t's default scene, 1 a second 3-D constituent, 2 the general mixture (several 1-D constituents, tables); nt: threads per workgroup
+    // (the build that reads short entry records where the run writes them: entry_form has asked lean_short_build)
+    const bool short_rec = h->entry_form_run == kEntryF4Short && lean_short_build(emit, mix, nt);
     const int v = (h->counting ? 4 : 0) + (h->solver == MI3D_SOLVER_P3D ? 2 : 0) + (emit ? 1 : 0);
 #define MI3D_LEAN_LAUNCH(C, P, M)                                                                                                        \
     do {                                                                                                                                 \
@@ -1351,6 +1368,7 @@ static hipError_t launch_lean(mi3d_solver *h, hipStream_t st, const DevScene &S,
             if (lds > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_transport_lean<C, P, M, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
             hipLaunchKernelGGL((k_transport_lean<C, P, M, 2>), dim3(grid), dim3(256), lds, st, S, nb, seed, off);                         \
         } else if (mix == 1) hipLaunchKernelGGL((k_transport_lean<C, P, M, 1>), dim3(grid), dim3(256), lds, st, S, nb, seed, off);        \
+        else if (short_rec) hipLaunchKernelGGL((k_transport_lean<C, P, 0, 0, 256, kEntryF4Short>), dim3(grid), dim3(256), lds, st, S, nb, seed, off); \
         else hipLaunchKernelGGL((k_transport_lean<C, P, M, 0>), dim3(grid), dim3(256), lds, st, S, nb, seed, off);                        \
     } while (0)
     switch (v) {
@@ -1974,19 +1992,32 @@ static uint64_t size_ev_lists(mi3d_solver *h, uint64_t nphoton, bool two_sets) {
 }
 
 // Entry records (k_entry, mi3d_kernel_lean.hip): the lean loop's builds without rays inside them take new photons where their
-// first voxel walk begins.  48 bytes per photon of a launch, never more than half of the memory that is free: without them
-// (no room, "entry_records" 0) the photons are launched inside the loop as before.  Points cold_host at the records.
+// first voxel walk begins.  48 bytes per photon of a launch (32 in the short form), never more than half of the memory that is free:
+// without them (no room, "entry_records" 0) the photons are launched inside the loop as before.  Points cold_host at the records and
+// notes their form in h->entry_form_run.
+// The form (mi3d_device.h): short where direction and pz are the same for every photon of the launch and the loop's build can do
+// without them -- a solar source without a cone from above, served by the column-view build of er3t's default scene
+// (lean_short_build; MIX 0 is never run in workgroups of 512) -- unless "entry_records" 2 asks for the long form everywhere.
+static int entry_form(const mi3d_solver *h, const RunPlan &plan) {
+    const DevCold &C = h->cold_host;
+    const bool launch_ok = C.cos_cone >= 1.0f && C.sdz < 0.0f && !plan.thermal && !h->thermal();
+    const bool build_ok = plan.loop == Loop::Column && lean_short_build(false, plan.mix_lean, 256);
+    return (h->entry_records == 1 && launch_ok && build_ok) ? kEntryF4Short : kEntryF4;
+}
+
 static bool use_entry_records(mi3d_solver *h, const RunPlan &plan, uint64_t nphoton) {
+    h->entry_form_run = 0;
 #if MI3D_LEAN_FAST
     // (the path-length estimator of the heating rates tallies the first flight too: its photons are launched inside the loop)
     if ((h->target & MI3D_TARGET_HEAT) && h->heat_estimator == 1) return false;
     if (plan.loop == Loop::General || plan.thermal || !h->entry_records || h->nx >= 65536 || h->ny >= 65536 || h->nz >= 32768) return false;
     DevBuf<float4> &E = h->pre[0].entry;
-    const size_t need = entry_f4((size_t)std::min<uint64_t>(nphoton, h->batch));
+    const int form = entry_form(h, plan);
+    const size_t need = entry_f4((size_t)std::min<uint64_t>(nphoton, h->batch), form);
     size_t free_b = free_bytes((size_t)8 << 30);
     free_b += E.cap * sizeof(float4);
     if (need > E.cap && need * sizeof(float4) > free_b / 2) return false;
-    if (E.alloc(need) == MI3D_OK) { h->cold_host.entry = E.p; return true; }
+    if (E.alloc(need) == MI3D_OK) { h->cold_host.entry = E.p; h->entry_form_run = form; return true; }
     (void)hipGetLastError();
 #endif
     return false;
@@ -2215,7 +2246,7 @@ static hipError_t launch_pre(mi3d_solver *h, const RunPlan &plan, int pset, bool
     if (eb == hipSuccess && pre_two && h->pre_main_used) { eb = hipStreamWaitEvent(ps, h->pre_main, 0); h->pre_main_used = false; }
     if (eb == hipSuccess && plan.sorted) eb = launch_bins(h, ps, plan.G, plan.ntile, seed, off, nb, PS.order.p, PS.cursor.p);
     if (eb == hipSuccess && use_entry)   // the photons of this launch up to their first voxel walk
-        eb = launch_entry(h, ps, S, nb, seed, off, plan.sorted ? (const uint32_t *)PS.order.p : (const uint32_t *)nullptr, PS.entry.p);
+        eb = launch_entry(h, ps, S, h->entry_form_run, nb, seed, off, plan.sorted ? (const uint32_t *)PS.order.p : (const uint32_t *)nullptr, PS.entry.p);
     if (eb == hipSuccess && pre_two) eb = hipEventRecord(PS.done, ps);
     if (eb == hipSuccess && pre_track && !pre_two) {
         if (!h->pre_main) eb = hipEventCreateWithFlags(&h->pre_main, hipEventDisableTiming);
@@ -2248,12 +2279,14 @@ int mi3d_run(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_of
         if (nvox > lim || (double)h->flux_elems() > lim || (double)h->rad_elems() > lim || (double)h->heat_elems() > lim)
             return fail(MI3D_EUNSUP, "grid too large for the 32-bit table indices of the transport kernel");
     }
+    h->entry_form_last = 0;
     DevScene S;
     if ((rc = fill_scene(h, S))) return rc;
     RunPlan plan = plan_run(h, nphoton);
     if (plan.sorted) {
         const size_t cap = (size_t)std::min<uint64_t>(nphoton, h->batch);
-        if ((rc = h->pre[0].order.alloc(cap)) || (rc = h->d_tile.alloc(cap))) return rc;
+        const size_t nblk = std::min<size_t>((cap + 4095) / 4096, 4096);     // (launch_bins: counts per tile and block, and per tile)
+        if ((rc = h->pre[0].order.alloc(cap)) || (rc = h->d_tile.alloc(cap)) || (rc = h->d_hist.alloc((size_t)plan.ntile * (nblk + 1)))) return rc;
     }
     h->cold_host.order = plan.sorted ? h->pre[0].order.p : nullptr;
 
@@ -2317,6 +2350,7 @@ int mi3d_run(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_of
         else if (err == hipSuccess) err = launch_column(h, plan, Sl, set, two_sets, rs, grid, nb, seed, off);
         if (err == hipSuccess && !run_timed) err = hipEventRecord(e1, h->stream);
         h->pre_last = pset;
+        h->entry_form_last = use_entry ? h->entry_form_run : 0; h->entry_n_last = nb;
         if (err == hipSuccess && (pre_two || pre_track)) {   // (the set may be written again once this launch's photon loop is through it)
             if (!PS.loop) err = hipEventCreateWithFlags(&PS.loop, hipEventDisableTiming);
             if (err == hipSuccess) err = hipEventRecord(PS.loop, h->stream);
@@ -2446,7 +2480,7 @@ int mi3d_set_tuning(mi3d_solver *h, const char *key, int value) {
     else if (k == "tl_split") { if (value < 1 || value > 64) return fail(MI3D_EINVAL, "tl_split=%d outside [1,64]", value); h->tl_split = value; }
     else if (k == "rays_wg" || k == "emit_wg") { if (value < 0 || value > 8) return fail(MI3D_EINVAL, "%s=%d outside [0,8]", key, value); (k == "rays_wg" ? h->rays_wg : h->emit_wg) = value; }
     else if (k == "cam_images") { if (value < -1 || value > 8) return fail(MI3D_EINVAL, "cam_images=%d outside [-1,8]", value); h->cam_images = value; }
-    else if (k == "entry_records") { HIPCHK(sync_main(h)); h->entry_records = value ? 1 : 0; if (!value) h->pre[0].entry.release(); }
+    else if (k == "entry_records") { if (value < 0 || value > 2) return fail(MI3D_EINVAL, "entry_records=%d outside [0,2]", value); HIPCHK(sync_main(h)); h->entry_records = value; if (!value) h->pre[0].entry.release(); }
     else if (k == "tally_runs") { HIPCHK(sync_main(h)); h->tally_runs = value ? 1 : 0; h->tl_per_photon = 0.0; h->tl_total_pp = 0.0; h->tl_runs_pp = 0.0; if (!value) for (auto &T : h->tl) T.runs.release(); }
     else if (k == "tally_lists") { HIPCHK(sync_main(h)); h->tally_lists = value ? 1 : 0; if (!value) for (auto &T : h->tl) T.release(); }
     else if (k == "own_stream") {
@@ -2802,6 +2836,21 @@ int mi3d_debug_order(mi3d_solver *h, uint64_t n, uint32_t *order_out, uint32_t *
     if (tile_end_out && ntile_max > 0)
         HIPCHK(hipMemcpy(tile_end_out, h->pre[h->pre_last].cursor.p, (size_t)std::min(ntile_max, kMaxTiles) * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return MI3D_OK;
+}
+
+int mi3d_debug_entry(mi3d_solver *h, uint64_t n, float *records_out) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    const int form = h->entry_form_last;
+    const mi3d_solver::PreSet &PS = h->pre[h->pre_last];
+    if (form == 0 || !PS.entry.p) return fail(MI3D_ESTATE, "the last launch had no entry records (mi3d_debug_entry)");
+    if (n > 0) {
+        if (!records_out) return fail(MI3D_EINVAL, "bad arguments to mi3d_debug_entry");
+        if (n > h->entry_n_last || entry_f4((size_t)n, form) > PS.entry.cap) return fail(MI3D_EINVAL, "mi3d_debug_entry: the last launch had %llu photons, not %llu", (unsigned long long)h->entry_n_last, (unsigned long long)n);
+        HIPCHK(sync_streams(h));
+        HIPCHK(hipMemcpy(records_out, PS.entry.p, entry_f4((size_t)n, form) * sizeof(float4), hipMemcpyDeviceToHost));
+    }
+    return form;
 }
 
 int mi3d_debug_thermal(mi3d_solver *h, double *ptot, double *cdf_out, uint64_t n) {

@@ -151,9 +151,16 @@ constexpr int kWin = 64;          // edge of the tally window in pixels (kWin * 
 //   [2] u2, u3, ix | iy<<16, k | mode<<16 | ran<<31      cell; M_FLY: ready to walk (ran: a run of uniform layers was crossed on the way),
 //                                                        M_UNIF: still at the top of the atmosphere (the rare ways a first flight ends)
 // In blocks of 64 records, part by part, like the event records: lanes with consecutive places read consecutive 16-byte pieces.
-constexpr int kEntryF4 = 3;
-__host__ __device__ inline size_t entry_f4(size_t n) { return ((n + 63) / 64) * 64 * (size_t)kEntryF4; }
-__host__ __device__ inline unsigned entry_index(unsigned pos) { return (pos >> 6) * (64u * (unsigned)kEntryF4) + (pos & 63u); }
+// The SHORT form (round 11), 32 bytes, for the launches in which a third of that is the same for every photon -- no solar cone
+// (cos_cone >= 1: rotate_dir is not called, the direction is the launch's sdx, sdy, sdz) and the sun from above (sdz < 0: a photon
+// that has not run stands at the top of layer nz - 1, one that has run downward at the top of layer knew = k: pz = lay[k].dz) --:
+//   [0] px, py, rem, u1
+//   [1] u2, u3, ix | iy<<16, k | mode<<16 | ran<<31
+// in the same blocks of 64 with two parts instead of three.  The loop's build knows the form at compile time (k_transport_lean's EF)
+// and takes direction and pz from the tables it holds in LDS; mi3d_api.hip chooses the build (entry_form).
+constexpr int kEntryF4 = 3, kEntryF4Short = 2;      // float4 parts of a record: the long form, the short form
+__host__ __device__ inline size_t entry_f4(size_t n, int form = kEntryF4) { return ((n + 63) / 64) * 64 * (size_t)form; }
+__host__ __device__ inline unsigned entry_index(unsigned pos, int form = kEntryF4) { return (pos >> 6) * (64u * (unsigned)form) + (pos & 63u); }
 // Event record (k_transport_lean<.,.,2> -> k_rays): a collision or surface reflection whose marched views are still to be served,
 // 52 bytes:
 //   [0] px, py, pz, w          position inside the voxel, weight after the event

@@ -25,7 +25,8 @@
 //      history and the next photon -- in the shared blocks B0 ... B7 of rounds 1-3, every MI3D_LEAN_FAST_PASS-th pass only (a pass
 //      with no collision pending is always such a full pass).  Ordered so that a history that ends in a full pass is replaced in
 //      the same pass, and new photons arrive as ENTRY RECORDS (k_entry below: launch, solar-cone jitter, first free path and the
-//      uniform layers above the clouds worked out in a kernel of its own where every lane has a photon): B4 reads 48 bytes and B7
+//      uniform layers above the clouds worked out in a kernel of its own where every lane has a photon): B4 reads 48 bytes (32 in the
+//      builds for short records, EF below) and B7
 //      sets up the first walk.
 // A lane's mode says what it waits for; there is no other bookkeeping between the blocks.
 #include "mi3d_device.h"
@@ -103,7 +104,9 @@ constexpr int M_DRAWR = 15;   // needs a Philox block for its roulette (M_DRAW h
 constexpr int M_DRAWL = 16;   // ... for its launch (no entry records)
 constexpr int M_ENTRY = 17;   // inside B4 only: the lane has asked for its entry record; ix and k hold the record's two packed words
 
-template <bool COUNT, bool P3D, int MARCH, int MIX, int NT = 256>
+// EF:  the form of the entry records B4 reads (mi3d_device.h): kEntryF4 the long one, kEntryF4Short the short one -- a property of the build,
+//      chosen by the host as MIX is (a run-time test of it inside B4 cost 0.8 %: profiles/r04/ab_entry_records_32_bytes_tried.log)
+template <bool COUNT, bool P3D, int MARCH, int MIX, int NT = 256, int EF = kEntryF4>
 #ifndef MI3D_LEAN_REG_WAVES
 #define MI3D_LEAN_REG_WAVES(COUNT, MARCH) MI3D_LEAN_WAVES(COUNT, MARCH)
 #endif
@@ -116,6 +119,7 @@ __global__ void __launch_bounds__(NT, (MIX >= 2 && NT == 256 && MARCH == 0 && !C
 k_transport_lean(const DevScene S, const uint64_t nphoton, const uint64_t seed, const uint64_t offset) {
     static_assert(MARCH == 0 || MARCH == 2, "marched views go through event records and k_rays");
     static_assert(MIX >= 0 && MIX <= 3 && (NT == 256 || NT == 512), "builds");
+    static_assert(EF == kEntryF4 || (EF == kEntryF4Short && MARCH == 0), "the event-writing builds read long entry records");
     // MIX 3 (round 6): the general mixture's COMMON scene known at compile time -- ONE 1-D constituent, Rayleigh (er3t's mca_atm_1d), and one
     // 3-D constituent whose selectors may name tables (the Mie branch as mca_atm.py:275-277 would write it): no loop over constituents, no second
     // voxel constituent, no run-time flags for either in the registers (+3 % on les128_mie over the same code with the flags read at run time)
@@ -264,6 +268,7 @@ k_transport_lean(const DevScene S, const uint64_t nphoton, const uint64_t seed, 
         const unsigned cell_ = (unsigned)ix, km_ = (unsigned)k;                                                      \
         ix = (int)(cell_ & 0xffffu); iy = (int)(cell_ >> 16);                                                        \
         k = (int)(km_ & 0xffffu);                                                                                    \
+        if (EF == kEntryF4Short) pz = lay[k].dz;    /* (short records: the top of the layer the photon stands in) */ \
         mode = ((km_ >> 16) & 0x7fffu) == (unsigned)M_FLY ? M_SETUP : M_UNIF;                                        \
         if (COUNT && (km_ >> 31)) cnt.steps++;      /* (the run of uniform layers k_entry has crossed) */            \
     } while (0)
@@ -761,15 +766,24 @@ k_transport_lean(const DevScene S, const uint64_t nphoton, const uint64_t seed, 
                 if (entry) {
                     // entry_index(pool_next + rank): the 64-lane block pool_next lies in from the scalar unit, the rest per lane
                     const unsigned j = (pool_next & 63u) + rank;
-                    const float4 *eb = entry + (size_t)(pool_next >> 6) * (size_t)(64 * kEntryF4);
-                    const unsigned eo = ((j >> 6) * (unsigned)(64 * kEntryF4) + (j & 63u)) * 16u;
-                    const float4 q0 = glb_load_f4<MI3D_ENTRY_NT_LOAD != 0>(eb, eo), q1 = glb_load_f4<MI3D_ENTRY_NT_LOAD != 0>(eb, eo + 1024u), q2 = glb_load_f4<MI3D_ENTRY_NT_LOAD != 0>(eb, eo + 2048u);
-                    px = q0.x; py = q0.y; pz = q0.z; rem = q0.w;
-                    ux = q1.x; uy = q1.y; uz = q1.z; u1 = q1.w;
-                    u2 = q2.x; u3 = q2.y;
+                    const float4 *eb = entry + (size_t)(pool_next >> 6) * (size_t)(64 * EF);
+                    const unsigned eo = ((j >> 6) * (unsigned)(64 * EF) + (j & 63u)) * 16u;
                     // (the two packed words wait in ix and k until the window has been looked after: unpacking them here would make the
                     //  wave wait for the record at once, and it comes from HBM)
-                    ix = __float_as_int(q2.z); k = __float_as_int(q2.w);
+                    if (EF == kEntryF4Short) {
+                        // short records: the direction is the launch's (no solar cone) and pz follows from k where the words are unpacked
+                        const float4 q0 = glb_load_f4<MI3D_ENTRY_NT_LOAD != 0>(eb, eo), q1 = glb_load_f4<MI3D_ENTRY_NT_LOAD != 0>(eb, eo + 1024u);
+                        px = q0.x; py = q0.y; rem = q0.z; u1 = q0.w;
+                        u2 = q1.x; u3 = q1.y;
+                        ix = __float_as_int(q1.z); k = __float_as_int(q1.w);
+                        ux = cold->sdx; uy = cold->sdy; uz = cold->sdz;
+                    } else {
+                        const float4 q0 = glb_load_f4<MI3D_ENTRY_NT_LOAD != 0>(eb, eo), q1 = glb_load_f4<MI3D_ENTRY_NT_LOAD != 0>(eb, eo + 1024u), q2 = glb_load_f4<MI3D_ENTRY_NT_LOAD != 0>(eb, eo + 2048u);
+                        px = q0.x; py = q0.y; pz = q0.z; rem = q0.w;
+                        ux = q1.x; uy = q1.y; uz = q1.z; u1 = q1.w;
+                        u2 = q2.x; u3 = q2.y;
+                        ix = __float_as_int(q2.z); k = __float_as_int(q2.w);
+                    }
                     mode = M_ENTRY;
                     w = 1.0f; direct = true; draw = 2;
                     kind = E_LAUNCH;
@@ -900,8 +914,12 @@ k_transport_lean(const DevScene S, const uint64_t nphoton, const uint64_t seed, 
 
 #ifdef MI3D_ONLY_HEADLINE    // (a quick listing of the headline build alone: tools/quick_listing.sh)
 template __global__ void k_transport_lean<false, false, 0, 0>(const DevScene, const uint64_t, const uint64_t, const uint64_t);
+template __global__ void k_transport_lean<false, false, 0, 0, 256, kEntryF4Short>(const DevScene, const uint64_t, const uint64_t, const uint64_t);
 #else
+// (short entry records: the column-view build of er3t's default scene, MIX 0 -- the headline's -- alone; a second 3-D constituent and the
+//  general mixtures read long records)
 #define MI3D_LEAN_INST(C, P) template __global__ void k_transport_lean<C, P, 0, 0>(const DevScene, const uint64_t, const uint64_t, const uint64_t); \
+                             template __global__ void k_transport_lean<C, P, 0, 0, 256, kEntryF4Short>(const DevScene, const uint64_t, const uint64_t, const uint64_t); \
                              template __global__ void k_transport_lean<C, P, 2, 0>(const DevScene, const uint64_t, const uint64_t, const uint64_t); \
                              template __global__ void k_transport_lean<C, P, 0, 1>(const DevScene, const uint64_t, const uint64_t, const uint64_t); \
                              template __global__ void k_transport_lean<C, P, 2, 1>(const DevScene, const uint64_t, const uint64_t, const uint64_t); \
@@ -933,6 +951,9 @@ struct EntryArgs {
 // (one photon per thread, no loop over photons: 28 registers.  Running it and the photon order of launch i + 1 on a second stream
 //  beside the photon loop of launch i was tried in round 4 -- they do run side by side then, and the loop loses more than the
 //  pre-pass takes alone: profiles/r04/prepass_beside_the_photon_loop_tried.log, tools/experiments/prepass_overlap.patch)
+// EF: the form of the records.  The short build stores the same values as the long one, computed by the same operations in the same
+// order, less the direction and pz (the launch has no solar cone: no rotate_dir in it; the host has checked, mi3d_api.hip: entry_form).
+template <int EF>
 __global__ void __launch_bounds__(256)
 k_entry(const EntryArgs A, const uint64_t nphoton, const uint64_t seed, const uint64_t offset, const uint32_t *__restrict__ order, float4 *__restrict__ entry) {
     const LayerRec *lay = A.lay;
@@ -956,7 +977,7 @@ k_entry(const EntryArgs A, const uint64_t nphoton, const uint64_t seed, const ui
         float ux = A.sdx, uy = A.sdy, uz = A.sdz;
         const float mu_cone = 1.0f - r2 * (1.0f - A.cos_cone);
         // ---- B5, the launch
-        if (!(A.cos_cone >= 1.0f)) rotate_dir(ux, uy, uz, mu_cone, r3);
+        if (EF != kEntryF4Short && !(A.cos_cone >= 1.0f)) rotate_dir(ux, uy, uz, mu_cone, r3);
         // ---- B6, the first flight
         draw4_fast(seed, id, 1u, r0, r1, r2, r3);
         float rem = -0.69314718f * __builtin_amdgcn_logf(r0);
@@ -991,11 +1012,19 @@ k_entry(const EntryArgs A, const uint64_t nphoton, const uint64_t seed, const ui
         }
         // (written once, read once by another kernel: non-temporal stores -- a streaming write of 24 GB per 5e8 photons)
         typedef float vf4 __attribute__((ext_vector_type(4)));
-        vf4 *e = reinterpret_cast<vf4 *>(entry) + entry_index(i);
-        __builtin_nontemporal_store((vf4){px, py, pz, rem}, e);
-        __builtin_nontemporal_store((vf4){ux, uy, uz, r1}, e + 64);
-        __builtin_nontemporal_store((vf4){r2, r3, __uint_as_float((unsigned)ix | ((unsigned)iy << 16)), __uint_as_float((unsigned)k | ((unsigned)mode << 16) | (ran << 31))}, e + 128);
+        vf4 *e = reinterpret_cast<vf4 *>(entry) + entry_index(i, EF);
+        const float cell = __uint_as_float((unsigned)ix | ((unsigned)iy << 16)), km = __uint_as_float((unsigned)k | ((unsigned)mode << 16) | (ran << 31));
+        if (EF == kEntryF4Short) {
+            __builtin_nontemporal_store((vf4){px, py, rem, r1}, e);
+            __builtin_nontemporal_store((vf4){r2, r3, cell, km}, e + 64);
+        } else {
+            __builtin_nontemporal_store((vf4){px, py, pz, rem}, e);
+            __builtin_nontemporal_store((vf4){ux, uy, uz, r1}, e + 64);
+            __builtin_nontemporal_store((vf4){r2, r3, cell, km}, e + 128);
+        }
     }
 }
+template __global__ void k_entry<kEntryF4>(const EntryArgs, const uint64_t, const uint64_t, const uint64_t, const uint32_t *__restrict__, float4 *__restrict__);
+template __global__ void k_entry<kEntryF4Short>(const EntryArgs, const uint64_t, const uint64_t, const uint64_t, const uint32_t *__restrict__, float4 *__restrict__);
 
 } // namespace mi3d

@@ -364,112 +364,157 @@ __device__ inline int launch_tile(const BinGeom G, uint64_t seed, uint64_t id) {
     return ty * G.ntx + ((ty & 1) ? G.ntx - 1 - tx : tx);   // boustrophedon: consecutive tiles are neighbours
 }
 
-// pass 1: tile of every photon index (kept, 2 bytes each) and the histogram over tiles
+// (Round 11) The sort leaves the same order whenever it is given the same launch: every block of passes 1 and 3 owns one contiguous slab
+// of the indices, a block's first slot in every tile follows from the counts of the blocks before it (pass 2), and inside a block the
+// place of an index follows from its chunk, its wave and its rank among the wave's indices of its tile -- a returning LDS atomic on a
+// counter of the wave's own, which the LDS serves in the wave's program order.  No atomic on global memory is left in the sort.
+
+// pass 1: tile of every photon index (kept, 2 bytes each) and the histogram over tiles of every block's slab, bhist[tile][block]
+// (round 11: the slabs are those of pass 3, which no longer counts them again -- that was a pass over tile[] with one 2-byte read in
+// flight per thread)
 __global__ void __launch_bounds__(256)
-k_bin_count(const BinGeom G, uint64_t seed, uint64_t offset, uint32_t n, uint16_t *tile, uint32_t *hist) {
+k_bin_count(const BinGeom G, uint64_t seed, uint64_t offset, uint32_t n, uint32_t slab, uint16_t *tile, uint32_t *bhist) {
     __shared__ uint32_t lh[kMaxTiles];
     const int nt = G.ntx * G.nty;
     for (int i = threadIdx.x; i < nt; i += blockDim.x) lh[i] = 0u;
     __syncthreads();
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const uint32_t lo = min(n, blockIdx.x * slab), hi = min(n, lo + slab);
+    for (uint32_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
         const int t = launch_tile(G, seed, offset + i);
         tile[i] = (uint16_t)t;
         atomicAdd(&lh[t], 1u);
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < nt; i += blockDim.x)
-        if (lh[i]) atomicAdd(&hist[i], lh[i]);
+    for (int i = threadIdx.x; i < nt; i += blockDim.x) bhist[(size_t)i * gridDim.x + blockIdx.x] = lh[i];
 }
 
-// pass 2 (one block): exclusive scan of the histogram -> where each tile's piece of the order begins.  256 threads, four tiles
-// each: one wave per SIMD (a block of 1024 threads finds no room on a compute unit while workgroups of a photon loop are resident).
-__global__ void __launch_bounds__(256)
-k_bin_scan(int nt, const uint32_t *hist, uint32_t *cursor) {
-    static_assert(kMaxTiles == 4 * 256, "four tiles per thread");
-    __shared__ uint32_t s[256];
-    const int t = threadIdx.x;
-    uint32_t h[4], sum = 0u;
-    for (int j = 0; j < 4; ++j) { h[j] = 4 * t + j < nt ? hist[4 * t + j] : 0u; sum += h[j]; }
-    s[t] = sum;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        const uint32_t v = t >= off ? s[t - off] : 0u;
-        __syncthreads();
-        s[t] += v;
-        __syncthreads();
-    }
-    uint32_t run = s[t] - sum;
-    for (int j = 0; j < 4; ++j) { if (4 * t + j < nt) cursor[4 * t + j] = run; run += h[j]; }
-}
-
-// pass 3: every block takes a contiguous slab of indices and reserves room for it in each tile's piece (one returning atomic per
-// tile and block); then, 4096 indices at a time, a counting sort INSIDE LDS -- counts per tile, scan, places -- and the sorted chunk is
-// copied out, the indices of a tile as one contiguous run.  (Written straight to their places the indices went out as 4-byte stores
-// to as many regions as there are tiles: 1.2 ms per 5e8 indices over 64 tiles, 3.5 ms over 100.)  The cursors end up as the tiles' ENDS
-// in the order: the lean loop's tally window reads them (DevCold::tile_end).
-constexpr int kScatterR = 16;   // indices per thread and chunk
-__global__ void __launch_bounds__(256)
-k_bin_scatter(int nt, uint32_t n, uint32_t slab, const uint16_t *tile, uint32_t *cursor, uint32_t *order) {
-    constexpr int NT = 256, CH = NT * kScatterR;
-    __shared__ uint32_t lcount[kMaxTiles], lstart[kMaxTiles], gbase[kMaxTiles], part[NT / 64];
-    __shared__ uint32_t sidx[CH];
-    __shared__ uint16_t stile[CH];
+// exclusive scan over the 256 threads of a block (inside the wave by shuffles, across the waves through LDS): returns what the threads
+// before this one hold, *total what all hold.  Every thread of the block calls it; part: 4 words of LDS, free again after the call.
+__device__ inline uint32_t block_scan_256(uint32_t sum, uint32_t *part, uint32_t *total) {
     const unsigned tid = threadIdx.x;
-    for (int i = tid; i < nt; i += NT) lcount[i] = 0u;
+    uint32_t incl = sum;
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t x = __shfl_up(incl, off, 64);
+        if ((tid & 63u) >= (unsigned)off) incl += x;
+    }
+    __syncthreads();      // (the words of the call before have been read)
+    if ((tid & 63u) == 63u) part[tid >> 6] = incl;
     __syncthreads();
-    const uint32_t lo = blockIdx.x * slab, hi = min(n, lo + slab);
-    for (uint32_t i = lo + tid; i < hi; i += NT) atomicAdd(&lcount[tile[i]], 1u);
-    __syncthreads();
-    for (int i = tid; i < nt; i += NT) gbase[i] = lcount[i] ? atomicAdd(&cursor[i], lcount[i]) : 0u;   // the slab's first slot in that tile
-    // (every thread owns `per` consecutive tiles: it zeroes, scans and moves on the counters of those)
+    uint32_t before = 0, all = 0;
+    for (unsigned wv = 0; wv < 4u; ++wv) { const uint32_t x = part[wv]; all += x; if (wv < (tid >> 6)) before += x; }
+    *total = all;
+    return before + incl - sum;
+}
+
+// pass 2 (one block per tile): exclusive scan of the tile's counts over the blocks, in place -> bhist[tile][block] is the block's first
+// slot inside the tile's piece of the order; hist[tile]: the tile's photons.  At most 4096 blocks: 16 consecutive counts per thread.
+__global__ void __launch_bounds__(256)
+k_bin_scan(int nblk, uint32_t *bhist, uint32_t *hist) {
+    __shared__ uint32_t part[4];
+    uint32_t *row = bhist + (size_t)blockIdx.x * nblk;
+    const int per = (nblk + 255) / 256;
+    const int lo = min((int)threadIdx.x * per, nblk), hi = min(lo + per, nblk);
+    uint32_t sum = 0u, total;
+    for (int i = lo; i < hi; ++i) sum += row[i];
+    uint32_t run = block_scan_256(sum, part, &total);
+    for (int i = lo; i < hi; ++i) { const uint32_t c = row[i]; row[i] = run; run += c; }
+    if (threadIdx.x == 0) hist[blockIdx.x] = total;
+}
+
+// pass 3: every block takes its slab of indices, whose first slot in each tile's piece pass 2 has left (no pass over tile[] to count,
+// no atomic on global memory); then, kScatterCH indices at a time, a counting sort INSIDE LDS -- a returning atomic per index on its
+// WAVE's counter of the tile gives its rank among the wave's indices of that tile in the chunk, a scan of the counts the places of the
+// tiles and of the waves inside them -- and the sorted chunk is copied out, the indices of a tile as one contiguous run.  (Written
+// straight to their places the indices went out as 4-byte stores to as many regions as there are tiles: 1.2 ms per 5e8 indices over 64
+// tiles, 3.5 ms over 100.)  The sorted chunk is held as 16-bit offsets into the chunk: 8192 indices in the LDS that 4096 32-bit indices
+// took, five barriers a chunk where there were six per 4096, and runs twice as long.  Block 0 leaves the tiles' ENDS in the order in the
+// cursors: the lean loop's tally window reads them (DevCold::tile_end).
+// Dynamic LDS (bin_scatter_lds): the waves' counters [4][nt], their places in the sorted chunk [4][nt], gbase [nt], gdst [nt], then
+// kScatterCH offsets and kScatterCH tiles of 16 bits.
+constexpr int kScatterR = 32;                   // indices per thread and chunk, in four groups of eight consecutive ones (one 16-byte read of tile[])
+constexpr int kScatterCH = 256 * kScatterR;     // indices per chunk
+static_assert(kScatterCH <= 65536 && kScatterR % 8 == 0, "offsets into a chunk are 16 bits; groups of eight");
+__host__ __device__ inline size_t bin_scatter_lds(int nt) { return (size_t)10 * nt * sizeof(uint32_t) + (size_t)2 * kScatterCH * sizeof(uint16_t); }
+__global__ void __launch_bounds__(256)
+k_bin_scatter(int nt, uint32_t n, uint32_t slab, const uint16_t *tile, const uint32_t *bhist, const uint32_t *hist, uint32_t *cursor, uint32_t *order) {
+    constexpr int NT = 256, NW = NT / 64, CH = kScatterCH, NG = kScatterR / 8;
+    extern __shared__ uint32_t bs_lds[];
+    __shared__ uint32_t part[NW];
+    uint32_t *wcount = bs_lds, *wstart = bs_lds + NW * nt, *gbase = bs_lds + 2 * NW * nt, *gdst = gbase + nt;
+    uint16_t *soff = reinterpret_cast<uint16_t *>(gdst + nt), *stile = soff + CH;
+    const unsigned tid = threadIdx.x;
+    uint32_t *mycount = wcount + (tid >> 6) * (unsigned)nt;
+    const uint32_t *mystart = wstart + (tid >> 6) * (unsigned)nt;
+    // (every thread owns `per` consecutive tiles: it scans and moves on the counters of those)
     const int per = (nt + NT - 1) / NT;
     const int tlo = min((int)tid * per, nt), thi = min(tlo + per, nt);
-    __syncthreads();
-    for (uint32_t c0 = lo; c0 < hi; c0 += CH) {
-        for (int i = tlo; i < thi; ++i) lcount[i] = 0u;
-        __syncthreads();
-        uint32_t t[kScatterR];
-#pragma unroll
-        for (int r = 0; r < kScatterR; ++r) {
-            const uint32_t i = c0 + (uint32_t)(r * NT) + tid;
-            t[r] = i < hi ? (uint32_t)tile[i] : 0xffffffffu;
-            if (t[r] != 0xffffffffu) atomicAdd(&lcount[t[r]], 1u);
-        }
-        __syncthreads();
-        // exclusive scan of the counts: inside the wave by shuffles, across the waves through LDS
-        uint32_t sum = 0;
-        for (int i = tlo; i < thi; ++i) sum += lcount[i];
-        uint32_t incl = sum;
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t x = __shfl_up(incl, off, 64);
-            if ((tid & 63u) >= (unsigned)off) incl += x;
-        }
-        if ((tid & 63u) == 63u) part[tid >> 6] = incl;
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-        for (unsigned wv = 0; wv < (unsigned)(NT / 64); ++wv) { const uint32_t x = part[wv]; total += x; if (wv < (tid >> 6)) before += x; }
-        uint32_t run = before + incl - sum;
+    {   // where the tiles' pieces begin (scan of their photons) and, in them, this block's
+        uint32_t sum = 0u, total;
+        for (int i = tlo; i < thi; ++i) sum += hist[i];
+        uint32_t run = block_scan_256(sum, part, &total);
         for (int i = tlo; i < thi; ++i) {
-            const uint32_t c = lcount[i];
-            lstart[i] = run; lcount[i] = run;
-            run += c;
+            gbase[i] = run + bhist[(size_t)i * gridDim.x + blockIdx.x];
+            run += hist[i];
+            if (blockIdx.x == 0) cursor[i] = run;
+            for (int wv = 0; wv < NW; ++wv) wcount[wv * nt + i] = 0u;
+        }
+    }
+    __syncthreads();
+    const uint32_t lo = min(n, blockIdx.x * slab), hi = min(n, lo + slab);   // (slab: a multiple of 8 -- 16-byte reads of tile[])
+    for (uint32_t c0 = lo; c0 < hi; c0 += CH) {
+        const uint32_t total = min((uint32_t)CH, hi - c0);
+        // tile << 16 | rank among the indices of that tile this wave has in the chunk (0xffffffff: beyond the slab)
+        uint32_t tr[kScatterR];
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            const uint32_t o = (uint32_t)(g * NT * 8) + tid * 8u;     // offset of the group's first index into the chunk
+            uint32_t w[4] = {0u, 0u, 0u, 0u};
+            if (o + 8u <= total) {
+                const uint4 q = *reinterpret_cast<const uint4 *>(tile + c0 + o);
+                w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
+            } else {
+                for (int r = 0; r < 8; ++r)
+                    if (o + (uint32_t)r < total) w[r >> 1] |= (uint32_t)tile[c0 + o + r] << ((r & 1) * 16);
+            }
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                const uint32_t t = (r & 1) ? (w[r >> 1] >> 16) : (w[r >> 1] & 0xffffu);
+                tr[g * 8 + r] = (o + (uint32_t)r < total) ? ((t << 16) | atomicAdd(&mycount[t], 1u)) : 0xffffffffu;
+            }
+        }
+        __syncthreads();
+        // exclusive scan of the counts -> the places of the tiles, and of the waves' shares inside them, in the sorted chunk and in the
+        // order; the counters are zero for the next chunk
+        uint32_t sum = 0, all;
+        for (int i = tlo; i < thi; ++i)
+            for (int wv = 0; wv < NW; ++wv) sum += wcount[wv * nt + i];
+        uint32_t run = block_scan_256(sum, part, &all);
+        for (int i = tlo; i < thi; ++i) {
+            gdst[i] = gbase[i] - run;     // (place j of the sorted chunk goes to gdst[its tile] + j: modulo 2^32)
+            const uint32_t run0 = run;
+            for (int wv = 0; wv < NW; ++wv) {
+                const uint32_t c = wcount[wv * nt + i];
+                wstart[wv * nt + i] = run;
+                wcount[wv * nt + i] = 0u;
+                run += c;
+            }
+            gbase[i] += run - run0;
         }
         __syncthreads();
 #pragma unroll
-        for (int r = 0; r < kScatterR; ++r)
-            if (t[r] != 0xffffffffu) {
-                const uint32_t p = atomicAdd(&lcount[t[r]], 1u);
-                sidx[p] = c0 + (uint32_t)(r * NT) + tid;
-                stile[p] = (uint16_t)t[r];
+        for (int g = 0; g < NG; ++g)
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                const uint32_t v = tr[g * 8 + r];
+                if (v != 0xffffffffu) {
+                    const uint32_t t = v >> 16, p = mystart[t] + (v & 0xffffu);
+                    soff[p] = (uint16_t)((uint32_t)(g * NT * 8) + tid * 8u + (uint32_t)r);
+                    stile[p] = (uint16_t)t;
+                }
             }
         __syncthreads();
-        for (uint32_t j = tid; j < total; j += NT) {
-            const uint32_t tt = stile[j];
-            order[gbase[tt] + (j - lstart[tt])] = sidx[j];
-        }
-        __syncthreads();
-        // (lcount[i] is where tile i ends in the sorted chunk by now)
-        for (int i = tlo; i < thi; ++i) gbase[i] += lcount[i] - lstart[i];
+        for (uint32_t j = tid; j < total; j += NT) order[gdst[stile[j]] + j] = c0 + soff[j];
+        // (the next chunk writes gdst / wstart behind two barriers, soff / stile behind three: every thread is through with this copy by then)
     }
 }
 

@@ -78,6 +78,7 @@ _SIGNATURES = [
     ('mi3d_stats_get'          , C.c_int   , [C.c_void_p, C.c_int, _fp, _fp, C.POINTER(C.c_int)]),
     ('mi3d_debug_philox'       , C.c_int   , [C.c_void_p, _u64, _u64, C.c_uint32, C.c_int, C.POINTER(C.c_uint32)]),
     ('mi3d_debug_order'        , C.c_int   , [C.c_void_p, _u64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int]),
+    ('mi3d_debug_entry'        , C.c_int   , [C.c_void_p, _u64, _fp]),
     ('mi3d_debug_thermal'      , C.c_int   , [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), _u64]),
     ('mi3d_debug_phase_tables' , C.c_int   , [C.c_void_p, C.c_int, C.c_int, _fp, _fp, _fp, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]),
     ('mi3d_debug_phase'        , C.c_int   , [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp]),
@@ -343,7 +344,7 @@ class Mi3dSolver:
 
     def set_tuning(self, **knobs):
         """launch-machinery knobs (include/mi3d.h: mi3d_set_tuning), e.g. set_tuning(evcap_log2=12, own_stream=1);
-        keys: tile_cols, batch_log2, evcap_log2, rad_spread, own_stream, tally_lists, tlcap_log2, entry_records, cam_images,
+        keys: tile_cols, batch_log2, evcap_log2, rad_spread, own_stream, tally_lists, tlcap_log2, entry_records (0 none, 1 short where allowed, 2 long always), cam_images,
         tally_window, rad_row_pad, vpad_col, vpad_row, overlap_rays, overlap_sort, overlap_pre, tl_split, rays_wg, emit_wg"""
         for key, value in knobs.items():
             self._chk(self.lib.mi3d_set_tuning(self._h, key.encode(), int(value)))
@@ -456,6 +457,21 @@ class Mi3dSolver:
         order = np.zeros(n, dtype=np.uint32); tend = np.zeros(ntile_max, dtype=np.uint32)
         self._chk(self.lib.mi3d_debug_order(self._h, int(n), order.ctypes.data_as(C.POINTER(C.c_uint32)), tend.ctypes.data_as(C.POINTER(C.c_uint32)), int(ntile_max)))
         return order, tend
+
+    def debug_entry(self, n=0):
+        """test hook: (form, records) of the last launch of the last run: form 3 the long entry records (48 bytes a photon), 2 the short
+        ones (32 bytes); records: the first n as they lie in memory, float32 [ceil(n / 64), form, 64, 4] (blocks of 64 photons, part by
+        part), or None for n = 0.  A launch without entry records raises OSError (include/mi3d.h: mi3d_debug_entry)"""
+        form = self.lib.mi3d_debug_entry(self._h, 0, None)
+        if form < 0:
+            self._chk(form)
+        if not n:
+            return form, None
+        rec = np.zeros(((int(n) + 63)//64, form, 64, 4), dtype=np.float32)
+        rc = self.lib.mi3d_debug_entry(self._h, int(n), _ptr(rec))
+        if rc < 0:
+            self._chk(rc)
+        return form, rec
 
     def debug_thermal(self, ncell):
         """test hook: (P_tot, the device CDF [ncell] float64) of the thermal source the last mi3d_prepare built"""

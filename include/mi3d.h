@@ -397,7 +397,8 @@ int mi3d_set_kernel(mi3d_solver *h, int choice);
  *   tally_window   1        0, 1       column-view tallies summed per workgroup in LDS around its photons' tile       profiles/r04/ab_no_tally_ablation   yes
  *   tally_lists    1        0, 1       flux tallies as sorted records (0: an atomic per level crossing)               profiles/r03/flux_tally_routes.log  yes
  *   tally_runs     1        0, 1       ... a flight through uniform layers as ONE run record, expanded by k_tl_runs   profiles/r06/ab_flux_run_records    yes
- *   entry_records  1        0, 1       new photons from a pre-pass kernel (48 bytes each, never > 1/2 of free memory)  profiles/r04/ab_block_c_entry_*     yes
+ *   entry_records  1        0..2       new photons from a pre-pass kernel (never > 1/2 of free memory): 0 none; 1 the   profiles/r04/ab_block_c_entry_*     yes
+ *                                      32-byte form where source and build allow, else 48 bytes; 2 always 48   profiles/r11/README.md
  *   cam_images     -1       -1..8      cameras: periodic images of the camera served within this many domain lengths  profiles/r04/camera_images.log      no
  *                                      (-1: 2 where the ray kernel serves the job, else the nearest with a warning)
  *   vpad_col/_row  0        0..4096    unused 16-byte records after every column / row of the voxel records           profiles/r04/stride_probe*.log      yes
@@ -509,8 +510,18 @@ int mi3d_debug_philox(mi3d_solver *h, uint64_t seed, uint64_t id0, uint32_t draw
 /* Test hook: the photon order of the LAST launch of the last mi3d_run (indices into the launch's id range sorted by start tile,
  * k_bin_*: a permutation of 0 .. n-1 for a launch of n photons) and, optionally, where each tile's piece of it ends (the cursors
  * k_bin_scatter leaves behind, which the lean loop's tally window reads; up to ntile_max words, 1024 at most).  MI3D_ESTATE when the
- * launch ran in id order (a small domain, fewer than 4096 photons, "tile_cols" 0). */
+ * launch ran in id order (a small domain, fewer than 4096 photons, "tile_cols" 0).  The order is the same whenever the same launch
+ * is sorted again (same photons, seed, offset and tiles): the sort takes no atomic on global memory. */
 int mi3d_debug_order(mi3d_solver *h, uint64_t n, uint32_t *order_out, uint32_t *tile_end_out, int ntile_max);
+/* Test hook: the entry records of the LAST launch of the last mi3d_run (k_entry -> the photon loop).  Returns their
+ * form -- 3: the long records, 48 bytes a photon; 2: the short ones, 32 bytes, written where the source has no cone and shines from
+ * above, the job is solar and the loop's build reads them ("entry_records" 1) -- or a negative error code: MI3D_ESTATE when the
+ * launch had no entry records.  n > 0: also copies the first n records to records_out as they lie in memory, in blocks of 64
+ * photons, part by part: float32 [ceil(n / 64)][form][64][4]; photon i of the launch's order is [i / 64][.][i % 64][.].
+ *   long:  part 0 px, py, pz, rem;  part 1 ux, uy, uz, r1;  part 2 r2, r3, ix | iy << 16, k | mode << 16 | ran << 31
+ *   short: part 0 px, py, rem, r1;  part 1 r2, r3, ix | iy << 16, k | mode << 16 | ran << 31
+ * n larger than the launch: MI3D_EINVAL. */
+int mi3d_debug_entry(mi3d_solver *h, uint64_t n, float *records_out);
 /* Test hook: the thermal source as mi3d_prepare built it.  *ptot (if not NULL) = P_tot; cdf_out (if not NULL) [n] = the device's
  * inclusive CDF of the cells' emitted power in float64, n = its number of cells (voxels, 1-D layers, surface cells: otherwise
  * MI3D_EINVAL).  MI3D_ESTATE when the job is not thermal or its source is not built yet. */
