@@ -35,6 +35,9 @@ namespace mi3d {
 #define MI3D_FLUX_FAST_PASS 8 // every n-th pass of phase B is a full one (block C serves the collisions in between: mi3d_kernel_lean.hip); with run records
                               // 4 / 6 / 8 / 12: 1.40 / 1.42 / 1.44 / 1.43e9 on les128_flux, 7.7 / 8.0 / 8.0 / 8.1e8 on les480_flux (profiles/r06/ab_flux_cadence.log)
 #endif
+#ifndef MI3D_FLUX_STEP_EARLY
+#define MI3D_FLUX_STEP_EARLY 1   // 1: a voxel step works out its geometry while its record is in flight (mi3d_kernel_lean.hip: MI3D_LEAN_STEP_EARLY); 0: the order of rounds 4-11
+#endif
 #ifndef MI3D_FLUX_THRESH
 #define MI3D_FLUX_THRESH 16   // phase A keeps stepping while at least this many lanes walk; 4 / 8 / 12 / 16 / 24 / 32: 8.1 / 8.9 / 9.1 / 9.1 / 8.6 / 8.2e8
 #endif
@@ -102,6 +105,9 @@ template <bool COUNT, bool P3D, int MIX, bool HEST>
 __global__ void __launch_bounds__(256, MI3D_FLUX_WAVES(COUNT))
 k_transport_flux(const DevScene S, const TallyList *__restrict__ TLp, const uint64_t nphoton, const uint64_t seed, const uint64_t offset) {
     constexpr bool TWO = (MIX == 1), GEN = (MIX == 2);
+    // the order of a voxel step (phase A).  One build keeps the old one: the early order costs the partial-3-D path-length build with two
+    // 3-D constituents 16 bytes of scratch where it had none
+    constexpr bool STEP_EARLY = MI3D_FLUX_STEP_EARLY != 0 && !(!COUNT && P3D && MIX == 1 && HEST);
     // (the list's description stays in memory: only the rare step that writes staged records out reads it, with scalar loads;
     //  as kernel arguments its ten pointers cost the walk spilled registers)
 #define TL (*TLp)
@@ -290,7 +296,49 @@ k_transport_flux(const DevScene S, const TallyList *__restrict__ TLp, const uint
             if (nfly == 0) break;
             if (nfly < MI3D_FLUX_THRESH && __ballot(mode != M_FLY && mode != M_DONE) != 0ull) break;
             if (COUNT) { cnt.a_slots++; if (flying) cnt.a_lanes++; }
-            if (flying) {
+            if (STEP_EARLY && flying) {
+                // (round 12: the order of mi3d_kernel_lean.hip's step -- the face, the cell behind it, the level crossing's read of the layer
+                //  table and the next record's place while the record is on its way, the wait for it last; what is tallied at a level
+                //  crossed and along the segment is worked out behind the compare, from the cell the photon leaves)
+                float tn = fminf(fminf(tx, ty), tz);
+                const bool zf = (tz == tn), xf = !zf && (tx == tn), yf = !zf && !xf;
+                const int cx = ix + stepx, cy = iy + stepy;
+                const int cxw = (unsigned)cx >= (unsigned)S.nx ? wrapx : cx, cyw = (unsigned)cy >= (unsigned)S.ny ? wrapy : cy;
+                const float txn = fmaf(S.dx, iux, tx), tyn = fmaf(S.dy, iuy, ty);
+                const int nix = xf ? cxw : ix, niy = yf ? cyw : iy;
+                const float ntx = xf ? txn : tx, nty = yf ? tyn : ty;
+                int nk = k; float ntz = tz;
+                bool leaves = false;
+                if (zf) {
+                    nk = k + stepk;
+                    const float4 Ln = lay4[nk * kL4];
+                    ntz = fmaf(Ln.x, iuz, tz);
+                    leaves = !(__float_as_int(Ln.w) & kLayStep3d);
+                }
+                unsigned off = (unsigned)niy * sy_b + (unsigned)nix * sx_b + (unsigned)nk * 16u;
+                asm volatile("" : "+v"(tn), "+v"(off));   // (without it the compiler sinks all of the above behind the wait)
+                const float dtau = rec.x * (tn - t);
+                if (COUNT) { cnt.steps++; cnt.steps3d++; }
+                if (dtau >= rem) mode = M_COLL;
+                else {
+                    if (HEST) {   // the segment through this cell: w kappa_a (tn - t), from the record the step has read
+                        const float ka = kabs_of(rec.x, rec.z, ix, iy, k, true);
+                        if (ka > 0.0f) { hidx = HEAT_CELL(ix, iy, k); hw = w * ka * (tn - t); }
+                    }
+                    rem -= dtau;
+                    t = tn;
+                    if (leaves) mode = M_UNIFW;
+                    else rec = *reinterpret_cast<const float4 *>(vbase + off);
+                    if (zf) {
+                        // a level crossed: the one above layer k going up, the one below it going down
+                        pidx = tbase + (unsigned)k * ncol + (unsigned)(iy * S.nx + ix);
+                        pw = w;
+                    }
+                    ix = nix; iy = niy; k = nk;
+                    tx = ntx; ty = nty; tz = ntz;
+                }
+            }
+            if (!STEP_EARLY && flying) {
                 const float tn = fminf(fminf(tx, ty), tz);
                 const float dtau = rec.x * (tn - t);
                 if (COUNT) { cnt.steps++; cnt.steps3d++; }

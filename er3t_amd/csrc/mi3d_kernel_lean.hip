@@ -67,6 +67,9 @@ namespace mi3d {
 #ifndef MI3D_LEAN_B4_DEFER
 #define MI3D_LEAN_B4_DEFER 1   // 1: B4 unpacks the entry records after the window logic, not before it (0: at once, as rounds 4-6 did)
 #endif
+#ifndef MI3D_LEAN_STEP_EARLY
+#define MI3D_LEAN_STEP_EARLY 1   // 1: a voxel step works out its geometry while its record is in flight and waits for the record last (0: the order of rounds 4-11)
+#endif
 #ifndef MI3D_LEAN_PEND
 #define MI3D_LEAN_PEND 1   // 1: consecutive tallies of one history into the same pixel are summed in a register before they leave
 #endif
@@ -125,6 +128,9 @@ k_transport_lean(const DevScene S, const uint64_t nphoton, const uint64_t seed, 
     // voxel constituent, no run-time flags for either in the registers (+3 % on les128_mie over the same code with the flags read at run time)
     constexpr bool MIXED = (MARCH != 0), EMIT = (MARCH == 2), TWO = (MIX == 1), GEN = (MIX >= 2), RAY1 = (MIX == 3);
     constexpr unsigned NW = NT / 64;
+    // the order of a voxel step (phase A).  A build whose registers, scratch or occupancy the early order made worse would keep the old one
+    // here, by its template arguments (the flux loop has one); none of this loop's does (profiles/r12/resource_usage.log)
+    constexpr bool STEP_EARLY = MI3D_LEAN_STEP_EARLY != 0;
     extern __shared__ float4 smem[];
     // layer table in LDS with one record more at either end: layer -1 (below the surface) and layer nz (above the top) read as
     // horizontally uniform layers of no thickness, so that the voxel walk needs no bounds check when it crosses a level: a photon
@@ -300,7 +306,46 @@ k_transport_lean(const DevScene S, const uint64_t nphoton, const uint64_t seed, 
             if (nfly == 0) break;
             if (nfly < (EMIT ? MI3D_LEAN_THRESH_EMIT : MI3D_LEAN_THRESH) && __ballot(mode != M_FLY && mode != M_DONE) != 0ull) break;
             if (COUNT) { cnt.a_slots++; if (flying) cnt.a_lanes++; }
-            if (flying) {
+            if (STEP_EARLY && flying) {
+                // (round 12) Nothing the step does but its one multiply needs the record, and the record is still on its way: which face
+                // is next, the cell behind it, its face parameter, the level crossing's read of the layer table and the next record's
+                // place are worked out FIRST and only then is the record waited for.  The same operations on the same operands as the
+                // order below; a lane whose collision lies in this cell commits nothing, so block C finds t, the parameters, the cell
+                // and the record as they were.
+                float tn = fminf(fminf(tx, ty), tz);
+                const bool zf = (tz == tn), xf = !zf && (tx == tn), yf = !zf && !xf;
+                const int cx = ix + stepx, cy = iy + stepy;
+                const int cxw = (unsigned)cx >= (unsigned)S.nx ? wrapx : cx, cyw = (unsigned)cy >= (unsigned)S.ny ? wrapy : cy;
+                const float txn = fmaf(S.dx, iux, tx), tyn = fmaf(S.dy, iuy, ty);
+                const int nix = xf ? cxw : ix, niy = yf ? cyw : iy;
+                const float ntx = xf ? txn : tx, nty = yf ? tyn : ty;
+                int nk = k; float ntz = tz;
+                bool leaves = false;                // the level crossed leads into a uniform layer (or out: the table's end records)
+                if (zf) {
+                    nk = k + (uz > 0.0f ? 1 : -1);                   // (-1 and nz: the table's end records, uniform layers)
+                    const float4 Ln = lay4[nk * kL4];
+                    ntz = fmaf(Ln.x, iuz, tz);
+                    leaves = !(__float_as_int(Ln.w) & kLayStep3d);
+                }
+                unsigned off = (unsigned)niy * sy_b + (unsigned)nix * sx_b + (unsigned)nk * 16u;
+                // (pinned: without it the compiler sinks all of the above behind the branch on dtau >= rem, that is behind the wait.  The
+                //  record's place takes the new cell and the level crossing with it; pinning the new cell and parameters as well costs the
+                //  headline build 16 bytes of scratch, and the x and y parameters are not on the way to the load)
+                asm volatile("" : "+v"(tn), "+v"(off));
+                const float dtau = rec.x * (tn - t);
+                if (COUNT) { cnt.steps++; cnt.steps3d++; }
+                MI3D_DIAG_CLEAR_STEP(COUNT, cnt, rec.z, dtau >= rem);
+                if (dtau >= rem) mode = M_COLL;     // the collision lies inside this voxel: at t + rem / bt (block C)
+                else {
+                    rem -= dtau;
+                    t = tn;
+                    ix = nix; iy = niy; k = nk;
+                    tx = ntx; ty = nty; tz = ntz;
+                    if (leaves) mode = M_UNIFW;
+                    else rec = *reinterpret_cast<const float4 *>(vbase + off);
+                }
+            }
+            if (!STEP_EARLY && flying) {
                 const float tn = fminf(fminf(tx, ty), tz);
                 const float dtau = rec.x * (tn - t);
                 if (COUNT) { cnt.steps++; cnt.steps3d++; }
