@@ -12,6 +12,7 @@ The module is also the drop-in solver executable:
     python -m er3t_amd.rtm.mca.mca_exe <Nphoton> <solver> <inp.txt> <out.bin>
 """
 
+import math
 import os
 import sys
 
@@ -93,10 +94,9 @@ def _check_thermal(nml, fdir):
 def thermal_heating(nml):
     """is this the namelist of a job that several ranks take one by one (run -> all-reduce -> the mi3d_get_* calls) instead of through
     JobRunner.run_batched?  A thermal job with the NET heating rate (Src_mtype = 3, Flx_mhrt = 2): its read-out subtracts the known emission
-    (include/mi3d.h: mi3d_get_heating), which JobRunner._normalise does not.  EVERY solar+thermal job (Src_mtype = 2): _normalise scales with
-    Src_flx mu0, a mixed job's photons stand for Src_flx (P_tot + P_sol) / (Lx Ly).  A thermal camera or point-radiometer job (Src_mtype = 3,
-    Rad_mrkind = 1): _normalise would scale a camera's tallies with Src_flx mu0 Lx Ly, a thermal photon stands for Src_flx P_tot / N
-    (include/mi3d.h: mi3d_get_radiance)"""
+    (include/mi3d.h: mi3d_get_heating), which JobRunner._normalise does not.  EVERY solar+thermal job (Src_mtype = 2) and a thermal camera
+    or point-radiometer job (Src_mtype = 3, Rad_mrkind = 1): run_batched refuses them -- it records the amplitude of solar jobs and of
+    thermal flux and satellite-radiance jobs only (source_amplitude), and lifting these refusals is a change of its own"""
     mtype = int(nml.get('Src_mtype', 1) or 1)
     return mtype == 2 or (mtype == 3 and int(nml.get('Wld_mtarget', 1)) == 1 and int(nml.get('Flx_mhrt', 0) or 0) == 2) \
         or (mtype == 3 and int(nml.get('Wld_mtarget', 1)) == 2 and int(nml.get('Rad_mrkind', 2)) == 1)
@@ -114,6 +114,15 @@ def direct_in_run_field(scene):
     radiometers (include/mi3d.h: mi3d_get_camera_direct); the fused route's reader separates it again (mca_out._from_fused)"""
     return getattr(scene, 'rad_kind', 2) == 1 and getattr(scene, 'cam_mpmap', 1) == 2 and bool(scene.target & TARGET_RADIANCE) \
         and getattr(scene, 'src_mtype', 1) == 1
+
+
+def source_amplitude(sol, sc):
+    """the power per unit domain area that the photons of the job loaded on <sol> stand for in all, the factor every read-out scales with
+    (include/mi3d.h: mi3d_get_radiance, mi3d_get_flux, mi3d_get_heating): Src_flx mu0 for the sun, Src_flx P_tot / (Lx Ly) for a thermal
+    job -- P_tot from the handle's own source, which changes from g to g with Atm_tmp1d -- in the library's order of operations"""
+    if getattr(sc, 'src_mtype', 1) == 3:
+        return sc.src_flx*sol.source_power()[0]/((sc.dx*sc.nx)*(sc.dy*sc.ny))
+    return sc.src_flx*abs(math.cos(sc.src_the*3.14159265358979323846/180.0))
 
 
 class JobRunner:
@@ -318,6 +327,7 @@ class JobRunner:
                 # (a tally this job does not have still needs somewhere to point: the handle's own buffer)
                 sol.bind(rad_ptr=ptr(0, sizes[0]), flux_ptr=ptr(sizes[0], sizes[1]), stream=stream.cuda_stream,
                          heat_ptr=ptr(sizes[0]+sizes[1], sizes[2]))
+                amp = source_amplitude(sol, sc)         # (per job: a thermal job's P_tot is that of ITS temperatures)
                 seed = int(nml.get('Wld_jseed', 0) or 0)
                 if seed == 0:
                     seed = _fresh_seed(self)
@@ -331,8 +341,7 @@ class JobRunner:
                 metas.append(dict(fname_out=fname_out, nphoton=int(nphoton), slot=slot, scene=sc,
                                   direct=sol.direct_levels() if sc.target & TARGET_FLUX else None,
                                   rdir=sol.camera_direct() if wants_rdir(sc) else None,
-                                  norm=dict(src_flx=sc.src_flx, mu0=sc.mu0, rad_kind=getattr(sc, 'rad_kind', 2), area=sc.nx*sc.dx*sc.ny*sc.dy,
-                                            dz=np.diff(sc.zgrd))))
+                                  norm=dict(amp=amp, rad_kind=getattr(sc, 'rad_kind', 2), lx=sc.dx*sc.nx, ly=sc.dy*sc.ny, dz=np.diff(sc.zgrd))))
                 i += 1
             for slot, sol in enumerate(self.sols[:nslot]):
                 sol.sync()
@@ -366,25 +375,26 @@ class JobRunner:
     def _normalise(row, sizes, m):
         """raw all-reduced tallies of one job (a row of the batch's float64 device tensor) -> the float32 arrays of its output file, still on
         the device (include/mi3d.h: mi3d_get_radiance, mi3d_get_flux, mi3d_get_heating state the same factors; float64 products and sums in
-        their order, rounded to float32 once)"""
+        their order, rounded to float32 once).  m['norm']['amp'] is the job's amplitude (source_amplitude): tests/test_gpu_readout.py holds
+        this function to the C read-outs bit for bit, solar and thermal"""
         import torch
         sc, n, p = m['scene'], float(m['nphoton']), m['norm']
         out = {}
         a, b, c = sizes
         if a:
-            fac = p['src_flx']*p['mu0']*(p['area'] if p['rad_kind'] == 1 else sc.nxr*sc.nyr)/n
+            fac = p['amp']*p['lx']*p['ly']/n if p['rad_kind'] == 1 else p['amp']*sc.nxr*sc.nyr/n
             out['rad'] = (row[:a]*fac).to(torch.float32).reshape(max(sc.nview, 1), sc.nyr, sc.nxr)[:sc.nview]
             if m.get('rdir') is not None:                              # the direct sun in the cameras: known, taken job by job
                 out['rdir'] = torch.as_tensor(np.asarray(m['rdir'], dtype=np.float32), device=row.device)
         if b:
             raw = row[a:a+b].reshape(3, sc.nz+1, sc.ny, sc.nx).clone()
             raw[1] += raw[0]                                           # raw planes: direct-down, DIFFUSE-down, up
-            f = raw*(p['src_flx']*p['mu0']*sc.nx*sc.ny/n)
+            f = raw*(p['amp']*sc.nx*sc.ny/n)
             f[:2] += torch.as_tensor(np.asarray(m['direct'], dtype=np.float64), device=row.device)[None, :, None, None]   # the known part of the direct beam (DESIGN.md §3)
             out['flux'] = f.to(torch.float32)
         if c:
             dz = torch.as_tensor(np.asarray(p['dz'], dtype=np.float64), device=row.device)
-            h = row[a+b:a+b+c].reshape(sc.nz, sc.ny, sc.nx)*(p['src_flx']*p['mu0']*sc.nx*sc.ny/n)/dz[:, None, None]
+            h = row[a+b:a+b+c].reshape(sc.nz, sc.ny, sc.nx)*(p['amp']*sc.nx*sc.ny/n)/dz[:, None, None]
             out['heat'] = h.to(torch.float32)
         return out
 

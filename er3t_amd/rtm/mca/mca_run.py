@@ -92,9 +92,9 @@ class mca_run:
         # One process: two solver handles take turns, job i+1 is launched before job i is read back and written, so that the
         # tail of a launch (as long as its longest history) and the writing of the output file run beside the next launch.
             # Under torchrun the jobs go through JobRunner.run_batched: one exchange per batch of jobs.
-        # (not the net heating rates of a thermal source: run_batched normalises with Src_flx mu0 and knows no emission.  Such jobs go one by
-        #  one: run, all-reduce of the raw tallies, then mi3d_get_heating on every rank.  Nor any solar+thermal job, whose photons stand for
-        #  Src_flx (P_tot + P_sol) / (Lx Ly): the mi3d_get_* read-outs know that amplitude)
+        # (not the net heating rates of a thermal source: run_batched knows no emission.  Such jobs go one by one: run, all-reduce of the raw
+        #  tallies, then mi3d_get_heating on every rank.  Nor any solar+thermal job or thermal camera, which run_batched refuses: it records
+        #  the amplitude of solar jobs, Src_flx mu0, and of thermal flux and satellite-radiance jobs, Src_flx P_tot / (Lx Ly), only)
         if runner.world > 1 and len(self.jobs) > 1 and not thermal_heating(mca_inp_read(self.jobs[0][0])):
             # several ranks: the raw tallies of a batch of jobs are exchanged with ONE all-reduce (JobRunner.run_batched)
             if self.verbose:
