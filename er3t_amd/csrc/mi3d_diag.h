@@ -37,6 +37,27 @@
 #define MI3D_FPC_TICK(COUNT_, cnt_, tick_, slot_old, slot_census) do { if ((slot_old) >= 0) MI3D_DIAG_TICK(COUNT_, cnt_, tick_, (slot_old) < 0 ? 0 : (slot_old)); } while (0)
 #endif
 
+// -DMI3D_WAIT_CENSUS (round 13, tools/wait_census.py, profiles/r13/wait_census_les480.log): what two waits of a pass of the lean photon loop cost.
+// The six clock counters become, in wave cycles: [0] phase A | [1] the pass's count and its read of the window's origin, up to the origin in a
+// scalar register | [2] block C's first wait (the records the walk's last step asked for; with MI3D_LEAN_C_EARLY the layer table with them) |
+// [3] two ticks back to back, once a pass: what a tick costs (it reads the clock through the scalar memory path and waits for it) | [4] the
+// rest of BSCHED + C | [5] the full pass and the loop's end.  The other ticks are off.  Exact to the cycle: a lane adds
+// (cycles + its number) / 64 and the lanes are summed.  NOT the shipped order to the instruction: the empty `asm volatile` that pins block C's early
+// reads is off in this build and an explicit `s_waitcnt vmcnt(0) lgkmcnt(0)` between two ticks stands where the record's first use would wait, and
+// it is the counting build (four waves per SIMD, not six): the figures say where a wave is parked, not what the plain build gains.
+#ifdef MI3D_WAIT_CENSUS
+#ifdef MI3D_FULL_CENSUS
+#error "MI3D_WAIT_CENSUS and MI3D_FULL_CENSUS share the six clock counters: build one census at a time"
+#endif
+#undef MI3D_DIAG_TICK
+#define MI3D_DIAG_TICK(COUNT_, cnt_, tick_, slot) do { } while (0)
+#define MI3D_WAIT_CENSUS_ON 1
+#define MI3D_WAIT_TICK(COUNT_, cnt_, tick_, slot) do { if (COUNT_) { const long long t_ = clock64(); (cnt_).cyc[slot] += (uint32_t)((t_ - (tick_) + (long long)(threadIdx.x & 63)) >> 6); (tick_) = t_; } } while (0)
+#else
+#define MI3D_WAIT_CENSUS_ON 0
+#define MI3D_WAIT_TICK(COUNT_, cnt_, tick_, slot) do { } while (0)
+#endif
+
 // -DMI3D_WIN_DIAG: le_steps3d counts the column-view tallies that stayed in the LDS tally window, le_steps all of them (82-90 %,
 // profiles/r04/win_offset_probe.log)
 #ifdef MI3D_WIN_DIAG

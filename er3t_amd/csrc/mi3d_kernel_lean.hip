@@ -70,6 +70,10 @@ namespace mi3d {
 #ifndef MI3D_LEAN_STEP_EARLY
 #define MI3D_LEAN_STEP_EARLY 1   // 1: a voxel step works out its geometry while its record is in flight and waits for the record last (0: the order of rounds 4-11)
 #endif
+#ifndef MI3D_LEAN_C_EARLY
+#define MI3D_LEAN_C_EARLY 1    // 1: block C issues its read of the layer table and the floors of |u| in front of its wait for the record, so that the LDS
+                               // answers under the voxel walk's last loads (round 13; 0: the order of rounds 4-12)
+#endif
 #ifndef MI3D_LEAN_PEND
 #define MI3D_LEAN_PEND 1   // 1: consecutive tallies of one history into the same pixel are summed in a register before they leave
 #endif
@@ -131,6 +135,8 @@ k_transport_lean(const DevScene S, const uint64_t nphoton, const uint64_t seed, 
     // the order of a voxel step (phase A).  A build whose registers, scratch or occupancy the early order made worse would keep the old one
     // here, by its template arguments (the flux loop has one); none of this loop's does (profiles/r12/resource_usage.log)
     constexpr bool STEP_EARLY = MI3D_LEAN_STEP_EARLY != 0;
+    // where block C issues the reads that do not need the record (round 13): every build takes the early order (profiles/r13/resource_usage.log)
+    constexpr bool C_EARLY = MI3D_LEAN_C_EARLY != 0;
     extern __shared__ float4 smem[];
     // layer table in LDS with one record more at either end: layer -1 (below the surface) and layer nz (above the top) read as
     // horizontally uniform layers of no thickness, so that the voxel walk needs no bounds check when it crosses a level: a photon
@@ -280,9 +286,11 @@ k_transport_lean(const DevScene S, const uint64_t nphoton, const uint64_t seed, 
     } while (0)
 #define MI3D_TICK(slot) MI3D_DIAG_TICK(COUNT, cnt, tick, slot)     // (mi3d_diag.h: instrumented build only)
 #define MI3D_TICKC(slot, census_slot) MI3D_FPC_TICK(COUNT, cnt, tick, slot, census_slot)   // (-DMI3D_FULL_CENSUS: another split; slot -1: that build only)
+#define MI3D_WTICK(slot) MI3D_WAIT_TICK(COUNT, cnt, tick, slot)    // (-DMI3D_WAIT_CENSUS: the waits of a pass; that build only)
     long long tick = COUNT ? clock64() : 0; (void)tick;   // instrumented build: wave clock ticks / 64 spent in A, walk end + B0, C + B2, B4, B5, B6 + B7
     unsigned pass_ctr = 0;
     for (;;) {
+        MI3D_WTICK(5);
         if (win_on) {   // (a pass begins: counted where the others see it, THEN the window's origin read -- in this order)
             my_pass++;
             // (relaxed atomics between compiler barriers: two LDS instructions in program order, which the LDS serves in that order --
@@ -295,6 +303,8 @@ k_transport_lean(const DevScene S, const uint64_t nphoton, const uint64_t seed, 
             worg = o_ == kWinNone ? 0x80008000u : o_;
             worg2 = o_ == kWinNone ? 0x80008000u : (((o_ & 0xffffu) - (unsigned)S.nxr) & 0xffffu) | (((o_ >> 16) - (unsigned)S.nyr) << 16);
         }
+        MI3D_WTICK(1);
+        MI3D_WTICK(3);    // (two ticks back to back: what a tick itself costs)
         // =================================== phase A: voxel steps ===================================
         // The record of the cell a photon is in arrived a step ago (or with the event that started the walk): the step multiplies its
         // extinction with the way to the nearest face, ends the walk where the collision lies inside the cell, and otherwise moves to
@@ -376,6 +386,7 @@ k_transport_lean(const DevScene S, const uint64_t nphoton, const uint64_t seed, 
 
         // =================================== phase B ===================================
         MI3D_TICK(0);
+        MI3D_WTICK(0);
         MI3D_MARK("BSCHED");
         if (COUNT) { cnt.b_slots++; if (mode != M_FLY && mode != M_DONE) cnt.b_lanes++; }
         // Every MI3D_LEAN_FAST_PASS-th pass is a full one; the passes between serve nothing but the collisions the voxel walk has
@@ -392,19 +403,42 @@ k_transport_lean(const DevScene S, const uint64_t nphoton, const uint64_t seed, 
         MI3D_MARK("C");
         bool fastc = (mode == M_COLL);
         float c_kstot = 0.0f, c_ks1 = 0.0f;
+        // (round 13) What C does not need the record for -- its read of the layer table, the floors of |u| -- in front of its first use of
+        // the record.  The lanes that collided have had their records for long, but the lanes still flying were given loads into the same
+        // registers by the walk's last step, so that first use waits for an L2 read; the LDS read stood behind that wait and had one of its own
+        // fifteen instructions later.  Now ONE wait serves both.  In every lane, not under the test for a collision: a lane without one reads
+        // the table at the layer it stands in (the table's end records included) and uses nothing of it, and the values need no registers
+        // set up on the way round the block (under the test: five more moves a pass and 0.3 % lost, profiles/r13/ab_kernel_les480.log).
+        // So the wait is unconditional too: EVERY pass now waits here for the walk's outstanding loads and for this read, where rounds 4-12
+        // waited only in a pass with a collision.  This
+        // holds for every build, the event-writing one included (les480_mv9: no difference beyond what its processes differ by,
+        // profiles/r13/ab_mv9_more.log).  The same operations on the same operands as the order of rounds 4-12.
+        float e_dz = 0.0f, e_ks1 = 0.0f, e_fx = 0.0f, e_fy = 0.0f, e_fz = 0.0f;
+        if (C_EARLY) {
+            e_dz = lay4[k * kL4].x;
+            e_ks1 = lay[k].ks1d[0];
+            e_fx = floor_abs(ux); e_fy = floor_abs(uy); e_fz = floor_abs(uz);
+#ifndef MI3D_WAIT_CENSUS
+            // (pinned: the record's first use stands behind the read and the floors, and the wait in front of it is for the record and the table)
+            asm volatile("" : "+v"(rec.x) : "v"(e_dz), "v"(e_fx), "v"(e_fy), "v"(e_fz));
+#endif
+        }
+        MI3D_WTICK(4);
+        if (COUNT && MI3D_WAIT_CENSUS_ON && __ballot(fastc) != 0ull) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // (C's first wait, on its own)
+        MI3D_WTICK(2);
         if (fastc) {
-            const float4 L = lay4[k * kL4];              // {dz, bt, zlo, flags}: a layer that is walked voxel by voxel
+            const float dz_k = C_EARLY ? e_dz : lay4[k * kL4].x;    // (the thickness of the layer, one that is walked voxel by voxel)
             const LayerRec &Lk = lay[k];
-            const float ks1 = Lk.ks1d[0];
+            const float ks1 = C_EARLY ? e_ks1 : Lk.ks1d[0];
             const float ibt = frcp(rec.x);
             const float tc = fmaf(rem, ibt, t);
             // (|u| floored as where the parameters were set up: a photon flying exactly along an axis keeps its place across it)
-            const float ax = __builtin_amdgcn_fmed3f((tx - tc) * floor_abs(ux), 0.0f, S.dx);
-            const float ay = __builtin_amdgcn_fmed3f((ty - tc) * floor_abs(uy), 0.0f, S.dy);
-            const float az = __builtin_amdgcn_fmed3f((tz - tc) * floor_abs(uz), 0.0f, L.x);
+            const float ax = __builtin_amdgcn_fmed3f((tx - tc) * (C_EARLY ? e_fx : floor_abs(ux)), 0.0f, S.dx);
+            const float ay = __builtin_amdgcn_fmed3f((ty - tc) * (C_EARLY ? e_fy : floor_abs(uy)), 0.0f, S.dy);
+            const float az = __builtin_amdgcn_fmed3f((tz - tc) * (C_EARLY ? e_fz : floor_abs(uz)), 0.0f, dz_k);
             px = ux > 0.0f ? S.dx - ax : ax;
             py = uy > 0.0f ? S.dy - ay : ay;
-            pz = uz > 0.0f ? L.x - az : az;
+            pz = uz > 0.0f ? dz_k - az : az;
             if (COUNT) cnt.scatter++;
             const float ks3 = rec.z;
             float kstot = ks1 + ks3;
@@ -441,7 +475,7 @@ k_transport_lean(const DevScene S, const uint64_t nphoton, const uint64_t seed, 
                         if (TWO && ev_ksb > 0.0f) P += ev_ksb * phase_eval_analytic(ev_apfb, uz);
                     }
                     const float c = w * P * frcp(kstot) * (0.25f / kPi);
-                    const float tau = rec.x * (L.x - pz) + rec.y;
+                    const float tau = rec.x * (dz_k - pz) + rec.y;
                     // the pixel under the event: its column where the image has one pixel per column (er3t's satellite images:
                     // Rad_nxr = Atm_nx, Rad_nyr = Atm_ny, mcarats.py:360-367)
                     int ir = ix, jr = iy;
@@ -520,6 +554,7 @@ k_transport_lean(const DevScene S, const uint64_t nphoton, const uint64_t seed, 
             }
         }
         MI3D_TICK(2);
+        MI3D_WTICK(4);
 
         // =================================== the rarer events: full passes ===================================
         if (full) {
@@ -925,6 +960,7 @@ k_transport_lean(const DevScene S, const uint64_t nphoton, const uint64_t seed, 
     }
 #undef MI3D_TICK
 #undef MI3D_TICKC
+#undef MI3D_WTICK
 #undef MI3D_ENTRY_UNPACK
     if (win_on) {
         // this wave adds to the window no more; the last one to leave empties it (a wave that leaves in the middle of a move leaves
