@@ -19,6 +19,7 @@
 #include "mi3d_kernel_lean.hip"
 #include "mi3d_kernel_rays.hip"
 #include "mi3d_kernel_flux.hip"
+#include "mi3d_kernel_backward.hip"
 
 using namespace mi3d;
 
@@ -114,6 +115,15 @@ struct mi3d_solver {
     DevBuf<double> d_th_cdf, d_th_bsum;
     DevBuf<DevThermal> d_th;
     bool dirty_thermal = false;
+    // backward Monte Carlo for the cameras of a thermal job (mi3d_set_camera_method 1; mi3d_kernel_backward.hip): {ka, B} of every cell
+    // (k_backward_cells, rebuilt with the thermal source), the count of capped histories, the read-out's normalised tally
+    int cam_method = 0;
+    bool dirty_bwd = true;
+    DevBuf<float2> d_bwd_cells;
+    DevBuf<unsigned long long> d_bwd_capped;
+    DevBuf<double> d_bwd_norm, d_bwd_score;
+    DevBuf<float> d_bwd_dir;
+    bool backward() const { return cam_method == 1 && src_mtype == 3 && rad_kind == 1 && nview > 0; }   // does the read-out divide by the pixels' own counts?
     int nview = 0, nxr = 1, nyr = 1;
     double view_the[MI3D_MAX_VIEW], view_phi[MI3D_MAX_VIEW], view_zloc[MI3D_MAX_VIEW], zref = 0.0;
     // cameras (mi3d_set_cameras): rad_kind 1, the views are point sensors
@@ -739,6 +749,25 @@ int build_thermal(mi3d_solver *h) {
     return MI3D_OK;
 }
 
+// Backward route (mi3d_set_camera_method 1): {ka, B(T)} of every cell of the thermal source, in the order of its CDF (k_backward_cells)
+int build_backward_cells(mi3d_solver *h) {
+    const size_t nvox = (size_t)h->nx * h->ny * h->nz3;
+    const bool sfc2d = !h->sfc2d_host.empty();
+    const size_t nsfc = sfc2d ? (size_t)h->nxb * h->nyb : 1;
+    const size_t ncell = nvox + (size_t)h->nz + nsfc;
+    int rc;
+    if ((rc = h->d_bwd_cells.alloc(ncell))) return rc;
+    if (!h->d_bwd_capped.p) {
+        if ((rc = h->d_bwd_capped.alloc(1))) return rc;
+        HIPCHK(hipMemsetAsync(h->d_bwd_capped.p, 0, sizeof(unsigned long long), h->stream));
+    }
+    hipLaunchKernelGGL(k_backward_cells, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, h->stream, thermal_grid(h),
+                       sfc2d ? h->nxb : 1, sfc2d ? h->nyb : 1, (const float *)(sfc2d ? h->d_sfc2d.p : nullptr), h->sfc_param[0],
+                       (const float *)(h->th_ntmps ? h->d_th_tmps.p : nullptr), h->d_bwd_cells.p);
+    HIPCHK(hipGetLastError());
+    return MI3D_OK;
+}
+
 // The direct sun in the cameras (k_cam_direct), per unit Src_flx; thermal jobs have none (zeros).
 constexpr double kCamDirMaxCells = 1048576.0;   // voxels one march may cross (a few hundred milliseconds of one thread at most)
 int build_camdir(mi3d_solver *h) {
@@ -866,6 +895,7 @@ int mi3d_destroy(mi3d_solver *h) {
     for (int w = 0; w < 2; ++w) { h->d_run_own[w].release(); h->d_sum[w].release(); h->d_sumsq[w].release(); h->d_factor[w].release(); }
     h->d_stat_out.release(); h->d_dir_level.release(); h->d_get_out.release(); h->d_get_add.release();
     h->d_th_tlev.release(); h->d_th_tmpa.release(); h->d_th_tmps.release(); h->d_th_cdf.release(); h->d_th_bsum.release(); h->d_th.release();
+    h->d_bwd_cells.release(); h->d_bwd_capped.release(); h->d_bwd_norm.release(); h->d_bwd_score.release(); h->d_bwd_dir.release();
     h->d_views.release(); h->d_cold.release(); h->d_tabrange.release(); h->d_bt1d.release(); h->d_dz.release(); h->d_bmin.release(); h->d_bmax.release();
     delete h;
     return MI3D_OK;
@@ -1083,6 +1113,16 @@ int mi3d_set_cameras(mi3d_solver *h, int ncam, const double *the_deg, const doub
     return MI3D_OK;
 }
 
+int mi3d_set_camera_method(mi3d_solver *h, int method) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (method != 0 && method != 1) return fail(MI3D_EINVAL, "camera method %d (0: forward local estimates, 1: backward Monte Carlo)", method);
+    if (method == h->cam_method) return MI3D_OK;
+    HIPCHK(sync_main(h));   // (as every call that changes what the kernels work on)
+    h->cam_method = method;
+    return MI3D_OK;
+}
+
 int mi3d_set_camera_map(mi3d_solver *h, int mpmap, int mrproj) {
     int rc = check_handle(h);
     if (rc) return rc;
@@ -1284,6 +1324,11 @@ int mi3d_prepare(mi3d_solver *h) {
     if (h->thermal() && h->dirty_thermal) {
         if ((rc = build_thermal(h))) return rc;
         h->dirty_thermal = false;
+        h->dirty_bwd = true;
+    }
+    if (h->cam_method == 1 && h->src_mtype == 3 && h->dirty_bwd) {
+        if ((rc = build_backward_cells(h))) return rc;
+        h->dirty_bwd = false;
     }
     if (h->rad_kind == 1 && h->nview > 0 && h->dirty_camdir) {
         if ((rc = build_camdir(h))) return rc;
@@ -1303,6 +1348,7 @@ int mi3d_reset(mi3d_solver *h) {
     HIPCHK(hipMemsetAsync(h->flux_ptr(), 0, h->flux_elems() * sizeof(tally_t), h->stream));
     if ((h->target & MI3D_TARGET_HEAT) && h->heat_ptr()) HIPCHK(hipMemsetAsync(h->heat_ptr(), 0, h->heat_elems() * sizeof(double), h->stream));
     HIPCHK(hipMemsetAsync(h->d_counters.p, 0, MI3D_NCOUNTER * sizeof(unsigned long long), h->stream));
+    if (h->d_bwd_capped.p) HIPCHK(hipMemsetAsync(h->d_bwd_capped.p, 0, sizeof(unsigned long long), h->stream));
     // (the accumulation image is folded and zeroed at the end of a successful mi3d_run; a run that failed half way -- an event
     //  list ran full, a launch failed -- leaves its partial tallies there)
     if (h->d_rad_acc.p) HIPCHK(hipMemsetAsync(h->d_rad_acc.p, 0, h->d_rad_acc.cap * sizeof(tally_t), h->stream));
@@ -1720,7 +1766,7 @@ static int choose_tile_cols(const mi3d_solver *h) {
 // ColumnRays: marched views and cameras, Rad_mrkind = 1 under the 3-D solver, through event lists and the ray kernel), at most two 3-D
 // constituents, byte offsets of the voxel records within 32 bits.  The lean flux kernel (mi3d_kernel_flux.hip, Flux): flux / heating
 // rates without radiance, the same scenes.  Everything else: the general loop, k_transport.
-enum class Loop { General, Column, ColumnRays, Flux };
+enum class Loop { General, Column, ColumnRays, Flux, Backward };
 
 struct RunPlan {
     Loop loop = Loop::General;
@@ -1770,8 +1816,11 @@ static RunPlan plan_run(const mi3d_solver *h, uint64_t nphoton) {
     if (h->src_mtype == 3 && h->kernel_choice == 0 && h->np3d <= 2 && tabs_ok && vox32 && !plan.flux && h->nview > 0 && plan.march && cells16 &&
         h->rad_kind == 1 && h->solver == MI3D_SOLVER_3D)
         plan.loop = Loop::ColumnRays;
+    // Backward Monte Carlo for the cameras of a thermal job (mi3d_set_camera_method 1): a kernel of its own; what it does
+    // not serve is refused by mi3d_run (backward_unsupported)
+    if (h->cam_method == 1) plan.loop = Loop::Backward;
     plan.mix_lean = (plan.mix == 2 && plan.loop != Loop::ColumnRays && rayleigh_1d(h) && h->np3d == 1) ? 3 : plan.mix;
-    if (plan.loop == Loop::General || (h->rad_kind == 1 && plan.loop != Loop::ColumnRays))
+    if (plan.loop != Loop::Backward && (plan.loop == Loop::General || (h->rad_kind == 1 && plan.loop != Loop::ColumnRays)))
         plan.why = h->kernel_choice != 0 ? "kernel choice 1"
                    : h->rad_kind == 1 && h->solver != MI3D_SOLVER_3D ? "cameras are served under the 3-D solver only"
                    : plan.flux && rad_job ? "flux (or heating rates) TOGETHER with radiance: two jobs, one per target, as er3t's mcarats_ng submits them (mcarats.py:238-245), each take a lean loop"
@@ -1804,7 +1853,8 @@ static void name_route(mi3d_solver *h, const RunPlan &plan, bool lists, uint64_t
     const int c = h->counting ? 1 : 0, p3d = h->solver == MI3D_SOLVER_P3D ? 1 : 0;
     char nm[96];
     const bool hpath = (h->target & MI3D_TARGET_HEAT) && h->heat_estimator == 1;
-    if (plan.loop == Loop::Flux && hpath) snprintf(nm, sizeof(nm), lists ? "k_transport_flux<%d,%d,%d,1> + k_tl_scatter + k_tl_sum" : "k_transport_flux<%d,%d,%d,1>", c, p3d, plan.mix);
+    if (plan.loop == Loop::Backward) snprintf(nm, sizeof(nm), "k_backward<%d> [thermal]", c);
+    else if (plan.loop == Loop::Flux && hpath) snprintf(nm, sizeof(nm), lists ? "k_transport_flux<%d,%d,%d,1> + k_tl_scatter + k_tl_sum" : "k_transport_flux<%d,%d,%d,1>", c, p3d, plan.mix);
     else if (plan.loop == Loop::Flux) snprintf(nm, sizeof(nm), lists ? "k_transport_flux<%d,%d,%d> + k_tl_scatter + k_tl_sum" : "k_transport_flux<%d,%d,%d>", c, p3d, plan.mix);
     else if (plan.loop == Loop::ColumnRays && plan.thermal) snprintf(nm, sizeof(nm), "k_transport<%d,2,0,0> [thermal] + k_rays", c);
     else if (plan.loop == Loop::ColumnRays) snprintf(nm, sizeof(nm), "k_transport_lean<%d,%d,2,%d> + k_rays", c, p3d, plan.mix_lean);
@@ -2256,10 +2306,104 @@ static hipError_t launch_pre(mi3d_solver *h, const RunPlan &plan, int pset, bool
     return eb;
 }
 
+// ---- the backward route (mi3d_set_camera_method 1; mi3d_kernel_backward.hip) ------------------------------------
+// What it serves: Src_mtype = 3, cameras (Rad_mrkind = 1), the 3-D solver, Lambertian surfaces.  Everything else: MI3D_EUNSUP, with the reason.
+static int backward_unsupported(const mi3d_solver *h) {
+    const char *why = h->src_mtype == 1 ? "a solar job (Src_mtype=1): the sun needs a local estimate of its own"
+                      : h->src_mtype == 2 ? "a solar+thermal job (Src_mtype=2): the sun needs a local estimate of its own"
+                      : !(h->target & MI3D_TARGET_RADIANCE) || (h->target & MI3D_TARGET_FLUX) ? "a flux or heating-rate job: the route serves radiance (cameras) alone"
+                      : h->rad_kind != 1 ? "satellite views (Rad_mrkind=2): the route serves cameras and point radiometers (Rad_mrkind=1)"
+                      : h->solver != MI3D_SOLVER_3D ? "independent columns or partial 3-D: cameras need the 3-D solver"
+                      : !h->sfc_lambert_only ? "a non-Lambertian surface (only Lambertian surfaces emit)"
+                      : nullptr;
+    if (why) return fail(MI3D_EUNSUP, "backward Monte Carlo (mi3d_set_camera_method 1) does not serve %s", why);
+    return MI3D_OK;
+}
+
+static int fill_backward(mi3d_solver *h, DevBackward &A) {
+    std::memset(&A, 0, sizeof(A));
+    const double Lx = h->dx * h->nx, Ly = h->dy * h->ny;
+    const bool sfc2d = !h->sfc2d_host.empty();
+    A.nx = h->nx; A.ny = h->ny; A.nz = h->nz; A.nz3 = h->nz3; A.k3lo = h->nz3 > 0 ? h->iz3l - 1 : 0; A.np1d = h->np1d; A.np3d = h->np3d;
+    A.nxb = sfc2d ? h->nxb : 1; A.nyb = sfc2d ? h->nyb : 1;
+    A.nview = h->nview; A.nxr = h->nxr; A.nyr = h->nyr;
+    A.cam_mode = kCamPoint | (h->cam_mpmap == 2 ? kCamRect : 0) | (h->cam_mrproj == 1 ? kCamCos : 0);
+    A.dx = (float)h->dx; A.dy = (float)h->dy; A.inv_dx = (float)(1.0 / h->dx); A.inv_dy = (float)(1.0 / h->dy);
+    A.ztoa = (float)h->zgrd[h->nz];
+    A.sfc_sx = (float)(A.nxb / Lx); A.sfc_sy = (float)(A.nyb / Ly);
+    A.wmin = (float)h->wmin; A.wfac = (float)h->wfac; A.src_flx = (float)h->src_flx;
+    A.nvox = (unsigned)((size_t)h->nx * h->ny * h->nz3); A.vcol_f4 = h->vcol_f4; A.vrow_f4 = h->vrow_f4;
+    A.lay = h->d_lay.p; A.vrec = h->d_vrec.p; A.csca = h->d_csca.p; A.cells = h->d_bwd_cells.p; A.cams = h->d_cams.p;
+    A.tab.tmu = h->d_tmu.p; A.tab.tp = h->d_tp.p; A.tab.tcdf = h->d_tcdf.p; A.tab.nang = h->nang; A.tab.npf = h->npf;
+    A.rad = h->rad_ptr(); A.counters = h->d_counters.p; A.capped = h->d_bwd_capped.p;
+    for (int iv = 0; iv < h->nview; ++iv)
+        if (!(h->view_zloc[iv] > h->zgrd[0]))
+            return fail(MI3D_EINVAL, "backward Monte Carlo: sensor %d stands on or below the surface (Rad_zloc=%g, surface at %g)", iv + 1, h->view_zloc[iv], h->zgrd[0]);
+    if ((double)h->nview * h->nxr * h->nyr > 2147483647.0) return fail(MI3D_EUNSUP, "image too large for the 32-bit pixel numbers of the backward kernel");
+    return MI3D_OK;
+}
+
+static int run_backward(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_offset) {
+    int rc = backward_unsupported(h);
+    if (rc) return rc;
+    if (nphoton == 0) return MI3D_OK;
+    DevBackward A;
+    if ((rc = fill_backward(h, A))) return rc;
+    RunPlan plan = plan_run(h, nphoton);
+    name_route(h, plan, false, nphoton);
+    h->entry_form_last = 0;
+    h->runs_unread++;
+    const int npix = h->nview * h->nxr * h->nyr;
+    const size_t lds = backward_lds(npix, h->nz, h->nview, false);
+    // workgroups of 256 lanes, as many as are resident at once (five waves per SIMD, four in the counting build: the register report in
+    // DESIGN.md §5.11): every lane walks its ids with a fixed stride, and a workgroup that had to queue would start when the others are through
+    const uint64_t cap = (uint64_t)h->num_cu * (h->counting ? 4 : 5);
+    for (uint64_t done = 0; done < nphoton; done += h->batch) {
+        const uint64_t nb = std::min<uint64_t>(h->batch, nphoton - done), off = photon_offset + done;
+        if (h->pending.size() >= 64 && (rc = drain_events(h))) return rc;
+        const uint64_t want = (nb + 255) / 256;
+        const unsigned grid = (unsigned)(want < cap ? want : cap);
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        HIPCHK(hipEventCreate(&e0));
+        hipError_t err = hipEventCreate(&e1);
+        if (err == hipSuccess) err = hipEventRecord(e0, h->stream);
+        if (err == hipSuccess) {
+            if (h->counting) hipLaunchKernelGGL((k_backward<true, false>), dim3(grid), dim3(256), lds, h->stream, A, seed, off, nb, (float *)nullptr, (double *)nullptr);
+            else hipLaunchKernelGGL((k_backward<false, false>), dim3(grid), dim3(256), lds, h->stream, A, seed, off, nb, (float *)nullptr, (double *)nullptr);
+            err = hipGetLastError();
+        }
+        if (err == hipSuccess) err = hipEventRecord(e1, h->stream);
+        if (err != hipSuccess) {
+            (void)hipEventDestroy(e0);
+            if (e1) (void)hipEventDestroy(e1);
+            return fail(MI3D_EDEVICE, "backward launch failed: %s", hipGetErrorString(err));
+        }
+        h->pending.emplace_back(e0, e1);
+        h->launches++;
+    }
+    return MI3D_OK;
+}
+
+// The tally a read-out scales: the raw one, or -- backward route -- the raw one divided pixel by pixel by the number of ids in
+// [0, nphoton_total) that map to the pixel (k_backward_norm), whose scale is then 1
+static int readout_tally(mi3d_solver *h, uint64_t nphoton_total, const tally_t *&tally, double &norm) {
+    tally = h->rad_ptr();
+    if (!h->backward()) return MI3D_OK;
+    const size_t n = (size_t)h->nview * h->nxr * h->nyr;
+    int rc = h->d_bwd_norm.alloc(n);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_backward_norm, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const double *)h->rad_ptr(), h->d_bwd_norm.p,
+                       (unsigned long long)nphoton_total, (unsigned)n);
+    HIPCHK(hipGetLastError());
+    tally = h->d_bwd_norm.p; norm = 1.0;
+    return MI3D_OK;
+}
+
 int mi3d_run(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_offset) {
     int rc = check_handle(h);
     if (rc) return rc;
     if ((rc = mi3d_prepare(h))) return rc;
+    if (h->cam_method == 1) return run_backward(h, nphoton, seed, photon_offset);
     if ((h->target & MI3D_TARGET_RADIANCE) && h->nview == 0)
         return fail(MI3D_ESTATE, "radiance requested but no view is set (mi3d_set_views)");
     if ((h->target & MI3D_TARGET_RADIANCE) && h->rad_kind == 1 && h->solver != MI3D_SOLVER_3D)
@@ -2518,12 +2662,14 @@ int mi3d_get_radiance(mi3d_solver *h, uint64_t nphoton_total, float *out) {
     const double amp = src_amp(h);
     // satellite: radiance averaged over the pixel's share of the domain area; camera: the tallies hold 1 / (r^2 dOmega) already and
     // a photon stands for Src_flx mu0 Lx Ly / N of power (thermal: Src_flx P_tot / N)
-    const double fac = h->rad_kind == 1 ? amp * (h->dx * h->nx) * (h->dy * h->ny) / (double)nphoton_total
-                                        : amp * (double)h->nxr * (double)h->nyr / (double)nphoton_total;
+    double fac = h->rad_kind == 1 ? amp * (h->dx * h->nx) * (h->dy * h->ny) / (double)nphoton_total
+                                  : amp * (double)h->nxr * (double)h->nyr / (double)nphoton_total;
     // (scaled on the device, k_get_field: nine views of 480 x 480 pixels were 16 MB of float64 to the host and a loop over them)
     if (n == 0) return MI3D_OK;
     if ((rc = h->d_get_out.alloc(n))) return rc;
-    hipLaunchKernelGGL(k_get_field, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const tally_t *)h->rad_ptr(), h->d_get_out.p, fac,
+    const tally_t *rad_tally = nullptr;
+    if ((rc = readout_tally(h, nphoton_total, rad_tally, fac))) return rc;   // (backward route: every pixel by its own count of histories)
+    hipLaunchKernelGGL(k_get_field, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, rad_tally, h->d_get_out.p, fac,
                        1u, 1u, -1L, (const double *)nullptr, n);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, h->d_get_out.p, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
@@ -2711,10 +2857,11 @@ int mi3d_stats_add(mi3d_solver *h, uint64_t nphoton_total, const float *factor_r
         // (this call reads the tallies of the job that has just run: a launch of it whose event list ran full fails the call HERE -- the next
         //  mi3d_reset would forget it, and the short tallies would be part of the run's mean and standard deviation for good)
         if ((rc = ev_settle(h))) return rc;
-        const double norm = w == 0 ? (h->rad_kind == 1 ? amp * (h->dx * h->nx) * (h->dy * h->ny) / (double)nphoton_total
+        double norm = w == 0 ? (h->rad_kind == 1 ? amp * (h->dx * h->nx) * (h->dy * h->ny) / (double)nphoton_total
                                                        : amp * (double)h->nxr * (double)h->nyr / (double)nphoton_total)
                                    : amp * (double)h->nx * (double)h->ny / (double)nphoton_total; // as mi3d_get_*
         const tally_t *tally = w == 0 ? h->rad_ptr() : h->flux_ptr();
+        if (w == 0 && (rc = readout_tally(h, nphoton_total, tally, norm))) return rc;   // (backward route: every pixel by its own count of histories)
         const double *dir_dev = nullptr;
         if (w == 1 && !h->dir_level.empty()) {
             std::vector<double> a(h->dir_level);
@@ -2867,6 +3014,31 @@ int mi3d_debug_thermal(mi3d_solver *h, double *ptot, double *cdf_out, uint64_t n
 }
 
 static_assert(MI3D_TAB_IDX_N == kTabIdxN, "include/mi3d.h states the length of a bucket index");
+
+int mi3d_debug_backward(mi3d_solver *h, uint64_t seed, uint64_t id0, int n, float *dir_out, double *score_out, uint64_t *capped_out) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (n < 0 || (n > 0 && (!dir_out || !score_out))) return fail(MI3D_EINVAL, "bad arguments to mi3d_debug_backward");
+    if (h->cam_method != 1) return fail(MI3D_ESTATE, "mi3d_debug_backward: the backward route is not selected (mi3d_set_camera_method 1)");
+    if ((rc = mi3d_prepare(h))) return rc;
+    if ((rc = backward_unsupported(h))) return rc;
+    if (n > 0) {
+        DevBackward A;
+        if ((rc = fill_backward(h, A))) return rc;
+        if ((rc = h->d_bwd_dir.alloc((size_t)3 * n)) || (rc = h->d_bwd_score.alloc(n))) return rc;
+        const size_t lds = backward_lds(h->nview * h->nxr * h->nyr, h->nz, h->nview, true);
+        hipLaunchKernelGGL((k_backward<false, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), lds, h->stream, A, seed, id0, (uint64_t)n, h->d_bwd_dir.p, h->d_bwd_score.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(dir_out, h->d_bwd_dir.p, (size_t)3 * n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(score_out, h->d_bwd_score.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    }
+    if (capped_out) {
+        *capped_out = 0;
+        if (h->d_bwd_capped.p) { unsigned long long c = 0; HIPCHK(hipMemcpyAsync(&c, h->d_bwd_capped.p, sizeof(c), hipMemcpyDeviceToHost, h->stream)); HIPCHK(hipStreamSynchronize(h->stream)); *capped_out = c; }
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MI3D_OK;
+}
 
 int mi3d_debug_phase_tables(mi3d_solver *h, int nang, int npf, float *mu, float *p, float *cdf, uint16_t *mu_idx, uint16_t *cdf_idx) {
     int rc = check_handle(h);

@@ -44,6 +44,13 @@ def _check_supported(nml, fdir=None):
             raise OSError('Error [mca_exe]: <Rad_nimg=%g> must be an integer from 0 to 8: the domain lengths around the nearest periodic image of a '
                           'camera within which its images are served (a key of this project).' % nimg)
     mtype = int(nml.get('Src_mtype', 1))
+    if nml.get('Rad_mbwd') is not None:
+        mbwd = float(np.ravel(nml.get('Rad_mbwd'))[0])
+        if mbwd not in (0.0, 1.0):
+            raise OSError('Error [mca_exe]: <Rad_mbwd=%g> is not supported (0: forward, 1: backward Monte Carlo; a key of this project).' % mbwd)
+        if mbwd == 1.0 and not (mtype == 3 and int(nml.get('Wld_mtarget', 1)) == 2 and int(nml.get('Rad_mrkind', 2)) == 1):
+            raise OSError('Error [mca_exe]: <Rad_mbwd=1> (backward Monte Carlo) belongs to the all-sky cameras and point radiometers (<Rad_mrkind=1>) of a '
+                          'thermal job (<Src_mtype=3>): a solar job\'s sun would need a local estimate of its own.')
     if mtype == 0:
         raise OSError('Error [mca_exe]: <Src_mtype=0> (local) is not supported: only the solar (1), the solar+thermal (2) or the thermal (3) source.')
     if mtype not in (1, 2, 3):
@@ -77,7 +84,9 @@ def _check_thermal(nml, fdir):
             raise OSError('Error [mca_exe]: all-sky cameras (<Rad_mrkind=1>) are not supported for a thermal job.')
         # a thermal all-sky camera or point radiometer: how much of the horizon the cyclic domain's images add decides a
         # hemispheric longwave reading, so the job file has to say it
-        if nml.get('Rad_nimg') is None:
+        # (... or that the job goes backwards, Rad_mbwd = 1: a line of sight then wraps through the whole cyclic domain)
+        backward = nml.get('Rad_mbwd') is not None and float(np.ravel(nml.get('Rad_mbwd'))[0]) == 1.0
+        if nml.get('Rad_nimg') is None and not backward:
             raise OSError('Error [mca_exe]: an all-sky camera or point radiometer (<Rad_mrkind=1>) of a thermal job needs <Rad_nimg>, the number of '
                           'domain lengths (0 to 8) around the nearest periodic image of a sensor within which its images are served '
                           '(a key of this project: mcarats_ng(source=\'thermal\', sensor_type=\'all-sky\' | \'irradiance\' | \'actinic\') writes it).')

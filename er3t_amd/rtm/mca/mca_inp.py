@@ -98,7 +98,8 @@ _CATALOGUE = [
         ('Rad_vmax', 'max angle along V'), ('Rad_qmax', 'max angle of the field-of-view cone'), ('Rad_xpos', 'relative X position'),
         ('Rad_ypos', 'relative Y position'), ('Rad_zloc', 'Z location [m]'), ('Rad_apsize', 'aperture size'),
         ('Rad_zref', 'Z of the reference level'),
-        ('Rad_nimg', 'cameras: periodic images of a sensor served within this many domain lengths of the nearest one, 0..8 (a key of this project)')]),
+        ('Rad_nimg', 'cameras: periodic images of a sensor served within this many domain lengths of the nearest one, 0..8 (a key of this project)'),
+        ('Rad_mbwd', 'cameras of a thermal job: 1 backward Monte Carlo, histories start at the sensor (a key of this project, written only when 1)')]),
 ]
 
 

@@ -105,6 +105,11 @@ class mcarats_ng:
                            serves these sensors too (a pyrgeometer, an IR radiometer, a thermal sky imager: DESIGN.md §5.10) and always writes
                            the key, 2 when None: the clear sky is limb-brightened in the window channels, and the images decide how much of
                            the horizon a hemispheric sensor sees.  A solar job file carries the key only when a value is given
+        camera_method ['forward']: 'backward' serves the sensors of a <source='thermal'> job (sensor_type 'all-sky' | 'irradiance' | 'actinic') by
+                           backward Monte Carlo: histories start at the sensor and collect the emission along their lines of sight
+                           (Rad_mbwd=1, a key of this project written only then: include/mi3d.h, mi3d_set_camera_method).
+                           No 1 / r^2 and no aperture clamp -- a sensor may stand inside a cloud or absorbing air --, the whole cyclic
+                           domain is seen: <camera_images> must not be given and Rad_nimg is not written
 
     Afterwards: input and output files under <fdir>; attributes Ng, Nrun, Nx, Ny, dx, dy, date, target, solver,
     photons (Nrun*Ng,), photons_per_set, fnames_inp[ir][ig], fnames_out[ir][ig], nml (list of Ng dictionaries).
@@ -118,7 +123,7 @@ class mcarats_ng:
                  sensor_azimuth_angle=0.0, sensor_altitude=705000.0, sensor_type='satellite', sensor_xpos=0.5,
                  sensor_ypos=0.5, solver='3d', photons=1e7, base_ratio=0.05, verbose=False, quiet=False,
                  abs_obj=None, keep_files=True, source='solar', wavelength=None, surface_temperature=None,
-                 heating_estimator='collision', camera_images=None):
+                 heating_estimator='collision', camera_images=None, camera_method='forward'):
 
         # one process per GPU (torch.distributed): rank 0 writes the job files, all ranks transport their share of every job
         from er3t_amd.dist import world_info, barrier
@@ -160,6 +165,16 @@ class mcarats_ng:
             raise OSError('Error [mcarats_ng]: <source=\'solar+thermal\'> with <sensor_type=%r> is not implemented: the direct sun in a camera of a mixed '
                           'job would need a normalisation of its own; <source=\'thermal\'> and <source=\'solar\'> serve these sensors.' % sensor_type)
         self.camera_images = None if camera_images is None else int(camera_images)
+        self.camera_method = str(camera_method).lower()
+        if self.camera_method not in ('forward', 'backward'):
+            raise OSError('Error [mcarats_ng]: <camera_method=%s> must be \'forward\' or \'backward\'.' % camera_method)
+        if self.camera_method == 'backward':
+            if self.source != 'thermal' or not self.point_sensor:
+                raise OSError('Error [mcarats_ng]: <camera_method=\'backward\'> needs <source=\'thermal\'> and <target=\'radiance\'> with '
+                              '<sensor_type=\'all-sky\' | \'irradiance\' | \'actinic\'>: backward histories collect emission; the sun would need a local estimate of its own.')
+            if camera_images is not None:
+                raise OSError('Error [mcarats_ng]: <camera_images> does not go with <camera_method=\'backward\'>: a line of sight wraps through the '
+                              'whole cyclic domain, no periodic images are enumerated.')
         self.heating_estimator = str(heating_estimator).lower()
         if self.heating_estimator not in ('collision', 'path'):
             raise OSError('Error [mcarats_ng]: <heating_estimator=%s> must be \'collision\' or \'path\'.' % heating_estimator)
@@ -239,7 +254,9 @@ class mcarats_ng:
 
         # (Rad_nimg: a thermal sensor job always says how far its periodic images are served -- 2 unless told otherwise --; a solar job file
         #  carries the key only when <camera_images> is given, and stays what it was, byte for byte, without)
-        if self.point_sensor and (self.camera_images is not None or self.source == 'thermal'):
+        if self.camera_method == 'backward':           # (written only then: every other job file stays what it was, byte for byte)
+            self._all({'Rad_mbwd': 1})
+        elif self.point_sensor and (self.camera_images is not None or self.source == 'thermal'):
             self._all({'Rad_nimg': 2 if self.camera_images is None else self.camera_images})
         if sensor_type.lower() in _SENSOR_MRPROJ:
             self._init_radiometers(sensor_type.lower(), sensor_zenith_angle, sensor_azimuth_angle, sensor_altitude, sensor_xpos, sensor_ypos)

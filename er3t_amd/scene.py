@@ -114,6 +114,9 @@ class Scene:
                                           # alone is complete to 75 degrees, lacks 43 % of the light at 82-86 and 96 % at 86-89; 1 / 2 / 3 images
                                           # recover 79 / 98 / 100 % of the last ring at 0.49 / 0.29 / 0.19 of the speed (profiles/r04/camera_images.log)
 
+    cam_method: int = 0                   # Rad_mbwd (a key of this project; include/mi3d.h: mi3d_set_camera_method): 0 the forward route, 1 backward
+                                          # Monte Carlo -- thermal cameras and point radiometers only; cam_images is then not used
+
     # job
     target: int = TARGET_FLUX
     solver: int = SOLVER_3D
@@ -172,11 +175,15 @@ class Scene:
                                   ('cam_vmax', 180.0), ('cam_apsize', 0.0)):
                 v = list(np.resize(np.asarray(getattr(self, name) if len(getattr(self, name)) else [default], dtype=np.float64), n))
                 setattr(self, name, v)
+            if self.cam_method not in (0, 1):
+                raise ValueError('Error [Scene]: <cam_method=%s> (Rad_mbwd) must be 0 (forward) or 1 (backward).' % self.cam_method)
             if self.cam_mpmap not in (1, 2) or self.cam_mrproj not in (0, 1):
                 raise ValueError('Error [Scene]: <cam_mpmap=%s> (Rad_mpmap) must be 1 or 2 and <cam_mrproj=%s> (Rad_mrproj) 0 or 1.'
                                  % (self.cam_mpmap, self.cam_mrproj))
         elif self.rad_kind != 2:
             raise ValueError('Error [Scene]: <rad_kind=%s> (Rad_mrkind) must be 1 or 2.' % self.rad_kind)
+        elif self.cam_method != 0:
+            raise ValueError('Error [Scene]: <cam_method=%s> (Rad_mbwd) belongs to cameras and point radiometers (<rad_kind=1>).' % self.cam_method)
         if self.src_mtype in (2, 3):
             if self.src_mtype == 2:
                 if self.src_fsol is None or not (float(self.src_fsol) >= 0.0) or not np.isfinite(float(self.src_fsol)):
@@ -332,6 +339,13 @@ class Scene:
             kw.pop('tmpa3d', None); kw.pop('tmps2d', None)
 
         mtarget = int(get('Wld_mtarget', 1))
+        # (a key of this project: backward Monte Carlo for the cameras and point radiometers of a thermal job)
+        mbwd = float(np.ravel(get('Rad_mbwd', 0))[0])
+        if mbwd not in (0.0, 1.0):
+            raise OSError('Error [Scene]: <Rad_mbwd=%g> is not supported (0: forward, 1: backward Monte Carlo).' % mbwd)
+        if mbwd == 1.0 and not (mtype == 3 and mtarget == 2 and int(get('Rad_mrkind', 2)) == 1):
+            raise OSError('Error [Scene]: <Rad_mbwd=1> (backward Monte Carlo) belongs to the cameras and point radiometers (<Rad_mrkind=1>) of a '
+                          'thermal job (<Src_mtype=3>).')
         if mtarget == 2:
             nrad = int(get('Rad_nrad', 1))
             the  = np.resize(np.asarray(get('Rad_the', 180.0), dtype=np.float64), nrad)
@@ -350,7 +364,8 @@ class Scene:
                     return list(np.resize(np.asarray(get(key, default), dtype=np.float64), nrad))
                 kw.update(rad_kind=1, cam_xpos=per_view('Rad_xpos', 0.5), cam_ypos=per_view('Rad_ypos', 0.5),
                           cam_psi=per_view('Rad_psi', 0.0), cam_qmax=per_view('Rad_qmax', 180.0), cam_umax=per_view('Rad_umax', 180.0),
-                          cam_vmax=per_view('Rad_vmax', 180.0), cam_apsize=per_view('Rad_apsize', 0.0), cam_mpmap=mpmap, cam_mrproj=mrproj)
+                          cam_vmax=per_view('Rad_vmax', 180.0), cam_apsize=per_view('Rad_apsize', 0.0), cam_mpmap=mpmap, cam_mrproj=mrproj,
+                          cam_method=int(mbwd))
                 # (a key of this project: the periodic images of a sensor the job asks for; without it the route's default, cam_images = -1)
                 if get('Rad_nimg') is not None:
                     nimg = float(np.ravel(get('Rad_nimg'))[0])

@@ -47,6 +47,7 @@ _SIGNATURES = [
     ('mi3d_set_views'          , C.c_int   , [C.c_void_p, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int, C.c_int]),
     ('mi3d_set_cameras'        , C.c_int   , [C.c_void_p, C.c_int] + [_dp]*10 + [C.c_int, C.c_int]),
     ('mi3d_set_camera_map'     , C.c_int   , [C.c_void_p, C.c_int, C.c_int]),
+    ('mi3d_set_camera_method'  , C.c_int   , [C.c_void_p, C.c_int]),
     ('mi3d_set_options'        , C.c_int   , [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int]),
     ('mi3d_set_le_roulette'    , C.c_int   , [C.c_void_p, C.c_double]),
     ('mi3d_set_le_weight_roulette', C.c_int, [C.c_void_p, C.c_double]),
@@ -80,6 +81,7 @@ _SIGNATURES = [
     ('mi3d_debug_order'        , C.c_int   , [C.c_void_p, _u64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int]),
     ('mi3d_debug_entry'        , C.c_int   , [C.c_void_p, _u64, _fp]),
     ('mi3d_debug_thermal'      , C.c_int   , [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), _u64]),
+    ('mi3d_debug_backward'     , C.c_int   , [C.c_void_p, _u64, _u64, C.c_int, _fp, _dp, C.POINTER(_u64)]),
     ('mi3d_debug_phase_tables' , C.c_int   , [C.c_void_p, C.c_int, C.c_int, _fp, _fp, _fp, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]),
     ('mi3d_debug_phase'        , C.c_int   , [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp]),
 ]
@@ -270,6 +272,14 @@ class Mi3dSolver:
         """cameras' pixel map (Rad_mpmap: 1 polar, 2 rectangular) and weighting (Rad_mrproj: 0 mean radiance, 1 cosine-weighted)"""
         self._chk(self.lib.mi3d_set_camera_map(self._h, int(mpmap), int(mrproj)))
 
+    def set_camera_method(self, method='forward'):
+        """how the cameras and point radiometers of a thermal job are served (include/mi3d.h: mi3d_set_camera_method): 'forward' (0), the
+        local estimates of forward photons, or 'backward' (1), histories that start at the sensor"""
+        m = {'forward': 0, 'backward': 1}.get(method, method)
+        if m not in (0, 1):
+            raise ValueError('Error [Mi3dSolver]: <method=%r> must be \'forward\' (0) or \'backward\' (1).' % (method,))
+        self._chk(self.lib.mi3d_set_camera_method(self._h, int(m)))
+
     def set_options(self, target=TARGET_FLUX, solver=0, wmin=0.2, wfac=1.0, column_le=True):
         self._chk(self.lib.mi3d_set_options(self._h, int(target), int(solver), float(wmin), float(wfac), 1 if column_le else 0))
 
@@ -307,6 +317,7 @@ class Mi3dSolver:
             self.set_tuning(cam_images=int(getattr(s, 'cam_images', -1)))
         else:
             self.set_views(s.view_the, s.view_phi, s.view_zloc, zref=s.zref, nxr=s.nxr, nyr=s.nyr)
+        self.set_camera_method(int(getattr(s, 'cam_method', 0)))
         self.set_options(s.target, s.solver, s.wmin, s.wfac, column_le)
         self.set_heating_estimator(int(getattr(s, 'heat_estimator', 0)))
         self.set_le_roulette(getattr(s, 'le_tau1', 0.0))
@@ -478,6 +489,13 @@ class Mi3dSolver:
         ptot = C.c_double(0.0); cdf = np.zeros(int(ncell), dtype=np.float64)
         self._chk(self.lib.mi3d_debug_thermal(self._h, C.byref(ptot), cdf.ctypes.data_as(C.POINTER(C.c_double)), int(ncell)))
         return float(ptot.value), cdf
+
+    def debug_backward(self, seed, id0, n):
+        """test hook of the backward route: (directions (n, 3) float32 away from the sensor, scores (n,) float64 as they enter the raw
+        tally, capped histories of the runs since the last reset) for the ids id0 .. id0 + n - 1 (include/mi3d.h: mi3d_debug_backward)"""
+        d = np.zeros((int(n), 3), dtype=np.float32); sc = np.zeros(int(n), dtype=np.float64); cap = _u64(0)
+        self._chk(self.lib.mi3d_debug_backward(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(id0), int(n), _ptr(d), _ptr(sc, _dp), C.byref(cap)))
+        return d, sc, int(cap.value)
 
     def debug_phase_tables(self, nang, npf):
         """test hook: the device's phase tables after set_phase + prepare: (mu [nang], p [npf, nang], cdf [npf, nang]) float32 and the

@@ -255,7 +255,8 @@ int mi3d_set_views(mi3d_solver *h, int nview, const double *the_deg, const doubl
  *   Solar+thermal jobs (mi3d_set_thermal 2) with cameras: MI3D_EUNSUP from mi3d_run -- their direct sun would need a second
  *              normalisation.
  *   The 1 / r^2 of an event inside the medium around a sensor is bounded by the Rad_apsize clamp alone: a sensor inside an
- *              absorbing layer reads low by the order of ka x apsize x B (what the clamp removes) and its noise is heavy-tailed. */
+ *              absorbing layer reads low by the order of ka x apsize x B (what the clamp removes) and its noise is heavy-tailed.
+ *              mi3d_set_camera_method 1 serves the same sensors backwards, without the clamp and without cam_images. */
 int mi3d_set_cameras(mi3d_solver *h, int ncam, const double *the_deg, const double *phi_deg, const double *psi_deg,
                      const double *xpos, const double *ypos, const double *zloc, const double *qmax_deg,
                      const double *umax_deg, const double *vmax_deg, const double *apsize, int nxr, int nyr);
@@ -272,6 +273,44 @@ int mi3d_set_cameras(mi3d_solver *h, int ncam, const double *the_deg, const doub
  *            cancels direction by direction and the image equals that of mrproj 0.
  * mi3d_get_radiance holds the scattered light only, for every map: the direct sun is mi3d_get_camera_direct. */
 int mi3d_set_camera_map(mi3d_solver *h, int mpmap, int mrproj);
+
+/* How the cameras and point radiometers of a THERMAL job are served: 0 (default) the forward route above, 1 backward (adjoint) Monte
+ * Carlo (er3t_amd/csrc/mi3d_kernel_backward.hip; the project's namelist key Rad_mbwd = 1).  A history starts at the
+ * sensor and flies backwards along a line of sight; it collects ka B(T) along its path and eps B(Ts) at the surface.  No 1 / r^2, no
+ * Rad_apsize clamp -- a sensor may stand inside an absorbing or cloudy cell --, and no cam_images / Rad_nimg: a line of sight wraps
+ * through the cyclic domain, all of which is seen.  The forward route is untouched by the choice.
+ *   Served     Src_mtype = 3, cameras (Rad_mrkind = 1), the 3-D solver, Lambertian surfaces (uniform or 2-D, Sfc_tmps2d included): the
+ *              limits of the forward thermal cameras.  Solar and solar+thermal jobs, satellite views, flux jobs, independent columns,
+ *              partial 3-D and non-Lambertian surfaces: MI3D_EUNSUP from mi3d_run, with the reason.  A sensor on or below the surface:
+ *              MI3D_EINVAL.  mi3d_last_kernel: "k_backward<C> [thermal]".
+ *   Pixel      npix = nview nyr nxr; history id belongs to the flat pixel p = id mod npix in the layout of the radiance tally: stratified,
+ *              so that a near-uniform radiance field keeps its near-zero variance.  The ids of a job are expected to cover
+ *              [0, nphoton_total): mi3d_get_radiance and mi3d_stats_add divide pixel p, on the device, by the exact number of ids in
+ *              that range that map to it, floor(N / npix) + (p < N mod npix); a pixel with none reads 0.  Raw tallies add over id
+ *              ranges and ranks as for every other job.
+ *   Direction  Philox block 0 of (seed, id): u0, u1 place the line of sight inside the pixel with the pixel's own weight, so that a score
+ *              is an unbiased sample of the pixel value as the forward route defines it.  Polar map: (U, V) uniform over the pixel's
+ *              square, theta = hypot(U, V), phi = atan2(V, U).  Rectangular map: phi uniform over the row; cos(theta) uniform over the
+ *              column (Rad_mrproj = 0) or sin^2(theta) (Rad_mrproj = 1).  Outside the cone Rad_qmax / 2 or theta > pi: the score is 0.
+ *   Start      at the sensor, in the cell that contains it (on a level or a cell face the direction decides); a sensor above the top
+ *              starts where its line enters the top, folded into the domain, and scores 0 if it never enters.
+ *   Flight     the free path is sampled from the SCATTERING coefficient alone (block c: u0 -> -ln u0); absorption is continuous: a
+ *              segment of length l inside one cell adds w B (1 - exp(-ka l)) and then w *= exp(-ka l), with exactly the ka and T of the
+ *              forward source (total extinction - total scattering of the float32 records; layer-mean temperature + Atm_tmpa3d), rounded
+ *              to float32 once.  Segments end at voxel faces inside the 3-D region (its uniform layers included: Atm_tmpa3d may vary),
+ *              at levels outside it.
+ *   Events     scattering: the constituent in proportion to k_s (u1), cos of the angle from its phase function (u2), azimuth (u3).
+ *              Surface: the score gets w eps B(Ts), w *= albedo, the new direction follows the cosine law and comes from the NEXT block
+ *              (u0, u1; u2 its roulette).  Top: the history ends, space is cold.  The roulette after a scattering takes u0 of a block
+ *              of its own, drawn only when it is played.  Blocks are consumed in sequence; (seed, id) -> score depends on nothing else.
+ *   Ending     the weight roulette (Pho_wmin, Pho_wfac) is played after a scattering or a reflection only: a scene that never scatters over
+ *              a black surface is deterministic given the direction.  A history whose weight falls below 1e-7 ends: a bias of at most
+ *              1e-7 max B, below float32 resolution.  A history that has taken 2^20 cell steps ends and is counted as CAPPED
+ *              (mi3d_debug_backward): a near-horizontal line through an empty layer would not end otherwise; for a hemispheric sensor in a
+ *              gap of height dz the share lost is of the order of (dz / (2^20 dx))^2 of an irradiance.
+ *   Units      those of the forward thermal cameras: absolute pixel-mean radiance in W m-2 sr-1 um-1 (the score carries Src_flx).
+ *              mi3d_get_camera_direct stays zeros.  Counters (counting builds): photons = histories, steps, steps3d, scatter, surface. */
+int mi3d_set_camera_method(mi3d_solver *h, int method);
 
 /* Job options = 1st/2nd CLI arguments and keys Wld_mtarget, Flx_mflx, Pho_wmin
  * (er3t/rtm/mca/mcarats.py:267-287,450-454; er3t/rtm/mca/mca_inp.py:196-198).
@@ -368,7 +407,9 @@ int mi3d_sync(mi3d_solver *h);
  * records, "k_transport_flux<COUNT,P3D,MIX> + k_tl_scatter + k_tl_sum": flux jobs -- MIX 0: one 1-D and one 3-D constituent with
  * analytic phase functions (er3t's default scene), 1: a second 3-D constituent, 2: the general mixture (several 1-D constituents,
  * tabulated phase functions staged in LDS) --, "k_transport<COUNT,MARCH,FLUX,P3D>": the general kernel (flux together with radiance,
- * more than two 3-D constituents, tables too large for the LDS, kernel choice 1); "" before the first launch).  For logs and
+ * more than two 3-D constituents, tables too large for the LDS, kernel choice 1); "k_backward<COUNT> [thermal]": the backward route of
+ * mi3d_set_camera_method 1, whatever mi3d_set_kernel says -- "batch_log2" is the one tuning knob it reads (ids per launch; a launch is
+ * min(ids / 256, what is resident at once: 5 per CU, 4 in the counting build) workgroups of 256 lanes, every lane walks its ids with a fixed stride); "" before the first launch).  For logs and
  * measurements (bench.py, profiles/): results do not depend on it. */
 const char *mi3d_last_kernel(mi3d_solver *h);
 /* Which build of the transport kernel may serve a launch: 0 (default) the lean ones wherever they apply -- marched satellite
@@ -526,6 +567,12 @@ int mi3d_debug_entry(mi3d_solver *h, uint64_t n, float *records_out);
  * inclusive CDF of the cells' emitted power in float64, n = its number of cells (voxels, 1-D layers, surface cells: otherwise
  * MI3D_EINVAL).  MI3D_ESTATE when the job is not thermal or its source is not built yet. */
 int mi3d_debug_thermal(mi3d_solver *h, double *ptot, double *cdf_out, uint64_t n);
+/* Test hook of the backward route (mi3d_set_camera_method 1; MI3D_ESTATE otherwise): single histories.  For ids id0 .. id0 + n - 1 under
+ * `seed`: dir_out [n][3] the world-space direction of the line of sight AWAY from the sensor (also where the score is 0: outside the
+ * cone), score_out [n] what the history adds to the raw tally of pixel id mod npix (Src_flx x the sum, not divided by anything).  Nothing
+ * is tallied.  capped_out (if not NULL): the histories of this handle's runs since the last mi3d_reset that ended at 2^20 cell steps;
+ * n = 0 asks for it alone. */
+int mi3d_debug_backward(mi3d_solver *h, uint64_t seed, uint64_t id0, int n, float *dir_out, double *score_out, uint64_t *capped_out);
 /* Test hook: the phase tables as they stand on the device after mi3d_set_phase + mi3d_prepare (each pointer may be NULL): mu [nang]
  * ascending, p and cdf [npf][nang] (float32, normalised), the bucket index of mu [MI3D_TAB_IDX_N] and those of the CDFs
  * [npf][MI3D_TAB_IDX_N] (uint16).  nang / npf must be the loaded ones (otherwise MI3D_EINVAL); MI3D_ESTATE when no table is loaded or

@@ -16,6 +16,13 @@ like-for-like comparison of the two.  Its rows carry the mean reading of the six
     python tools/thermal_rate.py [--photons 5e7] [--reps 3] [--legs radiance,flux,heat,heat_path]
     python tools/thermal_rate.py --legs mix,mix_thermal,mix_solar
     python tools/thermal_rate.py --legs cam --photons 1e7
+
+Leg 'bwd' (DESIGN.md 5.11): the same sixteen sensors by backward Monte Carlo (cam_method = 1) and, in the same session, by the forward
+route with cam_images = 2: histories (photons) per second, the relative standard error of every sensor's reading over 16 batches (mean
+and largest over the sensors) and the figure of merit 1 / (se^2 t), se the mean relative standard error of a sensor and t the kernel
+time of the 16 batches.  --photons: photons per forward batch; --histories: histories per backward batch (a multiple of 16).
+
+    python tools/thermal_rate.py --legs bwd --photons 1e7 --histories 1.6e6
 """
 
 import argparse
@@ -50,11 +57,42 @@ def pyrgeometers(scene, images, n=4, z=1.0):
                                nxr=1, nyr=1, cam_mpmap=2, cam_mrproj=1, cam_images=images)
 
 
+def merit_rows(sol, name, s, n_fwd, n_bwd, nb=16):
+    """the 'bwd' leg: the sensors of scene s by the backward and by the forward route, nb batches each over disjoint id ranges"""
+    rows = []
+    for target, method, n in (('bwd', 1, n_bwd), ('bwd_forward', 0, n_fwd)):
+        sc = dataclasses.replace(s, cam_method=method)
+        sol.load_scene(sc)
+        sol.reset(); sol.run(min(n, 2000000), seed=1); sol.sync()        # warm-up
+        vals, ms_all = [], 0.0
+        for b in range(nb):
+            sol.reset()
+            sol.run(n, seed=2, offset=b*n)
+            vals.append(np.pi*sol.radiance(n).astype(np.float64).ravel())
+            ms_all += sol.timing()[0]
+        v = np.array(vals)
+        mean, se = v.mean(axis=0), v.std(axis=0, ddof=1)/np.sqrt(nb)
+        rel = se/mean
+        t = ms_all*1e-3
+        row = dict(scene=name, target=target, kernel=sol.kernel_name(), histories_per_batch=n, batches=nb, histories_per_s=float(nb*n/t),
+                   kernel_s=float(t), f_down_sensor_mean=float(mean.mean()), rel_se_mean=float(rel.mean()), rel_se_max=float(rel.max()),
+                   merit=float(1.0/(rel.mean()**2*t)))
+        if method == 1:
+            row['capped'] = sol.debug_backward(2, 0, 0)[2]
+        else:
+            row['cam_images'] = sc.cam_images
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    sol.set_camera_method('forward')
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--photons', type=float, default=5e7)
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--legs', default='radiance,flux,heat,heat_path')
+    ap.add_argument('--histories', type=float, default=1.6e6)
     a = ap.parse_args()
     sol = Mi3dSolver(0)
     n = int(a.photons)
@@ -66,6 +104,10 @@ def main():
         legs = sum([['cam', 'cam0', 'cam0_general'] if t == 'cam' else [t] for t in a.legs.split(',')], [])
         for target in legs:
             general = False
+            if target == 'bwd':
+                sol.set_kernel(general=False)
+                rows += merit_rows(sol, name, pyrgeometers(thermal(les_scene(target='radiance', **kw), lev), 2), n, int(a.histories)//16*16)
+                continue
             if target in ('cam', 'cam0', 'cam0_general'):
                 s = pyrgeometers(thermal(les_scene(target='radiance', **kw), lev), 2 if target == 'cam' else 0)
                 general = target == 'cam0_general'
