@@ -77,6 +77,8 @@ struct DevBuf {
     }
 };
 
+constexpr double kWgtMaxElems = 2147483648.0;   // elements of the emission weights' tally npix x ncell served (mi3d_set_emission_weights)
+
 } // namespace
 
 struct mi3d_solver {
@@ -124,6 +126,20 @@ struct mi3d_solver {
     DevBuf<double> d_bwd_norm, d_bwd_score;
     DevBuf<float> d_bwd_dir;
     bool backward() const { return cam_method == 1 && src_mtype == 3 && rad_kind == 1 && nview > 0; }   // does the read-out divide by the pixels' own counts?
+    // per-cell emission weights of the backward route (mi3d_set_emission_weights 1): K_raw[npix][ncell], the library's own
+    // buffer (wgt_n elements, zeroed when it is made; 0: to be made or cleared by the next run) or the caller's (mi3d_bind_weights_buffer)
+    int emis_weights = 0;
+    int wgt_stage = -1;              // mi3d_set_tuning "wgt_stage": -1 the layer and surface part is summed in LDS where it fits, 0 never
+    int wgt_staged_last = 0;         // what the last launch of the weights build did
+    DevBuf<double> d_wgt_own;
+    DevBuf<float> d_wgt_out;         // the read-out's staging buffer
+    double *wgt_ext = nullptr;
+    size_t wgt_n = 0;
+    int wgt_cap = 0;                 // resident workgroups per CU of the weights build, as the runtime reports them for wgt_cap_lds bytes of LDS (0: not asked yet)
+    size_t wgt_cap_lds = 0;
+    int wgt_cap_counting = -1;
+    double *wgt_ptr() { return wgt_ext ? wgt_ext : d_wgt_own.p; }
+    size_t wgt_ncell() const { return (size_t)nx * ny * nz3 + (size_t)nz + (sfc2d_host.empty() ? (size_t)1 : (size_t)nxb * nyb); }
     int nview = 0, nxr = 1, nyr = 1;
     double view_the[MI3D_MAX_VIEW], view_phi[MI3D_MAX_VIEW], view_zloc[MI3D_MAX_VIEW], zref = 0.0;
     // cameras (mi3d_set_cameras): rad_kind 1, the views are point sensors
@@ -895,6 +911,7 @@ int mi3d_destroy(mi3d_solver *h) {
     for (int w = 0; w < 2; ++w) { h->d_run_own[w].release(); h->d_sum[w].release(); h->d_sumsq[w].release(); h->d_factor[w].release(); }
     h->d_stat_out.release(); h->d_dir_level.release(); h->d_get_out.release(); h->d_get_add.release();
     h->d_th_tlev.release(); h->d_th_tmpa.release(); h->d_th_tmps.release(); h->d_th_cdf.release(); h->d_th_bsum.release(); h->d_th.release();
+    h->d_wgt_own.release(); h->d_wgt_out.release();
     h->d_bwd_cells.release(); h->d_bwd_capped.release(); h->d_bwd_norm.release(); h->d_bwd_score.release(); h->d_bwd_dir.release();
     h->d_views.release(); h->d_cold.release(); h->d_tabrange.release(); h->d_bt1d.release(); h->d_dz.release(); h->d_bmin.release(); h->d_bmax.release();
     delete h;
@@ -1123,6 +1140,27 @@ int mi3d_set_camera_method(mi3d_solver *h, int method) {
     return MI3D_OK;
 }
 
+int mi3d_set_emission_weights(mi3d_solver *h, int on) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (on != 0 && on != 1) return fail(MI3D_EINVAL, "emission weights %d (0: off, 1: per-cell weights of the backward route)", on);
+    if (on == h->emis_weights) return MI3D_OK;
+    HIPCHK(sync_main(h));   // (as every call that changes what the kernels work on)
+    h->emis_weights = on;
+    if (!on) { h->d_wgt_own.release(); h->d_wgt_out.release(); h->wgt_n = 0; }   // (gigabytes, for a large job)
+    return MI3D_OK;
+}
+
+int mi3d_bind_weights_buffer(mi3d_solver *h, void *wgt_sum) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if ((double *)wgt_sum == h->wgt_ext) return MI3D_OK;
+    HIPCHK(sync_main(h));
+    h->wgt_ext = (double *)wgt_sum;
+    if (!wgt_sum) h->wgt_n = 0;   // (the library's own buffer is made anew, and zeroed, by the next run)
+    return MI3D_OK;
+}
+
 int mi3d_set_camera_map(mi3d_solver *h, int mpmap, int mrproj) {
     int rc = check_handle(h);
     if (rc) return rc;
@@ -1319,6 +1357,7 @@ int mi3d_prepare(mi3d_solver *h) {
             if ((rc = h->d_heat_own.alloc(h->heat_elems()))) return rc;
             HIPCHK(hipMemsetAsync(h->d_heat_own.p, 0, h->heat_elems() * sizeof(double), h->stream));
         }
+        h->wgt_n = 0;   // (the emission weights' own buffer: made and zeroed by the next run that tallies them, run_backward)
         h->dirty_tally = false;
     }
     if (h->thermal() && h->dirty_thermal) {
@@ -1349,6 +1388,11 @@ int mi3d_reset(mi3d_solver *h) {
     if ((h->target & MI3D_TARGET_HEAT) && h->heat_ptr()) HIPCHK(hipMemsetAsync(h->heat_ptr(), 0, h->heat_elems() * sizeof(double), h->stream));
     HIPCHK(hipMemsetAsync(h->d_counters.p, 0, MI3D_NCOUNTER * sizeof(unsigned long long), h->stream));
     if (h->d_bwd_capped.p) HIPCHK(hipMemsetAsync(h->d_bwd_capped.p, 0, sizeof(unsigned long long), h->stream));
+    if (h->emis_weights) {
+        const double ne = (double)h->nview * h->nxr * h->nyr * (double)h->wgt_ncell();
+        if (h->wgt_ext) { if (h->backward() && ne <= kWgtMaxElems) HIPCHK(hipMemsetAsync(h->wgt_ext, 0, (size_t)ne * sizeof(double), h->stream)); }
+        else if (h->wgt_n) HIPCHK(hipMemsetAsync(h->d_wgt_own.p, 0, h->wgt_n * sizeof(double), h->stream));
+    }
     // (the accumulation image is folded and zeroed at the end of a successful mi3d_run; a run that failed half way -- an event
     //  list ran full, a launch failed -- leaves its partial tallies there)
     if (h->d_rad_acc.p) HIPCHK(hipMemsetAsync(h->d_rad_acc.p, 0, h->d_rad_acc.cap * sizeof(tally_t), h->stream));
@@ -1853,7 +1897,8 @@ static void name_route(mi3d_solver *h, const RunPlan &plan, bool lists, uint64_t
     const int c = h->counting ? 1 : 0, p3d = h->solver == MI3D_SOLVER_P3D ? 1 : 0;
     char nm[96];
     const bool hpath = (h->target & MI3D_TARGET_HEAT) && h->heat_estimator == 1;
-    if (plan.loop == Loop::Backward) snprintf(nm, sizeof(nm), "k_backward<%d> [thermal]", c);
+    if (plan.loop == Loop::Backward && h->emis_weights) snprintf(nm, sizeof(nm), "k_backward<%d,W> [thermal]", c);
+    else if (plan.loop == Loop::Backward) snprintf(nm, sizeof(nm), "k_backward<%d> [thermal]", c);
     else if (plan.loop == Loop::Flux && hpath) snprintf(nm, sizeof(nm), lists ? "k_transport_flux<%d,%d,%d,1> + k_tl_scatter + k_tl_sum" : "k_transport_flux<%d,%d,%d,1>", c, p3d, plan.mix);
     else if (plan.loop == Loop::Flux) snprintf(nm, sizeof(nm), lists ? "k_transport_flux<%d,%d,%d> + k_tl_scatter + k_tl_sum" : "k_transport_flux<%d,%d,%d>", c, p3d, plan.mix);
     else if (plan.loop == Loop::ColumnRays && plan.thermal) snprintf(nm, sizeof(nm), "k_transport<%d,2,0,0> [thermal] + k_rays", c);
@@ -2354,10 +2399,37 @@ static int run_backward(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_
     h->entry_form_last = 0;
     h->runs_unread++;
     const int npix = h->nview * h->nxr * h->nyr;
-    const size_t lds = backward_lds(npix, h->nz, h->nview, false);
+    size_t lds = backward_lds(npix, h->nz, h->nview, false);
     // workgroups of 256 lanes, as many as are resident at once (five waves per SIMD, four in the counting build: the register report in
     // DESIGN.md §5.11): every lane walks its ids with a fixed stride, and a workgroup that had to queue would start when the others are through
-    const uint64_t cap = (uint64_t)h->num_cu * (h->counting ? 4 : 5);
+    uint64_t cap = (uint64_t)h->num_cu * (h->counting ? 4 : 5);
+    const bool wgt = h->emis_weights != 0;
+    BwdWeights W{};
+    if (wgt) {
+        // the weights build: its tally, made and zeroed here when it is the library's own; the launch's LDS; and the
+        // resident workgroups per CU from the build's own registers and that LDS, as the runtime works them out
+        W.ncell = (unsigned long long)h->wgt_ncell();
+        W.nls = (int)(W.ncell - A.nvox);
+        const double ne = (double)npix * (double)W.ncell;
+        if (ne > kWgtMaxElems)
+            return fail(MI3D_EUNSUP, "emission weights (mi3d_set_emission_weights 1): %d pixels x %llu cells are more than the 2^31 elements served", npix, W.ncell);
+        if (!h->wgt_ext && h->wgt_n != (size_t)ne) {
+            if ((rc = h->d_wgt_own.alloc((size_t)ne))) return rc;
+            HIPCHK(hipMemsetAsync(h->d_wgt_own.p, 0, (size_t)ne * sizeof(double), h->stream));
+            h->wgt_n = (size_t)ne;
+        }
+        W.K = h->wgt_ptr();
+        lds = backward_lds_w(npix, h->nz, h->nview, W.nls, h->wgt_stage != 0, W.stage);
+        h->wgt_staged_last = W.stage;
+        if (!h->wgt_cap || h->wgt_cap_lds != lds || h->wgt_cap_counting != h->counting) {
+            int nb = 0;
+            const hipError_t eo = h->counting ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_backward_w<true>, 256, lds)
+                                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_backward_w<false>, 256, lds);
+            if (eo != hipSuccess || nb < 1) return fail(MI3D_EDEVICE, "emission weights: no workgroup of the weights build fits a CU with %zu bytes of LDS", lds);
+            h->wgt_cap = nb; h->wgt_cap_lds = lds; h->wgt_cap_counting = h->counting;
+        }
+        cap = (uint64_t)h->num_cu * (uint64_t)h->wgt_cap;
+    }
     for (uint64_t done = 0; done < nphoton; done += h->batch) {
         const uint64_t nb = std::min<uint64_t>(h->batch, nphoton - done), off = photon_offset + done;
         if (h->pending.size() >= 64 && (rc = drain_events(h))) return rc;
@@ -2368,7 +2440,9 @@ static int run_backward(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_
         hipError_t err = hipEventCreate(&e1);
         if (err == hipSuccess) err = hipEventRecord(e0, h->stream);
         if (err == hipSuccess) {
-            if (h->counting) hipLaunchKernelGGL((k_backward<true, false>), dim3(grid), dim3(256), lds, h->stream, A, seed, off, nb, (float *)nullptr, (double *)nullptr);
+            if (wgt && h->counting) hipLaunchKernelGGL((k_backward_w<true>), dim3(grid), dim3(256), lds, h->stream, A, seed, off, nb, W);
+            else if (wgt) hipLaunchKernelGGL((k_backward_w<false>), dim3(grid), dim3(256), lds, h->stream, A, seed, off, nb, W);
+            else if (h->counting) hipLaunchKernelGGL((k_backward<true, false>), dim3(grid), dim3(256), lds, h->stream, A, seed, off, nb, (float *)nullptr, (double *)nullptr);
             else hipLaunchKernelGGL((k_backward<false, false>), dim3(grid), dim3(256), lds, h->stream, A, seed, off, nb, (float *)nullptr, (double *)nullptr);
             err = hipGetLastError();
         }
@@ -2404,6 +2478,8 @@ int mi3d_run(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_of
     if (rc) return rc;
     if ((rc = mi3d_prepare(h))) return rc;
     if (h->cam_method == 1) return run_backward(h, nphoton, seed, photon_offset);
+    if (h->emis_weights)
+        return fail(MI3D_EUNSUP, "emission weights (mi3d_set_emission_weights 1) are tallied by the backward route alone (mi3d_set_camera_method 1)");
     if ((h->target & MI3D_TARGET_RADIANCE) && h->nview == 0)
         return fail(MI3D_ESTATE, "radiance requested but no view is set (mi3d_set_views)");
     if ((h->target & MI3D_TARGET_RADIANCE) && h->rad_kind == 1 && h->solver != MI3D_SOLVER_3D)
@@ -2623,6 +2699,7 @@ int mi3d_set_tuning(mi3d_solver *h, const char *key, int value) {
     else if (k == "overlap_sort") { if (value < 0 || value > 2) return fail(MI3D_EINVAL, "overlap_sort=%d outside [0,2]", value); HIPCHK(sync_streams(h)); h->overlap_sort = value; if (!value) h->tl[1].release(); }
     else if (k == "tl_split") { if (value < 1 || value > 64) return fail(MI3D_EINVAL, "tl_split=%d outside [1,64]", value); h->tl_split = value; }
     else if (k == "rays_wg" || k == "emit_wg") { if (value < 0 || value > 8) return fail(MI3D_EINVAL, "%s=%d outside [0,8]", key, value); (k == "rays_wg" ? h->rays_wg : h->emit_wg) = value; }
+    else if (k == "wgt_stage") { HIPCHK(sync_main(h)); h->wgt_stage = value ? -1 : 0; }   // (0: the emission weights' layer and surface part goes to global atomics always)
     else if (k == "cam_images") { if (value < -1 || value > 8) return fail(MI3D_EINVAL, "cam_images=%d outside [-1,8]", value); h->cam_images = value; }
     else if (k == "entry_records") { if (value < 0 || value > 2) return fail(MI3D_EINVAL, "entry_records=%d outside [0,2]", value); HIPCHK(sync_main(h)); h->entry_records = value; if (!value) h->pre[0].entry.release(); }
     else if (k == "tally_runs") { HIPCHK(sync_main(h)); h->tally_runs = value ? 1 : 0; h->tl_per_photon = 0.0; h->tl_total_pp = 0.0; h->tl_runs_pp = 0.0; if (!value) for (auto &T : h->tl) T.runs.release(); }
@@ -3039,6 +3116,47 @@ int mi3d_debug_backward(mi3d_solver *h, uint64_t seed, uint64_t id0, int n, floa
     HIPCHK(hipStreamSynchronize(h->stream));
     return MI3D_OK;
 }
+
+// Read-out of the emission weights (mi3d_set_emission_weights 1): the rows of K_raw by the rule of k_backward_norm, rounded to
+// float32 on the device and brought over through a staging buffer of at most 2^26 elements; planck: cells[c].y as the kernel read it
+int mi3d_get_emission_weights(mi3d_solver *h, uint64_t nphoton_total, float *weights, float *planck) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (!weights) return fail(MI3D_EINVAL, "bad arguments to mi3d_get_emission_weights");
+    if (!h->emis_weights) return fail(MI3D_ESTATE, "mi3d_get_emission_weights: the weights are not tallied (mi3d_set_emission_weights 1)");
+    if (!h->backward()) return fail(MI3D_ESTATE, "mi3d_get_emission_weights: the backward route is not serving this job (mi3d_set_camera_method 1, Src_mtype=3, cameras)");
+    if ((rc = mi3d_prepare(h))) return rc;
+    const unsigned long long npix = (unsigned long long)h->nview * h->nxr * h->nyr, ncell = (unsigned long long)h->wgt_ncell();
+    if ((double)npix * (double)ncell > kWgtMaxElems)
+        return fail(MI3D_EUNSUP, "emission weights (mi3d_set_emission_weights 1): %llu pixels x %llu cells are more than the 2^31 elements served", npix, ncell);
+    const unsigned long long ne = npix * ncell;
+    HIPCHK(sync_main(h));
+    const double *K = h->wgt_ptr();
+    if (!K || (!h->wgt_ext && h->wgt_n != (size_t)ne)) {      // (nothing has been tallied for this scene yet)
+        std::memset(weights, 0, (size_t)ne * sizeof(float));
+    } else {
+        const unsigned long long chunk = std::min<unsigned long long>(ne, 1ull << 26);
+        if ((rc = h->d_wgt_out.alloc((size_t)chunk))) return rc;
+        for (unsigned long long e0 = 0; e0 < ne; e0 += chunk) {
+            const unsigned long long nn = std::min(chunk, ne - e0);
+            const unsigned grid = (unsigned)std::min<unsigned long long>((nn + 255) / 256, 65536);
+            hipLaunchKernelGGL(k_backward_norm_rows, dim3(grid), dim3(256), 0, h->stream, K, h->d_wgt_out.p, (unsigned long long)nphoton_total, (unsigned)npix, ncell, e0, nn);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(weights + e0, h->d_wgt_out.p, (size_t)nn * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipStreamSynchronize(h->stream));
+        }
+    }
+    if (planck) {
+        if (!h->d_bwd_cells.p) return fail(MI3D_ESTATE, "mi3d_get_emission_weights: the cells' Planck radiances have not been built");
+        std::vector<float2> cells((size_t)ncell);
+        HIPCHK(hipMemcpyAsync(cells.data(), h->d_bwd_cells.p, (size_t)ncell * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        for (size_t c = 0; c < (size_t)ncell; ++c) planck[c] = cells[c].y;
+    }
+    return MI3D_OK;
+}
+
+int mi3d_debug_weights_staged(mi3d_solver *h) { return h ? h->wgt_staged_last : 0; }
 
 int mi3d_debug_phase_tables(mi3d_solver *h, int nang, int npf, float *mu, float *p, float *cdf, uint16_t *mu_idx, uint16_t *cdf_idx) {
     int rc = check_handle(h);

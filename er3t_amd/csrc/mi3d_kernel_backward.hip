@@ -11,7 +11,10 @@
 //   k_backward<COUNT, DEBUG>   the histories: one lane owns one, one cell step per trip of the loop, a lane whose history has ended takes
 //                      its next id in the same trip.  DEBUG: mi3d_debug_backward -- the same code, direction and score of every id written out
 //                      instead of tallied
+//   k_backward_w<COUNT>   the same histories with mi3d_set_emission_weights 1: every term w (1 - exp(-ka l)) and w eps
+//                      that a history scores is also added to K_raw[pixel][cell], float64
 //   k_backward_norm    read-out: tally of pixel p / number of ids in [0, N) that map to p
+//   k_backward_norm_rows   the same rule for the rows of K_raw, rounded to float32
 //
 // Philox blocks of history (seed, id), counter (id, block), consumed in sequence; block 0 is the direction, every later decision takes
 // the NEXT block when it comes up:
@@ -46,6 +49,14 @@ struct DevBackward {
     double *rad;                       // [nview][nyr][nxr] raw sums
     unsigned long long *counters;      // [MI3D_NCOUNTER]
     unsigned long long *capped;        // histories ended by kBwdMaxCells
+};
+
+// What only the weights build receives (mi3d_set_emission_weights 1): the tally K_raw[npix][ncell] and how its layer and surface part
+// (nls = nz + nxb nyb cells per pixel) is summed -- stage: per workgroup in LDS, flushed once at the end; otherwise global atomics
+struct BwdWeights {
+    double *K;
+    unsigned long long ncell;
+    int nls, stage;
 };
 
 // One thread per cell, in the order of DevThermal's CDF (k_thermal_power): voxels in file order, layers, surface cells.
@@ -84,6 +95,17 @@ k_backward_norm(const double *__restrict__ tally, double *__restrict__ out, unsi
     const unsigned long long cnt = nphoton / npix + (p < nphoton % npix ? 1ull : 0ull);
     out[p] = cnt ? tally[p] / (double)cnt : 0.0;
 }
+// ... and for elements [e0, e0 + ne) of K_raw[npix][ncell]: element e belongs to pixel e / ncell
+__global__ void __launch_bounds__(256)
+k_backward_norm_rows(const double *__restrict__ K, float *__restrict__ out, unsigned long long nphoton, unsigned npix, unsigned long long ncell,
+                     unsigned long long e0, unsigned long long ne) {
+    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < ne; i += stride) {
+        const unsigned long long p = (e0 + i) / ncell;
+        const unsigned long long cnt = nphoton / npix + (p < nphoton % npix ? 1ull : 0ull);
+        out[i] = cnt ? (float)(K[e0 + i] / (double)cnt) : 0.0f;
+    }
+}
 
 // 1 - exp(-a) and exp(-a) for a >= 0: the series where the difference would cancel
 __device__ inline float bwd_absorb(const float a, float &e) {
@@ -99,245 +121,36 @@ __device__ inline int bwd_wrap(const int i, const float d, const int n) {
     return j < 0 ? 0 : (j >= n ? n - 1 : j);
 }
 
+// The histories, single-sourced for both entry points: mi3d_kernel_backward_body.inc is the body of either, with WGT a constant of the
+// entry point that includes it (and W the weights build's argument)
 template <bool COUNT, bool DEBUG>
 __global__ void __launch_bounds__(256)
 k_backward(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, float *__restrict__ dir_out, double *__restrict__ score_out) {
-    extern __shared__ double bwd_smem[];
-    const int npix = A.nview * A.nxr * A.nyr;
-    const bool lds_sums = !DEBUG && npix <= kBwdLdsPix;
-    double *sums = bwd_smem;
-    LayerRec *slay = reinterpret_cast<LayerRec *>(bwd_smem + (lds_sums ? ((npix + 1) & ~1) : 0));   // (16-byte aligned)
-    CamRec *scam = reinterpret_cast<CamRec *>(slay + A.nz);
-    if (lds_sums) for (int i = threadIdx.x; i < npix; i += blockDim.x) sums[i] = 0.0;
-    {   // layer table and cameras: 16-byte pieces
-        const float4 *src = reinterpret_cast<const float4 *>(A.lay);
-        float4 *dst = reinterpret_cast<float4 *>(slay);
-        for (int i = threadIdx.x; i < A.nz * 4; i += blockDim.x) dst[i] = src[i];
-        src = reinterpret_cast<const float4 *>(A.cams); dst = reinterpret_cast<float4 *>(scam);
-        for (int i = threadIdx.x; i < A.nview * 4; i += blockDim.x) dst[i] = src[i];
-    }
-    __syncthreads();
+    constexpr bool WGT = false;
+    const BwdWeights W{};
+#include "mi3d_kernel_backward_body.inc"
+}
 
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    uint64_t next = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;     // ids are handed out by a fixed stride
-    unsigned long long c_hist = 0, c_steps = 0, c_steps3d = 0, c_scat = 0, c_sfc = 0;
-
-    // the history's state
-    bool have = false;
-    uint64_t id = 0, slot = 0;
-    int pix = 0, ix = 0, iy = 0, k = 0;
-    float ux = 0.0f, uy = 0.0f, uz = 1.0f, tx = 0.0f, ty = 0.0f, tz = 0.0f, sx = 0.0f, sy = 0.0f, aiz = 0.0f;   // distances to the next x / y / z face, a cell's width along the line
-    float w = 0.0f, taus = 0.0f, r1 = 0.0f, r2 = 0.0f, r3 = 0.0f;
-    double score = 0.0;
-    uint32_t draw = 0;
-    unsigned steps = 0;
-
-    // the DDA anew from a position inside the cell (px, py from the low faces, pz from the layer's bottom) and the direction
-    auto set_dda = [&](const float px, const float py, const float pz, const float dzk) {
-        const float aix = frcp(floor_abs(ux)), aiy = frcp(floor_abs(uy));
-        aiz = frcp(floor_abs(uz));
-        sx = A.dx * aix; sy = A.dy * aiy;
-        tx = (ux > 0.0f ? A.dx - px : px) * aix;
-        ty = (uy > 0.0f ? A.dy - py : py) * aiy;
-        tz = (uz > 0.0f ? dzk - pz : pz) * aiz;
-    };
-    // the position inside the cell back from the DDA
-    auto pos_x = [&]() { const float d = tx * fabsf(ux); return fminf(fmaxf(ux > 0.0f ? A.dx - d : d, 0.0f), A.dx); };
-    auto pos_y = [&]() { const float d = ty * fabsf(uy); return fminf(fmaxf(uy > 0.0f ? A.dy - d : d, 0.0f), A.dy); };
-    auto new_flight = [&]() {
-        float u0;
-        draw4(seed, id, draw++, u0, r1, r2, r3);
-        taus = -__logf(u0);
-    };
-    // weight roulette (Pho_wmin, Pho_wfac) with the uniform number u: false: the history ends
-    auto roulette = [&](const float u) {
-        if (u * A.wfac < w) { w = A.wfac; return true; }
-        return false;
-    };
-
-    for (;;) {
-        bool ended = false;
-        if (!have) {
-            if (next >= n) break;
-            slot = next; id = id0 + next; next += stride;
-            have = true;
-            score = 0.0; w = 1.0f; steps = 0; draw = 1;
-            pix = (int)(id % (uint64_t)npix);
-            const int iv = pix / (A.nxr * A.nyr), rem = pix - iv * (A.nxr * A.nyr), jr = rem / A.nxr, ir = rem - jr * A.nxr;
-            const CamRec Cm = scam[iv];
-            float u0, u1, u2, u3;
-            draw4(seed, id, 0u, u0, u1, u2, u3);
-            float st, ct, ph;
-            bool ok = true;
-            if (!(A.cam_mode & kCamRect)) {
-                const float U = ((float)ir + u0 - 0.5f * (float)A.nxr) * frcp(Cm.inv_du), V = ((float)jr + u1 - 0.5f * (float)A.nyr) * frcp(Cm.inv_dv);
-                const float th = sqrtf(U * U + V * V);
-                ph = atan2f(V, U);
-                __sincosf(th, &st, &ct);
-                ok = th <= kPi;
-            } else {
-                const float du = 1.0f / Cm.inv_du, t0 = (float)ir * du, t1 = (float)(ir + 1) * du;
-                if (A.cam_mode & kCamCos) {
-                    const float s0 = sinf(t0), s1 = sinf(t1), s2 = fminf(fmaxf(fmaf(u0, s1 * s1 - s0 * s0, s0 * s0), 0.0f), 1.0f);
-                    st = sqrtf(s2); ct = sqrtf(1.0f - s2);
-                } else {
-                    const float c0 = cosf(t0), c1 = cosf(t1);
-                    ct = fminf(fmaxf(fmaf(u0, c1 - c0, c0), -1.0f), 1.0f);
-                    st = sqrtf(fmaxf(1.0f - ct * ct, 0.0f));
-                }
-                ph = ((float)jr + u1 - 0.5f * (float)A.nyr) / Cm.inv_dv;
-            }
-            float sp, cp;
-            sincosf(ph, &sp, &cp);
-            const float a = st * cp, b = st * sp;
-            ux = a * Cm.xx + b * Cm.yx + ct * Cm.zx;
-            uy = a * Cm.xy + b * Cm.yy + ct * Cm.zy;
-            uz = a * Cm.xz + b * Cm.yz + ct * Cm.zz;
-            const float nrm = 1.0f / sqrtf(ux * ux + uy * uy + uz * uz);
-            ux *= nrm; uy *= nrm; uz *= nrm;
-            if (DEBUG) { dir_out[3 * slot] = ux; dir_out[3 * slot + 1] = uy; dir_out[3 * slot + 2] = uz; }
-            if (!ok || ct < Cm.cos_half) ended = true;       // outside the image or the cone of view: 0
-            // where the history starts: the sensor, or where its line enters the top
-            float x = Cm.cx, y = Cm.cy, z = Cm.cz;
-            if (!ended && z >= A.ztoa) {
-                if (uz >= 0.0f) ended = true;                 // never enters
-                else { const float t = (z - A.ztoa) / -uz; x = fmaf(ux, t, x); y = fmaf(uy, t, y); z = A.ztoa; }
-            }
-            if (!ended) {
-                k = A.nz - 1;
-                if (z < A.ztoa) {
-                    k = 0;
-                    while (k < A.nz - 1 && z >= slay[k + 1].zlo) ++k;
-                    if (z == slay[k].zlo && uz < 0.0f && k > 0) --k;        // on a level: the direction decides the cell
-                }
-                float cfx = floorf(x * A.inv_dx), cfy = floorf(y * A.inv_dy);
-                float px = x - cfx * A.dx, py = y - cfy * A.dy;
-                if (px <= 0.0f && ux < 0.0f) { cfx -= 1.0f; px = A.dx; }    // on a face: likewise
-                if (py <= 0.0f && uy < 0.0f) { cfy -= 1.0f; py = A.dy; }
-                px = fminf(fmaxf(px, 0.0f), A.dx); py = fminf(fmaxf(py, 0.0f), A.dy);
-                ix = bwd_wrap(0, cfx, A.nx); iy = bwd_wrap(0, cfy, A.ny);
-                const float dzk = slay[k].dz;
-                set_dda(px, py, fminf(fmaxf(z - slay[k].zlo, 0.0f), dzk), dzk);
-                new_flight();
-            }
-        }
-        if (!ended) {
-            // ---- one cell step: the segment up to the next face (a level, outside the 3-D region) or to the end of the flight
-            const LayerRec &L = slay[k];
-            const bool in3d = (L.flags & kLayIn3d) != 0;
-            float ks = 0.0f, ks0 = 0.0f, apf0 = 0.0f;
-            float2 cell;
-            const int k3 = k - A.k3lo;
-            if (in3d) {
-                const float4 r = A.vrec[(size_t)iy * A.vrow_f4 + (size_t)ix * A.vcol_f4 + k3];
-                cell = A.cells[((size_t)k3 * A.ny + iy) * A.nx + ix];
-                ks0 = r.z; apf0 = r.w; ks = ks0;
-                for (int ip = 1; ip < A.np3d; ++ip) ks += A.csca[(((size_t)iy * A.nx + ix) * A.nz3 + k3) * A.np3d + ip].x;
-            } else cell = A.cells[A.nvox + k];
-            for (int ip = 0; ip < A.np1d; ++ip) ks += L.ks1d[ip];
-            const float dface = in3d ? fminf(fminf(tx, ty), tz) : tz;
-            const float dsc = ks > 0.0f ? taus * frcp(ks) : 3.0e38f;
-            const bool scat = dsc < dface;
-            const float ds = scat ? dsc : dface;
-            float e;
-            const float em = bwd_absorb(cell.x * ds, e);
-            score += (double)(w * cell.y * em);
-            w *= e;
-            steps++;
-            if (COUNT) { c_steps++; if (in3d) c_steps3d++; }
-            const bool hitz = !scat && (!in3d || (tz <= tx && tz <= ty)), hitx = !scat && !hitz && tx <= ty, hity = !scat && !hitz && !hitx;
-            tx -= ds; ty -= ds; tz -= ds;
-            taus = fmaxf(taus - ks * ds, 0.0f);
-            if (!in3d) {
-                // a layer without x / y faces: the columns crossed on the way
-                if (tx < 0.0f) { const float nc = floorf(-tx / sx) + 1.0f; tx = fminf(fmaxf(fmaf(nc, sx, tx), 0.0f), sx); ix = bwd_wrap(ix, ux > 0.0f ? nc : -nc, A.nx); }
-                if (ty < 0.0f) { const float nc = floorf(-ty / sy) + 1.0f; ty = fminf(fmaxf(fmaf(nc, sy, ty), 0.0f), sy); iy = bwd_wrap(iy, uy > 0.0f ? nc : -nc, A.ny); }
-            }
-            if (w < kBwdWeightEnd) ended = true;
-            else if (steps >= kBwdMaxCells) { ended = true; atomicAdd(A.capped, 1ull); }
-            else if (scat) {
-                // ---- scattering: the constituent in proportion to k_s (u1), its phase function (u2), the azimuth (u3)
-                if (COUNT) c_scat++;
-                const float target = r1 * ks;
-                float cum = 0.0f, apf = -2.0f, usel = 0.0f;
-                bool found = false;
-                const int ncomp = A.np1d + (in3d ? A.np3d : 0);
-                for (int q = 0; q < ncomp; ++q) {
-                    float kq, aq;
-                    if (q < A.np1d) { kq = L.ks1d[q]; aq = L.apf1d[q]; }
-                    else if (q == A.np1d) { kq = ks0; aq = apf0; }
-                    else { const float2 c = A.csca[(((size_t)iy * A.nx + ix) * A.nz3 + k3) * A.np3d + (q - A.np1d)]; kq = c.x; aq = c.y; }
-                    if (!found && (target < cum + kq || q == ncomp - 1)) { found = true; apf = aq; usel = kq > 0.0f ? (target - cum) * frcp(kq) : 0.0f; }
-                    cum += kq;
-                }
-                usel = fminf(fmaxf(usel, 0.0f), 1.0f);
-                const float mu = apf >= 1.0f ? phase_sample_table(A.tab, apf, r2, usel) : phase_sample_analytic(apf, r2);
-                const float px = pos_x(), py = pos_y();
-                const float dz0 = tz * fabsf(uz), pz = fminf(fmaxf(uz > 0.0f ? L.dz - dz0 : dz0, 0.0f), L.dz);
-                rotate_dir(ux, uy, uz, mu, r3);
-                set_dda(px, py, pz, L.dz);
-                if (w < A.wmin) {
-                    float q0, q1, q2, q3;
-                    draw4(seed, id, draw++, q0, q1, q2, q3);
-                    if (!roulette(q0)) ended = true;
-                }
-                if (!ended) new_flight();
-            } else if (hitx) { tx = sx; ix += ux > 0.0f ? 1 : -1; ix = ix < 0 ? A.nx - 1 : (ix >= A.nx ? 0 : ix); }
-            else if (hity) { ty = sy; iy += uy > 0.0f ? 1 : -1; iy = iy < 0 ? A.ny - 1 : (iy >= A.ny ? 0 : iy); }
-            else if (uz > 0.0f) {
-                if (++k >= A.nz) ended = true;                 // the top: space is cold
-                else tz = slay[k].dz * aiz;
-            } else if (--k >= 0) tz = slay[k].dz * aiz;
-            else {
-                // ---- the surface: it emits eps B(Ts) into the line of sight and reflects the rest (Lambertian)
-                if (COUNT) c_sfc++;
-                const float px = pos_x(), py = pos_y();
-                const int ib = min((int)(((float)ix * A.dx + px) * A.sfc_sx), A.nxb - 1), jb = min((int)(((float)iy * A.dy + py) * A.sfc_sy), A.nyb - 1);
-                const float2 sc = A.cells[A.nvox + A.nz + (size_t)max(jb, 0) * A.nxb + max(ib, 0)];
-                score += (double)(w * sc.x * sc.y);
-                w *= 1.0f - sc.x;
-                if (w < kBwdWeightEnd) ended = true;
-                else {
-                    float q0, q1, q2, q3;
-                    draw4(seed, id, draw++, q0, q1, q2, q3);
-                    const float cz = sqrtf(q0), sz = sqrtf(fmaxf(1.0f - q0, 0.0f));
-                    float sp, cp;
-                    sincos_turns(q1, sp, cp);
-                    ux = sz * cp; uy = sz * sp; uz = cz;
-                    k = 0;
-                    set_dda(px, py, 0.0f, slay[0].dz);
-                    if (w < A.wmin && !roulette(q2)) ended = true;
-                    if (!ended) new_flight();
-                }
-            }
-        }
-        if (ended) {
-            have = false;
-            const double s = score * (double)A.src_flx;
-            if (DEBUG) score_out[slot] = s;
-            else if (s != 0.0) {
-                if (lds_sums) atomicAdd(&sums[pix], s);
-                else atomicAdd(&A.rad[pix], s);
-            }
-            if (COUNT) c_hist++;
-        }
-    }
-    if (lds_sums) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < npix; i += blockDim.x) { const double s = sums[i]; if (s != 0.0) atomicAdd(&A.rad[i], s); }
-    }
-    if (COUNT && !DEBUG) {
-        atomicAdd(A.counters + MI3D_CNT_PHOTONS, c_hist);
-        atomicAdd(A.counters + MI3D_CNT_STEPS, c_steps);
-        atomicAdd(A.counters + MI3D_CNT_STEPS3D, c_steps3d);
-        atomicAdd(A.counters + MI3D_CNT_SCATTER, c_scat);
-        atomicAdd(A.counters + MI3D_CNT_SURFACE, c_sfc);
-    }
+template <bool COUNT>
+__global__ void __launch_bounds__(256)
+k_backward_w(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, const BwdWeights W) {
+    constexpr bool WGT = true, DEBUG = false;
+    float *const dir_out = nullptr; double *const score_out = nullptr;
+#include "mi3d_kernel_backward_body.inc"
 }
 
 // dynamic LDS of a launch: the workgroup's sums, the layer table, the cameras
 __host__ inline size_t backward_lds(int npix, int nz, int nview, bool debug) {
     return (size_t)((!debug && npix <= kBwdLdsPix) ? ((npix + 1) & ~1) : 0) * sizeof(double) + (size_t)nz * sizeof(LayerRec) + (size_t)nview * sizeof(CamRec);
+}
+// ... of a launch of the weights build.  stage: the layer and surface weights of every pixel are summed in LDS -- where the image's own
+// sums are, and the workgroup's dynamic LDS stays within 32 KB (five workgroups on a CU of 160 KB)
+constexpr size_t kBwdWgtLds = 32768;
+__host__ inline size_t backward_lds_w(int npix, int nz, int nview, int nls, bool allow_stage, int &stage) {
+    const size_t base = backward_lds(npix, nz, nview, false);
+    const size_t extra = (((size_t)npix * nls + 1) & ~(size_t)1) * sizeof(double);
+    stage = allow_stage && npix <= kBwdLdsPix && base + extra <= kBwdWgtLds ? 1 : 0;
+    return base + (stage ? extra : 0);
 }
 
 } // namespace mi3d

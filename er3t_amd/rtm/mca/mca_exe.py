@@ -51,6 +51,13 @@ def _check_supported(nml, fdir=None):
         if mbwd == 1.0 and not (mtype == 3 and int(nml.get('Wld_mtarget', 1)) == 2 and int(nml.get('Rad_mrkind', 2)) == 1):
             raise OSError('Error [mca_exe]: <Rad_mbwd=1> (backward Monte Carlo) belongs to the all-sky cameras and point radiometers (<Rad_mrkind=1>) of a '
                           'thermal job (<Src_mtype=3>): a solar job\'s sun would need a local estimate of its own.')
+    if nml.get('Rad_mwgt') is not None:
+        mwgt = float(np.ravel(nml.get('Rad_mwgt'))[0])
+        if mwgt not in (0.0, 1.0):
+            raise OSError('Error [mca_exe]: <Rad_mwgt=%g> is not supported (0: off, 1: per-cell emission weights; a key of this project).' % mwgt)
+        if mwgt == 1.0 and not (nml.get('Rad_mbwd') is not None and float(np.ravel(nml.get('Rad_mbwd'))[0]) == 1.0):
+            raise OSError('Error [mca_exe]: <Rad_mwgt=1> (emission weights) needs the backward route (<Rad_mbwd=1>): the weights are what backward '
+                          'histories collect along their lines of sight.')
     if mtype == 0:
         raise OSError('Error [mca_exe]: <Src_mtype=0> (local) is not supported: only the solar (1), the solar+thermal (2) or the thermal (3) source.')
     if mtype not in (1, 2, 3):
@@ -123,6 +130,19 @@ def direct_in_run_field(scene):
     radiometers (include/mi3d.h: mi3d_get_camera_direct); the fused route's reader separates it again (mca_out._from_fused)"""
     return getattr(scene, 'rad_kind', 2) == 1 and getattr(scene, 'cam_mpmap', 1) == 2 and bool(scene.target & TARGET_RADIANCE) \
         and getattr(scene, 'src_mtype', 1) == 1
+
+
+def weights_fname(fname_out):
+    """the extra file of a job with <Rad_mwgt=1> beside its out.bin: raw '<f4' [npix][ncell] weights, then [ncell] Planck radiances"""
+    return (fname_out[:-len('.out.bin')] if fname_out.endswith('.out.bin') else fname_out)+'.wgt.bin'
+
+
+def flatten_weights(w):
+    """Mi3dSolver.emission_weights() -> (K (npix, ncell), planck (ncell,)) float32 in tally order: voxels, layers, surface cells"""
+    n = w['layers'].shape[0]
+    p = w['planck']
+    return (np.concatenate([w['voxels'].reshape(n, -1), w['layers'], w['surface'].reshape(n, -1)], axis=1),
+            np.concatenate([p['voxels'].ravel(), p['layers'].ravel(), p['surface'].ravel()]))
 
 
 def source_amplitude(sol, sc):
@@ -233,12 +253,17 @@ class JobRunner:
             rad = torch.zeros(max(scene.nview, 1)*scene.nyr*scene.nxr, dtype=torch.float64, device=dev)       # raw tallies: float64
             flux = torch.zeros(3*(scene.nz+1)*scene.ny*scene.nx, dtype=torch.float64, device=dev)
             heat = torch.zeros(scene.nz*scene.ny*scene.nx, dtype=torch.float64, device=dev) if scene.target & TARGET_HEAT else None
-            self._tensors[slot] = (rad, flux, heat)
+            wgt = None
+            if getattr(scene, 'cam_weights', 0):       # (Rad_mwgt = 1: the emission weights' raw tally is all-reduced with the radiance)
+                nsfc = int(scene.jsfc.size) if scene.jsfc is not None else 1
+                wgt = torch.zeros(scene.nview*scene.nyr*scene.nxr*(scene.nx*scene.ny*scene.nz3+scene.nz+nsfc), dtype=torch.float64, device=dev)
+            self._tensors[slot] = (rad, flux, heat, wgt)
             if slot == 0:
                 stream = torch.cuda.current_stream(dev)
             else:
                 stream = self._streams[slot] = self._streams[slot] or torch.cuda.Stream(dev)
-            sol.bind(rad_ptr=rad.data_ptr(), flux_ptr=flux.data_ptr(), stream=stream.cuda_stream, heat_ptr=None if heat is None else heat.data_ptr())
+            sol.bind(rad_ptr=rad.data_ptr(), flux_ptr=flux.data_ptr(), stream=stream.cuda_stream, heat_ptr=None if heat is None else heat.data_ptr(),
+                     wgt_ptr=None if wgt is None else wgt.data_ptr())
         else:
             self._tensors[slot] = None
             sol.bind(None, None, None)
@@ -263,6 +288,8 @@ class JobRunner:
             out['rad'] = self.sol.radiance(nphoton)
             if wants_rdir(self.scene):
                 out['rdir'] = self.sol.camera_direct().astype(np.float32)
+            if getattr(self.scene, 'cam_weights', 0):
+                out['wgt'] = self.sol.emission_weights(nphoton)
         if self.scene.target & TARGET_FLUX:
             out['flux'] = self.sol.flux(nphoton)
         if self.scene.target & TARGET_HEAT:
@@ -280,6 +307,8 @@ class JobRunner:
             out['rad'] = sol.radiance(int(nphoton))
             if wants_rdir(scene):
                 out['rdir'] = sol.camera_direct().astype(np.float32)
+            if getattr(scene, 'cam_weights', 0):
+                out['wgt'] = self.job_weights(nphoton, slot=slot)
         if scene.target & TARGET_FLUX:
             out['flux'] = sol.flux(int(nphoton))
         if scene.target & TARGET_HEAT:
@@ -416,6 +445,18 @@ class JobRunner:
         self.sols[slot].run(cnt, seed=seed, offset=off)
         self.photons_done += cnt
 
+    def job_weights(self, nphoton, slot=0):
+        """the emission weights (Rad_mwgt = 1) of the job launched last on <slot>, a job of <nphoton> ids in all: Mi3dSolver.emission_weights();
+        several ranks sum their raw tallies first"""
+        sol = self.sols[slot]
+        if self._tensors[slot] is not None and self._tensors[slot][3] is not None:
+            import torch
+            sol.sync()
+            torch.cuda.synchronize(sol.device)
+            allreduce_tallies(self._tensors[slot][3])
+            torch.cuda.synchronize(sol.device)
+        return sol.emission_weights(int(nphoton))
+
     def stats_begin(self):
         """start gathering run statistics for the loaded scene (its shape and target)"""
         self._run_tensors = None
@@ -499,6 +540,11 @@ class JobRunner:
             if 'rdir' in result:                                 # point radiometers: the direct sun, a second variable of the same shape
                 variables.append(('rdir', 'direct solar radiance', np.transpose(result['rdir'], (2, 1, 0))))
             mca_out_write(fname_out, variables)
+            if 'wgt' in result:                                  # Rad_mwgt = 1: one extra file, out.bin and .ctl stay what they are
+                k, b = flatten_weights(result['wgt'])
+                with open(weights_fname(fname_out), 'wb') as f:
+                    np.ascontiguousarray(k, dtype='<f4').tofile(f)
+                    np.ascontiguousarray(b, dtype='<f4').tofile(f)
 
 
 _RUNNER = None

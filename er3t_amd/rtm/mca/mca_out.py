@@ -362,6 +362,132 @@ def read_radiometer_mca_out(mca_obj, abs_obj, mode='mean', squeeze=True):
     return data
 
 
+class weights_reducer:
+
+    """
+    The g / run reduction of the per-cell emission weights (mcarats_ng(emission_weights=True), Rad_mwgt = 1), with the factors of `rad`:
+    per run sum_g factor[ig] * K_g, over runs the mean and the population standard deviation.  Fed JOB BY JOB (add, then end_run after the
+    last g of a run) and summed in float64 as it goes: the arrays can be gigabytes, so what it holds does not grow with the number of
+    jobs -- the current run, the sum and the sum of squares over runs, and, only with keep_runs, one array per run (mode 'all').
+    `planck` is taken once, from the first job.  jobs_fed counts the calls of add.
+    """
+
+    def __init__(self, factors, keep_runs=False):
+        self.factors = np.asarray(factors, dtype=np.float64).ravel()
+        self.keep_runs = keep_runs
+        self.run = self.s1 = self.s2 = self.planck = None
+        self.runs, self.nrun, self.jobs_fed = [], 0, 0
+
+    def add(self, ig, weights, planck=None):
+        if self.run is None:
+            self.run = np.zeros(np.shape(weights), dtype=np.float64)
+            self.s1, self.s2 = np.zeros_like(self.run), np.zeros_like(self.run)
+        if self.planck is None and planck is not None:
+            self.planck = np.array(planck, dtype=np.float32)
+        self.run += self.factors[ig]*np.asarray(weights, dtype=np.float64)
+        self.jobs_fed += 1
+
+    def end_run(self):
+        self.s1 += self.run
+        self.s2 += self.run*self.run
+        if self.keep_runs:
+            self.runs.append(self.run.astype(np.float32))
+        self.run[...] = 0.0
+        self.nrun += 1
+
+    def mean(self):
+        return (self.s1/self.nrun).astype(np.float32)
+
+    def std(self):
+        m = self.s1/self.nrun
+        return np.sqrt(np.maximum(self.s2/self.nrun-m*m, 0.0)).astype(np.float32)
+
+
+def _weights_geometry(nml):
+    """(nview, nyr, nxr, nz3, ny, nx, nz, nyb, nxb) of a job with <Rad_mwgt=1> from its namelist"""
+    g = lambda k, d: int(np.ravel(nml.get(k, d) if nml.get(k) is not None else d)[0])
+    sfc2d = bool(nml.get('Sfc_inpfile')) and g('Sfc_nxb', 0) > 0
+    return (g('Rad_nrad', 1), g('Rad_nyr', 1), g('Rad_nxr', 1), g('Atm_nz3', 0), g('Atm_ny', 1), g('Atm_nx', 1), g('Atm_nz', 1),
+            g('Sfc_nyb', 1) if sfc2d else 1, g('Sfc_nxb', 1) if sfc2d else 1)
+
+
+def _weights_fields(k, geom, squeeze, pixels=True):
+    """K (npix, ncell[, Nr]) or planck (ncell,) in tally order -> its three parts in the layout of the 3-D outputs (f_up, heating_rate), the pixel
+    axes (Nxr, Nyr, Nview) last: voxels (Nx, Ny, Nz3, ...), layers (Nz, ...), surface (Nxb, Nyb, ...).  squeeze drops pixel axes of length 1"""
+    nview, nyr, nxr, nz3, ny, nx, nz, nyb, nxb = geom
+    nvox = nx*ny*nz3
+    k = np.asarray(k)
+    if not pixels:
+        return {'': np.ascontiguousarray(np.transpose(k[:nvox].reshape(nz3, ny, nx), (2, 1, 0))), '_layers': np.ascontiguousarray(k[nvox:nvox+nz]),
+                '_surface': np.ascontiguousarray(np.transpose(k[nvox+nz:].reshape(nyb, nxb), (1, 0)))}
+    tail = k.shape[2:]
+    pix = (nview, nyr, nxr)
+    v = k[:, :nvox].reshape(pix+(nz3, ny, nx)+tail)
+    l = k[:, nvox:nvox+nz].reshape(pix+(nz,)+tail)
+    s = k[:, nvox+nz:].reshape(pix+(nyb, nxb)+tail)
+    nt = len(tail)
+    v = np.transpose(v, (5, 4, 3, 2, 1, 0)+tuple(range(6, 6+nt)))
+    l = np.transpose(l, (3, 2, 1, 0)+tuple(range(4, 4+nt)))
+    s = np.transpose(s, (4, 3, 2, 1, 0)+tuple(range(5, 5+nt)))
+    if squeeze:
+        def drop(a, first):
+            keep = [i for i, n in enumerate(a.shape) if i < first or i >= first+3 or n > 1]
+            return a.reshape([a.shape[i] for i in keep])
+        v, l, s = drop(v, 3), drop(l, 1), drop(s, 2)
+    return {'': np.ascontiguousarray(v), '_layers': np.ascontiguousarray(l), '_surface': np.ascontiguousarray(s)}
+
+
+def read_emission_weights(mca_obj, abs_obj, mode='mean', squeeze=True):
+
+    """
+    The per-cell emission weights of mcarats_ng(camera_method='backward', emission_weights=True): K[pixel][cell], the share of a pixel's
+    reading that comes from a cell per unit Planck radiance there, combined over g and runs with the factors of `rad` (sum_g weight[ig] x_g
+    / 1000; mean and standard deviation over runs), so that  rad = sum over all cells of emission_weight * emission_planck  (jobs of
+    mcarats_ng carry Src_flx = 1).  keys: emission_weight (Nx, Ny, Nz3, pixels...), emission_weight_layers (Nz, pixels...),
+    emission_weight_surface (Nxb, Nyb, pixels...) -- pixel axes (Nxr, Nyr, Nview), those of length 1 dropped with squeeze; 'all' adds Nr --
+    (+ *_std for 'mean') and, once, emission_planck, emission_planck_layers, emission_planck_surface [W m-2 sr-1 um-1].  The file route reads
+    the jobs' .wgt.bin files one at a time; the fused route has reduced the same arrays while the jobs ran (mcarats_ng.run_fused).
+    """
+
+    from er3t_amd.rtm.mca.mca_inp import mca_inp_read
+    from er3t_amd.rtm.mca.mca_exe import weights_fname
+    mode = mode.lower()
+    if mode not in ('mean', 'all'):
+        raise OSError('Error [read_emission_weights]: Do not support <mode=%s>.' % mode)
+    geom = _weights_geometry(mca_inp_read(mca_obj.fnames_inp[0][0]))
+    fused = getattr(mca_obj, 'fused', None)
+    if fused is not None and 'wgt' in fused:
+        red = fused['wgt']
+    else:
+        factors, _ = g_factors(mca_obj, abs_obj, 1)
+        red = weights_reducer(factors[0], keep_runs=(mode == 'all'))
+        npix = geom[0]*geom[1]*geom[2]
+        for ir in range(mca_obj.Nrun):
+            for ig in range(mca_obj.Ng):
+                raw = np.fromfile(weights_fname(mca_obj.fnames_out[ir][ig]), dtype='<f4')
+                ncell = raw.size//(npix+1)
+                if raw.size != (npix+1)*ncell:
+                    raise OSError('Error [read_emission_weights]: <%s> does not hold %d + 1 rows.' % (weights_fname(mca_obj.fnames_out[ir][ig]), npix))
+                red.add(ig, raw[:npix*ncell].reshape(npix, ncell), raw[npix*ncell:])
+                del raw
+            red.end_run()
+    data = {}
+    info = {'': ['Nx', 'Ny', 'Nz3'], '_layers': ['Nz'], '_surface': ['Nxb', 'Nyb']}
+    def put(key, fields, name, units, extra):
+        for suf, arr in fields.items():
+            data[key+suf] = {'data': arr, 'name': name, 'units': units, 'dims_info': info[suf]+extra}
+    pixdims = [d for d, n in zip(['Nxr', 'Nyr', 'Nview'], (geom[2], geom[1], geom[0])) if n > 1 or not squeeze]
+    if mode == 'all':
+        if not red.runs:
+            raise OSError('Error [read_emission_weights]: the runs were not kept; use <mode=\'mean\'>.')
+        put('emission_weight', _weights_fields(np.stack(red.runs, axis=-1), geom, squeeze), 'Emission weight', 'N/A (per nm: the g-sum of rad)', pixdims+['Nr'])
+    else:
+        put('emission_weight', _weights_fields(red.mean(), geom, squeeze), 'Emission weight (mean)', 'N/A (per nm: the g-sum of rad)', pixdims)
+        put('emission_weight_std', _weights_fields(red.std(), geom, squeeze), 'Emission weight (standard deviation)', 'N/A (per nm: the g-sum of rad)', pixdims)
+    put('emission_planck', _weights_fields(red.planck, geom, squeeze, pixels=False), 'Planck radiance of the cells', 'W/m^2/um/sr', [])
+    return data
+
+
 class mca_out_ng:
 
     """
@@ -414,6 +540,8 @@ class mca_out_ng:
             self.data = read_heating_mca_out(self.mca, self.abs, mode=self.mode, squeeze=self.squeeze)
         else:
             raise OSError('Error [mca_out_ng]: Cannot read results of <target=%s>.' % self.mca.target)
+        if getattr(self.mca, 'emission_weights', False):
+            self.data.update(read_emission_weights(self.mca, self.abs, mode=self.mode, squeeze=self.squeeze))
 
     # ---- result cache ------------------------------------------------------------------------
     @staticmethod

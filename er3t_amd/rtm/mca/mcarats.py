@@ -110,6 +110,9 @@ class mcarats_ng:
                            (Rad_mbwd=1, a key of this project written only then: include/mi3d.h, mi3d_set_camera_method).
                            No 1 / r^2 and no aperture clamp -- a sensor may stand inside a cloud or absorbing air --, the whole cyclic
                            domain is seen: <camera_images> must not be given and Rad_nimg is not written
+        emission_weights [False]: with camera_method='backward': every job also tallies K[pixel][cell], the share of a pixel's reading that comes
+                           from a voxel, a layer or a surface cell per unit Planck radiance there (Rad_mwgt=1, a key of this project written
+                           only then: include/mi3d.h, mi3d_set_emission_weights); mca_out_ng returns data['emission_weight']
 
     Afterwards: input and output files under <fdir>; attributes Ng, Nrun, Nx, Ny, dx, dy, date, target, solver,
     photons (Nrun*Ng,), photons_per_set, fnames_inp[ir][ig], fnames_out[ir][ig], nml (list of Ng dictionaries).
@@ -123,7 +126,7 @@ class mcarats_ng:
                  sensor_azimuth_angle=0.0, sensor_altitude=705000.0, sensor_type='satellite', sensor_xpos=0.5,
                  sensor_ypos=0.5, solver='3d', photons=1e7, base_ratio=0.05, verbose=False, quiet=False,
                  abs_obj=None, keep_files=True, source='solar', wavelength=None, surface_temperature=None,
-                 heating_estimator='collision', camera_images=None, camera_method='forward'):
+                 heating_estimator='collision', camera_images=None, camera_method='forward', emission_weights=False):
 
         # one process per GPU (torch.distributed): rank 0 writes the job files, all ranks transport their share of every job
         from er3t_amd.dist import world_info, barrier
@@ -175,6 +178,10 @@ class mcarats_ng:
             if camera_images is not None:
                 raise OSError('Error [mcarats_ng]: <camera_images> does not go with <camera_method=\'backward\'>: a line of sight wraps through the '
                               'whole cyclic domain, no periodic images are enumerated.')
+        self.emission_weights = bool(emission_weights)
+        if self.emission_weights and self.camera_method != 'backward':
+            raise OSError('Error [mcarats_ng]: <emission_weights=True> needs <camera_method=\'backward\'>: the per-cell weights are what backward '
+                          'histories collect along their lines of sight.')
         self.heating_estimator = str(heating_estimator).lower()
         if self.heating_estimator not in ('collision', 'path'):
             raise OSError('Error [mcarats_ng]: <heating_estimator=%s> must be \'collision\' or \'path\'.' % heating_estimator)
@@ -256,6 +263,8 @@ class mcarats_ng:
         #  carries the key only when <camera_images> is given, and stays what it was, byte for byte, without)
         if self.camera_method == 'backward':           # (written only then: every other job file stays what it was, byte for byte)
             self._all({'Rad_mbwd': 1})
+            if self.emission_weights:                  # (likewise)
+                self._all({'Rad_mwgt': 1})
         elif self.point_sensor and (self.camera_images is not None or self.source == 'thermal'):
             self._all({'Rad_nimg': 2 if self.camera_images is None else self.camera_images})
         if sensor_type.lower() in _SENSOR_MRPROJ:
@@ -415,9 +424,9 @@ class mcarats_ng:
         with arrays in the solver's layout, rad (nview, ny, nx), flux (3: direct-down, total-down, up; nz+1; ny; nx).
         """
 
-        from er3t_amd.rtm.mca.mca_exe import get_runner, wants_rdir, direct_in_run_field
+        from er3t_amd.rtm.mca.mca_exe import get_runner, wants_rdir, direct_in_run_field, flatten_weights
         from er3t_amd.rtm.mca.mca_inp import mca_inp_read
-        from er3t_amd.rtm.mca.mca_out import g_factors
+        from er3t_amd.rtm.mca.mca_out import g_factors, weights_reducer
 
         runner = get_runner()
         if self.keep_files and runner.world > 1:
@@ -429,7 +438,9 @@ class mcarats_ng:
         # Two solver handles take turns (unless the per-job files are wanted: they are read back job by job): job i+1 is
         # launched before job i is folded into the run, so the tail of a launch -- as long as its longest history -- runs
         # beside the next launch.  The run field is still summed in job order (JobRunner.stats_add).
-        nslot = runner.use_slots(1 if self.keep_files else 2)
+        # (emission weights, Rad_mwgt = 1: every job's array is read back and reduced as the job ends -- one handle, like the per-job files)
+        nslot = runner.use_slots(1 if self.keep_files or self.emission_weights else 2)
+        wred = None
         for ir in range(self.Nrun):
             waiting = None          # (photons, factors, slot) of the job launched last, not yet folded into the run
             for ig in range(self.Ng):
@@ -449,11 +460,19 @@ class mcarats_ng:
                     rdir = runner.sols[slot].camera_direct().astype(np.float32)
                     rdir_run = (rdir_run if ig > 0 else np.zeros_like(rdir)) + rdir*factors[:, ig][:, None, None]
                 runner.launch(photons[ir, ig], int(nml['Wld_jseed']), slot=slot)
+                wgt = runner.job_weights(photons[ir, ig], slot=slot) if self.emission_weights else None
+                if wgt is not None:
+                    if wred is None:                   # (mca_out_ng's mode is not known yet: the runs are kept beside their mean)
+                        wred = weights_reducer(factors[0], keep_runs=True)
+                    wred.add(ig, *flatten_weights(wgt))
                 if self.keep_files:
                     result = {'rad': runner.sol.radiance(photons[ir, ig])} if self.target == 'radiance' else {'flux': runner.sol.flux(photons[ir, ig])}
                     if wants_rdir(scene):
                         result['rdir'] = runner.sol.camera_direct().astype(np.float32)
+                    if wgt is not None:
+                        result['wgt'] = wgt
                     runner.write(self.fnames_out[ir][ig], result)
+                del wgt
                 # (a job is folded into the run before its slot is launched on again: with one slot at once, with two after the
                 #  next job's launch)
                 if waiting is not None:
@@ -465,6 +484,8 @@ class mcarats_ng:
             if waiting is not None:
                 runner.stats_add(*waiting)
             runs.append(runner.stats_end_run(keep=True))
+            if wred is not None:
+                wred.end_run()
             if rdir_runs is not None or direct_in_run_field(scene):
                 rdir_runs = (rdir_runs or []) + [rdir_run]
         self.fused = runner.stats_result()
@@ -473,6 +494,8 @@ class mcarats_ng:
         if rdir_runs is not None:
             self.fused['rdir'] = {'runs': np.stack(rdir_runs, axis=-1)}
         self.fused['toa'] = toa
+        if wred is not None:
+            self.fused['wgt'] = wred
         self.kernel_ms = runner.kernel_ms - ms0
         self.photons_done = runner.photons_done - n0
         if not self.quiet and self.kernel_ms > 0.0:

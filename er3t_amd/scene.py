@@ -116,6 +116,8 @@ class Scene:
 
     cam_method: int = 0                   # Rad_mbwd (a key of this project; include/mi3d.h: mi3d_set_camera_method): 0 the forward route, 1 backward
                                           # Monte Carlo -- thermal cameras and point radiometers only; cam_images is then not used
+    cam_weights: int = 0                  # Rad_mwgt (a key of this project; include/mi3d.h: mi3d_set_emission_weights): 1 the backward route also
+                                          # tallies the per-cell emission weights K[pixel][cell] of every sensor; needs cam_method = 1
 
     # job
     target: int = TARGET_FLUX
@@ -184,6 +186,10 @@ class Scene:
             raise ValueError('Error [Scene]: <rad_kind=%s> (Rad_mrkind) must be 1 or 2.' % self.rad_kind)
         elif self.cam_method != 0:
             raise ValueError('Error [Scene]: <cam_method=%s> (Rad_mbwd) belongs to cameras and point radiometers (<rad_kind=1>).' % self.cam_method)
+        if self.cam_weights not in (0, 1):
+            raise ValueError('Error [Scene]: <cam_weights=%s> (Rad_mwgt) must be 0 or 1.' % (self.cam_weights,))
+        if self.cam_weights == 1 and not (self.rad_kind == 1 and self.cam_method == 1):
+            raise ValueError('Error [Scene]: <cam_weights=1> (Rad_mwgt) needs the backward route (<rad_kind=1>, <cam_method=1>).')
         if self.src_mtype in (2, 3):
             if self.src_mtype == 2:
                 if self.src_fsol is None or not (float(self.src_fsol) >= 0.0) or not np.isfinite(float(self.src_fsol)):
@@ -346,6 +352,12 @@ class Scene:
         if mbwd == 1.0 and not (mtype == 3 and mtarget == 2 and int(get('Rad_mrkind', 2)) == 1):
             raise OSError('Error [Scene]: <Rad_mbwd=1> (backward Monte Carlo) belongs to the cameras and point radiometers (<Rad_mrkind=1>) of a '
                           'thermal job (<Src_mtype=3>).')
+        # (a key of this project: per-cell emission weights of the backward route)
+        mwgt = float(np.ravel(get('Rad_mwgt', 0))[0])
+        if mwgt not in (0.0, 1.0):
+            raise OSError('Error [Scene]: <Rad_mwgt=%g> is not supported (0: off, 1: per-cell emission weights).' % mwgt)
+        if mwgt == 1.0 and mbwd != 1.0:
+            raise OSError('Error [Scene]: <Rad_mwgt=1> (emission weights) needs the backward route (<Rad_mbwd=1>).')
         if mtarget == 2:
             nrad = int(get('Rad_nrad', 1))
             the  = np.resize(np.asarray(get('Rad_the', 180.0), dtype=np.float64), nrad)
@@ -365,7 +377,7 @@ class Scene:
                 kw.update(rad_kind=1, cam_xpos=per_view('Rad_xpos', 0.5), cam_ypos=per_view('Rad_ypos', 0.5),
                           cam_psi=per_view('Rad_psi', 0.0), cam_qmax=per_view('Rad_qmax', 180.0), cam_umax=per_view('Rad_umax', 180.0),
                           cam_vmax=per_view('Rad_vmax', 180.0), cam_apsize=per_view('Rad_apsize', 0.0), cam_mpmap=mpmap, cam_mrproj=mrproj,
-                          cam_method=int(mbwd))
+                          cam_method=int(mbwd), cam_weights=int(mwgt))
                 # (a key of this project: the periodic images of a sensor the job asks for; without it the route's default, cam_images = -1)
                 if get('Rad_nimg') is not None:
                     nimg = float(np.ravel(get('Rad_nimg'))[0])

@@ -48,6 +48,10 @@ _SIGNATURES = [
     ('mi3d_set_cameras'        , C.c_int   , [C.c_void_p, C.c_int] + [_dp]*10 + [C.c_int, C.c_int]),
     ('mi3d_set_camera_map'     , C.c_int   , [C.c_void_p, C.c_int, C.c_int]),
     ('mi3d_set_camera_method'  , C.c_int   , [C.c_void_p, C.c_int]),
+    ('mi3d_set_emission_weights', C.c_int  , [C.c_void_p, C.c_int]),
+    ('mi3d_bind_weights_buffer', C.c_int   , [C.c_void_p, C.c_void_p]),
+    ('mi3d_get_emission_weights', C.c_int  , [C.c_void_p, _u64, _fp, _fp]),
+    ('mi3d_debug_weights_staged', C.c_int  , [C.c_void_p]),
     ('mi3d_set_options'        , C.c_int   , [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int]),
     ('mi3d_set_le_roulette'    , C.c_int   , [C.c_void_p, C.c_double]),
     ('mi3d_set_le_weight_roulette', C.c_int, [C.c_void_p, C.c_double]),
@@ -280,6 +284,11 @@ class Mi3dSolver:
             raise ValueError('Error [Mi3dSolver]: <method=%r> must be \'forward\' (0) or \'backward\' (1).' % (method,))
         self._chk(self.lib.mi3d_set_camera_method(self._h, int(m)))
 
+    def set_emission_weights(self, on=True):
+        """per-cell emission weights of the backward route (include/mi3d.h: mi3d_set_emission_weights): on, every run also tallies
+        K[pixel][cell], the share of a pixel's reading that comes from a cell per unit Planck radiance there"""
+        self._chk(self.lib.mi3d_set_emission_weights(self._h, 1 if on else 0))
+
     def set_options(self, target=TARGET_FLUX, solver=0, wmin=0.2, wfac=1.0, column_le=True):
         self._chk(self.lib.mi3d_set_options(self._h, int(target), int(solver), float(wmin), float(wfac), 1 if column_le else 0))
 
@@ -318,6 +327,7 @@ class Mi3dSolver:
         else:
             self.set_views(s.view_the, s.view_phi, s.view_zloc, zref=s.zref, nxr=s.nxr, nyr=s.nyr)
         self.set_camera_method(int(getattr(s, 'cam_method', 0)))
+        self.set_emission_weights(int(getattr(s, 'cam_weights', 0)))
         self.set_options(s.target, s.solver, s.wmin, s.wfac, column_le)
         self.set_heating_estimator(int(getattr(s, 'heat_estimator', 0)))
         self.set_le_roulette(getattr(s, 'le_tau1', 0.0))
@@ -333,9 +343,10 @@ class Mi3dSolver:
         self.prepare()
 
     # ---- execution ---------------------------------------------------------------------------
-    def bind(self, rad_ptr=None, flux_ptr=None, stream=None, heat_ptr=None):
+    def bind(self, rad_ptr=None, flux_ptr=None, stream=None, heat_ptr=None, wgt_ptr=None):
         self._chk(self.lib.mi3d_bind_device_buffers(self._h, C.c_void_p(rad_ptr or 0), C.c_void_p(flux_ptr or 0), C.c_void_p(stream or 0)))
         self._chk(self.lib.mi3d_bind_heating_buffer(self._h, C.c_void_p(heat_ptr or 0)))
+        self._chk(self.lib.mi3d_bind_weights_buffer(self._h, C.c_void_p(wgt_ptr or 0)))
 
     def prepare(self):
         self._chk(self.lib.mi3d_prepare(self._h))
@@ -356,7 +367,7 @@ class Mi3dSolver:
     def set_tuning(self, **knobs):
         """launch-machinery knobs (include/mi3d.h: mi3d_set_tuning), e.g. set_tuning(evcap_log2=12, own_stream=1);
         keys: tile_cols, batch_log2, evcap_log2, rad_spread, own_stream, tally_lists, tlcap_log2, entry_records (0 none, 1 short where allowed, 2 long always), cam_images,
-        tally_window, rad_row_pad, vpad_col, vpad_row, overlap_rays, overlap_sort, overlap_pre, tl_split, rays_wg, emit_wg"""
+        tally_window, rad_row_pad, vpad_col, vpad_row, overlap_rays, overlap_sort, overlap_pre, tl_split, rays_wg, emit_wg, wgt_stage"""
         for key, value in knobs.items():
             self._chk(self.lib.mi3d_set_tuning(self._h, key.encode(), int(value)))
 
@@ -375,6 +386,27 @@ class Mi3dSolver:
         if out.size:
             self._chk(self.lib.mi3d_get_radiance(self._h, int(nphoton_total), _ptr(out)))
         return out
+
+    def weights_shape(self):
+        """(npix, nvox, nz, nsfc) of the emission weights' tally for the scene loaded: K_raw is [npix][nvox + nz + nsfc] float64"""
+        s = self.scene
+        nsfc = int(s.jsfc.size) if s.jsfc is not None else 1
+        return s.nview*s.nyr*s.nxr, s.nx*s.ny*s.nz3, s.nz, nsfc
+
+    def emission_weights(self, nphoton_total):
+        """the per-cell emission weights of the backward route (include/mi3d.h: mi3d_get_emission_weights) for a job of nphoton_total ids:
+        'voxels' (npix, nz3, ny, nx), 'layers' (npix, nz), 'surface' (npix, nyb, nxb) -- 1 x 1 for a uniform surface -- and 'planck',
+        the float32 Planck radiances the kernel multiplied with, in the same three shapes without npix.  The reading of pixel p is
+        Src_flx sum_c K[p][c] planck[c] over all three parts"""
+        s = self.scene
+        npix, nvox, nz, nsfc = self.weights_shape()
+        ncell = nvox+nz+nsfc
+        k = np.zeros((npix, ncell), dtype=np.float32)
+        b = np.zeros(ncell, dtype=np.float32)
+        self._chk(self.lib.mi3d_get_emission_weights(self._h, int(nphoton_total), _ptr(k), _ptr(b)))
+        sshape = s.jsfc.shape if s.jsfc is not None else (1, 1)
+        return {'voxels': k[:, :nvox].reshape(npix, s.nz3, s.ny, s.nx), 'layers': k[:, nvox:nvox+nz], 'surface': k[:, nvox+nz:].reshape((npix,)+tuple(sshape)),
+                'planck': {'voxels': b[:nvox].reshape(s.nz3, s.ny, s.nx), 'layers': b[nvox:nvox+nz], 'surface': b[nvox+nz:].reshape(sshape)}}
 
     def flux(self, nphoton_total):
         out = np.zeros(self._shape_flux, dtype=np.float32)

@@ -24,6 +24,17 @@ def planck(wvl_um, T):
     return np.where(T > 0.0, b, 0.0)
 
 
+def dplanck_dT(wvl_um, T):
+    """dB/dT(lambda, T) in W m-2 sr-1 um-1 K-1: B x / (T (1 - exp(-x))), x = h c / (lambda k T) (T <= 0 gives 0).  With the emission weights
+    K of the backward route the Jacobian of a reading is dR_p/dT_c = Src_flx K[p][c] dB/dT(T_c)"""
+    wl = np.asarray(wvl_um, dtype=np.float64)*1.0e-6
+    T = np.asarray(T, dtype=np.float64)
+    with np.errstate(divide='ignore', over='ignore', invalid='ignore'):
+        x = H*C/(wl*K*T)
+        d = planck(wvl_um, T)*x/(T*(-np.expm1(-x)))
+    return np.where(T > 0.0, d, 0.0)
+
+
 def brightness_temperature(wvl_um, radiance):
     """the inverse of planck: T in K of a radiance in W m-2 sr-1 um-1 (radiance <= 0 gives 0)"""
     wl = np.asarray(wvl_um, dtype=np.float64)*1.0e-6

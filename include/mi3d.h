@@ -312,6 +312,35 @@ int mi3d_set_camera_map(mi3d_solver *h, int mpmap, int mrproj);
  *              mi3d_get_camera_direct stays zeros.  Counters (counting builds): photons = histories, steps, steps3d, scatter, surface. */
 int mi3d_set_camera_method(mi3d_solver *h, int method);
 
+/* Per-cell emission weights of the backward route (the project's namelist key Rad_mwgt = 1).  The path of a backward
+ * history, its weight w and ka do not depend on any temperature, so a pixel's reading is exactly linear in the cells' Planck radiances:
+ *     R_p = Src_flx  sum_c K[p][c] B_c,    K[p][c] = (1 / N_p) sum over p's histories and their segments in c of  w (1 - exp(-ka l))
+ * (a surface cell: w eps).  K is dimensionless: the share of the reading that comes from cell c per unit Planck radiance there.  It
+ * gives the attribution of a reading, its temperature Jacobian dR_p / dT_c = Src_flx K[p][c] dB/dT(T_c), and the reading for any other
+ * temperature field over the same optical properties.
+ *   Switch     mi3d_set_emission_weights: 0 (default) nothing of this runs -- kernels, names and results are those of the route without
+ *              it; 1: mi3d_run serves what the backward route serves and tallies K beside the radiance; with the forward method
+ *              (mi3d_set_camera_method 0) mi3d_run returns MI3D_EUNSUP and names the switch.  mi3d_last_kernel: "k_backward<C,W> [thermal]".
+ *              mi3d_debug_backward ignores the switch.  Switching off frees the library's tally.
+ *   Cells      ncell = nvox + nz + nxb nyb (1 x 1 for a uniform surface) in the order of the thermal source's CDF: voxels in file order
+ *              [nz3][ny][nx], then the nz layers, then the surface cells [nyb][nxb].  Layers inside the 3-D region carry nothing:
+ *              their voxels do.
+ *   Tally      K_raw[npix][ncell], float64 on the device, npix = nview nyr nxr in the layout of the radiance tally.  Every cell step with
+ *              a = w (1 - exp(-ka l)) != 0 (the float32 product) adds a to K_raw[pixel][cell]; the surface adds w eps.  No Src_flx.  The
+ *              score itself is formed as before, so the radiance of a run is that of the route without the switch up to the order of
+ *              its float64 sums.  Raw tallies add over id ranges and ranks; mi3d_reset zeroes them.  mi3d_bind_weights_buffer: a
+ *              caller-owned device buffer [npix][ncell] float64 for an all-reduce (NULL: the library's own).
+ *   Read-out   mi3d_get_emission_weights: row p divided, on the device, by the number of ids in [0, nphoton_total) that map to p (the
+ *              rule of mi3d_get_radiance on this route; a pixel without a history reads 0), rounded to float32 once.  weights
+ *              [npix][ncell]; planck [ncell] (may be NULL): the very float32 B the kernel multiplied with.
+ *   Size       npix ncell above 2^31 elements: MI3D_EUNSUP with both numbers; all index arithmetic is 64-bit.
+ *   Tuning     mi3d_set_tuning "wgt_stage" 0: the layer and surface part of the tally goes to global atomics always (default: summed per
+ *              workgroup in LDS where the launch's LDS stays within 32 KB); mi3d_debug_weights_staged: what the last launch did. */
+int mi3d_set_emission_weights(mi3d_solver *h, int on);
+int mi3d_bind_weights_buffer(mi3d_solver *h, void *wgt_sum);
+int mi3d_get_emission_weights(mi3d_solver *h, uint64_t nphoton_total, float *weights, float *planck);
+int mi3d_debug_weights_staged(mi3d_solver *h);
+
 /* Job options = 1st/2nd CLI arguments and keys Wld_mtarget, Flx_mflx, Pho_wmin
  * (er3t/rtm/mca/mcarats.py:267-287,450-454; er3t/rtm/mca/mca_inp.py:196-198).
  *   target   MI3D_TARGET_FLUX | MI3D_TARGET_RADIANCE (bit-or of both is allowed); MI3D_TARGET_FLUX | MI3D_TARGET_HEAT is the
@@ -453,6 +482,8 @@ int mi3d_set_kernel(mi3d_solver *h, int choice);
  *   rays_wg        0        0..8       workgroups per CU of the ray kernel's light build (0: its own figure, 6)        profiles/r05/ab_knobs_after_nt.log  yes
  *   emit_wg        0        0..8       ... of the event-writing photon loop (0: 5)                                     profiles/r05/ab_knobs_after_nt.log  yes
  *   own_stream     0        0, 1       a non-blocking stream of the handle's own instead of the NULL stream            tools/time_dropin.py                no
+ *   wgt_stage      1        0, 1       emission weights: layer and surface part summed per workgroup in LDS where it     tests/test_gpu_emission_weights.py  no
+ *                                      fits 32 KB (0: global atomics always)
  */
 int mi3d_set_tuning(mi3d_solver *h, const char *key, int value);
 

@@ -23,6 +23,9 @@ and largest over the sensors) and the figure of merit 1 / (se^2 t), se the mean 
 time of the 16 batches.  --photons: photons per forward batch; --histories: histories per backward batch (a multiple of 16).
 
     python tools/thermal_rate.py --legs bwd --photons 1e7 --histories 1.6e6
+Leg 'wgt' (DESIGN.md 5.12): the same sixteen sensors by backward Monte Carlo with the per-cell emission weights (cam_weights) off, then on:
+histories per second and kernel time of both, their ratio, and the cell steps of a history from the counting build.
+    python tools/thermal_rate.py --legs wgt --histories 1.6e6
 """
 
 import argparse
@@ -87,6 +90,48 @@ def merit_rows(sol, name, s, n_fwd, n_bwd, nb=16):
     return rows
 
 
+def weights_rows(sol, name, s, n, nb=16):
+    """the 'wgt' leg: the sensors of scene s by the backward route with the emission weights off, then on, nb batches each
+    over the same id ranges; the counting build, once, for the absorbing cell steps of a history (one float64 atomic each with the switch on)"""
+    rows, base = [], None
+    for on in (0, 1):
+        sol.load_scene(dataclasses.replace(s, cam_method=1, cam_weights=on))
+        sol.reset(); sol.run(n, seed=1); sol.sync()                      # warm-up
+        ms_all = 0.0
+        for b in range(nb):
+            sol.reset()
+            sol.run(n, seed=2, offset=b*n)
+            sol.sync()
+            ms_all += sol.timing()[0]
+        t = ms_all*1e-3
+        row = dict(scene=name, target='wgt_on' if on else 'wgt_off', kernel=sol.kernel_name(), histories_per_batch=n, batches=nb,
+                   histories_per_s=float(nb*n/t), kernel_s=float(t), capped=sol.debug_backward(2, 0, 0)[2])
+        if on:
+            k = sol.emission_weights(n)
+            nz_steps = sum(int(np.count_nonzero(k[p])) for p in ('voxels', 'layers', 'surface'))
+            row.update(npix=int(k['layers'].shape[0]), ncell=int(sum(k[p][0].size for p in ('voxels', 'layers', 'surface'))), cells_with_weight=nz_steps,
+                       sum_of_weights_mean=float(sum(k[p].astype(np.float64).sum() for p in ('voxels', 'layers', 'surface'))/k['layers'].shape[0]),
+                       lds_staged=int(sol.lib.mi3d_debug_weights_staged(sol._h)), slowdown=float(t/base))
+            del k
+        else:
+            base = t
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    sol.set_counting(True)
+    try:
+        sol.reset(); sol.run(n, seed=2); sol.sync()
+        c = sol.counters()
+        row = dict(scene=name, target='wgt_steps', kernel=sol.kernel_name(), histories=n, steps_per_history=c['steps']/n, steps3d_per_history=c['steps3d']/n,
+                   cell_steps_per_s_switch_on=float(c['steps']/n*rows[1]['histories_per_s']))
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    finally:
+        sol.set_counting(False)
+        sol.set_emission_weights(False)
+        sol.set_camera_method('forward')
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--photons', type=float, default=5e7)
@@ -107,6 +152,10 @@ def main():
             if target == 'bwd':
                 sol.set_kernel(general=False)
                 rows += merit_rows(sol, name, pyrgeometers(thermal(les_scene(target='radiance', **kw), lev), 2), n, int(a.histories)//16*16)
+                continue
+            if target == 'wgt':
+                sol.set_kernel(general=False)
+                rows += weights_rows(sol, name, pyrgeometers(thermal(les_scene(target='radiance', **kw), lev), 2), int(a.histories)//16*16)
                 continue
             if target in ('cam', 'cam0', 'cam0_general'):
                 s = pyrgeometers(thermal(les_scene(target='radiance', **kw), lev), 2 if target == 'cam' else 0)
