@@ -3223,4 +3223,48 @@ int mi3d_debug_phase(mi3d_solver *h, int path, int tab_lo, int tab_n, int n, con
     return done(MI3D_OK);
 }
 
+constexpr int kDebugMaxPoints = 1 << 26;      // (the hooks below index [n][3] arrays with 32-bit integers)
+
+int mi3d_debug_rotate(mi3d_solver *h, int n, const float *dir, const float *mu, const float *uphi, float *dir_out, float *sincos_out) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (n <= 0 || n > kDebugMaxPoints || !dir || !mu || !uphi || !dir_out || !sincos_out) return fail(MI3D_EINVAL, "bad arguments to mi3d_debug_rotate");
+    DevBuf<float> d_in, d_out;
+    const size_t m = (size_t)n;
+    auto done = [&](int code) { d_in.release(); d_out.release(); return code; };
+    if ((rc = d_in.alloc(5 * m)) || (rc = d_out.alloc(5 * m))) return done(rc);
+    if (hipMemcpy(d_in.p, dir, 3 * m * sizeof(float), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_in.p + 3 * m, mu, m * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_in.p + 4 * m, uphi, m * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+        return done(fail(MI3D_EDEVICE, "mi3d_debug_rotate: copy to the device failed"));
+    const unsigned nblk = (unsigned)std::min<size_t>((m + 255) / 256, 1024);
+    hipLaunchKernelGGL(k_debug_rotate, dim3(nblk), dim3(256), 0, h->stream, n, d_in.p, d_in.p + 3 * m, d_in.p + 4 * m, d_out.p, d_out.p + 3 * m);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = sync_main(h);
+    if (e == hipSuccess) e = hipMemcpy(dir_out, d_out.p, 3 * m * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(sincos_out, d_out.p + 3 * m, 2 * m * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return done(fail(MI3D_EDEVICE, "mi3d_debug_rotate: %s", hipGetErrorString(e)));
+    return done(MI3D_OK);
+}
+
+int mi3d_debug_surface(mi3d_solver *h, int path, int n, int type, const float *param, const float *din, const float *dout, float *out) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (path < 0 || path > 2 || n <= 0 || n > kDebugMaxPoints || !param || !din || (path == 0 && !dout) || !out) return fail(MI3D_EINVAL, "bad arguments to mi3d_debug_surface");
+    const Sfc sf = {type, param[0], param[1], param[2], param[3], param[4]};
+    DevBuf<float> d_in, d_out;
+    const size_t m = (size_t)n;
+    auto done = [&](int code) { d_in.release(); d_out.release(); return code; };
+    if ((rc = d_in.alloc(6 * m)) || (rc = d_out.alloc(m))) return done(rc);
+    if (hipMemcpy(d_in.p, din, 3 * m * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        (path == 0 && hipMemcpy(d_in.p + 3 * m, dout, 3 * m * sizeof(float), hipMemcpyHostToDevice) != hipSuccess))
+        return done(fail(MI3D_EDEVICE, "mi3d_debug_surface: copy to the device failed"));
+    const unsigned nblk = (unsigned)std::min<size_t>((m + 255) / 256, 1024);
+    hipLaunchKernelGGL(k_debug_surface, dim3(nblk), dim3(256), 0, h->stream, path, n, sf, d_in.p, d_in.p + 3 * m, d_out.p);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = sync_main(h);
+    if (e == hipSuccess) e = hipMemcpy(out, d_out.p, m * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return done(fail(MI3D_EDEVICE, "mi3d_debug_surface: %s", hipGetErrorString(e)));
+    return done(MI3D_OK);
+}
+
 } // extern "C"

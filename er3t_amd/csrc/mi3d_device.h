@@ -704,13 +704,26 @@ __device__ inline void sincos_turns(float u, float &s, float &c) {
 }
 
 // rotate (ux,uy,uz) by polar cosine mu and azimuth 2*pi*uphi
+// Accuracy contract ("rotate_dir"; held point by point by tests/test_gpu_device_geometry.py): the frame comes from
+// den2 = 1 - uz^2, which in float32 differs from the true ux^2 + uy^2 by up to 4 x 2^-24 absolute, so the part of the new direction
+// perpendicular to the old one is mis-scaled by a relative 2 x 2^-24 / h2 (h2 the squared horizontal part): the realised scattering
+// cosine is off by that much, 2e-5 within 0.1 rad of the vertical, 2e-3 within 0.01 rad.  The threshold below is NOT a distance from
+// the pole: den2 is a multiple of 2^-24 = 6e-8 or exactly 0, so `den2 < 1e-10f` reads `den2 == 0`, |uz| = 1 in float32 (below some
+// 0.3 mrad).  A direction without horizontal part takes the same branch whatever its uz (both components below 1e-10 in size: only
+// the axis itself, a normalised direction off it has den2 = 0 long before): the general formula would multiply that part's zeros and
+// leave the photon on the axis, or normalise the zero vector to NaN -- a vertical direction one ulp short of unit length has
+// den2 = 2^-23.  (One maximum and one minimum on the vector unit, 0.4 % of the benchmark: profiles/r16/ab_bench.log; a second comparison
+// joined by `||` cost every photon loop one more spilled scalar register.)
 __device__ inline void rotate_dir(float &ux, float &uy, float &uz, float mu, float uphi) {
     const float st = fsqrt(fmaxf(0.0f, 1.0f - mu * mu));
     float sp, cp;
     sincos_turns(uphi, sp, cp);
     const float den2 = 1.0f - uz * uz;
     float nx, ny, nz;
-    if (den2 < 1e-10f) {
+    float hmax, pole;     // (as fminf(den2, fmaxf(|ux|, |uy|)) the compiler puts two canonicalising v_max in front: four instructions, 0.9 % of the benchmark)
+    asm("v_max_f32_e64 %0, |%1|, |%2|" : "=v"(hmax) : "v"(ux), "v"(uy));
+    asm("v_min_f32_e32 %0, %1, %2" : "=v"(pole) : "v"(den2), "v"(hmax));
+    if (pole < 1e-10f) {
         const float sg = uz >= 0.0f ? 1.0f : -1.0f;
         nx = st * cp; ny = st * sp; nz = mu * sg;
     } else {

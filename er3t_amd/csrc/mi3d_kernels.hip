@@ -175,6 +175,31 @@ k_debug_phase(const DevCold *gcold, const int path, const int n, const float *__
     }
 }
 
+// Test hooks (mi3d_debug_rotate, mi3d_debug_surface): rotate_dir / sincos_turns and the surface routines of mi3d_device.h themselves on the
+// caller's points, one point per lane in a grid-stride loop.
+__global__ void __launch_bounds__(256)
+k_debug_rotate(const int n, const float *__restrict__ dir, const float *__restrict__ mu, const float *__restrict__ uphi,
+               float *__restrict__ dir_out, float *__restrict__ sincos_out) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        float ux = dir[3 * i], uy = dir[3 * i + 1], uz = dir[3 * i + 2], s, c;
+        rotate_dir(ux, uy, uz, mu[i], uphi[i]);
+        sincos_turns(uphi[i], s, c);
+        dir_out[3 * i] = ux; dir_out[3 * i + 1] = uy; dir_out[3 * i + 2] = uz;
+        sincos_out[2 * i] = s; sincos_out[2 * i + 1] = c;
+    }
+}
+
+__global__ void __launch_bounds__(256)
+k_debug_surface(const int path, const int n, const Sfc sf, const float *__restrict__ din, const float *__restrict__ dout, float *__restrict__ out) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        float r;
+        if (path == 1) r = fresnel_unpolarised(sf.p2, sf.p3, din[3 * i]);
+        else if (path == 2) r = dsm_shadow_lambda(din[3 * i], sf.p0);
+        else r = surface_R(sf, din[3 * i], din[3 * i + 1], din[3 * i + 2], dout[3 * i], dout[3 * i + 1], dout[3 * i + 2]);
+        out[i] = r;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // thermal source (Src_mtype = 3, include/mi3d.h: mi3d_set_thermal)
 // ---------------------------------------------------------------------------------------------

@@ -88,6 +88,8 @@ _SIGNATURES = [
     ('mi3d_debug_backward'     , C.c_int   , [C.c_void_p, _u64, _u64, C.c_int, _fp, _dp, C.POINTER(_u64)]),
     ('mi3d_debug_phase_tables' , C.c_int   , [C.c_void_p, C.c_int, C.c_int, _fp, _fp, _fp, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]),
     ('mi3d_debug_phase'        , C.c_int   , [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp]),
+    ('mi3d_debug_rotate'       , C.c_int   , [C.c_void_p, C.c_int, _fp, _fp, _fp, _fp, _fp]),
+    ('mi3d_debug_surface'      , C.c_int   , [C.c_void_p, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp]),
 ]
 
 TAB_IDX_N = 514     # entries of a bucket index into the phase tables (include/mi3d.h: MI3D_TAB_IDX_N)
@@ -548,6 +550,35 @@ class Mi3dSolver:
         p = np.zeros(x.size, dtype=np.float32); m = np.zeros(x.size, dtype=np.float32)
         self._chk(self.lib.mi3d_debug_phase(self._h, int(path), int(tab_lo), int(tab_n), x.size, _ptr(apf), _ptr(x), _ptr(usel), _ptr(p), _ptr(m)))
         return p, m
+
+    def debug_rotate(self, dirs, mu, uphi):
+        """test hook: (directions (n, 3) float32 after rotate_dir(dirs[i], mu[i], uphi[i]), (n, 2) float32 sine and cosine of sincos_turns(uphi[i]))
+        from the device's own routines (include/mi3d.h: mi3d_debug_rotate)"""
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        mu = np.ascontiguousarray(np.broadcast_to(np.asarray(mu, dtype=np.float32), d.shape[:1]))
+        uphi = np.ascontiguousarray(np.broadcast_to(np.asarray(uphi, dtype=np.float32), d.shape[:1]))
+        out = np.zeros_like(d); sc = np.zeros((d.shape[0], 2), dtype=np.float32)
+        self._chk(self.lib.mi3d_debug_rotate(self._h, d.shape[0], _ptr(d), _ptr(mu), _ptr(uphi), _ptr(out), _ptr(sc)))
+        return out, sc
+
+    def debug_surface(self, path, sfc_type, param, din, dout=None):
+        """test hook: float32 per point from the device's own surface routines; path 0: surface_R(Sfc{sfc_type, param[0..4]}, din[i], dout[i]),
+        1: fresnel_unpolarised(param[2], param[3], din[i]), 2: dsm_shadow_lambda(din[i], param[0]); din: (n, 3) for path 0, (n,) for paths
+        1 and 2 (include/mi3d.h: mi3d_debug_surface)"""
+        par = np.zeros(5, dtype=np.float32)
+        par[:len(param)] = np.asarray(param, dtype=np.float32)
+        if int(path) == 0:
+            a = np.ascontiguousarray(din, dtype=np.float32).reshape(-1, 3)
+            b = np.ascontiguousarray(dout, dtype=np.float32).reshape(-1, 3)
+            if a.shape != b.shape:
+                raise ValueError('debug_surface: din and dout differ in shape')
+        else:
+            x = np.ascontiguousarray(np.ravel(din), dtype=np.float32)
+            a = np.zeros((x.size, 3), dtype=np.float32); a[:, 0] = x
+            b = None
+        out = np.zeros(a.shape[0], dtype=np.float32)
+        self._chk(self.lib.mi3d_debug_surface(self._h, int(path), a.shape[0], int(sfc_type), _ptr(par), _ptr(a), None if b is None else _ptr(b), _ptr(out)))
+        return out
 
     def philox(self, seed, id0, draw, n):
         out = np.zeros((n, 4), dtype=np.uint32)

@@ -618,6 +618,18 @@ int mi3d_debug_phase_tables(mi3d_solver *h, int nang, int npf, float *mu, float 
  * selector >= 1 must refer to staged tables only: otherwise MI3D_EINVAL); paths 0 and 3 ignore it.  No photon kernel is involved. */
 int mi3d_debug_phase(mi3d_solver *h, int path, int tab_lo, int tab_n, int n, const float *apf, const float *x, const float *usel,
                      float *p_out, float *mu_out);
+/* Test hook: the device's rotate_dir and sincos_turns (er3t_amd/csrc/mi3d_device.h) on n points.  dir [n][3] the direction before the
+ * collision (as the caller gives it: not normalised here), mu [n] the cosine of the scattering angle, uphi [n] the azimuth in turns;
+ * dir_out [n][3] the direction rotate_dir leaves, sincos_out [n][2] = sincos_turns(uphi[i]): sine, cosine.  Needs no scene.  n <= 0, n > 2^26 or a
+ * NULL pointer: MI3D_EINVAL.  No photon kernel is involved. */
+int mi3d_debug_rotate(mi3d_solver *h, int n, const float *dir, const float *mu, const float *uphi, float *dir_out, float *sincos_out);
+/* Test hook: the device's surface routines (er3t_amd/csrc/mi3d_device.h) on n points; needs no scene.  path:
+ *   0  out[i] = surface_R(Sfc{type, param[0..4]}, din[i], dout[i]): the reflectance factor for light travelling along din[i] (downward)
+ *      that leaves along dout[i] (upward); MI3D_SFC_LSRT and MI3D_SFC_DSM take their routines, every other type code the Lambertian branch
+ *   1  out[i] = fresnel_unpolarised(param[2], param[3], din[i][0])        2  out[i] = dsm_shadow_lambda(din[i][0], param[0])
+ * Paths 1 and 2 read din[i][0] alone and ignore type; dout may be NULL for them.  A path outside 0 .. 2, n <= 0, n > 2^26 or a missing
+ * pointer: MI3D_EINVAL.  No photon kernel is involved. */
+int mi3d_debug_surface(mi3d_solver *h, int path, int n, int type, const float *param, const float *din, const float *dout, float *out);
 
 #ifdef __cplusplus
 }

@@ -1171,6 +1171,11 @@ double orc_lsrt(double fiso, double fgeo, double fvol, const double din[3], cons
     return lsrt_R(fiso, fgeo, fvol, din, dout);
 }
 
+/* rotate_dir on n points: dir [n][3] is rotated in place by the polar cosine mu[i] and the azimuth phi[i] (radians) */
+void orc_rotate(int n, double *dir, const double *mu, const double *phi) {
+    for (int i = 0; i < n; ++i) rotate_dir(dir + 3 * i, mu[i], phi[i]);
+}
+
 double orc_fresnel(double nr, double ni, double cos_inc) { return fresnel_unpolarised(nr, ni, cos_inc); }
 
 /* reflectance factor of the diffuse-specular mixture for n outgoing directions */

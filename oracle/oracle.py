@@ -74,6 +74,8 @@ def lib():
         _LIB.orc_philox_raw.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         _LIB.orc_lsrt.restype = C.c_double
         _LIB.orc_lsrt.argtypes = [C.c_double]*3 + [_dp, _dp]
+        _LIB.orc_rotate.restype = None
+        _LIB.orc_rotate.argtypes = [C.c_int, _dp, _dp, _dp]
         _LIB.orc_fresnel.restype = C.c_double
         _LIB.orc_fresnel.argtypes = [C.c_double]*3
         _LIB.orc_dsm.restype = None
@@ -223,6 +225,15 @@ def philox_raw(ctr, key):
 def lsrt(fiso, fgeo, fvol, din, dout):
     a = np.ascontiguousarray(din, dtype=np.float64); b = np.ascontiguousarray(dout, dtype=np.float64)
     return lib().orc_lsrt(fiso, fgeo, fvol, _ptr(a, _dp), _ptr(b, _dp))
+
+
+def rotate(dirs, mu, phi):
+    """the oracle's rotate_dir on n points: directions (n, 3), polar cosines (n,), azimuths in radians (n,) -> rotated directions (n, 3)"""
+    d = np.array(dirs, dtype=np.float64, order='C').reshape(-1, 3)
+    m = np.ascontiguousarray(np.broadcast_to(np.asarray(mu, dtype=np.float64), d.shape[:1]))
+    f = np.ascontiguousarray(np.broadcast_to(np.asarray(phi, dtype=np.float64), d.shape[:1]))
+    lib().orc_rotate(d.shape[0], _ptr(d, _dp), _ptr(m, _dp), _ptr(f, _dp))
+    return d
 
 
 def fresnel(nr, ni, cos_inc):

@@ -23,7 +23,8 @@ def test_header_declares_the_expected_surface():
     for must in ('mi3d_create', 'mi3d_destroy', 'mi3d_set_atm1d', 'mi3d_set_atm3d', 'mi3d_set_phase', 'mi3d_set_surface',
                  'mi3d_set_surface2d', 'mi3d_set_source', 'mi3d_set_views', 'mi3d_set_options', 'mi3d_run',
                  'mi3d_get_radiance', 'mi3d_get_flux', 'mi3d_get_counters', 'mi3d_last_error', 'mi3d_bind_device_buffers',
-                 'mi3d_debug_philox', 'mi3d_debug_order', 'mi3d_debug_thermal', 'mi3d_debug_phase_tables', 'mi3d_debug_phase'):
+                 'mi3d_debug_philox', 'mi3d_debug_order', 'mi3d_debug_thermal', 'mi3d_debug_phase_tables', 'mi3d_debug_phase', 'mi3d_debug_rotate',
+                 'mi3d_debug_surface'):
         assert must in syms
 
 
