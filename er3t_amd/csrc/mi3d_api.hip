@@ -125,7 +125,18 @@ struct mi3d_solver {
     DevBuf<unsigned long long> d_bwd_capped;
     DevBuf<double> d_bwd_norm, d_bwd_score;
     DevBuf<float> d_bwd_dir;
-    bool backward() const { return cam_method == 1 && src_mtype == 3 && rad_kind == 1 && nview > 0; }   // does the read-out divide by the pixels' own counts?
+    // ... and for the satellite views of a thermal job (mi3d_set_view_method 1): the switch, the tile hand-out's chunk
+    // (mi3d_set_tuning "bwd_chunk"; -1: chosen per launch, at most kBwdChunkAuto; 0: the camera route's stride; n >= 1: exactly n), the chunk
+    // of the launch made last, and the resident workgroups per CU of the build launched last
+    int view_method = 0;
+    int bwd_chunk = -1;
+    int bwd_chunk_last = 0;
+    int sat_cap = 0, sat_cap_counting = -1; size_t sat_cap_lds = 0;
+    DevBuf<float> d_bwd_start;
+    bool sat_backward() const { return view_method == 1 && cam_method == 0 && rad_kind == 2; }           // is the job sent to k_backward_v?
+    bool backward() const {                                                                               // does the read-out divide by the pixels' own counts?
+        return src_mtype == 3 && nview > 0 && ((cam_method == 1 && rad_kind == 1) || sat_backward());
+    }
     // per-cell emission weights of the backward route (mi3d_set_emission_weights 1): K_raw[npix][ncell], the library's own
     // buffer (wgt_n elements, zeroed when it is made; 0: to be made or cleared by the next run) or the caller's (mi3d_bind_weights_buffer)
     int emis_weights = 0;
@@ -912,7 +923,7 @@ int mi3d_destroy(mi3d_solver *h) {
     h->d_stat_out.release(); h->d_dir_level.release(); h->d_get_out.release(); h->d_get_add.release();
     h->d_th_tlev.release(); h->d_th_tmpa.release(); h->d_th_tmps.release(); h->d_th_cdf.release(); h->d_th_bsum.release(); h->d_th.release();
     h->d_wgt_own.release(); h->d_wgt_out.release();
-    h->d_bwd_cells.release(); h->d_bwd_capped.release(); h->d_bwd_norm.release(); h->d_bwd_score.release(); h->d_bwd_dir.release();
+    h->d_bwd_cells.release(); h->d_bwd_capped.release(); h->d_bwd_norm.release(); h->d_bwd_score.release(); h->d_bwd_dir.release(); h->d_bwd_start.release();
     h->d_views.release(); h->d_cold.release(); h->d_tabrange.release(); h->d_bt1d.release(); h->d_dz.release(); h->d_bmin.release(); h->d_bmax.release();
     delete h;
     return MI3D_OK;
@@ -1137,6 +1148,16 @@ int mi3d_set_camera_method(mi3d_solver *h, int method) {
     if (method == h->cam_method) return MI3D_OK;
     HIPCHK(sync_main(h));   // (as every call that changes what the kernels work on)
     h->cam_method = method;
+    return MI3D_OK;
+}
+
+int mi3d_set_view_method(mi3d_solver *h, int method) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (method != 0 && method != 1) return fail(MI3D_EINVAL, "view method %d (0: forward local estimates, 1: backward Monte Carlo)", method);
+    if (method == h->view_method) return MI3D_OK;
+    HIPCHK(sync_main(h));   // (as every call that changes what the kernels work on)
+    h->view_method = method;
     return MI3D_OK;
 }
 
@@ -1365,7 +1386,7 @@ int mi3d_prepare(mi3d_solver *h) {
         h->dirty_thermal = false;
         h->dirty_bwd = true;
     }
-    if (h->cam_method == 1 && h->src_mtype == 3 && h->dirty_bwd) {
+    if ((h->cam_method == 1 || h->view_method == 1) && h->src_mtype == 3 && h->dirty_bwd) {
         if ((rc = build_backward_cells(h))) return rc;
         h->dirty_bwd = false;
     }
@@ -1862,7 +1883,7 @@ static RunPlan plan_run(const mi3d_solver *h, uint64_t nphoton) {
         plan.loop = Loop::ColumnRays;
     // Backward Monte Carlo for the cameras of a thermal job (mi3d_set_camera_method 1): a kernel of its own; what it does
     // not serve is refused by mi3d_run (backward_unsupported)
-    if (h->cam_method == 1) plan.loop = Loop::Backward;
+    if (h->cam_method == 1 || h->sat_backward()) plan.loop = Loop::Backward;
     plan.mix_lean = (plan.mix == 2 && plan.loop != Loop::ColumnRays && rayleigh_1d(h) && h->np3d == 1) ? 3 : plan.mix;
     if (plan.loop != Loop::Backward && (plan.loop == Loop::General || (h->rad_kind == 1 && plan.loop != Loop::ColumnRays)))
         plan.why = h->kernel_choice != 0 ? "kernel choice 1"
@@ -1897,7 +1918,8 @@ static void name_route(mi3d_solver *h, const RunPlan &plan, bool lists, uint64_t
     const int c = h->counting ? 1 : 0, p3d = h->solver == MI3D_SOLVER_P3D ? 1 : 0;
     char nm[96];
     const bool hpath = (h->target & MI3D_TARGET_HEAT) && h->heat_estimator == 1;
-    if (plan.loop == Loop::Backward && h->emis_weights) snprintf(nm, sizeof(nm), "k_backward<%d,W> [thermal]", c);
+    if (plan.loop == Loop::Backward && h->sat_backward()) snprintf(nm, sizeof(nm), "k_backward<%d,V> [thermal]", c);
+    else if (plan.loop == Loop::Backward && h->emis_weights) snprintf(nm, sizeof(nm), "k_backward<%d,W> [thermal]", c);
     else if (plan.loop == Loop::Backward) snprintf(nm, sizeof(nm), "k_backward<%d> [thermal]", c);
     else if (plan.loop == Loop::Flux && hpath) snprintf(nm, sizeof(nm), lists ? "k_transport_flux<%d,%d,%d,1> + k_tl_scatter + k_tl_sum" : "k_transport_flux<%d,%d,%d,1>", c, p3d, plan.mix);
     else if (plan.loop == Loop::Flux) snprintf(nm, sizeof(nm), lists ? "k_transport_flux<%d,%d,%d> + k_tl_scatter + k_tl_sum" : "k_transport_flux<%d,%d,%d>", c, p3d, plan.mix);
@@ -2365,7 +2387,22 @@ static int backward_unsupported(const mi3d_solver *h) {
     return MI3D_OK;
 }
 
-static int fill_backward(mi3d_solver *h, DevBackward &A) {
+// ... and what the satellite-view build serves (mi3d_set_view_method 1): Src_mtype = 3, the views of mi3d_set_views
+// (Rad_mrkind = 2), a radiance job of the 3-D solver over Lambertian surfaces, without emission weights
+static int backward_views_unsupported(const mi3d_solver *h) {
+    const char *why = h->src_mtype == 1 ? "a solar job (Src_mtype=1): the sun needs a local estimate of its own"
+                      : h->src_mtype == 2 ? "a solar+thermal job (Src_mtype=2): the sun needs a local estimate of its own"
+                      : !(h->target & MI3D_TARGET_RADIANCE) || (h->target & MI3D_TARGET_FLUX) ? "a flux or heating-rate job: the route serves radiance (satellite images) alone"
+                      : h->rad_kind != 2 ? "cameras and point radiometers (Rad_mrkind=1): their switch is mi3d_set_camera_method (Rad_mbwd)"
+                      : h->solver != MI3D_SOLVER_3D ? "independent columns or partial 3-D: a line of sight crosses columns, it needs the 3-D solver"
+                      : !h->sfc_lambert_only ? "a non-Lambertian surface (only Lambertian surfaces emit)"
+                      : h->emis_weights ? "emission weights (mi3d_set_emission_weights 1): an image times the cells is out of its scope"
+                      : nullptr;
+    if (why) return fail(MI3D_EUNSUP, "backward Monte Carlo for satellite views (mi3d_set_view_method 1, Rad_mvbwd=1) does not serve %s", why);
+    return MI3D_OK;
+}
+
+static int fill_backward(mi3d_solver *h, DevBackward &A, bool sat = false) {
     std::memset(&A, 0, sizeof(A));
     const double Lx = h->dx * h->nx, Ly = h->dy * h->ny;
     const bool sfc2d = !h->sfc2d_host.empty();
@@ -2381,19 +2418,36 @@ static int fill_backward(mi3d_solver *h, DevBackward &A) {
     A.lay = h->d_lay.p; A.vrec = h->d_vrec.p; A.csca = h->d_csca.p; A.cells = h->d_bwd_cells.p; A.cams = h->d_cams.p;
     A.tab.tmu = h->d_tmu.p; A.tab.tp = h->d_tp.p; A.tab.tcdf = h->d_tcdf.p; A.tab.nang = h->nang; A.tab.npf = h->npf;
     A.rad = h->rad_ptr(); A.counters = h->d_counters.p; A.capped = h->d_bwd_capped.p;
-    for (int iv = 0; iv < h->nview; ++iv)
+    if (sat) { A.cam_mode = 0; A.cams = nullptr; }
+    for (int iv = 0; iv < h->nview; ++iv) {
+        if (sat && !(std::cos(h->view_the[iv] * 3.14159265358979323846 / 180.0) < 0.0)) continue;   // (an up-looking view's plane is raised to the surface)
         if (!(h->view_zloc[iv] > h->zgrd[0]))
-            return fail(MI3D_EINVAL, "backward Monte Carlo: sensor %d stands on or below the surface (Rad_zloc=%g, surface at %g)", iv + 1, h->view_zloc[iv], h->zgrd[0]);
+            return fail(MI3D_EINVAL, sat ? "backward Monte Carlo: the sensor plane of view %d lies on or below the surface (Rad_zloc=%g, surface at %g)"
+                                         : "backward Monte Carlo: sensor %d stands on or below the surface (Rad_zloc=%g, surface at %g)", iv + 1, h->view_zloc[iv], h->zgrd[0]);
+    }
     if ((double)h->nview * h->nxr * h->nyr > 2147483647.0) return fail(MI3D_EUNSUP, "image too large for the 32-bit pixel numbers of the backward kernel");
     return MI3D_OK;
 }
 
+// What k_backward_v receives beside DevBackward
+static void fill_backward_views(const mi3d_solver *h, BwdSat &S, float *start_out) {
+    const double Lx = h->dx * h->nx, Ly = h->dy * h->ny;
+    std::memset(&S, 0, sizeof(S));
+    S.views = h->d_views.p;
+    S.pix_dx = (float)(Lx / h->nxr); S.pix_dy = (float)(Ly / h->nyr);
+    S.Lx = (float)Lx; S.Ly = (float)Ly; S.inv_Lx = (float)(1.0 / Lx); S.inv_Ly = (float)(1.0 / Ly);
+    S.jch = h->bwd_chunk < 0 ? kBwdChunkAuto : h->bwd_chunk;
+    S.start_out = start_out;
+}
+
 static int run_backward(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_offset) {
-    int rc = backward_unsupported(h);
+    const bool sat = h->sat_backward();
+    int rc = sat ? backward_views_unsupported(h) : backward_unsupported(h);
     if (rc) return rc;
+    if (h->nview == 0) return fail(MI3D_ESTATE, "radiance requested but no view is set (%s)", sat ? "mi3d_set_views" : "mi3d_set_cameras");
     if (nphoton == 0) return MI3D_OK;
     DevBackward A;
-    if ((rc = fill_backward(h, A))) return rc;
+    if ((rc = fill_backward(h, A, sat))) return rc;
     RunPlan plan = plan_run(h, nphoton);
     name_route(h, plan, false, nphoton);
     h->entry_form_last = 0;
@@ -2430,17 +2484,47 @@ static int run_backward(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_
         }
         cap = (uint64_t)h->num_cu * (uint64_t)h->wgt_cap;
     }
+    BwdSat S{};
+    uint64_t ntile = 0;
+    if (sat) {
+        // the satellite-view build: its LDS, and the resident workgroups per CU of the build launched, as the runtime works them out
+        fill_backward_views(h, S, nullptr);
+        lds = backward_lds_v(npix, h->nz, h->nview, false, S.jch > 0);
+        ntile = (uint64_t)h->nview * (uint64_t)((h->nxr + 7) / 8) * (uint64_t)((h->nyr + 7) / 8);
+        if (!h->sat_cap || h->sat_cap_lds != lds || h->sat_cap_counting != h->counting) {
+            int nb = 0;
+            const hipError_t eo = h->counting ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_backward_v<true, false>, 256, lds)
+                                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_backward_v<false, false>, 256, lds);
+            if (eo != hipSuccess || nb < 1) return fail(MI3D_EDEVICE, "backward Monte Carlo for satellite views: no workgroup fits a CU with %zu bytes of LDS", lds);
+            h->sat_cap = nb; h->sat_cap_lds = lds; h->sat_cap_counting = h->counting;
+        }
+        cap = (uint64_t)h->num_cu * (uint64_t)h->sat_cap;
+    }
     for (uint64_t done = 0; done < nphoton; done += h->batch) {
         const uint64_t nb = std::min<uint64_t>(h->batch, nphoton - done), off = photon_offset + done;
         if (h->pending.size() >= 64 && (rc = drain_events(h))) return rc;
-        const uint64_t want = (nb + 255) / 256;
+        uint64_t want = (nb + 255) / 256;
+        BwdSat Sl = S;
+        if (sat && S.jch > 0) {
+            // a wave per item of the tile hand-out, four to a workgroup.  A chunk the caller set is taken as it is; the default (-1) is at most
+            // kBwdChunkAuto: where tiles x chunks would leave resident waves without an item (a small image, few histories per pixel) the
+            // launch takes a smaller one
+            const uint64_t jmax = (nb + (uint64_t)npix - 1) / (uint64_t)npix, per_tile = (cap * 4 + ntile - 1) / ntile;
+            uint64_t jch = (uint64_t)S.jch;
+            if (h->bwd_chunk < 0 && per_tile > 1) jch = std::min<uint64_t>(jch, std::max<uint64_t>(1, jmax / per_tile));
+            Sl.jch = (int)jch;
+            want = (ntile * ((jmax + jch - 1) / jch) + 3) / 4;
+        }
         const unsigned grid = (unsigned)(want < cap ? want : cap);
+        if (sat) h->bwd_chunk_last = Sl.jch;
         hipEvent_t e0 = nullptr, e1 = nullptr;
         HIPCHK(hipEventCreate(&e0));
         hipError_t err = hipEventCreate(&e1);
         if (err == hipSuccess) err = hipEventRecord(e0, h->stream);
         if (err == hipSuccess) {
-            if (wgt && h->counting) hipLaunchKernelGGL((k_backward_w<true>), dim3(grid), dim3(256), lds, h->stream, A, seed, off, nb, W);
+            if (sat && h->counting) hipLaunchKernelGGL((k_backward_v<true, false>), dim3(grid), dim3(256), lds, h->stream, A, seed, off, nb, (float *)nullptr, (double *)nullptr, Sl);
+            else if (sat) hipLaunchKernelGGL((k_backward_v<false, false>), dim3(grid), dim3(256), lds, h->stream, A, seed, off, nb, (float *)nullptr, (double *)nullptr, Sl);
+            else if (wgt && h->counting) hipLaunchKernelGGL((k_backward_w<true>), dim3(grid), dim3(256), lds, h->stream, A, seed, off, nb, W);
             else if (wgt) hipLaunchKernelGGL((k_backward_w<false>), dim3(grid), dim3(256), lds, h->stream, A, seed, off, nb, W);
             else if (h->counting) hipLaunchKernelGGL((k_backward<true, false>), dim3(grid), dim3(256), lds, h->stream, A, seed, off, nb, (float *)nullptr, (double *)nullptr);
             else hipLaunchKernelGGL((k_backward<false, false>), dim3(grid), dim3(256), lds, h->stream, A, seed, off, nb, (float *)nullptr, (double *)nullptr);
@@ -2477,7 +2561,8 @@ int mi3d_run(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_of
     int rc = check_handle(h);
     if (rc) return rc;
     if ((rc = mi3d_prepare(h))) return rc;
-    if (h->cam_method == 1) return run_backward(h, nphoton, seed, photon_offset);
+    if (h->view_method == 1 && h->rad_kind != 2) return backward_views_unsupported(h);   // (names the switch: it belongs to the views of mi3d_set_views)
+    if (h->cam_method == 1 || h->view_method == 1) return run_backward(h, nphoton, seed, photon_offset);
     if (h->emis_weights)
         return fail(MI3D_EUNSUP, "emission weights (mi3d_set_emission_weights 1) are tallied by the backward route alone (mi3d_set_camera_method 1)");
     if ((h->target & MI3D_TARGET_RADIANCE) && h->nview == 0)
@@ -2699,6 +2784,10 @@ int mi3d_set_tuning(mi3d_solver *h, const char *key, int value) {
     else if (k == "overlap_sort") { if (value < 0 || value > 2) return fail(MI3D_EINVAL, "overlap_sort=%d outside [0,2]", value); HIPCHK(sync_streams(h)); h->overlap_sort = value; if (!value) h->tl[1].release(); }
     else if (k == "tl_split") { if (value < 1 || value > 64) return fail(MI3D_EINVAL, "tl_split=%d outside [1,64]", value); h->tl_split = value; }
     else if (k == "rays_wg" || k == "emit_wg") { if (value < 0 || value > 8) return fail(MI3D_EINVAL, "%s=%d outside [0,8]", key, value); (k == "rays_wg" ? h->rays_wg : h->emit_wg) = value; }
+    else if (k == "bwd_chunk") {   // (the satellite views' backward route: histories of a pixel per item of the tile hand-out; 0: the camera route's stride)
+        if (value < -1 || value > 65536) return fail(MI3D_EINVAL, "bwd_chunk=%d outside [-1,65536]", value);
+        HIPCHK(sync_main(h)); h->bwd_chunk = value;
+    }
     else if (k == "wgt_stage") { HIPCHK(sync_main(h)); h->wgt_stage = value ? -1 : 0; }   // (0: the emission weights' layer and surface part goes to global atomics always)
     else if (k == "cam_images") { if (value < -1 || value > 8) return fail(MI3D_EINVAL, "cam_images=%d outside [-1,8]", value); h->cam_images = value; }
     else if (k == "entry_records") { if (value < 0 || value > 2) return fail(MI3D_EINVAL, "entry_records=%d outside [0,2]", value); HIPCHK(sync_main(h)); h->entry_records = value; if (!value) h->pre[0].entry.release(); }
@@ -3117,6 +3206,37 @@ int mi3d_debug_backward(mi3d_solver *h, uint64_t seed, uint64_t id0, int n, floa
     return MI3D_OK;
 }
 
+int mi3d_debug_backward_views(mi3d_solver *h, uint64_t seed, uint64_t id0, int n, float *start_out, float *dir_out, double *score_out, uint64_t *capped_out) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (n < 0 || (n > 0 && (!start_out || !dir_out || !score_out))) return fail(MI3D_EINVAL, "bad arguments to mi3d_debug_backward_views");
+    if (h->view_method != 1 || h->cam_method != 0) return fail(MI3D_ESTATE, "mi3d_debug_backward_views: the route is not selected (mi3d_set_view_method 1, mi3d_set_camera_method 0)");
+    if ((rc = mi3d_prepare(h))) return rc;
+    if ((rc = backward_views_unsupported(h))) return rc;
+    if (h->nview == 0) return fail(MI3D_ESTATE, "mi3d_debug_backward_views: no view is set (mi3d_set_views)");
+    if (n > 0) {
+        DevBackward A;
+        BwdSat S;
+        if ((rc = fill_backward(h, A, true))) return rc;
+        if ((rc = h->d_bwd_start.alloc((size_t)3 * n)) || (rc = h->d_bwd_dir.alloc((size_t)3 * n)) || (rc = h->d_bwd_score.alloc(n))) return rc;
+        fill_backward_views(h, S, h->d_bwd_start.p);
+        // (every slot is written by the history of its id: the hand-out reaches every id of [id0, id0 + n) whatever the grid)
+        const size_t lds = backward_lds_v(h->nview * h->nxr * h->nyr, h->nz, h->nview, true, S.jch > 0);
+        hipLaunchKernelGGL((k_backward_v<false, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), lds, h->stream, A, seed, id0, (uint64_t)n, h->d_bwd_dir.p,
+                           h->d_bwd_score.p, S);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(start_out, h->d_bwd_start.p, (size_t)3 * n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(dir_out, h->d_bwd_dir.p, (size_t)3 * n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(score_out, h->d_bwd_score.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    }
+    if (capped_out) {
+        *capped_out = 0;
+        if (h->d_bwd_capped.p) { unsigned long long c = 0; HIPCHK(hipMemcpyAsync(&c, h->d_bwd_capped.p, sizeof(c), hipMemcpyDeviceToHost, h->stream)); HIPCHK(hipStreamSynchronize(h->stream)); *capped_out = c; }
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return MI3D_OK;
+}
+
 // Read-out of the emission weights (mi3d_set_emission_weights 1): the rows of K_raw by the rule of k_backward_norm, rounded to
 // float32 on the device and brought over through a staging buffer of at most 2^26 elements; planck: cells[c].y as the kernel read it
 int mi3d_get_emission_weights(mi3d_solver *h, uint64_t nphoton_total, float *weights, float *planck) {
@@ -3157,6 +3277,7 @@ int mi3d_get_emission_weights(mi3d_solver *h, uint64_t nphoton_total, float *wei
 }
 
 int mi3d_debug_weights_staged(mi3d_solver *h) { return h ? h->wgt_staged_last : 0; }
+int mi3d_debug_backward_chunk(mi3d_solver *h) { return h ? h->bwd_chunk_last : 0; }
 
 int mi3d_debug_phase_tables(mi3d_solver *h, int nang, int npf, float *mu, float *p, float *cdf, uint16_t *mu_idx, uint16_t *cdf_idx) {
     int rc = check_handle(h);

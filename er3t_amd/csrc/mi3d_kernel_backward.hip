@@ -13,6 +13,10 @@
 //                      instead of tallied
 //   k_backward_w<COUNT>   the same histories with mi3d_set_emission_weights 1: every term w (1 - exp(-ka l)) and w eps
 //                      that a history scores is also added to K_raw[pixel][cell], float64
+//   k_backward_v<COUNT, DEBUG>   the same histories for the satellite views of mi3d_set_view_method 1: block 0 places the
+//                      line of sight on the view's registration level inside pixel id mod npix, the history starts where that line meets the
+//                      sensor plane; the views are staged in LDS where the cameras were; ids are handed out by tiles of 8 x 8 pixels
+//                      ("bwd_chunk" >= 1) and a lane sums its pixel's scores in a register.  DEBUG: mi3d_debug_backward_views
 //   k_backward_norm    read-out: tally of pixel p / number of ids in [0, N) that map to p
 //   k_backward_norm_rows   the same rule for the rows of K_raw, rounded to float32
 //
@@ -31,6 +35,7 @@ namespace mi3d {
 
 constexpr unsigned kBwdMaxCells = 1u << 20;   // cell steps after which a history ends and is counted as capped
 constexpr float kBwdWeightEnd = 1.0e-7f;      // a history whose weight falls below this ends (bias <= 1e-7 max B)
+constexpr int kBwdChunkAuto = 4;              // mi3d_set_tuning "bwd_chunk" -1: the largest chunk of the tile hand-out
 constexpr int kBwdLdsPix = 2048;              // images up to this many pixels are summed per workgroup in LDS
 
 struct DevBackward {
@@ -57,6 +62,15 @@ struct BwdWeights {
     double *K;
     unsigned long long ncell;
     int nls, stage;
+};
+
+// What only the satellite-view build receives (mi3d_set_view_method 1): the views, the pixel size on the registration level, the domain,
+// the tile hand-out's chunk (jch histories of a pixel per item; 0: the plain stride of the camera route) and the debug entry's start points
+struct BwdSat {
+    const ViewRec *views;              // [nview]
+    float pix_dx, pix_dy, Lx, Ly, inv_Lx, inv_Ly;
+    int jch;
+    float *start_out;                  // [n][3] (DEBUG)
 };
 
 // One thread per cell, in the order of DevThermal's CDF (k_thermal_power): voxels in file order, layers, surface cells.
@@ -126,22 +140,37 @@ __device__ inline int bwd_wrap(const int i, const float d, const int n) {
 template <bool COUNT, bool DEBUG>
 __global__ void __launch_bounds__(256)
 k_backward(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, float *__restrict__ dir_out, double *__restrict__ score_out) {
-    constexpr bool WGT = false;
+    constexpr bool WGT = false, SAT = false;
     const BwdWeights W{};
+    const BwdSat S{};
 #include "mi3d_kernel_backward_body.inc"
 }
 
 template <bool COUNT>
 __global__ void __launch_bounds__(256)
 k_backward_w(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, const BwdWeights W) {
-    constexpr bool WGT = true, DEBUG = false;
+    constexpr bool WGT = true, DEBUG = false, SAT = false;
     float *const dir_out = nullptr; double *const score_out = nullptr;
+    const BwdSat S{};
+#include "mi3d_kernel_backward_body.inc"
+}
+
+template <bool COUNT, bool DEBUG>
+__global__ void __launch_bounds__(256)
+k_backward_v(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, float *__restrict__ dir_out, double *__restrict__ score_out,
+             const BwdSat S) {
+    constexpr bool WGT = false, SAT = true;
+    const BwdWeights W{};
 #include "mi3d_kernel_backward_body.inc"
 }
 
 // dynamic LDS of a launch: the workgroup's sums, the layer table, the cameras
 __host__ inline size_t backward_lds(int npix, int nz, int nview, bool debug) {
     return (size_t)((!debug && npix <= kBwdLdsPix) ? ((npix + 1) & ~1) : 0) * sizeof(double) + (size_t)nz * sizeof(LayerRec) + (size_t)nview * sizeof(CamRec);
+}
+// ... of the satellite-view build: the views instead of the cameras; no sums where the tile hand-out keeps them in registers
+__host__ inline size_t backward_lds_v(int npix, int nz, int nview, bool debug, bool tiles) {
+    return (size_t)((!debug && !tiles && npix <= kBwdLdsPix) ? ((npix + 1) & ~1) : 0) * sizeof(double) + (size_t)nz * sizeof(LayerRec) + (size_t)nview * sizeof(ViewRec);
 }
 // ... of a launch of the weights build.  stage: the layer and surface weights of every pixel are summed in LDS -- where the image's own
 // sums are, and the workgroup's dynamic LDS stays within 32 KB (five workgroups on a CU of 160 KB)

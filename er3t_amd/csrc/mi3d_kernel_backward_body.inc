@@ -1,29 +1,49 @@
 // mi3d_kernel_backward_body.inc — the histories of the backward route, the one body of k_backward<COUNT, DEBUG> and k_backward_w<COUNT>
-// (mi3d_kernel_backward.hip includes it inside either).  What it expects in scope: COUNT, DEBUG, WGT (compile-time constants), the arguments
-// A, seed, id0, n, dir_out, score_out, and W (BwdWeights: read where WGT holds, the weights build of DESIGN.md §5.12).
+// and k_backward_v<COUNT, DEBUG> (mi3d_kernel_backward.hip includes it inside each).  What it expects in scope: COUNT, DEBUG, WGT, SAT
+// (compile-time constants), the arguments A, seed, id0, n, dir_out, score_out, W (BwdWeights: read where WGT holds, the weights build of
+// DESIGN.md §5.12) and S (BwdSat: read where SAT holds, the satellite-view build of DESIGN.md §5.14).
     extern __shared__ double bwd_smem[];
     const int npix = A.nview * A.nxr * A.nyr;
-    const bool lds_sums = !DEBUG && npix <= kBwdLdsPix;
+    const bool tiles = SAT && S.jch > 0;                                     // the tile hand-out (mi3d_set_tuning "bwd_chunk" >= 1)
+    const bool lds_sums = !DEBUG && npix <= kBwdLdsPix && !tiles;
     double *sums = bwd_smem;
     const bool wstage = WGT && W.stage != 0;                                 // (the host sets it only where lds_sums holds)
     const int nls = WGT ? W.nls : 1, nwsum = wstage ? npix * nls : 0;
     double *wsum = bwd_smem + (lds_sums ? ((npix + 1) & ~1) : 0);           // [npix][nls] the workgroup's layer and surface weights
     LayerRec *slay = reinterpret_cast<LayerRec *>(bwd_smem + (lds_sums ? ((npix + 1) & ~1) : 0) + (WGT ? ((nwsum + 1) & ~1) : 0));   // (16-byte aligned)
     CamRec *scam = reinterpret_cast<CamRec *>(slay + A.nz);
+    const ViewRec *sview = reinterpret_cast<const ViewRec *>(scam);         // (SAT: the views stand where the cameras would)
     if (lds_sums) for (int i = threadIdx.x; i < npix; i += blockDim.x) sums[i] = 0.0;
     if (WGT) for (int i = threadIdx.x; i < nwsum; i += blockDim.x) wsum[i] = 0.0;
-    {   // layer table and cameras: 16-byte pieces
+    {   // layer table and cameras (SAT: views): 16-byte pieces
         const float4 *src = reinterpret_cast<const float4 *>(A.lay);
         float4 *dst = reinterpret_cast<float4 *>(slay);
         for (int i = threadIdx.x; i < A.nz * 4; i += blockDim.x) dst[i] = src[i];
-        src = reinterpret_cast<const float4 *>(A.cams); dst = reinterpret_cast<float4 *>(scam);
-        for (int i = threadIdx.x; i < A.nview * 4; i += blockDim.x) dst[i] = src[i];
+        src = SAT ? reinterpret_cast<const float4 *>(S.views) : reinterpret_cast<const float4 *>(A.cams); dst = reinterpret_cast<float4 *>(scam);
+        for (int i = threadIdx.x; i < A.nview * (SAT ? 2 : 4); i += blockDim.x) dst[i] = src[i];
     }
     __syncthreads();
 
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     uint64_t next = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;     // ids are handed out by a fixed stride
     unsigned long long c_hist = 0, c_steps = 0, c_steps3d = 0, c_scat = 0, c_sfc = 0;
+
+    // The tile hand-out of the SAT build (DESIGN.md §5.14).  An item is (tile of 8 x 8 pixels, chunk of up to jch consecutive histories of each
+    // of its pixels), number tile * nchunk + chunk; wave w of the launch takes the items w, w + nwaves, ...; lane L owns pixel (L & 7, L >> 3)
+    // of the tile.  Every lane walks this sequence on its own.  Pixel p's ids in the batch [id0, id0 + n) are id0 + r + j npix with
+    // r = (p - id0) mod npix, j < cnt = n / npix + (r < n mod npix): the two 64-bit remainders are the launch's, taken once.
+    const int lane = threadIdx.x & 63;
+    const uint64_t nwaves = stride >> 6;
+    const int tiles_x = SAT ? (A.nxr + 7) >> 3 : 1, tiles_v = SAT ? tiles_x * ((A.nyr + 7) >> 3) : 1;
+    const int off_m = tiles ? (int)(id0 % (uint64_t)npix) : 0, n_m = tiles ? (int)(n % (uint64_t)npix) : 0;
+    const uint64_t n_q = tiles ? n / (uint64_t)npix : 0;
+    const uint64_t jch = tiles ? (uint64_t)S.jch : 1;
+    const uint64_t nchunk = tiles ? (n_q + (n_m ? 1 : 0) + jch - 1) / jch : 1;
+    const uint64_t nitems = tiles ? (uint64_t)A.nview * (uint64_t)tiles_v * nchunk : 0;
+    uint64_t item = next >> 6, idn = 0;      // the lane's next item; the next id of its chunk ...
+    unsigned jn = 0;                         // ... and how many of the chunk are left
+    double acc = 0.0;                        // the sum of the scores of pixel accpix since it last changed
+    int accpix = 0;
 
     // the history's state
     bool have = false;
@@ -44,9 +64,10 @@
         ty = (uy > 0.0f ? A.dy - py : py) * aiy;
         tz = (uz > 0.0f ? dzk - pz : pz) * aiz;
     };
-    // the position inside the cell back from the DDA
-    auto pos_x = [&]() { const float d = tx * fabsf(ux); return fminf(fmaxf(ux > 0.0f ? A.dx - d : d, 0.0f), A.dx); };
-    auto pos_y = [&]() { const float d = ty * fabsf(uy); return fminf(fmaxf(uy > 0.0f ? A.dy - d : d, 0.0f), A.dy); };
+    // the position inside the cell back from the DDA.  SAT: a vertical view flies with ux = uy = 0 exactly, where t * |u| would be 0 and the
+    // position lost: the floor of set_dda's reciprocal gives it back (the camera builds never draw an exact 0 and keep their code)
+    auto pos_x = [&]() { const float d = tx * (SAT ? floor_abs(ux) : fabsf(ux)); return fminf(fmaxf(ux > 0.0f ? A.dx - d : d, 0.0f), A.dx); };
+    auto pos_y = [&]() { const float d = ty * (SAT ? floor_abs(uy) : fabsf(uy)); return fminf(fmaxf(uy > 0.0f ? A.dy - d : d, 0.0f), A.dy); };
     auto new_flight = [&]() {
         float u0;
         draw4(seed, id, draw++, u0, r1, r2, r3);
@@ -61,47 +82,89 @@
     for (;;) {
         bool ended = false;
         if (!have) {
-            if (next >= n) break;
-            slot = next; id = id0 + next; next += stride;
+            if (tiles) {
+                while (jn == 0u && item < nitems) {
+                    const uint64_t tile = item / nchunk, chunk = item - tile * nchunk;
+                    item += nwaves;
+                    const int iv = (int)tile / tiles_v, rem = (int)tile - iv * tiles_v, tj = rem / tiles_x, ti = rem - tj * tiles_x;
+                    const int ir = ti * 8 + (lane & 7), jr = tj * 8 + (lane >> 3);
+                    if (ir >= A.nxr || jr >= A.nyr) continue;                  // the tile is clipped at the image's edge
+                    const int p = (iv * A.nyr + jr) * A.nxr + ir;
+                    const int r = p - off_m + (p < off_m ? npix : 0);
+                    if ((uint64_t)r >= n) continue;                             // no id of this pixel in the batch
+                    const uint64_t cnt = n_q + (r < n_m ? 1u : 0u), j0 = chunk * jch;
+                    if (j0 >= cnt) continue;
+                    jn = (unsigned)(cnt - j0 < jch ? cnt - j0 : jch);
+                    idn = id0 + (uint64_t)r + j0 * (uint64_t)npix;
+                    if (p != accpix) {
+                        if (!DEBUG && acc != 0.0) atomicAdd(&A.rad[accpix], acc);
+                        acc = 0.0; accpix = p;
+                    }
+                }
+                if (jn == 0u) break;
+                id = idn; slot = id - id0; idn += (uint64_t)npix; --jn;
+                pix = accpix;
+            } else {
+                if (next >= n) break;
+                slot = next; id = id0 + next; next += stride;
+                pix = (int)(id % (uint64_t)npix);
+            }
             have = true;
             score = 0.0; w = 1.0f; steps = 0; draw = 1;
-            pix = (int)(id % (uint64_t)npix);
             const int iv = pix / (A.nxr * A.nyr), rem = pix - iv * (A.nxr * A.nyr), jr = rem / A.nxr, ir = rem - jr * A.nxr;
-            const CamRec Cm = scam[iv];
             float u0, u1, u2, u3;
             draw4(seed, id, 0u, u0, u1, u2, u3);
-            float st, ct, ph;
-            bool ok = true;
-            if (!(A.cam_mode & kCamRect)) {
-                const float U = ((float)ir + u0 - 0.5f * (float)A.nxr) * frcp(Cm.inv_du), V = ((float)jr + u1 - 0.5f * (float)A.nyr) * frcp(Cm.inv_dv);
-                const float th = sqrtf(U * U + V * V);
-                ph = atan2f(V, U);
-                __sincosf(th, &st, &ct);
-                ok = th <= kPi;
-            } else {
-                const float du = 1.0f / Cm.inv_du, t0 = (float)ir * du, t1 = (float)(ir + 1) * du;
-                if (A.cam_mode & kCamCos) {
-                    const float s0 = sinf(t0), s1 = sinf(t1), s2 = fminf(fmaxf(fmaf(u0, s1 * s1 - s0 * s0, s0 * s0), 0.0f), 1.0f);
-                    st = sqrtf(s2); ct = sqrtf(1.0f - s2);
-                } else {
-                    const float c0 = cosf(t0), c1 = cosf(t1);
-                    ct = fminf(fmaxf(fmaf(u0, c1 - c0, c0), -1.0f), 1.0f);
-                    st = sqrtf(fmaxf(1.0f - ct * ct, 0.0f));
+            float x, y, z;
+            if (SAT) {
+                // a satellite view: the point (xr, yr) inside the pixel on the registration level, the line through it along the view
+                // direction, and where that line meets the sensor plane z = zs (mi3d.h, mi3d_set_view_method)
+                const ViewRec V = sview[iv];
+                const float xr = ((float)ir + u0) * S.pix_dx, yr = ((float)jr + u1) * S.pix_dy;
+                const float tq = (V.zs - V.zreg) / V.vz;                      // (up-looking: zreg is zs, 0)
+                x = fmaf(V.vx, tq, xr); y = fmaf(V.vy, tq, yr); z = V.zs;
+                x -= S.Lx * floorf(x * S.inv_Lx); y -= S.Ly * floorf(y * S.inv_Ly);
+                x = x >= S.Lx ? x - S.Lx : x; y = y >= S.Ly ? y - S.Ly : y;
+                x = fmaxf(x, 0.0f); y = fmaxf(y, 0.0f);
+                ux = -V.vx; uy = -V.vy; uz = -V.vz;
+                if (DEBUG) {
+                    dir_out[3 * slot] = ux; dir_out[3 * slot + 1] = uy; dir_out[3 * slot + 2] = uz;
+                    S.start_out[3 * slot] = x; S.start_out[3 * slot + 1] = y; S.start_out[3 * slot + 2] = z;
                 }
-                ph = ((float)jr + u1 - 0.5f * (float)A.nyr) / Cm.inv_dv;
+            } else {
+                const CamRec Cm = scam[iv];
+                float st, ct, ph;
+                bool ok = true;
+                if (!(A.cam_mode & kCamRect)) {
+                    const float U = ((float)ir + u0 - 0.5f * (float)A.nxr) * frcp(Cm.inv_du), V = ((float)jr + u1 - 0.5f * (float)A.nyr) * frcp(Cm.inv_dv);
+                    const float th = sqrtf(U * U + V * V);
+                    ph = atan2f(V, U);
+                    __sincosf(th, &st, &ct);
+                    ok = th <= kPi;
+                } else {
+                    const float du = 1.0f / Cm.inv_du, t0 = (float)ir * du, t1 = (float)(ir + 1) * du;
+                    if (A.cam_mode & kCamCos) {
+                        const float s0 = sinf(t0), s1 = sinf(t1), s2 = fminf(fmaxf(fmaf(u0, s1 * s1 - s0 * s0, s0 * s0), 0.0f), 1.0f);
+                        st = sqrtf(s2); ct = sqrtf(1.0f - s2);
+                    } else {
+                        const float c0 = cosf(t0), c1 = cosf(t1);
+                        ct = fminf(fmaxf(fmaf(u0, c1 - c0, c0), -1.0f), 1.0f);
+                        st = sqrtf(fmaxf(1.0f - ct * ct, 0.0f));
+                    }
+                    ph = ((float)jr + u1 - 0.5f * (float)A.nyr) / Cm.inv_dv;
+                }
+                float sp, cp;
+                sincosf(ph, &sp, &cp);
+                const float a = st * cp, b = st * sp;
+                ux = a * Cm.xx + b * Cm.yx + ct * Cm.zx;
+                uy = a * Cm.xy + b * Cm.yy + ct * Cm.zy;
+                uz = a * Cm.xz + b * Cm.yz + ct * Cm.zz;
+                const float nrm = 1.0f / sqrtf(ux * ux + uy * uy + uz * uz);
+                ux *= nrm; uy *= nrm; uz *= nrm;
+                if (DEBUG) { dir_out[3 * slot] = ux; dir_out[3 * slot + 1] = uy; dir_out[3 * slot + 2] = uz; }
+                if (!ok || ct < Cm.cos_half) ended = true;       // outside the image or the cone of view: 0
+                // where the history starts: the sensor, or where its line enters the top
+                x = Cm.cx; y = Cm.cy; z = Cm.cz;
             }
-            float sp, cp;
-            sincosf(ph, &sp, &cp);
-            const float a = st * cp, b = st * sp;
-            ux = a * Cm.xx + b * Cm.yx + ct * Cm.zx;
-            uy = a * Cm.xy + b * Cm.yy + ct * Cm.zy;
-            uz = a * Cm.xz + b * Cm.yz + ct * Cm.zz;
-            const float nrm = 1.0f / sqrtf(ux * ux + uy * uy + uz * uz);
-            ux *= nrm; uy *= nrm; uz *= nrm;
-            if (DEBUG) { dir_out[3 * slot] = ux; dir_out[3 * slot + 1] = uy; dir_out[3 * slot + 2] = uz; }
-            if (!ok || ct < Cm.cos_half) ended = true;       // outside the image or the cone of view: 0
-            // where the history starts: the sensor, or where its line enters the top
-            float x = Cm.cx, y = Cm.cy, z = Cm.cz;
             if (!ended && z >= A.ztoa) {
                 if (uz >= 0.0f) ended = true;                 // never enters
                 else { const float t = (z - A.ztoa) / -uz; x = fmaf(ux, t, x); y = fmaf(uy, t, y); z = A.ztoa; }
@@ -234,6 +297,7 @@
             have = false;
             const double s = score * (double)A.src_flx;
             if (DEBUG) score_out[slot] = s;
+            else if (tiles) acc += s;
             else if (s != 0.0) {
                 if (lds_sums) atomicAdd(&sums[pix], s);
                 else atomicAdd(&A.rad[pix], s);
@@ -241,6 +305,7 @@
             if (COUNT) c_hist++;
         }
     }
+    if (tiles && !DEBUG && acc != 0.0) atomicAdd(&A.rad[accpix], acc);
     if (lds_sums) {
         __syncthreads();
         for (int i = threadIdx.x; i < npix; i += blockDim.x) { const double s = sums[i]; if (s != 0.0) atomicAdd(&A.rad[i], s); }

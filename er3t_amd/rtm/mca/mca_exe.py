@@ -29,7 +29,11 @@ __all__ = ['JobRunner', 'run_job', 'main']
 _WARNED = set()
 
 
-def _check_supported(nml, fdir=None):
+def _flag(nml, key):
+    return float(np.ravel(nml.get(key))[0]) if nml.get(key) is not None else 0.0
+
+
+def _check_supported(nml, fdir=None, solver=None):
     if int(nml.get('Wld_moptim', 0) or 0) != 0 and 'moptim' not in _WARNED and world_info()[0] == 0:
         # (MCARaTS' biasing optimisations, er3t/rtm/mca/mca_inp.py:27-33; er3t sets 2 for tune=True, mcarats.py:257-260)
         _WARNED.add('moptim')
@@ -51,6 +55,19 @@ def _check_supported(nml, fdir=None):
         if mbwd == 1.0 and not (mtype == 3 and int(nml.get('Wld_mtarget', 1)) == 2 and int(nml.get('Rad_mrkind', 2)) == 1):
             raise OSError('Error [mca_exe]: <Rad_mbwd=1> (backward Monte Carlo) belongs to the all-sky cameras and point radiometers (<Rad_mrkind=1>) of a '
                           'thermal job (<Src_mtype=3>): a solar job\'s sun would need a local estimate of its own.')
+    if nml.get('Rad_mvbwd') is not None:
+        mvbwd = float(np.ravel(nml.get('Rad_mvbwd'))[0])
+        if mvbwd not in (0.0, 1.0):
+            raise OSError('Error [mca_exe]: <Rad_mvbwd=%g> is not supported (0: forward, 1: backward Monte Carlo for satellite views; a key of this '
+                          'project).' % mvbwd)
+        if mvbwd == 1.0:
+            why = 'a thermal job (<Src_mtype=3>): a solar job\'s sun would need a local estimate of its own' if mtype != 3 \
+                else 'a radiance job (<Wld_mtarget=2>): fluxes and heating rates are not served backwards' if int(nml.get('Wld_mtarget', 1)) != 2 \
+                else 'satellite views (<Rad_mrkind=2>): cameras and point radiometers have <Rad_mbwd>' if int(nml.get('Rad_mrkind', 2)) != 2 \
+                else 'no emission weights (<Rad_mwgt=1> is served for cameras and point radiometers alone)' if _flag(nml, 'Rad_mwgt') == 1.0 \
+                else None
+            if why:
+                raise OSError('Error [mca_exe]: <Rad_mvbwd=1> (backward Monte Carlo for satellite views) needs %s.' % why)
     if nml.get('Rad_mwgt') is not None:
         mwgt = float(np.ravel(nml.get('Rad_mwgt'))[0])
         if mwgt not in (0.0, 1.0):
@@ -72,6 +89,9 @@ def _check_supported(nml, fdir=None):
             raise OSError('Error [mca_exe]: <Src_fsol=%g> of a solar+thermal job (<Src_mtype=2>) must be finite and >= 0.' % fsol)
     if mtype in (2, 3):
         _check_thermal(nml, fdir)
+    if solver is not None and int(solver) != 0 and _flag(nml, 'Rad_mvbwd') == 1.0:
+        raise OSError('Error [mca_exe]: <Rad_mvbwd=1> (backward Monte Carlo for satellite views) needs the 3-D solver: a line of sight crosses '
+                      'columns (independent columns and partial 3-D are not served).')
 
 
 def _check_thermal(nml, fdir):
@@ -115,7 +135,8 @@ def thermal_heating(nml):
     thermal flux and satellite-radiance jobs only (source_amplitude), and lifting these refusals is a change of its own"""
     mtype = int(nml.get('Src_mtype', 1) or 1)
     return mtype == 2 or (mtype == 3 and int(nml.get('Wld_mtarget', 1)) == 1 and int(nml.get('Flx_mhrt', 0) or 0) == 2) \
-        or (mtype == 3 and int(nml.get('Wld_mtarget', 1)) == 2 and int(nml.get('Rad_mrkind', 2)) == 1)
+        or (mtype == 3 and int(nml.get('Wld_mtarget', 1)) == 2 and int(nml.get('Rad_mrkind', 2)) == 1) \
+        or (mtype == 3 and _flag(nml, 'Rad_mvbwd') == 1.0)      # (satellite views served backwards: every pixel is divided by its own count of histories)
 
 
 def wants_rdir(scene):
@@ -220,7 +241,7 @@ class JobRunner:
         return tuple(keys)
 
     def load(self, nml, fdir, solver, slot=0):
-        _check_supported(nml, fdir)
+        _check_supported(nml, fdir, solver=solver)
         sol = self.sols[slot]
         key = (self._file_key(nml, fdir), int(solver))
         if key == self._key3d[slot]:
@@ -348,6 +369,10 @@ class JobRunner:
                     raise OSError('Error [mca_exe]: the cameras and point radiometers of a thermal job (Rad_mrkind=1) are not served by the batched route '
                                   '(a camera\'s tallies are scaled with the emitted power: include/mi3d.h, mi3d_get_radiance); run such jobs one by one '
                                   '(run_job), as mca_run does.')
+                if getattr(sc, 'view_method', 0) == 1:
+                    raise OSError('Error [mca_exe]: satellite views served backwards (Rad_mvbwd=1) are not served by the batched route (every pixel is '
+                                  'divided by its own count of histories: include/mi3d.h, mi3d_set_view_method); run such jobs one by one (run_job), '
+                                  'as mca_run does.')
                 sizes = (max(sc.nview, 1)*sc.nyr*sc.nxr if sc.target & TARGET_RADIANCE else 0,
                          3*(sc.nz+1)*sc.ny*sc.nx if sc.target & TARGET_FLUX else 0,
                          sc.nz*sc.ny*sc.nx if sc.target & TARGET_HEAT else 0)

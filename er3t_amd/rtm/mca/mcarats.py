@@ -110,6 +110,12 @@ class mcarats_ng:
                            (Rad_mbwd=1, a key of this project written only then: include/mi3d.h, mi3d_set_camera_method).
                            No 1 / r^2 and no aperture clamp -- a sensor may stand inside a cloud or absorbing air --, the whole cyclic
                            domain is seen: <camera_images> must not be given and Rad_nimg is not written
+        view_method ['forward']: 'backward' serves the satellite views of a <source='thermal'>, <target='radiance'>, <sensor_type='satellite'>,
+                           <solver='3d'> job by backward Monte Carlo: every history starts on the sensor plane inside its pixel and collects
+                           the emission along the view's line of sight, every pixel gets the same number of histories (Rad_mvbwd=1, a key of
+                           this project written only then: include/mi3d.h, mi3d_set_view_method).  Sequences of sensor angles
+                           (several views in one simulation) are served; `mca_out_ng` is unchanged: rad, bt and the view axis come out as for
+                           the forward job
         emission_weights [False]: with camera_method='backward': every job also tallies K[pixel][cell], the share of a pixel's reading that comes
                            from a voxel, a layer or a surface cell per unit Planck radiance there (Rad_mwgt=1, a key of this project written
                            only then: include/mi3d.h, mi3d_set_emission_weights); mca_out_ng returns data['emission_weight']
@@ -126,7 +132,7 @@ class mcarats_ng:
                  sensor_azimuth_angle=0.0, sensor_altitude=705000.0, sensor_type='satellite', sensor_xpos=0.5,
                  sensor_ypos=0.5, solver='3d', photons=1e7, base_ratio=0.05, verbose=False, quiet=False,
                  abs_obj=None, keep_files=True, source='solar', wavelength=None, surface_temperature=None,
-                 heating_estimator='collision', camera_images=None, camera_method='forward', emission_weights=False):
+                 heating_estimator='collision', camera_images=None, camera_method='forward', emission_weights=False, view_method='forward'):
 
         # one process per GPU (torch.distributed): rank 0 writes the job files, all ranks transport their share of every job
         from er3t_amd.dist import world_info, barrier
@@ -178,6 +184,19 @@ class mcarats_ng:
             if camera_images is not None:
                 raise OSError('Error [mcarats_ng]: <camera_images> does not go with <camera_method=\'backward\'>: a line of sight wraps through the '
                               'whole cyclic domain, no periodic images are enumerated.')
+        self.view_method = str(view_method).lower()
+        if self.view_method not in ('forward', 'backward'):
+            raise OSError('Error [mcarats_ng]: <view_method=%s> must be \'forward\' or \'backward\'.' % view_method)
+        if self.view_method == 'backward':
+            if self.source != 'thermal' or str(target).lower() not in _TARGETS['radiance'] or 'satellite' not in str(sensor_type).lower():
+                raise OSError('Error [mcarats_ng]: <view_method=\'backward\'> needs <source=\'thermal\'> and <target=\'radiance\'> with '
+                              '<sensor_type=\'satellite\'>: backward histories collect emission; the sun would need a local estimate of its own '
+                              '(cameras and point radiometers: <camera_method>).')
+            if _match(solver, _SOLVERS, 'solver') != '3D':
+                raise OSError('Error [mcarats_ng]: <view_method=\'backward\'> needs <solver=\'3d\'>: a line of sight crosses columns.')
+            if emission_weights:
+                raise OSError('Error [mcarats_ng]: <emission_weights=True> does not go with <view_method=\'backward\'>: the weights of an image times '
+                              'the cells are not served.')
         self.emission_weights = bool(emission_weights)
         if self.emission_weights and self.camera_method != 'backward':
             raise OSError('Error [mcarats_ng]: <emission_weights=True> needs <camera_method=\'backward\'>: the per-cell weights are what backward '
@@ -261,7 +280,9 @@ class mcarats_ng:
 
         # (Rad_nimg: a thermal sensor job always says how far its periodic images are served -- 2 unless told otherwise --; a solar job file
         #  carries the key only when <camera_images> is given, and stays what it was, byte for byte, without)
-        if self.camera_method == 'backward':           # (written only then: every other job file stays what it was, byte for byte)
+        if self.view_method == 'backward':             # (written only then: every other job file stays what it was, byte for byte)
+            self._all({'Rad_mvbwd': 1})
+        if self.camera_method == 'backward':           # (likewise)
             self._all({'Rad_mbwd': 1})
             if self.emission_weights:                  # (likewise)
                 self._all({'Rad_mwgt': 1})

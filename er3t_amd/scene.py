@@ -116,6 +116,8 @@ class Scene:
 
     cam_method: int = 0                   # Rad_mbwd (a key of this project; include/mi3d.h: mi3d_set_camera_method): 0 the forward route, 1 backward
                                           # Monte Carlo -- thermal cameras and point radiometers only; cam_images is then not used
+    view_method: int = 0                  # Rad_mvbwd (a key of this project; include/mi3d.h: mi3d_set_view_method): 0 the forward route, 1 backward
+                                          # Monte Carlo for the satellite views (rad_kind = 2) of a thermal job
     cam_weights: int = 0                  # Rad_mwgt (a key of this project; include/mi3d.h: mi3d_set_emission_weights): 1 the backward route also
                                           # tallies the per-cell emission weights K[pixel][cell] of every sensor; needs cam_method = 1
 
@@ -186,6 +188,11 @@ class Scene:
             raise ValueError('Error [Scene]: <rad_kind=%s> (Rad_mrkind) must be 1 or 2.' % self.rad_kind)
         elif self.cam_method != 0:
             raise ValueError('Error [Scene]: <cam_method=%s> (Rad_mbwd) belongs to cameras and point radiometers (<rad_kind=1>).' % self.cam_method)
+        if self.view_method not in (0, 1) or isinstance(self.view_method, float):
+            raise ValueError('Error [Scene]: <view_method=%s> (Rad_mvbwd) must be 0 (forward) or 1 (backward).' % (self.view_method,))
+        if self.view_method == 1 and self.rad_kind != 2:
+            raise ValueError('Error [Scene]: <view_method=1> (Rad_mvbwd) belongs to satellite views (<rad_kind=2>); cameras and point radiometers '
+                             'have <cam_method> (Rad_mbwd).')
         if self.cam_weights not in (0, 1):
             raise ValueError('Error [Scene]: <cam_weights=%s> (Rad_mwgt) must be 0 or 1.' % (self.cam_weights,))
         if self.cam_weights == 1 and not (self.rad_kind == 1 and self.cam_method == 1):
@@ -352,6 +359,13 @@ class Scene:
         if mbwd == 1.0 and not (mtype == 3 and mtarget == 2 and int(get('Rad_mrkind', 2)) == 1):
             raise OSError('Error [Scene]: <Rad_mbwd=1> (backward Monte Carlo) belongs to the cameras and point radiometers (<Rad_mrkind=1>) of a '
                           'thermal job (<Src_mtype=3>).')
+        # (a key of this project: backward Monte Carlo for the satellite views of a thermal job)
+        mvbwd = float(np.ravel(get('Rad_mvbwd', 0))[0])
+        if mvbwd not in (0.0, 1.0):
+            raise OSError('Error [Scene]: <Rad_mvbwd=%g> is not supported (0: forward, 1: backward Monte Carlo for satellite views).' % mvbwd)
+        if mvbwd == 1.0 and not (mtype == 3 and mtarget == 2 and int(get('Rad_mrkind', 2)) == 2 and int(solver) == SOLVER_3D):
+            raise OSError('Error [Scene]: <Rad_mvbwd=1> (backward Monte Carlo) belongs to the satellite views (<Rad_mrkind=2>) of a thermal radiance '
+                          'job (<Src_mtype=3>, <Wld_mtarget=2>) under the 3-D solver.')
         # (a key of this project: per-cell emission weights of the backward route)
         mwgt = float(np.ravel(get('Rad_mwgt', 0))[0])
         if mwgt not in (0.0, 1.0):
@@ -386,6 +400,8 @@ class Scene:
                     kw.update(cam_images=int(nimg))
             elif mrkind != 2:
                 raise OSError('Error [Scene]: <Rad_mrkind=%d> is not supported (1: camera, 2: satellite).' % mrkind)
+            else:
+                kw.update(view_method=int(mvbwd))
         elif mtarget == 1:
             mhrt = int(get('Flx_mhrt', 0) or 0)
             if mhrt == 2 and mtype not in (2, 3):

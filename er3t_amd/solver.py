@@ -48,10 +48,12 @@ _SIGNATURES = [
     ('mi3d_set_cameras'        , C.c_int   , [C.c_void_p, C.c_int] + [_dp]*10 + [C.c_int, C.c_int]),
     ('mi3d_set_camera_map'     , C.c_int   , [C.c_void_p, C.c_int, C.c_int]),
     ('mi3d_set_camera_method'  , C.c_int   , [C.c_void_p, C.c_int]),
+    ('mi3d_set_view_method'    , C.c_int   , [C.c_void_p, C.c_int]),
     ('mi3d_set_emission_weights', C.c_int  , [C.c_void_p, C.c_int]),
     ('mi3d_bind_weights_buffer', C.c_int   , [C.c_void_p, C.c_void_p]),
     ('mi3d_get_emission_weights', C.c_int  , [C.c_void_p, _u64, _fp, _fp]),
     ('mi3d_debug_weights_staged', C.c_int  , [C.c_void_p]),
+    ('mi3d_debug_backward_chunk', C.c_int  , [C.c_void_p]),
     ('mi3d_set_options'        , C.c_int   , [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int]),
     ('mi3d_set_le_roulette'    , C.c_int   , [C.c_void_p, C.c_double]),
     ('mi3d_set_le_weight_roulette', C.c_int, [C.c_void_p, C.c_double]),
@@ -86,6 +88,7 @@ _SIGNATURES = [
     ('mi3d_debug_entry'        , C.c_int   , [C.c_void_p, _u64, _fp]),
     ('mi3d_debug_thermal'      , C.c_int   , [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), _u64]),
     ('mi3d_debug_backward'     , C.c_int   , [C.c_void_p, _u64, _u64, C.c_int, _fp, _dp, C.POINTER(_u64)]),
+    ('mi3d_debug_backward_views', C.c_int  , [C.c_void_p, _u64, _u64, C.c_int, _fp, _fp, _dp, C.POINTER(_u64)]),
     ('mi3d_debug_phase_tables' , C.c_int   , [C.c_void_p, C.c_int, C.c_int, _fp, _fp, _fp, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]),
     ('mi3d_debug_phase'        , C.c_int   , [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp]),
     ('mi3d_debug_rotate'       , C.c_int   , [C.c_void_p, C.c_int, _fp, _fp, _fp, _fp, _fp]),
@@ -286,6 +289,14 @@ class Mi3dSolver:
             raise ValueError('Error [Mi3dSolver]: <method=%r> must be \'forward\' (0) or \'backward\' (1).' % (method,))
         self._chk(self.lib.mi3d_set_camera_method(self._h, int(m)))
 
+    def set_view_method(self, method='forward'):
+        """how the satellite views of a thermal job are served (include/mi3d.h: mi3d_set_view_method): 'forward' (0), the local estimates of
+        forward photons, or 'backward' (1), histories that start on the sensor plane of their pixel"""
+        m = {'forward': 0, 'backward': 1}.get(method, method)
+        if m not in (0, 1):
+            raise ValueError('Error [Mi3dSolver]: <method=%r> must be \'forward\' (0) or \'backward\' (1).' % (method,))
+        self._chk(self.lib.mi3d_set_view_method(self._h, int(m)))
+
     def set_emission_weights(self, on=True):
         """per-cell emission weights of the backward route (include/mi3d.h: mi3d_set_emission_weights): on, every run also tallies
         K[pixel][cell], the share of a pixel's reading that comes from a cell per unit Planck radiance there"""
@@ -329,6 +340,7 @@ class Mi3dSolver:
         else:
             self.set_views(s.view_the, s.view_phi, s.view_zloc, zref=s.zref, nxr=s.nxr, nyr=s.nyr)
         self.set_camera_method(int(getattr(s, 'cam_method', 0)))
+        self.set_view_method(int(getattr(s, 'view_method', 0)))
         self.set_emission_weights(int(getattr(s, 'cam_weights', 0)))
         self.set_options(s.target, s.solver, s.wmin, s.wfac, column_le)
         self.set_heating_estimator(int(getattr(s, 'heat_estimator', 0)))
@@ -530,6 +542,15 @@ class Mi3dSolver:
         d = np.zeros((int(n), 3), dtype=np.float32); sc = np.zeros(int(n), dtype=np.float64); cap = _u64(0)
         self._chk(self.lib.mi3d_debug_backward(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(id0), int(n), _ptr(d), _ptr(sc, _dp), C.byref(cap)))
         return d, sc, int(cap.value)
+
+    def debug_backward_views(self, seed, id0, n):
+        """test hook of the backward route for satellite views: (start points (n, 3) float32, directions (n, 3) float32 of flight, scores
+        (n,) float64 as they enter the raw tally, capped histories of the runs since the last reset) for the ids id0 .. id0 + n - 1
+        (include/mi3d.h: mi3d_debug_backward_views)"""
+        st = np.zeros((int(n), 3), dtype=np.float32); d = np.zeros((int(n), 3), dtype=np.float32); sc = np.zeros(int(n), dtype=np.float64); cap = _u64(0)
+        self._chk(self.lib.mi3d_debug_backward_views(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(id0), int(n), _ptr(st), _ptr(d), _ptr(sc, _dp),
+                                                     C.byref(cap)))
+        return st, d, sc, int(cap.value)
 
     def debug_phase_tables(self, nang, npf):
         """test hook: the device's phase tables after set_phase + prepare: (mu [nang], p [npf, nang], cdf [npf, nang]) float32 and the

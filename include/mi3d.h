@@ -312,6 +312,40 @@ int mi3d_set_camera_map(mi3d_solver *h, int mpmap, int mrproj);
  *              mi3d_get_camera_direct stays zeros.  Counters (counting builds): photons = histories, steps, steps3d, scatter, surface. */
 int mi3d_set_camera_method(mi3d_solver *h, int method);
 
+/* How the satellite views (mi3d_set_views, Rad_mrkind = 2) of a THERMAL job are served: 0 (default) the forward route -- local estimates
+ * from every emission and collision --, 1 backward (adjoint) Monte Carlo (er3t_amd/csrc/mi3d_kernel_backward.hip; the
+ * project's namelist key Rad_mvbwd = 1).  A history starts on the sensor plane of its pixel's view and flies backwards along the view's
+ * line of sight; from its first flight on it is the history of mi3d_set_camera_method 1.  Every pixel gets the same number of
+ * histories.  The forward route, and mi3d_set_camera_method with every refusal it has, are untouched by the choice; anything but 0 or 1
+ * is MI3D_EINVAL.
+ *   Served     Src_mtype = 3, the views of mi3d_set_views, a radiance job of the 3-D solver, Lambertian surfaces (uniform or 2-D, Sfc_tmps2d
+ *              included).  Solar and solar+thermal jobs, flux jobs, independent columns, partial 3-D, non-Lambertian surfaces, and
+ *              mi3d_set_emission_weights 1 (an image times the cells): MI3D_EUNSUP from mi3d_run, with the reason.  The switch is
+ *              accepted while cameras are set (mi3d_set_cameras); mi3d_run then returns MI3D_EUNSUP and names it.  A down-looking view
+ *              whose sensor plane lies on or below the surface: MI3D_EINVAL.  mi3d_last_kernel: "k_backward<C,V> [thermal]".
+ *   Pixel      as for mi3d_set_camera_method 1: npix = nview nyr nxr, history id belongs to the flat pixel p = id mod npix in the tally
+ *              layout [view][jr][ir]; mi3d_get_radiance, mi3d_stats_add and the fused statistics divide pixel p by the exact number of
+ *              ids of [0, nphoton_total) that map to it.
+ *   Sample     Philox block 0 of (seed, id): u0, u1.  The point (xr, yr) = ((ir + u0) Lx / nxr, (jr + u1) Ly / nyr) lies on the view's
+ *              registration level z = zreg, the level on which the forward route finds a line of sight's pixel: Rad_zref for a
+ *              down-looking view, the sensor plane for an up-looking one.  v = (-sin the cos phi, -sin the sin phi, -cos the) is the unit
+ *              vector towards the sensor, an all but vertical one snapped to (0, 0, +-1) as the forward route snaps it; the sensor plane is
+ *              zs = min(Rad_zloc, top), raised to the surface for an up-looking view.  The pixel value is the radiance along v averaged
+ *              over the pixel's footprint on z = zreg: what the forward route's tally estimates.
+ *   Start      down-looking (vz > 0): (xr, yr) + (vx, vy) / vz (zs - Rad_zref), folded into the cyclic domain, at z = zs; up-looking:
+ *              (xr, yr, zs).  The history flies along -v; an up-looking plane at or above the top scores 0.  On a level or a cell face
+ *              the direction decides the cell.
+ *   Flight, events, ending, units   those of mi3d_set_camera_method 1 from the first flight on, with the same sequence of Philox blocks
+ *              (block 0 places the line, the first flight takes block 1): absolute radiance in W m-2 sr-1 um-1, the score carries Src_flx.
+ *   Hand-out   mi3d_set_tuning "bwd_chunk" n >= 1: every view's image is cut into tiles of 8 x 8 pixels; a wave takes (tile, chunk of up
+ *              to n consecutive histories of each of its pixels) by a fixed stride, lane L owns pixel L of the tile and sums its scores
+ *              in a register, one atomic per pixel change.  0: the stride of the camera route, an atomic per history.  -1 (default): the
+ *              tile hand-out with a chunk chosen per launch, at most 4: a launch whose tiles x chunks would leave resident waves
+ *              without an item takes a smaller one.  Results differ by the order of float64 sums only.  "batch_log2" is read as by the
+ *              camera route.  mi3d_debug_backward_chunk: the chunk of the launch made last (0: the stride).  No view set: MI3D_ESTATE. */
+int mi3d_set_view_method(mi3d_solver *h, int method);
+int mi3d_debug_backward_chunk(mi3d_solver *h);
+
 /* Per-cell emission weights of the backward route (the project's namelist key Rad_mwgt = 1).  The path of a backward
  * history, its weight w and ka do not depend on any temperature, so a pixel's reading is exactly linear in the cells' Planck radiances:
  *     R_p = Src_flx  sum_c K[p][c] B_c,    K[p][c] = (1 / N_p) sum over p's histories and their segments in c of  w (1 - exp(-ka l))
@@ -437,7 +471,7 @@ int mi3d_sync(mi3d_solver *h);
  * analytic phase functions (er3t's default scene), 1: a second 3-D constituent, 2: the general mixture (several 1-D constituents,
  * tabulated phase functions staged in LDS) --, "k_transport<COUNT,MARCH,FLUX,P3D>": the general kernel (flux together with radiance,
  * more than two 3-D constituents, tables too large for the LDS, kernel choice 1); "k_backward<COUNT> [thermal]": the backward route of
- * mi3d_set_camera_method 1, whatever mi3d_set_kernel says -- "batch_log2" is the one tuning knob it reads (ids per launch; a launch is
+ * mi3d_set_camera_method 1 ("k_backward<COUNT,V> [thermal]": of mi3d_set_view_method 1), whatever mi3d_set_kernel says -- "batch_log2" is the one tuning knob it reads (ids per launch; a launch is
  * min(ids / 256, what is resident at once: 5 per CU, 4 in the counting build) workgroups of 256 lanes, every lane walks its ids with a fixed stride); "" before the first launch).  For logs and
  * measurements (bench.py, profiles/): results do not depend on it. */
 const char *mi3d_last_kernel(mi3d_solver *h);
@@ -484,6 +518,8 @@ int mi3d_set_kernel(mi3d_solver *h, int choice);
  *   own_stream     0        0, 1       a non-blocking stream of the handle's own instead of the NULL stream            tools/time_dropin.py                no
  *   wgt_stage      1        0, 1       emission weights: layer and surface part summed per workgroup in LDS where it     tests/test_gpu_emission_weights.py  no
  *                                      fits 32 KB (0: global atomics always)
+ *   bwd_chunk      -1       -1..65536  mi3d_set_view_method 1: consecutive histories of a pixel in an item of the tile       profiles/r17/thermal_rate_sat.log   no
+ *                                      hand-out (0: the camera route's stride, an atomic per history; -1: per launch, at most 4)
  */
 int mi3d_set_tuning(mi3d_solver *h, const char *key, int value);
 
@@ -604,6 +640,11 @@ int mi3d_debug_thermal(mi3d_solver *h, double *ptot, double *cdf_out, uint64_t n
  * is tallied.  capped_out (if not NULL): the histories of this handle's runs since the last mi3d_reset that ended at 2^20 cell steps;
  * n = 0 asks for it alone. */
 int mi3d_debug_backward(mi3d_solver *h, uint64_t seed, uint64_t id0, int n, float *dir_out, double *score_out, uint64_t *capped_out);
+/* Test hook of the backward route for satellite views (mi3d_set_view_method 1 with mi3d_set_camera_method 0; MI3D_ESTATE otherwise): the
+ * same for ids id0 .. id0 + n - 1, through the hand-out "bwd_chunk" selects.  start_out [n][3] where history id starts (folded into the
+ * domain, z = the sensor plane), dir_out [n][3] its direction -v, score_out [n] what it adds to the raw tally of pixel id mod npix. */
+int mi3d_debug_backward_views(mi3d_solver *h, uint64_t seed, uint64_t id0, int n, float *start_out, float *dir_out, double *score_out,
+                              uint64_t *capped_out);
 /* Test hook: the phase tables as they stand on the device after mi3d_set_phase + mi3d_prepare (each pointer may be NULL): mu [nang]
  * ascending, p and cdf [npf][nang] (float32, normalised), the bucket index of mu [MI3D_TAB_IDX_N] and those of the CDFs
  * [npf][MI3D_TAB_IDX_N] (uint16).  nang / npf must be the loaded ones (otherwise MI3D_EINVAL); MI3D_ESTATE when no table is loaded or

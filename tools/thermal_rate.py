@@ -26,6 +26,12 @@ time of the 16 batches.  --photons: photons per forward batch; --histories: hist
 Leg 'wgt' (DESIGN.md 5.12): the same sixteen sensors by backward Monte Carlo with the per-cell emission weights (cam_weights) off, then on:
 histories per second and kernel time of both, their ratio, and the cell steps of a history from the counting build.
     python tools/thermal_rate.py --legs wgt --histories 1.6e6
+Leg 'sat' (DESIGN.md 5.14): a satellite image with a nadir and a 45 degree view in one job, by the forward route and by backward Monte Carlo
+(view_method = 1) under "bwd_chunk" 0 (the stride hand-out), 4, 8, 16, 32 and -1 (the default: chosen per launch): 16 batches each over
+disjoint id ranges; histories (photons) per second, kernel time, the chunk the launches ran with, the relative standard error per pixel over
+the batches (mean and largest over the pixels) and the figure of merit 1 / (se^2 t), se the mean relative standard error of a pixel.
+--photons: photons per forward batch; --per-pixel: histories per pixel and backward batch (32: every chunk of the list is a launch of its own).
+    python tools/thermal_rate.py --legs sat --photons 2e6 --per-pixel 32
 """
 
 import argparse
@@ -90,6 +96,43 @@ def merit_rows(sol, name, s, n_fwd, n_bwd, nb=16):
     return rows
 
 
+def sat_rows(sol, name, s, n_fwd, per_pixel, chunks=(0, 4, 8, 16, 32, -1), nb=16):
+    """the 'sat' leg: the image of scene s (a nadir and a 45 degree view in one job) by the forward route and by the backward route under
+    every hand-out of `chunks`, nb batches each over disjoint id ranges"""
+    s = dataclasses.replace(s, view_the=[180.0, 135.0], view_phi=[0.0, 0.0], view_zloc=[1.0e6, 1.0e6], nxr=s.nx, nyr=s.ny)
+    npix = 2*s.nx*s.ny
+    rows = []
+    try:
+        for method, chunk, n in [(0, None, n_fwd)]+[(1, c, per_pixel*npix) for c in chunks]:
+            if chunk is not None:
+                sol.set_tuning(bwd_chunk=chunk)
+            sol.load_scene(dataclasses.replace(s, view_method=method))
+            sol.reset(); sol.run(min(n, 2000000), seed=1); sol.sync()        # warm-up
+            tot, sq, ms_all = np.zeros((2, s.ny, s.nx)), np.zeros((2, s.ny, s.nx)), 0.0
+            for b in range(nb):
+                sol.reset()
+                sol.run(n, seed=2, offset=b*n)
+                r = sol.radiance(n).astype(np.float64)
+                tot += r; sq += r*r
+                ms_all += sol.timing()[0]
+            mean = tot/nb
+            se = np.sqrt(np.maximum(sq/nb-mean*mean, 0.0)/(nb-1))
+            ok = mean > 0.0
+            rel = se[ok]/mean[ok]
+            t = ms_all*1e-3
+            row = dict(scene=name, target='sat_backward' if method else 'sat_forward', kernel=sol.kernel_name(), histories_per_batch=n, batches=nb,
+                       histories_per_s=float(nb*n/t), kernel_s=float(t), image_mean=[float(m.mean()) for m in mean], pixels_without_a_score=int((~ok).sum()),
+                       rel_se_mean=float(rel.mean()), rel_se_max=float(rel.max()), merit=float(1.0/(rel.mean()**2*t)))
+            if method:
+                row.update(bwd_chunk=chunk, chunk_launched=sol.lib.mi3d_debug_backward_chunk(sol._h), capped=sol.debug_backward_views(2, 0, 0)[3])
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    finally:
+        sol.set_tuning(bwd_chunk=-1)
+        sol.set_view_method('forward')
+    return rows
+
+
 def weights_rows(sol, name, s, n, nb=16):
     """the 'wgt' leg: the sensors of scene s by the backward route with the emission weights off, then on, nb batches each
     over the same id ranges; the counting build, once, for the absorbing cell steps of a history (one float64 atomic each with the switch on)"""
@@ -138,6 +181,8 @@ def main():
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--legs', default='radiance,flux,heat,heat_path')
     ap.add_argument('--histories', type=float, default=1.6e6)
+    ap.add_argument('--per-pixel', type=int, default=32)
+    ap.add_argument('--scenes', default='les128,les480')
     a = ap.parse_args()
     sol = Mi3dSolver(0)
     n = int(a.photons)
@@ -146,12 +191,18 @@ def main():
                              ('les480', dict(nx=480, ny=480, nz3=100, levels=z_levels_config4(), z_top=1.6, seed=20251004), z_levels_config4())):
         from er3t_amd.synth import z_levels_config2
         lev = levels if levels is not None else z_levels_config2()
+        if name not in a.scenes.split(','):
+            continue
         legs = sum([['cam', 'cam0', 'cam0_general'] if t == 'cam' else [t] for t in a.legs.split(',')], [])
         for target in legs:
             general = False
             if target == 'bwd':
                 sol.set_kernel(general=False)
                 rows += merit_rows(sol, name, pyrgeometers(thermal(les_scene(target='radiance', **kw), lev), 2), n, int(a.histories)//16*16)
+                continue
+            if target == 'sat':
+                sol.set_kernel(general=False)
+                rows += sat_rows(sol, name, thermal(les_scene(target='radiance', **kw), lev), n, a.per_pixel)
                 continue
             if target == 'wgt':
                 sol.set_kernel(general=False)
