@@ -79,6 +79,11 @@ struct DevBuf {
 
 constexpr double kWgtMaxElems = 2147483648.0;   // elements of the emission weights' tally npix x ncell served (mi3d_set_emission_weights)
 
+// The three builds of the backward route (mi3d_kernel_backward.hip): k_backward, k_backward_w, k_backward_v ...
+enum class BwdRoute { Camera = 0, Weights = 1, Views = 2 };
+// ... and what the runtime said of one of them: workgroups resident per CU for `lds` bytes of dynamic LDS (0: not asked yet)
+struct BwdCap { int blocks = 0, counting = -1; size_t lds = 0; };
+
 } // namespace
 
 struct mi3d_solver {
@@ -127,12 +132,12 @@ struct mi3d_solver {
     DevBuf<float> d_bwd_dir;
     // ... and for the satellite views of a thermal job (mi3d_set_view_method 1): the switch, the tile hand-out's chunk
     // (mi3d_set_tuning "bwd_chunk"; -1: chosen per launch, at most kBwdChunkAuto; 0: the camera route's stride; n >= 1: exactly n), the chunk
-    // of the launch made last, and the resident workgroups per CU of the build launched last
+    // of the launch made last
     int view_method = 0;
     int bwd_chunk = -1;
     int bwd_chunk_last = 0;
-    int sat_cap = 0, sat_cap_counting = -1; size_t sat_cap_lds = 0;
     DevBuf<float> d_bwd_start;
+    BwdCap bwd_cap[3];               // per BwdRoute: the resident workgroups per CU of the build launched last (backward_resident)
     bool sat_backward() const { return view_method == 1 && cam_method == 0 && rad_kind == 2; }           // is the job sent to k_backward_v?
     bool backward() const {                                                                               // does the read-out divide by the pixels' own counts?
         return src_mtype == 3 && nview > 0 && ((cam_method == 1 && rad_kind == 1) || sat_backward());
@@ -146,9 +151,6 @@ struct mi3d_solver {
     DevBuf<float> d_wgt_out;         // the read-out's staging buffer
     double *wgt_ext = nullptr;
     size_t wgt_n = 0;
-    int wgt_cap = 0;                 // resident workgroups per CU of the weights build, as the runtime reports them for wgt_cap_lds bytes of LDS (0: not asked yet)
-    size_t wgt_cap_lds = 0;
-    int wgt_cap_counting = -1;
     double *wgt_ptr() { return wgt_ext ? wgt_ext : d_wgt_own.p; }
     size_t wgt_ncell() const { return (size_t)nx * ny * nz3 + (size_t)nz + (sfc2d_host.empty() ? (size_t)1 : (size_t)nxb * nyb); }
     int nview = 0, nxr = 1, nyr = 1;
@@ -2374,51 +2376,45 @@ static hipError_t launch_pre(mi3d_solver *h, const RunPlan &plan, int pset, bool
 }
 
 // ---- the backward route (mi3d_set_camera_method 1; mi3d_kernel_backward.hip) ------------------------------------
-// What it serves: Src_mtype = 3, cameras (Rad_mrkind = 1), the 3-D solver, Lambertian surfaces.  Everything else: MI3D_EUNSUP, with the reason.
-static int backward_unsupported(const mi3d_solver *h) {
+// What it serves: Src_mtype = 3, a radiance job of the 3-D solver over Lambertian surfaces.  The switch of the cameras
+// (mi3d_set_camera_method 1) serves cameras and point radiometers (Rad_mrkind = 1), with or without emission weights; the switch of the
+// satellite views (sat: mi3d_set_view_method 1) the views of mi3d_set_views (Rad_mrkind = 2), without them.
+// Everything else: MI3D_EUNSUP, with the reason.
+static int backward_unsupported(const mi3d_solver *h, bool sat) {
     const char *why = h->src_mtype == 1 ? "a solar job (Src_mtype=1): the sun needs a local estimate of its own"
                       : h->src_mtype == 2 ? "a solar+thermal job (Src_mtype=2): the sun needs a local estimate of its own"
-                      : !(h->target & MI3D_TARGET_RADIANCE) || (h->target & MI3D_TARGET_FLUX) ? "a flux or heating-rate job: the route serves radiance (cameras) alone"
-                      : h->rad_kind != 1 ? "satellite views (Rad_mrkind=2): the route serves cameras and point radiometers (Rad_mrkind=1)"
-                      : h->solver != MI3D_SOLVER_3D ? "independent columns or partial 3-D: cameras need the 3-D solver"
+                      : !(h->target & MI3D_TARGET_RADIANCE) || (h->target & MI3D_TARGET_FLUX) ? (sat ? "a flux or heating-rate job: the route serves radiance (satellite images) alone"
+                                                                                                      : "a flux or heating-rate job: the route serves radiance (cameras) alone")
+                      : h->rad_kind != (sat ? 2 : 1) ? (sat ? "cameras and point radiometers (Rad_mrkind=1): their switch is mi3d_set_camera_method (Rad_mbwd)"
+                                                            : "satellite views (Rad_mrkind=2): the route serves cameras and point radiometers (Rad_mrkind=1)")
+                      : h->solver != MI3D_SOLVER_3D ? (sat ? "independent columns or partial 3-D: a line of sight crosses columns, it needs the 3-D solver"
+                                                           : "independent columns or partial 3-D: cameras need the 3-D solver")
                       : !h->sfc_lambert_only ? "a non-Lambertian surface (only Lambertian surfaces emit)"
+                      : sat && h->emis_weights ? "emission weights (mi3d_set_emission_weights 1): an image times the cells is out of its scope"
                       : nullptr;
-    if (why) return fail(MI3D_EUNSUP, "backward Monte Carlo (mi3d_set_camera_method 1) does not serve %s", why);
+    if (why)
+        return fail(MI3D_EUNSUP, sat ? "backward Monte Carlo for satellite views (mi3d_set_view_method 1, Rad_mvbwd=1) does not serve %s"
+                                     : "backward Monte Carlo (mi3d_set_camera_method 1) does not serve %s", why);
     return MI3D_OK;
 }
 
-// ... and what the satellite-view build serves (mi3d_set_view_method 1): Src_mtype = 3, the views of mi3d_set_views
-// (Rad_mrkind = 2), a radiance job of the 3-D solver over Lambertian surfaces, without emission weights
-static int backward_views_unsupported(const mi3d_solver *h) {
-    const char *why = h->src_mtype == 1 ? "a solar job (Src_mtype=1): the sun needs a local estimate of its own"
-                      : h->src_mtype == 2 ? "a solar+thermal job (Src_mtype=2): the sun needs a local estimate of its own"
-                      : !(h->target & MI3D_TARGET_RADIANCE) || (h->target & MI3D_TARGET_FLUX) ? "a flux or heating-rate job: the route serves radiance (satellite images) alone"
-                      : h->rad_kind != 2 ? "cameras and point radiometers (Rad_mrkind=1): their switch is mi3d_set_camera_method (Rad_mbwd)"
-                      : h->solver != MI3D_SOLVER_3D ? "independent columns or partial 3-D: a line of sight crosses columns, it needs the 3-D solver"
-                      : !h->sfc_lambert_only ? "a non-Lambertian surface (only Lambertian surfaces emit)"
-                      : h->emis_weights ? "emission weights (mi3d_set_emission_weights 1): an image times the cells is out of its scope"
-                      : nullptr;
-    if (why) return fail(MI3D_EUNSUP, "backward Monte Carlo for satellite views (mi3d_set_view_method 1, Rad_mvbwd=1) does not serve %s", why);
-    return MI3D_OK;
-}
-
-static int fill_backward(mi3d_solver *h, DevBackward &A, bool sat = false) {
+static int fill_backward(mi3d_solver *h, DevBackward &A, bool sat) {
     std::memset(&A, 0, sizeof(A));
     const double Lx = h->dx * h->nx, Ly = h->dy * h->ny;
     const bool sfc2d = !h->sfc2d_host.empty();
     A.nx = h->nx; A.ny = h->ny; A.nz = h->nz; A.nz3 = h->nz3; A.k3lo = h->nz3 > 0 ? h->iz3l - 1 : 0; A.np1d = h->np1d; A.np3d = h->np3d;
     A.nxb = sfc2d ? h->nxb : 1; A.nyb = sfc2d ? h->nyb : 1;
     A.nview = h->nview; A.nxr = h->nxr; A.nyr = h->nyr;
-    A.cam_mode = kCamPoint | (h->cam_mpmap == 2 ? kCamRect : 0) | (h->cam_mrproj == 1 ? kCamCos : 0);
+    A.cam_mode = sat ? 0 : kCamPoint | (h->cam_mpmap == 2 ? kCamRect : 0) | (h->cam_mrproj == 1 ? kCamCos : 0);
     A.dx = (float)h->dx; A.dy = (float)h->dy; A.inv_dx = (float)(1.0 / h->dx); A.inv_dy = (float)(1.0 / h->dy);
     A.ztoa = (float)h->zgrd[h->nz];
     A.sfc_sx = (float)(A.nxb / Lx); A.sfc_sy = (float)(A.nyb / Ly);
     A.wmin = (float)h->wmin; A.wfac = (float)h->wfac; A.src_flx = (float)h->src_flx;
     A.nvox = (unsigned)((size_t)h->nx * h->ny * h->nz3); A.vcol_f4 = h->vcol_f4; A.vrow_f4 = h->vrow_f4;
-    A.lay = h->d_lay.p; A.vrec = h->d_vrec.p; A.csca = h->d_csca.p; A.cells = h->d_bwd_cells.p; A.cams = h->d_cams.p;
+    A.lay = h->d_lay.p; A.vrec = h->d_vrec.p; A.csca = h->d_csca.p; A.cells = h->d_bwd_cells.p;
+    A.cams = sat ? nullptr : h->d_cams.p;          // (the views travel in BwdSat)
     A.tab.tmu = h->d_tmu.p; A.tab.tp = h->d_tp.p; A.tab.tcdf = h->d_tcdf.p; A.tab.nang = h->nang; A.tab.npf = h->npf;
     A.rad = h->rad_ptr(); A.counters = h->d_counters.p; A.capped = h->d_bwd_capped.p;
-    if (sat) { A.cam_mode = 0; A.cams = nullptr; }
     for (int iv = 0; iv < h->nview; ++iv) {
         if (sat && !(std::cos(h->view_the[iv] * 3.14159265358979323846 / 180.0) < 0.0)) continue;   // (an up-looking view's plane is raised to the surface)
         if (!(h->view_zloc[iv] > h->zgrd[0]))
@@ -2440,9 +2436,57 @@ static void fill_backward_views(const mi3d_solver *h, BwdSat &S, float *start_ou
     S.start_out = start_out;
 }
 
+// The one place that names the builds of the histories: the kernel of (route, counting, debug), as the runtime takes it for a launch and
+// for an occupancy query.  The weights build has no debug form (nullptr); the debug forms do not count
+static const void *backward_build(BwdRoute route, bool counting, bool debug) {
+    switch (route) {
+    case BwdRoute::Camera:
+        if (debug) return (const void *)k_backward<false, true>;
+        return counting ? (const void *)k_backward<true, false> : (const void *)k_backward<false, false>;
+    case BwdRoute::Weights:
+        if (debug) return nullptr;
+        return counting ? (const void *)k_backward_w<true> : (const void *)k_backward_w<false>;
+    case BwdRoute::Views:
+        if (debug) return (const void *)k_backward_v<false, true>;
+        return counting ? (const void *)k_backward_v<true, false> : (const void *)k_backward_v<false, false>;
+    }
+    return nullptr;
+}
+
+// One launch.  The kernel arguments in the order of the entry points: (A, seed, id0, n), then (dir_out, score_out) for the cameras,
+// (W) for the weights build, (dir_out, score_out, S) for the views
+static hipError_t backward_launch(BwdRoute route, bool counting, bool debug, unsigned grid, size_t lds, hipStream_t stream, DevBackward A, uint64_t seed,
+                                  uint64_t id0, uint64_t n, float *dir_out, double *score_out, BwdWeights W, BwdSat S) {
+    const void *kernel = backward_build(route, counting, debug);
+    if (!kernel) return hipErrorInvalidValue;
+    void *cam[] = {&A, &seed, &id0, &n, &dir_out, &score_out}, *wgt[] = {&A, &seed, &id0, &n, &W}, *sat[] = {&A, &seed, &id0, &n, &dir_out, &score_out, &S};
+    return hipLaunchKernel(kernel, dim3(grid), dim3(256), route == BwdRoute::Camera ? cam : route == BwdRoute::Weights ? wgt : sat, lds, stream);
+}
+
+// Workgroups of the build that are resident on the device at once.  The weights and view builds ask the runtime, once per (route, LDS
+// bytes, counting).  The camera build takes five waves per SIMD, four in the counting build (the register report in DESIGN.md §5.11),
+// the grid it has always had: asking the runtime instead could change that grid where LDS limits residency, a change of behaviour
+// that belongs to a pull request of its own.
+static int backward_resident(mi3d_solver *h, BwdRoute route, size_t lds, uint64_t &cap) {
+    BwdCap &c = h->bwd_cap[(int)route];
+    if (route == BwdRoute::Camera) c.blocks = h->counting ? 4 : 5;
+    else if (!c.blocks || c.lds != lds || c.counting != h->counting) {
+        int nb = 0;
+        const hipError_t eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, backward_build(route, h->counting != 0, false), 256, lds);
+        if (eo != hipSuccess || nb < 1) {
+            if (route == BwdRoute::Weights) return fail(MI3D_EDEVICE, "emission weights: no workgroup of the weights build fits a CU with %zu bytes of LDS", lds);
+            return fail(MI3D_EDEVICE, "backward Monte Carlo for satellite views: no workgroup fits a CU with %zu bytes of LDS", lds);
+        }
+        c.blocks = nb; c.lds = lds; c.counting = h->counting;
+    }
+    cap = (uint64_t)h->num_cu * (uint64_t)c.blocks;
+    return MI3D_OK;
+}
+
 static int run_backward(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_offset) {
-    const bool sat = h->sat_backward();
-    int rc = sat ? backward_views_unsupported(h) : backward_unsupported(h);
+    const bool sat = h->sat_backward(), wgt = h->emis_weights != 0;
+    const BwdRoute route = sat ? BwdRoute::Views : wgt ? BwdRoute::Weights : BwdRoute::Camera;
+    int rc = backward_unsupported(h, sat);
     if (rc) return rc;
     if (h->nview == 0) return fail(MI3D_ESTATE, "radiance requested but no view is set (%s)", sat ? "mi3d_set_views" : "mi3d_set_cameras");
     if (nphoton == 0) return MI3D_OK;
@@ -2453,15 +2497,9 @@ static int run_backward(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_
     h->entry_form_last = 0;
     h->runs_unread++;
     const int npix = h->nview * h->nxr * h->nyr;
-    size_t lds = backward_lds(npix, h->nz, h->nview, false);
-    // workgroups of 256 lanes, as many as are resident at once (five waves per SIMD, four in the counting build: the register report in
-    // DESIGN.md §5.11): every lane walks its ids with a fixed stride, and a workgroup that had to queue would start when the others are through
-    uint64_t cap = (uint64_t)h->num_cu * (h->counting ? 4 : 5);
-    const bool wgt = h->emis_weights != 0;
     BwdWeights W{};
     if (wgt) {
-        // the weights build: its tally, made and zeroed here when it is the library's own; the launch's LDS; and the
-        // resident workgroups per CU from the build's own registers and that LDS, as the runtime works them out
+        // the weights build: its tally, made and zeroed here when it is the library's own
         W.ncell = (unsigned long long)h->wgt_ncell();
         W.nls = (int)(W.ncell - A.nvox);
         const double ne = (double)npix * (double)W.ncell;
@@ -2473,33 +2511,25 @@ static int run_backward(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_
             h->wgt_n = (size_t)ne;
         }
         W.K = h->wgt_ptr();
-        lds = backward_lds_w(npix, h->nz, h->nview, W.nls, h->wgt_stage != 0, W.stage);
-        h->wgt_staged_last = W.stage;
-        if (!h->wgt_cap || h->wgt_cap_lds != lds || h->wgt_cap_counting != h->counting) {
-            int nb = 0;
-            const hipError_t eo = h->counting ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_backward_w<true>, 256, lds)
-                                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_backward_w<false>, 256, lds);
-            if (eo != hipSuccess || nb < 1) return fail(MI3D_EDEVICE, "emission weights: no workgroup of the weights build fits a CU with %zu bytes of LDS", lds);
-            h->wgt_cap = nb; h->wgt_cap_lds = lds; h->wgt_cap_counting = h->counting;
-        }
-        cap = (uint64_t)h->num_cu * (uint64_t)h->wgt_cap;
     }
     BwdSat S{};
     uint64_t ntile = 0;
     if (sat) {
-        // the satellite-view build: its LDS, and the resident workgroups per CU of the build launched, as the runtime works them out
         fill_backward_views(h, S, nullptr);
-        lds = backward_lds_v(npix, h->nz, h->nview, false, S.jch > 0);
         ntile = (uint64_t)h->nview * (uint64_t)((h->nxr + 7) / 8) * (uint64_t)((h->nyr + 7) / 8);
-        if (!h->sat_cap || h->sat_cap_lds != lds || h->sat_cap_counting != h->counting) {
-            int nb = 0;
-            const hipError_t eo = h->counting ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_backward_v<true, false>, 256, lds)
-                                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_backward_v<false, false>, 256, lds);
-            if (eo != hipSuccess || nb < 1) return fail(MI3D_EDEVICE, "backward Monte Carlo for satellite views: no workgroup fits a CU with %zu bytes of LDS", lds);
-            h->sat_cap = nb; h->sat_cap_lds = lds; h->sat_cap_counting = h->counting;
-        }
-        cap = (uint64_t)h->num_cu * (uint64_t)h->sat_cap;
     }
+    // the launch's LDS (backward_lds).  The weights build stages its layer and surface weights there
+    // where the image's sums are and the whole stays within kBwdWgtLds
+    const bool lds_sums = backward_lds_sums(npix, false, S.jch > 0);
+    if (wgt) {
+        W.stage = h->wgt_stage != 0 && lds_sums && backward_lds(npix, h->nz, h->nview, W.nls, lds_sums, true, false) <= kBwdWgtLds ? 1 : 0;
+        h->wgt_staged_last = W.stage;
+    }
+    const size_t lds = backward_lds(npix, h->nz, h->nview, W.nls, lds_sums, W.stage != 0, sat);
+    // workgroups of 256 lanes, as many as are resident at once: every lane walks its ids with a fixed stride, and a workgroup that had to
+    // queue would start when the others are through
+    uint64_t cap = 0;
+    if ((rc = backward_resident(h, route, lds, cap))) return rc;
     for (uint64_t done = 0; done < nphoton; done += h->batch) {
         const uint64_t nb = std::min<uint64_t>(h->batch, nphoton - done), off = photon_offset + done;
         if (h->pending.size() >= 64 && (rc = drain_events(h))) return rc;
@@ -2521,15 +2551,7 @@ static int run_backward(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_
         HIPCHK(hipEventCreate(&e0));
         hipError_t err = hipEventCreate(&e1);
         if (err == hipSuccess) err = hipEventRecord(e0, h->stream);
-        if (err == hipSuccess) {
-            if (sat && h->counting) hipLaunchKernelGGL((k_backward_v<true, false>), dim3(grid), dim3(256), lds, h->stream, A, seed, off, nb, (float *)nullptr, (double *)nullptr, Sl);
-            else if (sat) hipLaunchKernelGGL((k_backward_v<false, false>), dim3(grid), dim3(256), lds, h->stream, A, seed, off, nb, (float *)nullptr, (double *)nullptr, Sl);
-            else if (wgt && h->counting) hipLaunchKernelGGL((k_backward_w<true>), dim3(grid), dim3(256), lds, h->stream, A, seed, off, nb, W);
-            else if (wgt) hipLaunchKernelGGL((k_backward_w<false>), dim3(grid), dim3(256), lds, h->stream, A, seed, off, nb, W);
-            else if (h->counting) hipLaunchKernelGGL((k_backward<true, false>), dim3(grid), dim3(256), lds, h->stream, A, seed, off, nb, (float *)nullptr, (double *)nullptr);
-            else hipLaunchKernelGGL((k_backward<false, false>), dim3(grid), dim3(256), lds, h->stream, A, seed, off, nb, (float *)nullptr, (double *)nullptr);
-            err = hipGetLastError();
-        }
+        if (err == hipSuccess) err = backward_launch(route, h->counting != 0, false, grid, lds, h->stream, A, seed, off, nb, nullptr, nullptr, W, Sl);
         if (err == hipSuccess) err = hipEventRecord(e1, h->stream);
         if (err != hipSuccess) {
             (void)hipEventDestroy(e0);
@@ -2561,7 +2583,7 @@ int mi3d_run(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_of
     int rc = check_handle(h);
     if (rc) return rc;
     if ((rc = mi3d_prepare(h))) return rc;
-    if (h->view_method == 1 && h->rad_kind != 2) return backward_views_unsupported(h);   // (names the switch: it belongs to the views of mi3d_set_views)
+    if (h->view_method == 1 && h->rad_kind != 2) return backward_unsupported(h, true);   // (names the switch: it belongs to the views of mi3d_set_views)
     if (h->cam_method == 1 || h->view_method == 1) return run_backward(h, nphoton, seed, photon_offset);
     if (h->emis_weights)
         return fail(MI3D_EUNSUP, "emission weights (mi3d_set_emission_weights 1) are tallied by the backward route alone (mi3d_set_camera_method 1)");
@@ -3181,20 +3203,22 @@ int mi3d_debug_thermal(mi3d_solver *h, double *ptot, double *cdf_out, uint64_t n
 
 static_assert(MI3D_TAB_IDX_N == kTabIdxN, "include/mi3d.h states the length of a bucket index");
 
-int mi3d_debug_backward(mi3d_solver *h, uint64_t seed, uint64_t id0, int n, float *dir_out, double *score_out, uint64_t *capped_out) {
-    int rc = check_handle(h);
-    if (rc) return rc;
-    if (n < 0 || (n > 0 && (!dir_out || !score_out))) return fail(MI3D_EINVAL, "bad arguments to mi3d_debug_backward");
-    if (h->cam_method != 1) return fail(MI3D_ESTATE, "mi3d_debug_backward: the backward route is not selected (mi3d_set_camera_method 1)");
-    if ((rc = mi3d_prepare(h))) return rc;
-    if ((rc = backward_unsupported(h))) return rc;
+// The two debug entries of the backward route behind their own checks: the ids [id0, id0 + n) through the DEBUG build, and the capped
+// count.  sat: the satellite views' entry, which also writes where every history starts (start_out)
+static int debug_backward(mi3d_solver *h, bool sat, uint64_t seed, uint64_t id0, int n, float *start_out, float *dir_out, double *score_out, uint64_t *capped_out) {
+    int rc;
     if (n > 0) {
         DevBackward A;
-        if ((rc = fill_backward(h, A))) return rc;
-        if ((rc = h->d_bwd_dir.alloc((size_t)3 * n)) || (rc = h->d_bwd_score.alloc(n))) return rc;
-        const size_t lds = backward_lds(h->nview * h->nxr * h->nyr, h->nz, h->nview, true);
-        hipLaunchKernelGGL((k_backward<false, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), lds, h->stream, A, seed, id0, (uint64_t)n, h->d_bwd_dir.p, h->d_bwd_score.p);
-        HIPCHK(hipGetLastError());
+        BwdSat S{};
+        if ((rc = fill_backward(h, A, sat))) return rc;
+        if ((sat && (rc = h->d_bwd_start.alloc((size_t)3 * n))) || (rc = h->d_bwd_dir.alloc((size_t)3 * n)) || (rc = h->d_bwd_score.alloc(n))) return rc;
+        if (sat) fill_backward_views(h, S, h->d_bwd_start.p);
+        // (every slot is written by the history of its id: the hand-out reaches every id of [id0, id0 + n) whatever the grid)
+        const int npix = h->nview * h->nxr * h->nyr;
+        const size_t lds = backward_lds(npix, h->nz, h->nview, 1, backward_lds_sums(npix, true, S.jch > 0), false, sat);
+        HIPCHK(backward_launch(sat ? BwdRoute::Views : BwdRoute::Camera, false, true, (unsigned)((n + 255) / 256), lds, h->stream, A, seed, id0, (uint64_t)n,
+                               h->d_bwd_dir.p, h->d_bwd_score.p, BwdWeights{}, S));
+        if (sat) HIPCHK(hipMemcpyAsync(start_out, h->d_bwd_start.p, (size_t)3 * n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipMemcpyAsync(dir_out, h->d_bwd_dir.p, (size_t)3 * n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipMemcpyAsync(score_out, h->d_bwd_score.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     }
@@ -3206,35 +3230,25 @@ int mi3d_debug_backward(mi3d_solver *h, uint64_t seed, uint64_t id0, int n, floa
     return MI3D_OK;
 }
 
+int mi3d_debug_backward(mi3d_solver *h, uint64_t seed, uint64_t id0, int n, float *dir_out, double *score_out, uint64_t *capped_out) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (n < 0 || (n > 0 && (!dir_out || !score_out))) return fail(MI3D_EINVAL, "bad arguments to mi3d_debug_backward");
+    if (h->cam_method != 1) return fail(MI3D_ESTATE, "mi3d_debug_backward: the backward route is not selected (mi3d_set_camera_method 1)");
+    if ((rc = mi3d_prepare(h))) return rc;
+    if ((rc = backward_unsupported(h, false))) return rc;
+    return debug_backward(h, false, seed, id0, n, nullptr, dir_out, score_out, capped_out);
+}
+
 int mi3d_debug_backward_views(mi3d_solver *h, uint64_t seed, uint64_t id0, int n, float *start_out, float *dir_out, double *score_out, uint64_t *capped_out) {
     int rc = check_handle(h);
     if (rc) return rc;
     if (n < 0 || (n > 0 && (!start_out || !dir_out || !score_out))) return fail(MI3D_EINVAL, "bad arguments to mi3d_debug_backward_views");
     if (h->view_method != 1 || h->cam_method != 0) return fail(MI3D_ESTATE, "mi3d_debug_backward_views: the route is not selected (mi3d_set_view_method 1, mi3d_set_camera_method 0)");
     if ((rc = mi3d_prepare(h))) return rc;
-    if ((rc = backward_views_unsupported(h))) return rc;
+    if ((rc = backward_unsupported(h, true))) return rc;
     if (h->nview == 0) return fail(MI3D_ESTATE, "mi3d_debug_backward_views: no view is set (mi3d_set_views)");
-    if (n > 0) {
-        DevBackward A;
-        BwdSat S;
-        if ((rc = fill_backward(h, A, true))) return rc;
-        if ((rc = h->d_bwd_start.alloc((size_t)3 * n)) || (rc = h->d_bwd_dir.alloc((size_t)3 * n)) || (rc = h->d_bwd_score.alloc(n))) return rc;
-        fill_backward_views(h, S, h->d_bwd_start.p);
-        // (every slot is written by the history of its id: the hand-out reaches every id of [id0, id0 + n) whatever the grid)
-        const size_t lds = backward_lds_v(h->nview * h->nxr * h->nyr, h->nz, h->nview, true, S.jch > 0);
-        hipLaunchKernelGGL((k_backward_v<false, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), lds, h->stream, A, seed, id0, (uint64_t)n, h->d_bwd_dir.p,
-                           h->d_bwd_score.p, S);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(start_out, h->d_bwd_start.p, (size_t)3 * n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipMemcpyAsync(dir_out, h->d_bwd_dir.p, (size_t)3 * n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipMemcpyAsync(score_out, h->d_bwd_score.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    }
-    if (capped_out) {
-        *capped_out = 0;
-        if (h->d_bwd_capped.p) { unsigned long long c = 0; HIPCHK(hipMemcpyAsync(&c, h->d_bwd_capped.p, sizeof(c), hipMemcpyDeviceToHost, h->stream)); HIPCHK(hipStreamSynchronize(h->stream)); *capped_out = c; }
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return MI3D_OK;
+    return debug_backward(h, true, seed, id0, n, start_out, dir_out, score_out, capped_out);
 }
 
 // Read-out of the emission weights (mi3d_set_emission_weights 1): the rows of K_raw by the rule of k_backward_norm, rounded to

@@ -101,12 +101,16 @@ k_backward_cells(const ThermalGrid G, int nxb, int nyb, const float *sfc2d, floa
     out[i] = make_float2((float)a, (float)b);
 }
 
-// tally[p] / (number of ids in [0, N) with id mod npix == p), 0 where that number is 0
+// the number of ids in [0, N) with id mod npix == p
+__device__ inline unsigned long long bwd_pixel_ids(const unsigned long long nphoton, const unsigned npix, const unsigned long long p) {
+    return nphoton / npix + (p < nphoton % npix ? 1ull : 0ull);
+}
+// tally[p] / (number of ids in [0, N) that map to p), 0 where that number is 0
 __global__ void __launch_bounds__(256)
 k_backward_norm(const double *__restrict__ tally, double *__restrict__ out, unsigned long long nphoton, unsigned npix) {
     const unsigned p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= npix) return;
-    const unsigned long long cnt = nphoton / npix + (p < nphoton % npix ? 1ull : 0ull);
+    const unsigned long long cnt = bwd_pixel_ids(nphoton, npix, p);
     out[p] = cnt ? tally[p] / (double)cnt : 0.0;
 }
 // ... and for elements [e0, e0 + ne) of K_raw[npix][ncell]: element e belongs to pixel e / ncell
@@ -115,8 +119,7 @@ k_backward_norm_rows(const double *__restrict__ K, float *__restrict__ out, unsi
                      unsigned long long e0, unsigned long long ne) {
     const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
     for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < ne; i += stride) {
-        const unsigned long long p = (e0 + i) / ncell;
-        const unsigned long long cnt = nphoton / npix + (p < nphoton % npix ? 1ull : 0ull);
+        const unsigned long long cnt = bwd_pixel_ids(nphoton, npix, (e0 + i) / ncell);
         out[i] = cnt ? (float)(K[e0 + i] / (double)cnt) : 0.0f;
     }
 }
@@ -164,22 +167,18 @@ k_backward_v(const DevBackward A, const uint64_t seed, const uint64_t id0, const
 #include "mi3d_kernel_backward_body.inc"
 }
 
-// dynamic LDS of a launch: the workgroup's sums, the layer table, the cameras
-__host__ inline size_t backward_lds(int npix, int nz, int nview, bool debug) {
-    return (size_t)((!debug && npix <= kBwdLdsPix) ? ((npix + 1) & ~1) : 0) * sizeof(double) + (size_t)nz * sizeof(LayerRec) + (size_t)nview * sizeof(CamRec);
+// The dynamic LDS of a launch of any build, in bytes: the host's statement of what the top of mi3d_kernel_backward_body.inc lays out, in
+// that order -- the workgroup's image sums [npix] (lds_sums), the staged layer and surface weights [npix][nls] (wstage), the layer table
+// [nz], the cameras or -- sat -- the views [nview]; the two sums rounded up to an even number of doubles
+__host__ inline size_t backward_lds(int npix, int nz, int nview, int nls, bool lds_sums, bool wstage, bool sat) {
+    const size_t sums = lds_sums ? (((size_t)npix + 1) & ~(size_t)1) : 0, wsum = wstage ? (((size_t)npix * nls + 1) & ~(size_t)1) : 0;
+    return (sums + wsum) * sizeof(double) + (size_t)nz * sizeof(LayerRec) + (size_t)nview * (sat ? sizeof(ViewRec) : sizeof(CamRec));
 }
-// ... of the satellite-view build: the views instead of the cameras; no sums where the tile hand-out keeps them in registers
-__host__ inline size_t backward_lds_v(int npix, int nz, int nview, bool debug, bool tiles) {
-    return (size_t)((!debug && !tiles && npix <= kBwdLdsPix) ? ((npix + 1) & ~1) : 0) * sizeof(double) + (size_t)nz * sizeof(LayerRec) + (size_t)nview * sizeof(ViewRec);
-}
-// ... of a launch of the weights build.  stage: the layer and surface weights of every pixel are summed in LDS -- where the image's own
-// sums are, and the workgroup's dynamic LDS stays within 32 KB (five workgroups on a CU of 160 KB)
+// are the image's sums taken per workgroup in LDS?  Not by the debug entries, which tally nothing, and not under the tile hand-out, which
+// keeps them in registers (the body's `lds_sums`)
+__host__ inline bool backward_lds_sums(int npix, bool debug, bool tiles) { return !debug && npix <= kBwdLdsPix && !tiles; }
+// The weights build stages its layer and surface weights where the image's own sums are in LDS and the workgroup's dynamic LDS stays
+// within 32 KB (five workgroups on a CU of 160 KB)
 constexpr size_t kBwdWgtLds = 32768;
-__host__ inline size_t backward_lds_w(int npix, int nz, int nview, int nls, bool allow_stage, int &stage) {
-    const size_t base = backward_lds(npix, nz, nview, false);
-    const size_t extra = (((size_t)npix * nls + 1) & ~(size_t)1) * sizeof(double);
-    stage = allow_stage && npix <= kBwdLdsPix && base + extra <= kBwdWgtLds ? 1 : 0;
-    return base + (stage ? extra : 0);
-}
 
 } // namespace mi3d
