@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -827,6 +828,29 @@ int build_camdir(mi3d_solver *h) {
     return MI3D_OK;
 }
 
+// ---- what the selectors and launchers of the forward routes' builds are made of (below: entry_build ... launch_general, launch_flux) -----
+// Run-time flags as compile-time ones: f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...).  f is instantiated for every
+// combination of its flags, so a selector names a kernel with flags only where the family has all of them
+template <class F, bool... Bs>
+static auto with_flags(F &&f, std::integer_sequence<bool, Bs...>) { return f(std::bool_constant<Bs>{}...); }
+template <class F, bool... Bs, class... Rest>
+static auto with_flags(F &&f, std::integer_sequence<bool, Bs...>, bool b, Rest... rest) {
+    return b ? with_flags(f, std::integer_sequence<bool, Bs..., true>{}, rest...) : with_flags(f, std::integer_sequence<bool, Bs..., false>{}, rest...);
+}
+template <class F, class... Flags>
+static auto with_flags(F &&f, bool b, Flags... rest) { return with_flags(f, std::integer_sequence<bool>{}, b, rest...); }
+
+// One launch of a build.  More than the default 64 KB of dynamic LDS: the runtime is told first, for that kernel, on every such launch.
+// No build (the selector knows none for what it was asked): an error, never another kernel.  The arguments go through the typed pointer:
+// the compiler checks them against the family's signature
+template <class... Params, class... Args>
+static hipError_t launch_build(void (*kernel)(Params...), unsigned grid, unsigned threads, size_t lds, hipStream_t st, Args &&...args) {
+    if (!kernel) return hipErrorInvalidValue;
+    if (lds > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, st, std::forward<Args>(args)...);
+    return hipGetLastError();
+}
+
 } // namespace
 
 // =================================================================================================
@@ -1444,6 +1468,97 @@ static hipError_t launch_bins(mi3d_solver *h, hipStream_t st, const BinGeom &G, 
     return hipGetLastError();
 }
 
+// ---- the forward routes' builds: one selector per kernel family, one launch path ---------------------------------
+// What a run fixes of its builds, stated once (plan_run): the instrumented build, the partial 3-D solver, k_transport's SRC (0 the sun,
+// 1 thermal emission, 2 both) and the path-length estimator of the heating rates (k_transport_flux's HEST, kTargetHeatPath of the scene)
+struct RunBuild { bool counting = false, p3d = false, hpath = false; int src = 0; };
+
+using EntryFn = void (*)(EntryArgs, uint64_t, uint64_t, uint64_t, const uint32_t *, float4 *);
+using LeanFn = void (*)(DevScene, uint64_t, uint64_t, uint64_t);
+using RaysFn = void (*)(DevScene, uint64_t);
+using GeneralFn = void (*)(DevScene, uint64_t, uint64_t, uint64_t, const DevThermal *);
+using FluxFn = void (*)(DevScene, const TallyList *, uint64_t, uint64_t, uint64_t);
+using TlRunsFn = void (*)(TallyList, RunGeom, tally_t *);
+using TlScatterFn = void (*)(TallyList, tally_t *, unsigned, double *, unsigned);
+
+// k_entry<EF> (mi3d_kernel_lean.hip): the build that writes long records or the one that writes short ones (entry_form)
+static EntryFn entry_build(int form) { return form == kEntryF4Short ? k_entry<kEntryF4Short> : form == kEntryF4 ? k_entry<kEntryF4> : nullptr; }
+
+// The builds of the lean loop that read short entry records (mi3d_kernel_lean.hip: k_transport_lean<., ., 0, 0, 256, kEntryF4Short>)
+static bool lean_short_build(bool emit, int mix, int nt) { return !emit && mix == 0 && nt == 256; }
+
+// k_transport_lean<C, P, MARCH, MIX, NT, EF> (mi3d_kernel_lean.hip), ten builds for each (C, P).  emit: MARCH 2, the loop that writes event
+// records for k_rays; mix: 0 er3t's default scene, 1 a second 3-D constituent, 2 the general mixture (several 1-D constituents, tables), 3
+// its common scene in the column view (plan_run: mix_lean); nt: threads per workgroup; short_rec: the run's entry records are short ones.
+// Workgroups of 512 and mix 3 belong to the column view (never emit), and 512 to mix 2 and 3
+static LeanFn lean_build(bool counting, bool p3d, bool emit, int mix, int nt, bool short_rec) {
+    return with_flags([=](auto C, auto P) -> LeanFn {
+        constexpr bool c = decltype(C)::value, p = decltype(P)::value;
+        if (short_rec) return lean_short_build(emit, mix, nt) ? k_transport_lean<c, p, 0, 0, 256, kEntryF4Short> : nullptr;
+        if (nt == 512 && !emit) return mix == 2 ? k_transport_lean<c, p, 0, 2, 512> : mix == 3 ? k_transport_lean<c, p, 0, 3, 512> : nullptr;
+        if (nt != 256) return nullptr;
+        switch (mix) {
+        case 0: return emit ? k_transport_lean<c, p, 2, 0> : k_transport_lean<c, p, 0, 0>;
+        case 1: return emit ? k_transport_lean<c, p, 2, 1> : k_transport_lean<c, p, 0, 1>;
+        case 2: return emit ? k_transport_lean<c, p, 2, 2> : k_transport_lean<c, p, 0, 2>;
+        case 3: return emit ? nullptr : k_transport_lean<c, p, 0, 3>;
+        }
+        return nullptr;
+    }, counting, p3d);
+}
+
+// k_rays<C, P, HEAVY, CAM, PLAIN, THERM> (mi3d_kernel_rays.hip).  Satellite views: the light build, its form for scenes of analytic
+// phase functions alone (plain) and the heavy one (reflections off LSRT / DSM surfaces), each for (C, P).  Cameras: the 3-D solver's
+// build whose rays carry their own direction, and the one of a thermal job, each for C
+static RaysFn rays_build(bool counting, bool p3d, bool heavy, bool camera, bool plain, bool thermal) {
+    return with_flags([=](auto C, auto P) -> RaysFn {
+        constexpr bool c = decltype(C)::value, p = decltype(P)::value;
+        if (camera) {
+            if (p || heavy || plain) return nullptr;
+            return thermal ? k_rays<c, false, false, true, false, true> : k_rays<c, false, false, true>;
+        }
+        if (thermal || (heavy && plain)) return nullptr;
+        return plain ? k_rays<c, p, false, false, true> : heavy ? k_rays<c, p, true, false, false> : k_rays<c, p, false, false, false>;
+    }, counting, p3d);
+}
+
+// k_transport<C, MARCHK, F, P, SRC> (mi3d_kernels.hip).  march: 0 / 1 the photon loop without / with the rays of marched views inside it,
+// every (C, F, P, SRC); 2 the thermal radiance builds of the 3-D solver that write event records for k_rays' thermal camera build
+static GeneralFn general_build(bool counting, int march, bool flux, bool p3d, int src) {
+    if (march < 0 || march > 2 || src < 0 || src > 2) return nullptr;
+    if (march == 2) {
+        if (flux || p3d || src != 1) return nullptr;
+        return counting ? k_transport<true, 2, false, false, 1> : k_transport<false, 2, false, false, 1>;
+    }
+    return with_flags([=](auto C, auto M, auto F, auto P) -> GeneralFn {
+        constexpr bool c = decltype(C)::value, f = decltype(F)::value, p = decltype(P)::value;
+        constexpr int m = decltype(M)::value ? 1 : 0;
+        return src == 2 ? k_transport<c, m, f, p, 2> : src == 1 ? k_transport<c, m, f, p, 1> : k_transport<c, m, f, p, 0>;
+    }, counting, march == 1, flux, p3d);
+}
+
+// k_transport_flux<C, P, MIX, HEST> (mi3d_kernel_flux.hip): every combination.  mix: 0, 1, 2 as the lean loop's; hpath: the path-length
+// estimator of the heating rates
+static FluxFn flux_build(bool counting, bool p3d, int mix, bool hpath) {
+    return with_flags([=](auto C, auto P, auto H) -> FluxFn {
+        constexpr bool c = decltype(C)::value, p = decltype(P)::value, hp = decltype(H)::value;
+        return mix == 0 ? k_transport_flux<c, p, 0, hp> : mix == 1 ? k_transport_flux<c, p, 1, hp> : mix == 2 ? k_transport_flux<c, p, 2, hp> : nullptr;
+    }, counting, p3d, hpath);
+}
+
+// k_tl_runs<W, G, NTR> (mi3d_kernel_flux.hip).  write: the pass that writes the runs' records (the other counts them); hist_wg: one
+// workgroup per workgroup of the photon loop, not per wave; wide: 512 threads, with hist_wg only
+static TlRunsFn tl_runs_build(bool write, bool hist_wg, bool wide) {
+    return with_flags([=](auto W) -> TlRunsFn {
+        constexpr bool w = decltype(W)::value;
+        if (!hist_wg) return wide ? nullptr : k_tl_runs<w, 1, 256>;
+        return wide ? k_tl_runs<w, 4, 512> : k_tl_runs<w, 4, 256>;
+    }, write);
+}
+
+// k_tl_scatter<NT, R, G> (mi3d_kernel_flux.hip): the sort of one wave's records, or (hist_wg) of a workgroup's in 64-KB tiles
+static TlScatterFn tl_scatter_build(bool hist_wg) { return hist_wg ? k_tl_scatter<1024, 8, 4> : k_tl_scatter<MI3D_TLS_NT, MI3D_TLS_R, 1>; }
+
 // The photons of a launch up to their first voxel walk (k_entry, mi3d_kernel_lean.hip); one photon per thread: the stream of records
 // leaves at the rate a plain copy reaches.  form: the build that writes long records or the one that writes short ones (entry_form).
 static hipError_t launch_entry(mi3d_solver *h, hipStream_t st, const DevScene &S, int form, uint64_t nb, uint64_t seed, uint64_t off, const uint32_t *order, float4 *entry) {
@@ -1453,134 +1568,32 @@ static hipError_t launch_entry(mi3d_solver *h, hipStream_t st, const DevScene &S
     A.Lx = C.Lx; A.Ly = C.Ly; A.dx = S.dx; A.dy = S.dy; A.inv_dx = C.inv_dx; A.inv_dy = C.inv_dy; A.inv_nx = C.inv_nx; A.inv_ny = C.inv_ny;
     A.sdx = C.sdx; A.sdy = C.sdy; A.sdz = C.sdz; A.cos_cone = C.cos_cone;
     A.nx = S.nx; A.ny = S.ny; A.nz = S.nz; A.solver = S.solver; A.target = S.target; A.kdir = S.kdir;
-    if (form == kEntryF4Short) hipLaunchKernelGGL(k_entry<kEntryF4Short>, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, A, nb, seed, off, order, entry);
-    else hipLaunchKernelGGL(k_entry<kEntryF4>, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, A, nb, seed, off, order, entry);
-    return hipGetLastError();
+    return launch_build(entry_build(form), (unsigned)((nb + 255) / 256), 256, 0, st, A, nb, seed, off, order, entry);
 }
 
-// The builds of the lean loop that read short entry records (mi3d_kernel_lean.hip: k_transport_lean<., ., 0, 0, 256, kEntryF4Short>)
-static bool lean_short_build(bool emit, int mix, int nt) { return !emit && mix == 0 && nt == 256; }
-
-static hipError_t launch_lean(mi3d_solver *h, hipStream_t st, const DevScene &S, bool emit, int mix, int nt, unsigned grid, size_t lds, uint64_t nb, uint64_t seed, uint64_t off) {
-    // mix: 0 er3t's default scene, 1 a second 3-D constituent, 2 the general mixture (several 1-D constituents, tables); nt: threads per workgroup
-    // (the build that reads short entry records where the run writes them: entry_form has asked lean_short_build)
-    const bool short_rec = h->entry_form_run == kEntryF4Short && lean_short_build(emit, mix, nt);
-    const int v = (h->counting ? 4 : 0) + (h->solver == MI3D_SOLVER_P3D ? 2 : 0) + (emit ? 1 : 0);
-#define MI3D_LEAN_LAUNCH(C, P, M)                                                                                                        \
-    do {                                                                                                                                 \
-        if (mix == 3 && nt == 512) {                                                                                                     \
-            if (lds > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_transport_lean<C, P, 0, 3, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            hipLaunchKernelGGL((k_transport_lean<C, P, 0, 3, 512>), dim3(grid), dim3(512), lds, st, S, nb, seed, off);                    \
-        } else if (mix == 3) {                                                                                                           \
-            if (lds > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_transport_lean<C, P, 0, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            hipLaunchKernelGGL((k_transport_lean<C, P, 0, 3>), dim3(grid), dim3(256), lds, st, S, nb, seed, off);                         \
-        } else if (mix == 2 && nt == 512 && (M) == 0) {                                                                                  \
-            if (lds > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_transport_lean<C, P, 0, 2, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            hipLaunchKernelGGL((k_transport_lean<C, P, 0, 2, 512>), dim3(grid), dim3(512), lds, st, S, nb, seed, off);                    \
-        } else if (mix == 2) {                                                                                                           \
-            if (lds > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_transport_lean<C, P, M, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            hipLaunchKernelGGL((k_transport_lean<C, P, M, 2>), dim3(grid), dim3(256), lds, st, S, nb, seed, off);                         \
-        } else if (mix == 1) hipLaunchKernelGGL((k_transport_lean<C, P, M, 1>), dim3(grid), dim3(256), lds, st, S, nb, seed, off);        \
-        else if (short_rec) hipLaunchKernelGGL((k_transport_lean<C, P, 0, 0, 256, kEntryF4Short>), dim3(grid), dim3(256), lds, st, S, nb, seed, off); \
-        else hipLaunchKernelGGL((k_transport_lean<C, P, M, 0>), dim3(grid), dim3(256), lds, st, S, nb, seed, off);                        \
-    } while (0)
-    switch (v) {
-        case 0: MI3D_LEAN_LAUNCH(false, false, 0); break;
-        case 1: MI3D_LEAN_LAUNCH(false, false, 2); break;
-        case 2: MI3D_LEAN_LAUNCH(false, true, 0); break;
-        case 3: MI3D_LEAN_LAUNCH(false, true, 2); break;
-        case 4: MI3D_LEAN_LAUNCH(true, false, 0); break;
-        case 5: MI3D_LEAN_LAUNCH(true, false, 2); break;
-        case 6: MI3D_LEAN_LAUNCH(true, true, 0); break;
-        default: MI3D_LEAN_LAUNCH(true, true, 2); break;
-    }
-#undef MI3D_LEAN_LAUNCH
-    return hipGetLastError();
+// The lean loop of a launch.  The build that reads short entry records where the run writes them: entry_form has asked lean_short_build,
+// and a run that wrote short records for any other build finds none here
+static hipError_t launch_lean(mi3d_solver *h, const RunBuild &B, hipStream_t st, const DevScene &S, bool emit, int mix, int nt, unsigned grid, size_t lds, uint64_t nb, uint64_t seed, uint64_t off) {
+    return launch_build(lean_build(B.counting, B.p3d, emit, mix, nt, h->entry_form_run == kEntryF4Short), grid, (unsigned)nt, lds, st, S, nb, seed, off);
 }
 
-static hipError_t launch_rays(mi3d_solver *h, hipStream_t st, const DevScene &S, bool heavy, size_t lds, uint64_t seed) {
-    if (h->rad_kind == 1) {   // cameras: the build whose rays carry their own direction (3-D solver: mi3d_run has checked)
-        const unsigned gridc = (unsigned)h->num_cu * 4u;
-        if (h->src_mtype == 3) {   // (a thermal job's events: emissions among them)
-            if (lds > 65536) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_rays<true, false, false, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_rays<false, false, false, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            }
-            if (h->counting) hipLaunchKernelGGL((k_rays<true, false, false, true, false, true>), dim3(gridc), dim3(256), lds, st, S, seed);
-            else hipLaunchKernelGGL((k_rays<false, false, false, true, false, true>), dim3(gridc), dim3(256), lds, st, S, seed);
-            return hipGetLastError();
-        }
-        if (lds > 65536) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_rays<true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_rays<false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        }
-        if (h->counting) hipLaunchKernelGGL((k_rays<true, false, false, true>), dim3(gridc), dim3(256), lds, st, S, seed);
-        else hipLaunchKernelGGL((k_rays<false, false, false, true>), dim3(gridc), dim3(256), lds, st, S, seed);
-        return hipGetLastError();
-    }
-    const unsigned grid = (unsigned)h->num_cu * (unsigned)((h->rays_wg > 0 && !heavy) ? std::min(h->rays_wg, MI3D_RAYS_WAVES(h->counting != 0, heavy)) : MI3D_RAYS_WAVES(h->counting != 0, heavy));
-    const bool p3d = h->solver == MI3D_SOLVER_P3D;
-    const bool plain = (S.target & kTargetPlainPhase) != 0 && !heavy;     // (the heavy build evaluates surface models only)
-    // (more than the default 64 KB of dynamic LDS -- staged tables behind the pools --: say so, as launch_lean and launch_flux do)
-#define MI3D_LAUNCH_RAYS(C, P, X)                                                                                                    \
-    do {                                                                                                                             \
-        if (plain) {                                                                                                                 \
-            if (lds > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_rays<C, P, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            hipLaunchKernelGGL((k_rays<C, P, false, false, true>), dim3(grid), dim3(256), lds, st, S, seed);                          \
-        } else {                                                                                                                     \
-            if (lds > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_rays<C, P, X, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            hipLaunchKernelGGL((k_rays<C, P, X, false, false>), dim3(grid), dim3(256), lds, st, S, seed);                             \
-        }                                                                                                                            \
-    } while (0)
-    switch ((h->counting ? 4 : 0) | (p3d ? 2 : 0) | (heavy ? 1 : 0)) {
-        case 0: MI3D_LAUNCH_RAYS(false, false, false); break;
-        case 1: MI3D_LAUNCH_RAYS(false, false, true); break;
-        case 2: MI3D_LAUNCH_RAYS(false, true, false); break;
-        case 3: MI3D_LAUNCH_RAYS(false, true, true); break;
-        case 4: MI3D_LAUNCH_RAYS(true, false, false); break;
-        case 5: MI3D_LAUNCH_RAYS(true, false, true); break;
-        case 6: MI3D_LAUNCH_RAYS(true, true, false); break;
-        default: MI3D_LAUNCH_RAYS(true, true, true); break;
-    }
-#undef MI3D_LAUNCH_RAYS
-    return hipGetLastError();
+// The ray kernel behind the event-writing loops (LDS beyond 64 KB: staged tables behind the pools)
+static hipError_t launch_rays(mi3d_solver *h, const RunBuild &B, hipStream_t st, const DevScene &S, bool heavy, size_t lds, uint64_t seed) {
+    const bool camera = h->rad_kind == 1;   // cameras: the build whose rays carry their own direction (3-D solver: mi3d_run has checked)
+    const bool thermal = camera && h->src_mtype == 3;   // (a thermal job's events: emissions among them)
+    const bool plain = (S.target & kTargetPlainPhase) != 0 && !heavy && !camera;     // (the heavy build evaluates surface models only)
+    const int waves = camera ? 4 : (h->rays_wg > 0 && !heavy) ? std::min(h->rays_wg, MI3D_RAYS_WAVES(B.counting, heavy)) : MI3D_RAYS_WAVES(B.counting, heavy);
+    return launch_build(rays_build(B.counting, B.p3d, heavy, camera, plain, thermal), (unsigned)h->num_cu * (unsigned)waves, 256, lds, st, S, seed);
 }
-
-// as many workgroups as are resident at once (a workgroup that starts after the pool is empty only stages LDS and leaves)
-#ifndef MI3D_BLOCKS_PER_CU
-#define MI3D_BLOCKS_PER_CU(MARCH, COUNT) MI3D_WAVES(MARCH, COUNT)
-#endif
 
 // The general photon loop (mi3d_kernels.hip): every job the lean loops do not serve, the thermal source's among them
 // (emit: the thermal builds that write event records for k_rays instead of marching the rays of the cameras themselves, k_transport<.,2,...>)
-static hipError_t launch_general(mi3d_solver *h, const DevScene &S, bool march, bool flux, unsigned grid, uint64_t nb, uint64_t seed, uint64_t off, bool emit = false) {
+static hipError_t launch_general(mi3d_solver *h, const RunBuild &B, hipStream_t st, const DevScene &S, int march, bool flux, unsigned grid, uint64_t nb, uint64_t seed, uint64_t off) {
     const int tb = 256;
     const size_t lds = (size_t)h->nz * sizeof(LayerRec) + MI3D_MAX_VIEW * sizeof(ViewRec) + sizeof(DevCold) + (size_t)9 * tb * sizeof(float) +
                        (size_t)(h->tab_n > 0 ? (1 + 2 * h->tab_n) * h->nang * sizeof(float) : 0);
-    const int src = h->src_mtype == 3 ? 1 : h->src_mtype == 2 ? 2 : 0;   // k_transport's SRC
-    const DevThermal *th = src ? h->d_th.p : nullptr;
-    if (emit) {
-        if (h->counting) hipLaunchKernelGGL((k_transport<true, 2, false, false, 1>), dim3(grid), dim3(tb), lds, h->stream, S, nb, seed, off, th);
-        else hipLaunchKernelGGL((k_transport<false, 2, false, false, 1>), dim3(grid), dim3(tb), lds, h->stream, S, nb, seed, off, th);
-        return hipGetLastError();
-    }
-#define MI3D_LAUNCH_T(C, M, F, T)                                                                                                      \
-    do { if (h->solver == MI3D_SOLVER_P3D) hipLaunchKernelGGL((k_transport<C, M, F, true, T>), dim3(grid), dim3(tb), lds, h->stream, S, nb, seed, off, th); \
-         else hipLaunchKernelGGL((k_transport<C, M, F, false, T>), dim3(grid), dim3(tb), lds, h->stream, S, nb, seed, off, th); } while (0)
-#define MI3D_LAUNCH(C, M, F) do { if (src == 2) MI3D_LAUNCH_T(C, M, F, 2); else if (src == 1) MI3D_LAUNCH_T(C, M, F, 1); else MI3D_LAUNCH_T(C, M, F, 0); } while (0)
-    switch ((h->counting ? 4 : 0) | (march ? 2 : 0) | (flux ? 1 : 0)) {
-        case 0: MI3D_LAUNCH(false, false, false); break;
-        case 1: MI3D_LAUNCH(false, false, true); break;
-        case 2: MI3D_LAUNCH(false, true, false); break;
-        case 3: MI3D_LAUNCH(false, true, true); break;
-        case 4: MI3D_LAUNCH(true, false, false); break;
-        case 5: MI3D_LAUNCH(true, false, true); break;
-        case 6: MI3D_LAUNCH(true, true, false); break;
-        default: MI3D_LAUNCH(true, true, true); break;
-    }
-#undef MI3D_LAUNCH
-#undef MI3D_LAUNCH_T
-    return hipGetLastError();
+    const DevThermal *th = B.src ? h->d_th.p : nullptr;
+    return launch_build(general_build(B.counting, march, flux, B.p3d, B.src), grid, tb, lds, st, S, nb, seed, off, th);
 }
 
 // Photons a launch may have so that its events fit the lists, at `per_photon` events per photon (0: nothing known yet, a
@@ -1640,7 +1653,7 @@ static int ev_note(mi3d_solver *h, uint64_t ev_cap, uint64_t nb, hipStream_t st,
 }
 
 // the photon loop of a flux job and, with record lists, their sort (tset: the set of lists; two_streams: the sort on the sort stream)
-static hipError_t launch_flux(mi3d_solver *h, int tset, bool two_streams, const DevScene &S, const TallyList &TL0, int mix, unsigned grid, size_t lds, uint64_t nb, uint64_t seed, uint64_t off) {
+static hipError_t launch_flux(mi3d_solver *h, const RunBuild &B, int tset, bool two_streams, const DevScene &S, const TallyList &TL0, int mix, unsigned grid, size_t lds, uint64_t nb, uint64_t seed, uint64_t off) {
     hipStream_t st = h->stream;
     mi3d_solver::TlSet &T = h->tl[tset];
     TallyList TL = TL0;
@@ -1666,25 +1679,7 @@ static hipError_t launch_flux(mi3d_solver *h, int tset, bool two_streams, const 
     if (T.pend.on && (e0 = launch_sum(h, tset, st)) != hipSuccess) return e0;
     // (the set's cursors: behind the wait -- the sort of the launch that used the set last writes one of them and copies them out on its stream)
     if (TL.cap && (e0 = hipMemsetAsync(TL.cursor, 0, 3 * sizeof(unsigned long long), st)) != hipSuccess) return e0;
-#define MI3D_FLUX_LAUNCH_H(C, P, H)                                                                                         \
-    do {                                                                                                                    \
-        if (mix == 2) {                                                                                                     \
-            if (lds > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_transport_flux<C, P, 2, H>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            hipLaunchKernelGGL((k_transport_flux<C, P, 2, H>), dim3(grid), dim3(256), lds, st, S, TLd, nb, seed, off);       \
-        } else if (mix == 1) hipLaunchKernelGGL((k_transport_flux<C, P, 1, H>), dim3(grid), dim3(256), lds, st, S, TLd, nb, seed, off);  \
-        else hipLaunchKernelGGL((k_transport_flux<C, P, 0, H>), dim3(grid), dim3(256), lds, st, S, TLd, nb, seed, off);      \
-    } while (0)
-    // (the path-length estimator of the heating rates: builds of their own)
-#define MI3D_FLUX_LAUNCH(C, P) do { if (S.target & kTargetHeatPath) MI3D_FLUX_LAUNCH_H(C, P, true); else MI3D_FLUX_LAUNCH_H(C, P, false); } while (0)
-    switch ((h->counting ? 2 : 0) | (h->solver == MI3D_SOLVER_P3D ? 1 : 0)) {
-        case 0: MI3D_FLUX_LAUNCH(false, false); break;
-        case 1: MI3D_FLUX_LAUNCH(false, true); break;
-        case 2: MI3D_FLUX_LAUNCH(true, false); break;
-        default: MI3D_FLUX_LAUNCH(true, true); break;
-    }
-#undef MI3D_FLUX_LAUNCH
-#undef MI3D_FLUX_LAUNCH_H
-    hipError_t err = hipGetLastError();
+    hipError_t err = launch_build(flux_build(B.counting, B.p3d, mix, B.hpath), grid, 256, lds, st, S, TLd, nb, seed, off);
     if (err == hipSuccess) {
         if (!h->tldesc_ev[slot]) err = hipEventCreateWithFlags(&h->tldesc_ev[slot], hipEventDisableTiming);
         if (err == hipSuccess) err = hipEventRecord(h->tldesc_ev[slot], st);
@@ -1715,44 +1710,27 @@ static hipError_t launch_flux(mi3d_solver *h, int tset, bool two_streams, const 
     Gm.inv_nx = h->cold_host.inv_nx; Gm.inv_ny = h->cold_host.inv_ny; Gm.nz = h->nz; Gm.nx = h->nx; Gm.ny = h->ny; Gm.diag = h->d_counters.p;
     const size_t lds_runs = tl_runs_lds(TL.nbins, h->nz);
     // (large tables of bins: workgroups of 512 threads -- twice the waves on the same LDS)
-    const bool runs_wide = lds_runs > 40960;
-#define MI3D_RUNS_LAUNCH(W)                                                                                                          \
-    do {                                                                                                                             \
-        if (TL.hist_wg && runs_wide) {                                                                                               \
-            if (lds_runs > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_tl_runs<W, 4, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_runs); \
-            hipLaunchKernelGGL((k_tl_runs<W, 4, 512>), dim3((unsigned)TL.nwave / 4u), dim3(512), lds_runs, st, TL, Gm, S.flux);        \
-        } else if (TL.hist_wg) {                                                                                                     \
-            if (lds_runs > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_tl_runs<W, 4, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_runs); \
-            hipLaunchKernelGGL((k_tl_runs<W, 4, 256>), dim3((unsigned)TL.nwave / 4u), dim3(256), lds_runs, st, TL, Gm, S.flux);        \
-        } else {                                                                                                                     \
-            if (lds_runs > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_tl_runs<W, 1, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_runs); \
-            hipLaunchKernelGGL((k_tl_runs<W, 1, 256>), dim3((unsigned)TL.nwave), dim3(256), lds_runs, st, TL, Gm, S.flux);             \
-        }                                                                                                                            \
-    } while (0)
-    if (TL.run_cap) MI3D_RUNS_LAUNCH(false);
+    const bool hist_wg = TL.hist_wg != 0, runs_wide = hist_wg && lds_runs > 40960;
+    const unsigned sort_grid = hist_wg ? (unsigned)TL.nwave / 4u : (unsigned)TL.nwave;   // (a workgroup of the sort per workgroup of the loop, or per wave)
+    const unsigned nflux = (unsigned)h->flux_elems(), nheat = (unsigned)(heat ? h->heat_elems() : 0);
+    if (TL.run_cap && (err = launch_build(tl_runs_build(false, hist_wg, runs_wide), sort_grid, runs_wide ? 512 : 256, lds_runs, st, TL, Gm, S.flux)) != hipSuccess) return err;
     hipLaunchKernelGGL(k_tl_wavescan<256>, dim3((unsigned)TL.nbins), dim3(256), 0, st, TL);
     hipLaunchKernelGGL(k_tl_prefix<256>, dim3(1), dim3(256), 0, st, TL);
-    // (workgroups of 256 threads with 16-KB tiles -- eight records per thread --, up to eight to a CU: 8.9e8 photons/s on the 128 x 128 flux
-    //  scene; 16 / 32 records per thread 8.7e8 / 6.7e8, 4: 8.5e8; 128 / 512 / 1024 threads 8.7e8 / 7.5e8 / 7.9e8: profiles/r03/flux_records_experiments.log)
-    const size_t lds_sc = ((size_t)4 * TL.nbins + 16 + 2 * kTlIds) * sizeof(uint32_t) + (size_t)MI3D_TLS_R * MI3D_TLS_NT * sizeof(uint2);
-    if (TL.hist_wg) {
-        // tallies of more than 1024 bins: one workgroup of the sort per workgroup of the photon loop (four waves' chunk lists, one
-        // histogram), 1024 threads and 64-KB tiles -- the tables over the bins (60 KB at 5000 bins) leave room for one workgroup per CU,
-        // and every tile pays for a pass over them: 5.4e8 photons/s on 480 x 480 x 100 against 4.0e8 with 256 threads (atomics: 3.35e8)
-        const size_t lds_b = ((size_t)3 * TL.nbins + 16 + 2 * kTlIds) * sizeof(uint32_t) + (size_t)8 * 1024 * sizeof(uint2);
-        if (lds_b > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_tl_scatter<1024, 8, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
-        hipLaunchKernelGGL((k_tl_scatter<1024, 8, 4>), dim3((unsigned)TL.nwave / 4u), dim3(1024), lds_b, st, TL, S.flux, (unsigned)h->flux_elems(), heat, (unsigned)(heat ? h->heat_elems() : 0));
-    } else {
-        if (lds_sc > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_tl_scatter<MI3D_TLS_NT, MI3D_TLS_R, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sc);
-        hipLaunchKernelGGL((k_tl_scatter<MI3D_TLS_NT, MI3D_TLS_R, 1>), dim3((unsigned)TL.nwave), dim3(MI3D_TLS_NT), lds_sc, st, TL, S.flux, (unsigned)h->flux_elems(), heat, (unsigned)(heat ? h->heat_elems() : 0));
-    }
+    // One wave's records: workgroups of 256 threads with 16-KB tiles -- eight records per thread --, up to eight to a CU: 8.9e8 photons/s on the
+    // 128 x 128 flux scene; 16 / 32 records per thread 8.7e8 / 6.7e8, 4: 8.5e8; 128 / 512 / 1024 threads 8.7e8 / 7.5e8 / 7.9e8:
+    // profiles/r03/flux_records_experiments.log.
+    // Tallies of more than 1024 bins (hist_wg): one workgroup of the sort per workgroup of the photon loop (four waves' chunk lists, one
+    // histogram), 1024 threads and 64-KB tiles -- the tables over the bins (60 KB at 5000 bins) leave room for one workgroup per CU,
+    // and every tile pays for a pass over them: 5.4e8 photons/s on 480 x 480 x 100 against 4.0e8 with 256 threads (atomics: 3.35e8)
+    const size_t lds_sc = hist_wg ? ((size_t)3 * TL.nbins + 16 + 2 * kTlIds) * sizeof(uint32_t) + (size_t)8 * 1024 * sizeof(uint2)
+                                  : ((size_t)4 * TL.nbins + 16 + 2 * kTlIds) * sizeof(uint32_t) + (size_t)MI3D_TLS_R * MI3D_TLS_NT * sizeof(uint2);
+    if ((err = launch_build(tl_scatter_build(hist_wg), sort_grid, hist_wg ? 1024 : MI3D_TLS_NT, lds_sc, st, TL, S.flux, nflux, heat, nheat)) != hipSuccess) return err;
     // ... and the runs' records, level by level, behind each row's share of every bin
-    if (TL.run_cap) MI3D_RUNS_LAUNCH(true);
-#undef MI3D_RUNS_LAUNCH
+    if (TL.run_cap && (err = launch_build(tl_runs_build(true, hist_wg, runs_wide), sort_grid, runs_wide ? 512 : 256, lds_runs, st, TL, Gm, S.flux)) != hipSuccess) return err;
     if (two_streams && (err = hipEventRecord(T.scattered, st)) != hipSuccess) return err;
     const int split = std::max(1, std::min(64, (h->num_cu * 8) / TL.nbins));
     mi3d_solver::PendingSum &P = T.pend;
-    P.on = true; P.TL = TL; P.flux = S.flux; P.nflux = (unsigned)h->flux_elems(); P.heat = heat; P.nheat = (unsigned)(heat ? h->heat_elems() : 0); P.split = split;
+    P.on = true; P.TL = TL; P.flux = S.flux; P.nflux = nflux; P.heat = heat; P.nheat = nheat; P.split = split;
     // one stream: the sums straight behind the sort.  Two: they wait for the main stream's next pause -- the next launch of this set, or a join
     if (!two_streams) return launch_sum(h, tset, st);
     return hipGetLastError();
@@ -1838,6 +1816,7 @@ enum class Loop { General, Column, ColumnRays, Flux, Backward };
 struct RunPlan {
     Loop loop = Loop::General;
     bool march = false, flux = false, thermal = false;
+    RunBuild build;              // what the run fixes of its kernels' builds, for the launchers and name_route
     // builds of the lean loops (`mix`): 0 er3t's default scene -- one 1-D and one 3-D constituent, analytic phase functions --, 1 a second
     // 3-D constituent, 2 (round 5) the general mixture: several 1-D constituents and / or TABULATED phase functions, in 1-D layers
     // (func_ref_vs_cot's cloud slab, rtm/mca/util.py:153) or in voxels (the Mie branch as mca_atm.py:275-277 would write it).  mix_lean: the
@@ -1852,6 +1831,10 @@ struct RunPlan {
 static RunPlan plan_run(const mi3d_solver *h, uint64_t nphoton) {
     RunPlan plan;
     plan.thermal = h->thermal();   // (a mixed job's photons start anywhere too: id order, the general loop)
+    plan.build.counting = h->counting != 0;
+    plan.build.p3d = h->solver == MI3D_SOLVER_P3D;
+    plan.build.src = h->src_mtype == 3 ? 1 : h->src_mtype == 2 ? 2 : 0;
+    plan.build.hpath = (h->target & MI3D_TARGET_HEAT) && h->heat_estimator == 1;   // (fill_scene: kTargetHeatPath)
     plan.march = (h->target & MI3D_TARGET_RADIANCE) && h->nmarch > 0;
     plan.flux = (h->target & MI3D_TARGET_FLUX) != 0;
     int tc = plan.thermal ? 0 : choose_tile_cols(h);   // (a thermal photon does not start at the top: id order)
@@ -1917,9 +1900,9 @@ static int cam_fallback(mi3d_solver *h, const char *why) {
 // (mi3d_set_kernel 1) but landed there: the loop of round 1 serves it correctly and at a fraction of the lean loops' speed (bench.py's
 // `general_kernel` leg has the figure).  Thermal jobs take the general loop by design.
 static void name_route(mi3d_solver *h, const RunPlan &plan, bool lists, uint64_t nphoton) {
-    const int c = h->counting ? 1 : 0, p3d = h->solver == MI3D_SOLVER_P3D ? 1 : 0;
+    const int c = plan.build.counting ? 1 : 0, p3d = plan.build.p3d ? 1 : 0;
     char nm[96];
-    const bool hpath = (h->target & MI3D_TARGET_HEAT) && h->heat_estimator == 1;
+    const bool hpath = plan.build.hpath;
     if (plan.loop == Loop::Backward && h->sat_backward()) snprintf(nm, sizeof(nm), "k_backward<%d,V> [thermal]", c);
     else if (plan.loop == Loop::Backward && h->emis_weights) snprintf(nm, sizeof(nm), "k_backward<%d,W> [thermal]", c);
     else if (plan.loop == Loop::Backward) snprintf(nm, sizeof(nm), "k_backward<%d> [thermal]", c);
@@ -1928,7 +1911,7 @@ static void name_route(mi3d_solver *h, const RunPlan &plan, bool lists, uint64_t
     else if (plan.loop == Loop::ColumnRays && plan.thermal) snprintf(nm, sizeof(nm), "k_transport<%d,2,0,0> [thermal] + k_rays", c);
     else if (plan.loop == Loop::ColumnRays) snprintf(nm, sizeof(nm), "k_transport_lean<%d,%d,2,%d> + k_rays", c, p3d, plan.mix_lean);
     else if (plan.loop == Loop::Column) snprintf(nm, sizeof(nm), "k_transport_lean<%d,%d,0,%d>", c, p3d, plan.mix_lean);
-    else if (h->src_mtype == 2) snprintf(nm, sizeof(nm), hpath ? "k_transport<%d,%d,%d,%d> [solar+thermal] [heating: path length]" : "k_transport<%d,%d,%d,%d> [solar+thermal]", c, plan.march ? 1 : 0, plan.flux ? 1 : 0, p3d);
+    else if (plan.build.src == 2) snprintf(nm, sizeof(nm), hpath ? "k_transport<%d,%d,%d,%d> [solar+thermal] [heating: path length]" : "k_transport<%d,%d,%d,%d> [solar+thermal]", c, plan.march ? 1 : 0, plan.flux ? 1 : 0, p3d);
     else snprintf(nm, sizeof(nm), plan.thermal ? (hpath ? "k_transport<%d,%d,%d,%d> [thermal] [heating: path length]" : "k_transport<%d,%d,%d,%d> [thermal]") : hpath ? "k_transport<%d,%d,%d,%d> [heating: path length]" : "k_transport<%d,%d,%d,%d>", c, plan.march ? 1 : 0, plan.flux ? 1 : 0, p3d);
     h->last_kernel = nm;
     if (plan.loop == Loop::General && h->kernel_choice == 0 && !h->general_warned && nphoton >= 4096 && !plan.thermal) {
@@ -2128,7 +2111,7 @@ static bool use_entry_records(mi3d_solver *h, const RunPlan &plan, uint64_t npho
     h->entry_form_run = 0;
 #if MI3D_LEAN_FAST
     // (the path-length estimator of the heating rates tallies the first flight too: its photons are launched inside the loop)
-    if ((h->target & MI3D_TARGET_HEAT) && h->heat_estimator == 1) return false;
+    if (plan.build.hpath) return false;
     if (plan.loop == Loop::General || plan.thermal || !h->entry_records || h->nx >= 65536 || h->ny >= 65536 || h->nz >= 32768) return false;
     DevBuf<float4> &E = h->pre[0].entry;
     const int form = entry_form(h, plan);
@@ -2263,10 +2246,10 @@ static int launch_photons(mi3d_solver *h, const RunPlan &plan, uint64_t ev_cap, 
 // The column-view loop of a launch (set: its event lists) and, with marched views, the ray kernels of the events it has written: on their
 // own stream rs beside the next launch's photon loop where there are two sets
 static hipError_t launch_column(mi3d_solver *h, const RunPlan &plan, const DevScene &Sl, int set, bool two_sets, hipStream_t rs, unsigned grid, uint64_t nb, uint64_t seed, uint64_t off) {
-    const bool split = plan.loop == Loop::ColumnRays;
+    const bool split = plan.loop == Loop::ColumnRays, counting = plan.build.counting;
     mi3d_solver::EvSet &E = h->ev[set];
     const size_t lds_col = (size_t)(h->nz + 2) * sizeof(LayerRec) + MI3D_MAX_VIEW * sizeof(ViewRec) + sizeof(DevCold);   // (+2: the lean loop's end records)
-    const int emit_wg = h->counting ? 4 : (h->emit_wg > 0 ? std::min(h->emit_wg, MI3D_LEAN_EMIT_GRID) : MI3D_LEAN_EMIT_GRID);
+    const int emit_wg = counting ? 4 : (h->emit_wg > 0 ? std::min(h->emit_wg, MI3D_LEAN_EMIT_GRID) : MI3D_LEAN_EMIT_GRID);
     const unsigned gridp = split ? (unsigned)std::min<uint64_t>((nb + 255) / 256, (uint64_t)h->num_cu * emit_wg) : grid;
     DevScene Sx = Sl;
     if (set) Sx.cold = h->d_cold.p + 1;       // (this launch's set of event lists)
@@ -2274,16 +2257,16 @@ static hipError_t launch_column(mi3d_solver *h, const RunPlan &plan, const DevSc
     // (the set is free once the ray kernels of the launch that used it last are through it)
     if (two_sets && E.used) err = hipStreamWaitEvent(h->stream, E.rays, 0);
     if (err == hipSuccess && split) err = hipMemsetAsync(E.evctr.p, 0, kCtrWords * kCtrStride * sizeof(unsigned long long), h->stream);
-    if (err == hipSuccess && plan.thermal) err = launch_general(h, Sx, false, false, gridp, nb, seed, off, true);   // (thermal cameras: the general loop writes the records)
+    if (err == hipSuccess && plan.thermal) err = launch_general(h, plan.build, h->stream, Sx, 2, false, gridp, nb, seed, off);   // (thermal cameras: the general loop writes the records)
     else if (err == hipSuccess) {
         // (the general mixture with staged tables AND a tally window: three workgroups of 512 threads keep six waves per SIMD where
         //  six of 256 would not find the LDS)
         const size_t lds_lean = lds_col + (h->cold_host.tile_end ? kWinLds : 0) + plan.lds_tab;
-        const bool wide = plan.mix >= 2 && !split && !h->counting && lds_lean * 3 <= (size_t)160 * 1024 && lds_lean * 6 > (size_t)160 * 1024;
+        const bool wide = plan.mix >= 2 && !split && !counting && lds_lean * 3 <= (size_t)160 * 1024 && lds_lean * 6 > (size_t)160 * 1024;
         unsigned gridw = wide ? (unsigned)std::min<uint64_t>((nb + 511) / 512, (uint64_t)h->num_cu * 3) : gridp;
         // (the general mixture in workgroups of 256: as many as its registers -- five waves per SIMD -- and its LDS let a CU hold)
-        if (plan.mix >= 2 && !wide && !split && !h->counting) gridw = std::min<unsigned>(gridw, (unsigned)h->num_cu * (unsigned)std::max<size_t>(1, std::min<size_t>(MI3D_GEN_NARROW_WAVES, ((size_t)160 * 1024) / lds_lean)));
-        err = launch_lean(h, h->stream, Sx, split, plan.mix_lean, wide ? 512 : 256, gridw, lds_lean, nb, seed, off);
+        if (plan.mix >= 2 && !wide && !split && !counting) gridw = std::min<unsigned>(gridw, (unsigned)h->num_cu * (unsigned)std::max<size_t>(1, std::min<size_t>(MI3D_GEN_NARROW_WAVES, ((size_t)160 * 1024) / lds_lean)));
+        err = launch_lean(h, plan.build, h->stream, Sx, split, plan.mix_lean, wide ? 512 : 256, gridw, lds_lean, nb, seed, off);
     }
     if (err != hipSuccess || !split) return err;
     if (two_sets) {
@@ -2291,9 +2274,9 @@ static hipError_t launch_column(mi3d_solver *h, const RunPlan &plan, const DevSc
         if (err == hipSuccess) err = hipStreamWaitEvent(rs, E.emit, 0);
     }
     const bool plain_scene = (Sl.target & kTargetPlainPhase) != 0 && h->rad_kind != 1;
-    if (err == hipSuccess) err = launch_rays(h, rs, Sx, false, lds_col + rays_lds_extra(h->nz, h->rad_kind == 1) + (plain_scene ? 0 : plan.lds_tab), seed);
+    if (err == hipSuccess) err = launch_rays(h, plan.build, rs, Sx, false, lds_col + rays_lds_extra(h->nz, h->rad_kind == 1) + (plain_scene ? 0 : plan.lds_tab), seed);
     if (err == hipSuccess && !h->sfc_lambert_only && h->rad_kind != 1)   // the reflections off LSRT / DSM surfaces it left aside
-        err = launch_rays(h, rs, Sx, true, lds_col + rays_lds_extra(h->nz) + plan.lds_tab, seed);
+        err = launch_rays(h, plan.build, rs, Sx, true, lds_col + rays_lds_extra(h->nz) + plan.lds_tab, seed);
     return err;
 }
 
@@ -2626,9 +2609,9 @@ int mi3d_run(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_of
     if (h->rad_kind == 1 && plan.loop != Loop::ColumnRays && (rc = cam_fallback(h, plan.why))) return rc;
     if ((rc = event_lists(h, plan, nphoton, ev_cap, two_sets))) return rc;
     name_route(h, plan, TL[0].cap != 0, nphoton);
-    const uint64_t cap = (uint64_t)h->num_cu * (plan.loop == Loop::Flux ? MI3D_FLUX_WAVES(h->counting != 0)
-                                                : plan.loop == Loop::General ? MI3D_BLOCKS_PER_CU(plan.march, h->counting != 0)
-                                                                             : MI3D_LEAN_WAVES(h->counting != 0, plan.march));
+    const uint64_t cap = (uint64_t)h->num_cu * (plan.loop == Loop::Flux ? MI3D_FLUX_WAVES(plan.build.counting)
+                                                : plan.loop == Loop::General ? MI3D_WAVES(plan.march, plan.build.counting)
+                                                                             : MI3D_LEAN_WAVES(plan.build.counting, plan.march));
     const bool use_entry = use_entry_records(h, plan, nphoton);   // (fill_scene has cleared cold_host.entry)
     const bool pre_two = pre_second_set(h, plan, use_entry, two_sets, nphoton);
     // (a launch of a kind that MAY be followed by a two-stream launch on this handle leaves the events the latter waits for, also when it runs on one stream itself)
@@ -2671,9 +2654,9 @@ int mi3d_run(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_of
         const int tset = tl_two ? (int)(h->tl_launch_no & 1) : 0;
         hipStream_t const rs = two_sets ? h->rays_stream : h->stream;
         if (err == hipSuccess && plan.loop == Loop::Flux) {
-            err = launch_flux(h, tset, tl_two, Sl, TL[tset], plan.mix, grid, lds_fl, nb, seed, off);
+            err = launch_flux(h, plan.build, tset, tl_two, Sl, TL[tset], plan.mix, grid, lds_fl, nb, seed, off);
             if (err == hipSuccess && tl_two) { err = hipEventRecord(h->tl[tset].sorted, h->tl_stream); h->tl[tset].used = true; h->tl_unjoined = true; }
-        } else if (err == hipSuccess && plan.loop == Loop::General) err = launch_general(h, Sl, plan.march, plan.flux, grid, nb, seed, off);
+        } else if (err == hipSuccess && plan.loop == Loop::General) err = launch_general(h, plan.build, h->stream, Sl, plan.march ? 1 : 0, plan.flux, grid, nb, seed, off);
         else if (err == hipSuccess) err = launch_column(h, plan, Sl, set, two_sets, rs, grid, nb, seed, off);
         if (err == hipSuccess && !run_timed) err = hipEventRecord(e1, h->stream);
         h->pre_last = pset;
