@@ -79,9 +79,10 @@ struct DevBuf {
 };
 
 constexpr double kWgtMaxElems = 2147483648.0;   // elements of the emission weights' tally npix x ncell served (mi3d_set_emission_weights)
+constexpr double kPrfMaxElems = 2147483648.0;   // elements of the view profiles' tally npix x (nz + 1) x 2 served (mi3d_set_view_profiles)
 
-// The three builds of the backward route (mi3d_kernel_backward.hip): k_backward, k_backward_w, k_backward_v ...
-enum class BwdRoute { Camera = 0, Weights = 1, Views = 2 };
+// The four builds of the backward route (mi3d_kernel_backward.hip): k_backward, k_backward_w, k_backward_v, k_backward_vp ...
+enum class BwdRoute { Camera = 0, Weights = 1, Views = 2, Profiles = 3 };
 // ... and what the runtime said of one of them: workgroups resident per CU for `lds` bytes of dynamic LDS (0: not asked yet)
 struct BwdCap { int blocks = 0, counting = -1; size_t lds = 0; };
 
@@ -138,7 +139,7 @@ struct mi3d_solver {
     int bwd_chunk = -1;
     int bwd_chunk_last = 0;
     DevBuf<float> d_bwd_start;
-    BwdCap bwd_cap[3];               // per BwdRoute: the resident workgroups per CU of the build launched last (backward_resident)
+    BwdCap bwd_cap[4];               // per BwdRoute: the resident workgroups per CU of the build launched last (backward_resident)
     bool sat_backward() const { return view_method == 1 && cam_method == 0 && rad_kind == 2; }           // is the job sent to k_backward_v?
     bool backward() const {                                                                               // does the read-out divide by the pixels' own counts?
         return src_mtype == 3 && nview > 0 && ((cam_method == 1 && rad_kind == 1) || sat_backward());
@@ -153,6 +154,17 @@ struct mi3d_solver {
     double *wgt_ext = nullptr;
     size_t wgt_n = 0;
     double *wgt_ptr() { return wgt_ext ? wgt_ext : d_wgt_own.p; }
+    // per-layer profiles of the backward route's satellite views (mi3d_set_view_profiles 1): P_raw[npix][nz + 1][2], pairs
+    // {K, C}; the library's own buffer (prf_n elements, zeroed when it is made; 0: to be made by the next run) or the caller's
+    // (mi3d_bind_view_profiles_buffer); prf_ran: a run has tallied them since the switch was set and the scene laid out
+    int view_profiles = 0;
+    DevBuf<double> d_prf_own;
+    DevBuf<float> d_prf_out;         // the read-out's staging buffer
+    double *prf_ext = nullptr;
+    size_t prf_n = 0;
+    bool prf_ran = false;
+    double *prf_ptr() { return prf_ext ? prf_ext : d_prf_own.p; }
+    double prf_elems() const { return (double)nview * nxr * nyr * ((double)nz + 1.0) * 2.0; }
     size_t wgt_ncell() const { return (size_t)nx * ny * nz3 + (size_t)nz + (sfc2d_host.empty() ? (size_t)1 : (size_t)nxb * nyb); }
     int nview = 0, nxr = 1, nyr = 1;
     double view_the[MI3D_MAX_VIEW], view_phi[MI3D_MAX_VIEW], view_zloc[MI3D_MAX_VIEW], zref = 0.0;
@@ -949,6 +961,7 @@ int mi3d_destroy(mi3d_solver *h) {
     h->d_stat_out.release(); h->d_dir_level.release(); h->d_get_out.release(); h->d_get_add.release();
     h->d_th_tlev.release(); h->d_th_tmpa.release(); h->d_th_tmps.release(); h->d_th_cdf.release(); h->d_th_bsum.release(); h->d_th.release();
     h->d_wgt_own.release(); h->d_wgt_out.release();
+    h->d_prf_own.release(); h->d_prf_out.release();
     h->d_bwd_cells.release(); h->d_bwd_capped.release(); h->d_bwd_norm.release(); h->d_bwd_score.release(); h->d_bwd_dir.release(); h->d_bwd_start.release();
     h->d_views.release(); h->d_cold.release(); h->d_tabrange.release(); h->d_bt1d.release(); h->d_dz.release(); h->d_bmin.release(); h->d_bmax.release();
     delete h;
@@ -1208,6 +1221,28 @@ int mi3d_bind_weights_buffer(mi3d_solver *h, void *wgt_sum) {
     return MI3D_OK;
 }
 
+int mi3d_set_view_profiles(mi3d_solver *h, int on) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (on != 0 && on != 1) return fail(MI3D_EINVAL, "view profiles %d (0: off, 1: per-layer weighting functions of the backward route's satellite views)", on);
+    if (on == h->view_profiles) return MI3D_OK;
+    HIPCHK(sync_main(h));   // (as every call that changes what the kernels work on)
+    h->view_profiles = on;
+    h->prf_ran = false;
+    if (!on) { h->d_prf_own.release(); h->d_prf_out.release(); h->prf_n = 0; }
+    return MI3D_OK;
+}
+
+int mi3d_bind_view_profiles_buffer(mi3d_solver *h, void *raw) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if ((double *)raw == h->prf_ext) return MI3D_OK;
+    HIPCHK(sync_main(h));
+    h->prf_ext = (double *)raw;
+    if (!raw) h->prf_n = 0;   // (the library's own buffer is made anew, and zeroed, by the next run)
+    return MI3D_OK;
+}
+
 int mi3d_set_camera_map(mi3d_solver *h, int mpmap, int mrproj) {
     int rc = check_handle(h);
     if (rc) return rc;
@@ -1405,6 +1440,7 @@ int mi3d_prepare(mi3d_solver *h) {
             HIPCHK(hipMemsetAsync(h->d_heat_own.p, 0, h->heat_elems() * sizeof(double), h->stream));
         }
         h->wgt_n = 0;   // (the emission weights' own buffer: made and zeroed by the next run that tallies them, run_backward)
+        h->prf_n = 0; h->prf_ran = false;   // (likewise the view profiles')
         h->dirty_tally = false;
     }
     if (h->thermal() && h->dirty_thermal) {
@@ -1439,6 +1475,11 @@ int mi3d_reset(mi3d_solver *h) {
         const double ne = (double)h->nview * h->nxr * h->nyr * (double)h->wgt_ncell();
         if (h->wgt_ext) { if (h->backward() && ne <= kWgtMaxElems) HIPCHK(hipMemsetAsync(h->wgt_ext, 0, (size_t)ne * sizeof(double), h->stream)); }
         else if (h->wgt_n) HIPCHK(hipMemsetAsync(h->d_wgt_own.p, 0, h->wgt_n * sizeof(double), h->stream));
+    }
+    if (h->view_profiles) {
+        const double ne = h->prf_elems();
+        if (h->prf_ext) { if (h->sat_backward() && ne <= kPrfMaxElems) HIPCHK(hipMemsetAsync(h->prf_ext, 0, (size_t)ne * sizeof(double), h->stream)); }
+        else if (h->prf_n) HIPCHK(hipMemsetAsync(h->d_prf_own.p, 0, h->prf_n * sizeof(double), h->stream));
     }
     // (the accumulation image is folded and zeroed at the end of a successful mi3d_run; a run that failed half way -- an event
     //  list ran full, a launch failed -- leaves its partial tallies there)
@@ -1903,7 +1944,8 @@ static void name_route(mi3d_solver *h, const RunPlan &plan, bool lists, uint64_t
     const int c = plan.build.counting ? 1 : 0, p3d = plan.build.p3d ? 1 : 0;
     char nm[96];
     const bool hpath = plan.build.hpath;
-    if (plan.loop == Loop::Backward && h->sat_backward()) snprintf(nm, sizeof(nm), "k_backward<%d,V> [thermal]", c);
+    if (plan.loop == Loop::Backward && h->sat_backward() && h->view_profiles) snprintf(nm, sizeof(nm), "k_backward<%d,V,P> [thermal]", c);
+    else if (plan.loop == Loop::Backward && h->sat_backward()) snprintf(nm, sizeof(nm), "k_backward<%d,V> [thermal]", c);
     else if (plan.loop == Loop::Backward && h->emis_weights) snprintf(nm, sizeof(nm), "k_backward<%d,W> [thermal]", c);
     else if (plan.loop == Loop::Backward) snprintf(nm, sizeof(nm), "k_backward<%d> [thermal]", c);
     else if (plan.loop == Loop::Flux && hpath) snprintf(nm, sizeof(nm), lists ? "k_transport_flux<%d,%d,%d,1> + k_tl_scatter + k_tl_sum" : "k_transport_flux<%d,%d,%d,1>", c, p3d, plan.mix);
@@ -2420,7 +2462,7 @@ static void fill_backward_views(const mi3d_solver *h, BwdSat &S, float *start_ou
 }
 
 // The one place that names the builds of the histories: the kernel of (route, counting, debug), as the runtime takes it for a launch and
-// for an occupancy query.  The weights build has no debug form (nullptr); the debug forms do not count
+// for an occupancy query.  The weights and profiles builds have no debug form (nullptr); the debug forms do not count
 static const void *backward_build(BwdRoute route, bool counting, bool debug) {
     switch (route) {
     case BwdRoute::Camera:
@@ -2432,21 +2474,26 @@ static const void *backward_build(BwdRoute route, bool counting, bool debug) {
     case BwdRoute::Views:
         if (debug) return (const void *)k_backward_v<false, true>;
         return counting ? (const void *)k_backward_v<true, false> : (const void *)k_backward_v<false, false>;
+    case BwdRoute::Profiles:
+        if (debug) return nullptr;
+        return counting ? (const void *)k_backward_vp<true> : (const void *)k_backward_vp<false>;
     }
     return nullptr;
 }
 
 // One launch.  The kernel arguments in the order of the entry points: (A, seed, id0, n), then (dir_out, score_out) for the cameras,
-// (W) for the weights build, (dir_out, score_out, S) for the views
+// (W) for the weights build, (dir_out, score_out, S) for the views, (S, P) for the views' profiles build
 static hipError_t backward_launch(BwdRoute route, bool counting, bool debug, unsigned grid, size_t lds, hipStream_t stream, DevBackward A, uint64_t seed,
-                                  uint64_t id0, uint64_t n, float *dir_out, double *score_out, BwdWeights W, BwdSat S) {
+                                  uint64_t id0, uint64_t n, float *dir_out, double *score_out, BwdWeights W, BwdSat S, BwdProfiles P) {
     const void *kernel = backward_build(route, counting, debug);
     if (!kernel) return hipErrorInvalidValue;
-    void *cam[] = {&A, &seed, &id0, &n, &dir_out, &score_out}, *wgt[] = {&A, &seed, &id0, &n, &W}, *sat[] = {&A, &seed, &id0, &n, &dir_out, &score_out, &S};
-    return hipLaunchKernel(kernel, dim3(grid), dim3(256), route == BwdRoute::Camera ? cam : route == BwdRoute::Weights ? wgt : sat, lds, stream);
+    void *cam[] = {&A, &seed, &id0, &n, &dir_out, &score_out}, *wgt[] = {&A, &seed, &id0, &n, &W}, *sat[] = {&A, &seed, &id0, &n, &dir_out, &score_out, &S},
+         *prf[] = {&A, &seed, &id0, &n, &S, &P};
+    return hipLaunchKernel(kernel, dim3(grid), dim3(256),
+                           route == BwdRoute::Camera ? cam : route == BwdRoute::Weights ? wgt : route == BwdRoute::Views ? sat : prf, lds, stream);
 }
 
-// Workgroups of the build that are resident on the device at once.  The weights and view builds ask the runtime, once per (route, LDS
+// Workgroups of the build that are resident on the device at once.  The weights, view and profiles builds ask the runtime, once per (route, LDS
 // bytes, counting).  The camera build takes five waves per SIMD, four in the counting build (the register report in DESIGN.md §5.11),
 // the grid it has always had: asking the runtime instead could change that grid where LDS limits residency, a change of behaviour
 // that belongs to a pull request of its own.
@@ -2458,6 +2505,7 @@ static int backward_resident(mi3d_solver *h, BwdRoute route, size_t lds, uint64_
         const hipError_t eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, backward_build(route, h->counting != 0, false), 256, lds);
         if (eo != hipSuccess || nb < 1) {
             if (route == BwdRoute::Weights) return fail(MI3D_EDEVICE, "emission weights: no workgroup of the weights build fits a CU with %zu bytes of LDS", lds);
+            if (route == BwdRoute::Profiles) return fail(MI3D_EDEVICE, "view profiles: no workgroup of the profiles build fits a CU with %zu bytes of LDS", lds);
             return fail(MI3D_EDEVICE, "backward Monte Carlo for satellite views: no workgroup fits a CU with %zu bytes of LDS", lds);
         }
         c.blocks = nb; c.lds = lds; c.counting = h->counting;
@@ -2468,7 +2516,8 @@ static int backward_resident(mi3d_solver *h, BwdRoute route, size_t lds, uint64_
 
 static int run_backward(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_offset) {
     const bool sat = h->sat_backward(), wgt = h->emis_weights != 0;
-    const BwdRoute route = sat ? BwdRoute::Views : wgt ? BwdRoute::Weights : BwdRoute::Camera;
+    const bool prf = sat && h->view_profiles != 0;
+    const BwdRoute route = prf ? BwdRoute::Profiles : sat ? BwdRoute::Views : wgt ? BwdRoute::Weights : BwdRoute::Camera;
     int rc = backward_unsupported(h, sat);
     if (rc) return rc;
     if (h->nview == 0) return fail(MI3D_ESTATE, "radiance requested but no view is set (%s)", sat ? "mi3d_set_views" : "mi3d_set_cameras");
@@ -2494,6 +2543,21 @@ static int run_backward(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_
             h->wgt_n = (size_t)ne;
         }
         W.K = h->wgt_ptr();
+    }
+    BwdProfiles P{};
+    if (prf) {
+        // the profiles build: its tally, made and zeroed here when it is the library's own
+        P.nrow = h->nz + 1;
+        const double ne = h->prf_elems();
+        if (ne > kPrfMaxElems)
+            return fail(MI3D_EUNSUP, "view profiles (mi3d_set_view_profiles 1): %d pixels x %d rows x 2 are more than the 2^31 elements served", npix, P.nrow);
+        if (!h->prf_ext && h->prf_n != (size_t)ne) {
+            if ((rc = h->d_prf_own.alloc((size_t)ne))) return rc;
+            HIPCHK(hipMemsetAsync(h->d_prf_own.p, 0, (size_t)ne * sizeof(double), h->stream));
+            h->prf_n = (size_t)ne;
+        }
+        P.raw = h->prf_ptr();
+        h->prf_ran = true;
     }
     BwdSat S{};
     uint64_t ntile = 0;
@@ -2534,7 +2598,7 @@ static int run_backward(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_
         HIPCHK(hipEventCreate(&e0));
         hipError_t err = hipEventCreate(&e1);
         if (err == hipSuccess) err = hipEventRecord(e0, h->stream);
-        if (err == hipSuccess) err = backward_launch(route, h->counting != 0, false, grid, lds, h->stream, A, seed, off, nb, nullptr, nullptr, W, Sl);
+        if (err == hipSuccess) err = backward_launch(route, h->counting != 0, false, grid, lds, h->stream, A, seed, off, nb, nullptr, nullptr, W, Sl, P);
         if (err == hipSuccess) err = hipEventRecord(e1, h->stream);
         if (err != hipSuccess) {
             (void)hipEventDestroy(e0);
@@ -2566,6 +2630,11 @@ int mi3d_run(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_of
     int rc = check_handle(h);
     if (rc) return rc;
     if ((rc = mi3d_prepare(h))) return rc;
+    if (h->view_profiles && (h->view_method != 1 || h->rad_kind != 2 || h->cam_method != 0 || h->emis_weights))
+        return fail(MI3D_EUNSUP, "view profiles (mi3d_set_view_profiles 1) are tallied by the backward route for satellite views alone (mi3d_set_view_method 1 "
+                                 "with mi3d_set_views, mi3d_set_camera_method 0, mi3d_set_emission_weights 0): not with %s",
+                    h->view_method != 1 ? "mi3d_set_view_method 0" : h->rad_kind != 2 ? "cameras (mi3d_set_cameras)" : h->cam_method != 0 ? "mi3d_set_camera_method 1"
+                                                                                                                      : "mi3d_set_emission_weights 1");
     if (h->view_method == 1 && h->rad_kind != 2) return backward_unsupported(h, true);   // (names the switch: it belongs to the views of mi3d_set_views)
     if (h->cam_method == 1 || h->view_method == 1) return run_backward(h, nphoton, seed, photon_offset);
     if (h->emis_weights)
@@ -3200,7 +3269,7 @@ static int debug_backward(mi3d_solver *h, bool sat, uint64_t seed, uint64_t id0,
         const int npix = h->nview * h->nxr * h->nyr;
         const size_t lds = backward_lds(npix, h->nz, h->nview, 1, backward_lds_sums(npix, true, S.jch > 0), false, sat);
         HIPCHK(backward_launch(sat ? BwdRoute::Views : BwdRoute::Camera, false, true, (unsigned)((n + 255) / 256), lds, h->stream, A, seed, id0, (uint64_t)n,
-                               h->d_bwd_dir.p, h->d_bwd_score.p, BwdWeights{}, S));
+                               h->d_bwd_dir.p, h->d_bwd_score.p, BwdWeights{}, S, BwdProfiles{}));
         if (sat) HIPCHK(hipMemcpyAsync(start_out, h->d_bwd_start.p, (size_t)3 * n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipMemcpyAsync(dir_out, h->d_bwd_dir.p, (size_t)3 * n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipMemcpyAsync(score_out, h->d_bwd_score.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -3269,6 +3338,36 @@ int mi3d_get_emission_weights(mi3d_solver *h, uint64_t nphoton_total, float *wei
         HIPCHK(hipMemcpyAsync(cells.data(), h->d_bwd_cells.p, (size_t)ncell * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
         for (size_t c = 0; c < (size_t)ncell; ++c) planck[c] = cells[c].y;
+    }
+    return MI3D_OK;
+}
+
+// Read-out of the view profiles (mi3d_set_view_profiles 1): the rows of P_raw by the rule of k_backward_norm, its pairs parted and
+// rounded to float32 on the device and brought over through a staging buffer of at most 2 x 2^25 elements
+int mi3d_get_view_profiles(mi3d_solver *h, uint64_t nphoton_total, float *weight, float *contribution) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (!h->view_profiles) return fail(MI3D_ESTATE, "mi3d_get_view_profiles: the profiles are not tallied (mi3d_set_view_profiles 1)");
+    if ((rc = mi3d_prepare(h))) return rc;
+    if (!h->sat_backward() || !h->prf_ran || !h->prf_ptr() || (!h->prf_ext && h->prf_n != (size_t)h->prf_elems()))
+        return fail(MI3D_ESTATE, "mi3d_get_view_profiles: nothing has been tallied (mi3d_run with mi3d_set_view_method 1 and mi3d_set_view_profiles 1)");
+    const unsigned long long npix = (unsigned long long)h->nview * h->nxr * h->nyr, nrow = (unsigned long long)h->nz + 1;
+    if (h->prf_elems() > kPrfMaxElems)
+        return fail(MI3D_EUNSUP, "view profiles (mi3d_set_view_profiles 1): %llu pixels x %llu rows x 2 are more than the 2^31 elements served", npix, nrow);
+    const unsigned long long ne = npix * nrow;
+    HIPCHK(sync_main(h));
+    const double *raw = h->prf_ptr();
+    const unsigned long long chunk = std::min<unsigned long long>(ne, 1ull << 25);
+    if ((rc = h->d_prf_out.alloc((size_t)chunk * 2))) return rc;
+    for (unsigned long long e0 = 0; e0 < ne; e0 += chunk) {
+        const unsigned long long nn = std::min(chunk, ne - e0);
+        const unsigned grid = (unsigned)std::min<unsigned long long>((nn + 255) / 256, 65536);
+        hipLaunchKernelGGL(k_backward_norm_profiles, dim3(grid), dim3(256), 0, h->stream, raw, h->d_prf_out.p, h->d_prf_out.p + chunk,
+                           (unsigned long long)nphoton_total, (unsigned)npix, nrow, e0, nn);
+        HIPCHK(hipGetLastError());
+        if (weight) HIPCHK(hipMemcpyAsync(weight + e0, h->d_prf_out.p, (size_t)nn * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        if (contribution) HIPCHK(hipMemcpyAsync(contribution + e0, h->d_prf_out.p + chunk, (size_t)nn * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
     }
     return MI3D_OK;
 }

@@ -17,8 +17,12 @@
 //                      line of sight on the view's registration level inside pixel id mod npix, the history starts where that line meets the
 //                      sensor plane; the views are staged in LDS where the cameras were; ids are handed out by tiles of 8 x 8 pixels
 //                      ("bwd_chunk" >= 1) and a lane sums its pixel's scores in a register.  DEBUG: mi3d_debug_backward_views
+//   k_backward_vp<COUNT>   the histories of k_backward_v with mi3d_set_view_profiles 1: every term w (1 - exp(-ka l)),
+//                      w eps and every term of the score is also added to P_raw[pixel][layer | surface], float64, a run of one (pixel, row)
+//                      summed in registers and flushed when it changes
 //   k_backward_norm    read-out: tally of pixel p / number of ids in [0, N) that map to p
 //   k_backward_norm_rows   the same rule for the rows of K_raw, rounded to float32
+//   k_backward_norm_profiles   the same rule for the rows of P_raw, its pairs {K, C} parted into two float32 arrays
 //
 // Philox blocks of history (seed, id), counter (id, block), consumed in sequence; block 0 is the direction, every later decision takes
 // the NEXT block when it comes up:
@@ -71,6 +75,13 @@ struct BwdSat {
     float pix_dx, pix_dy, Lx, Ly, inv_Lx, inv_Ly;
     int jch;
     float *start_out;                  // [n][3] (DEBUG)
+};
+
+// What only the profiles build receives (mi3d_set_view_profiles 1): the tally P_raw[npix][nrow][2] of pairs {K, C}, nrow = nz + 1 (the
+// layers from the surface up, then the surface)
+struct BwdProfiles {
+    double *raw;
+    int nrow;
 };
 
 // One thread per cell, in the order of DevThermal's CDF (k_thermal_power): voxels in file order, layers, surface cells.
@@ -138,23 +149,25 @@ __device__ inline int bwd_wrap(const int i, const float d, const int n) {
     return j < 0 ? 0 : (j >= n ? n - 1 : j);
 }
 
-// The histories, single-sourced for both entry points: mi3d_kernel_backward_body.inc is the body of either, with WGT a constant of the
-// entry point that includes it (and W the weights build's argument)
+// The histories, single-sourced for all entry points: mi3d_kernel_backward_body.inc is the body of each, with WGT, SAT and PRF constants
+// of the entry point that includes it (and W, S, P the arguments of the builds that read them)
 template <bool COUNT, bool DEBUG>
 __global__ void __launch_bounds__(256)
 k_backward(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, float *__restrict__ dir_out, double *__restrict__ score_out) {
-    constexpr bool WGT = false, SAT = false;
+    constexpr bool WGT = false, SAT = false, PRF = false;
     const BwdWeights W{};
     const BwdSat S{};
+    const BwdProfiles P{};
 #include "mi3d_kernel_backward_body.inc"
 }
 
 template <bool COUNT>
 __global__ void __launch_bounds__(256)
 k_backward_w(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, const BwdWeights W) {
-    constexpr bool WGT = true, DEBUG = false, SAT = false;
+    constexpr bool WGT = true, DEBUG = false, SAT = false, PRF = false;
     float *const dir_out = nullptr; double *const score_out = nullptr;
     const BwdSat S{};
+    const BwdProfiles P{};
 #include "mi3d_kernel_backward_body.inc"
 }
 
@@ -162,9 +175,32 @@ template <bool COUNT, bool DEBUG>
 __global__ void __launch_bounds__(256)
 k_backward_v(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, float *__restrict__ dir_out, double *__restrict__ score_out,
              const BwdSat S) {
-    constexpr bool WGT = false, SAT = true;
+    constexpr bool WGT = false, SAT = true, PRF = false;
+    const BwdWeights W{};
+    const BwdProfiles P{};
+#include "mi3d_kernel_backward_body.inc"
+}
+
+template <bool COUNT>
+__global__ void __launch_bounds__(256)
+k_backward_vp(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, const BwdSat S, const BwdProfiles P) {
+    constexpr bool WGT = false, DEBUG = false, SAT = true, PRF = true;
+    float *const dir_out = nullptr; double *const score_out = nullptr;
     const BwdWeights W{};
 #include "mi3d_kernel_backward_body.inc"
+}
+
+// The rule of k_backward_norm_rows for rows [e0, e0 + ne) of P_raw[npix * nrow][2]: row e belongs to pixel e / nrow.  (It stands behind
+// the histories so that the code of the kernels before it lies where it lay.)
+__global__ void __launch_bounds__(256)
+k_backward_norm_profiles(const double *__restrict__ raw, float *__restrict__ outK, float *__restrict__ outC, unsigned long long nphoton, unsigned npix,
+                         unsigned long long nrow, unsigned long long e0, unsigned long long ne) {
+    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < ne; i += stride) {
+        const unsigned long long cnt = bwd_pixel_ids(nphoton, npix, (e0 + i) / nrow);
+        outK[i] = cnt ? (float)(raw[2 * (e0 + i)] / (double)cnt) : 0.0f;
+        outC[i] = cnt ? (float)(raw[2 * (e0 + i) + 1] / (double)cnt) : 0.0f;
+    }
 }
 
 // The dynamic LDS of a launch of any build, in bytes: the host's statement of what the top of mi3d_kernel_backward_body.inc lays out, in

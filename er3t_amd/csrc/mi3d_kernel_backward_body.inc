@@ -1,7 +1,8 @@
 // mi3d_kernel_backward_body.inc — the histories of the backward route, the one body of k_backward<COUNT, DEBUG> and k_backward_w<COUNT>
-// and k_backward_v<COUNT, DEBUG> (mi3d_kernel_backward.hip includes it inside each).  What it expects in scope: COUNT, DEBUG, WGT, SAT
-// (compile-time constants), the arguments A, seed, id0, n, dir_out, score_out, W (BwdWeights: read where WGT holds, the weights build of
-// DESIGN.md §5.12) and S (BwdSat: read where SAT holds, the satellite-view build of DESIGN.md §5.14).
+// and k_backward_v<COUNT, DEBUG> and k_backward_vp<COUNT> (mi3d_kernel_backward.hip includes it inside each).  What it expects in scope:
+// COUNT, DEBUG, WGT, SAT, PRF (compile-time constants), the arguments A, seed, id0, n, dir_out, score_out, W (BwdWeights: read where WGT
+// holds, the weights build of DESIGN.md §5.12), S (BwdSat: read where SAT holds, the satellite-view build of DESIGN.md §5.14) and P
+// (BwdProfiles: read where PRF holds, the per-layer profiles of the satellite views, DESIGN.md §5.16).
     extern __shared__ double bwd_smem[];
     const int npix = A.nview * A.nxr * A.nyr;
     const bool tiles = SAT && S.jch > 0;                                     // the tile hand-out (mi3d_set_tuning "bwd_chunk" >= 1)
@@ -44,6 +45,23 @@
     unsigned jn = 0;                         // ... and how many of the chunk are left
     double acc = 0.0;                        // the sum of the scores of pixel accpix since it last changed
     int accpix = 0;
+    // PRF: the lane's run -- the sums of the terms of row run_e = pix nrow + k of P.raw since (pix, k) last changed.  A slant line takes
+    // several cell steps inside a layer and, under the tile hand-out, a lane keeps its pixel: a run ends in two atomics, not a step
+    int run_e = -1;                          // (npix nrow <= 2^30: the host refuses a tally of more than 2^31 elements)
+    double accK = 0.0, accC = 0.0;
+    auto prf_flush = [&]() {
+        if (run_e >= 0) {
+            if (accK != 0.0) atomicAdd(&P.raw[2 * (size_t)run_e], accK);
+            if (accC != 0.0) atomicAdd(&P.raw[2 * (size_t)run_e + 1], accC);
+        }
+        accK = 0.0; accC = 0.0;
+    };
+    // the terms a (of K) and c (of C, the very term the score takes) of row `row` of pixel p
+    auto prf_add = [&](const int p, const int row, const float a, const float c) {
+        const int e = p * P.nrow + row;
+        if (e != run_e) { prf_flush(); run_e = e; }
+        accK += (double)a; accC += (double)c;
+    };
 
     // the history's state
     bool have = false;
@@ -208,6 +226,10 @@
             float e;
             const float em = bwd_absorb(cell.x * ds, e);
             score += (double)(w * cell.y * em);
+            if (PRF) {
+                const float a = w * em;
+                if (a != 0.0f) prf_add(pix, k, a, w * cell.y * em);
+            }
             if (WGT) {
                 const float a = w * em;
                 if (a != 0.0f) {
@@ -269,6 +291,10 @@
                 const int ib = min((int)(((float)ix * A.dx + px) * A.sfc_sx), A.nxb - 1), jb = min((int)(((float)iy * A.dy + py) * A.sfc_sy), A.nyb - 1);
                 const float2 sc = A.cells[A.nvox + A.nz + (size_t)max(jb, 0) * A.nxb + max(ib, 0)];
                 score += (double)(w * sc.x * sc.y);
+                if (PRF) {
+                    const float a = w * sc.x;
+                    if (a != 0.0f) prf_add(pix, A.nz, a, w * sc.x * sc.y);
+                }
                 if (WGT) {
                     const float a = w * sc.x;
                     const int s = max(jb, 0) * A.nxb + max(ib, 0);
@@ -306,6 +332,7 @@
         }
     }
     if (tiles && !DEBUG && acc != 0.0) atomicAdd(&A.rad[accpix], acc);
+    if (PRF) prf_flush();
     if (lds_sums) {
         __syncthreads();
         for (int i = threadIdx.x; i < npix; i += blockDim.x) { const double s = sums[i]; if (s != 0.0) atomicAdd(&A.rad[i], s); }

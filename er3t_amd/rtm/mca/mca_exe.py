@@ -75,6 +75,14 @@ def _check_supported(nml, fdir=None, solver=None):
         if mwgt == 1.0 and not (nml.get('Rad_mbwd') is not None and float(np.ravel(nml.get('Rad_mbwd'))[0]) == 1.0):
             raise OSError('Error [mca_exe]: <Rad_mwgt=1> (emission weights) needs the backward route (<Rad_mbwd=1>): the weights are what backward '
                           'histories collect along their lines of sight.')
+    if nml.get('Rad_mvprf') is not None:
+        mvprf = float(np.ravel(nml.get('Rad_mvprf'))[0])
+        if mvprf not in (0.0, 1.0):
+            raise OSError('Error [mca_exe]: <Rad_mvprf=%g> is not supported (0: off, 1: per-layer weighting functions of satellite views; a key of '
+                          'this project).' % mvprf)
+        if mvprf == 1.0 and _flag(nml, 'Rad_mvbwd') != 1.0:
+            raise OSError('Error [mca_exe]: <Rad_mvprf=1> (view profiles) needs the backward route for satellite views (<Rad_mvbwd=1>): the profiles '
+                          'are what backward histories collect along their lines of sight.')
     if mtype == 0:
         raise OSError('Error [mca_exe]: <Src_mtype=0> (local) is not supported: only the solar (1), the solar+thermal (2) or the thermal (3) source.')
     if mtype not in (1, 2, 3):
@@ -156,6 +164,30 @@ def direct_in_run_field(scene):
 def weights_fname(fname_out):
     """the extra file of a job with <Rad_mwgt=1> beside its out.bin: raw '<f4' [npix][ncell] weights, then [ncell] Planck radiances"""
     return (fname_out[:-len('.out.bin')] if fname_out.endswith('.out.bin') else fname_out)+'.wgt.bin'
+
+
+def profiles_fname(fname_out):
+    """the extra file of a job with <Rad_mvprf=1> beside its out.bin: raw '<f4' [2][npix][nz+1], the weights, then the contributions"""
+    return (fname_out[:-len('.out.bin')] if fname_out.endswith('.out.bin') else fname_out)+'.prf.bin'
+
+
+def flatten_profiles(p):
+    """Mi3dSolver.view_profiles() -> float32 (2, npix, nz+1): the weights, then the contributions, pixels in tally order"""
+    nrow = p['weight'].shape[-1]
+    return np.stack([np.asarray(p['weight'], dtype=np.float32).reshape(-1, nrow), np.asarray(p['contribution'], dtype=np.float32).reshape(-1, nrow)])
+
+
+def write_profiles(fname, prf):
+    """<prf>: (2, npix, nz+1) -> the .prf.bin file"""
+    np.ascontiguousarray(prf, dtype='<f4').tofile(fname)
+
+
+def read_profiles(fname, npix, nrow):
+    """the .prf.bin file -> float32 (2, npix, nz+1)"""
+    raw = np.fromfile(fname, dtype='<f4')
+    if raw.size != 2*npix*nrow:
+        raise OSError('Error [read_profiles]: <%s> does not hold 2 x %d x %d values.' % (fname, npix, nrow))
+    return raw.reshape(2, npix, nrow).astype(np.float32)
 
 
 def flatten_weights(w):
@@ -278,13 +310,16 @@ class JobRunner:
             if getattr(scene, 'cam_weights', 0):       # (Rad_mwgt = 1: the emission weights' raw tally is all-reduced with the radiance)
                 nsfc = int(scene.jsfc.size) if scene.jsfc is not None else 1
                 wgt = torch.zeros(scene.nview*scene.nyr*scene.nxr*(scene.nx*scene.ny*scene.nz3+scene.nz+nsfc), dtype=torch.float64, device=dev)
-            self._tensors[slot] = (rad, flux, heat, wgt)
+            prf = None
+            if getattr(scene, 'view_profiles', 0):     # (Rad_mvprf = 1: the view profiles' raw tally likewise)
+                prf = torch.zeros(scene.nview*scene.nyr*scene.nxr*(scene.nz+1)*2, dtype=torch.float64, device=dev)
+            self._tensors[slot] = (rad, flux, heat, wgt, prf)
             if slot == 0:
                 stream = torch.cuda.current_stream(dev)
             else:
                 stream = self._streams[slot] = self._streams[slot] or torch.cuda.Stream(dev)
             sol.bind(rad_ptr=rad.data_ptr(), flux_ptr=flux.data_ptr(), stream=stream.cuda_stream, heat_ptr=None if heat is None else heat.data_ptr(),
-                     wgt_ptr=None if wgt is None else wgt.data_ptr())
+                     wgt_ptr=None if wgt is None else wgt.data_ptr(), prf_ptr=None if prf is None else prf.data_ptr())
         else:
             self._tensors[slot] = None
             sol.bind(None, None, None)
@@ -311,6 +346,8 @@ class JobRunner:
                 out['rdir'] = self.sol.camera_direct().astype(np.float32)
             if getattr(self.scene, 'cam_weights', 0):
                 out['wgt'] = self.sol.emission_weights(nphoton)
+            if getattr(self.scene, 'view_profiles', 0):
+                out['prf'] = self.sol.view_profiles(nphoton)
         if self.scene.target & TARGET_FLUX:
             out['flux'] = self.sol.flux(nphoton)
         if self.scene.target & TARGET_HEAT:
@@ -330,6 +367,8 @@ class JobRunner:
                 out['rdir'] = sol.camera_direct().astype(np.float32)
             if getattr(scene, 'cam_weights', 0):
                 out['wgt'] = self.job_weights(nphoton, slot=slot)
+            if getattr(scene, 'view_profiles', 0):
+                out['prf'] = self.job_profiles(nphoton, slot=slot)
         if scene.target & TARGET_FLUX:
             out['flux'] = sol.flux(int(nphoton))
         if scene.target & TARGET_HEAT:
@@ -482,6 +521,18 @@ class JobRunner:
             torch.cuda.synchronize(sol.device)
         return sol.emission_weights(int(nphoton))
 
+    def job_profiles(self, nphoton, slot=0):
+        """the view profiles (Rad_mvprf = 1) of the job launched last on <slot>, a job of <nphoton> ids in all: Mi3dSolver.view_profiles();
+        several ranks sum their raw tallies first"""
+        sol = self.sols[slot]
+        if self._tensors[slot] is not None and self._tensors[slot][4] is not None:
+            import torch
+            sol.sync()
+            torch.cuda.synchronize(sol.device)
+            allreduce_tallies(self._tensors[slot][4])
+            torch.cuda.synchronize(sol.device)
+        return sol.view_profiles(int(nphoton))
+
     def stats_begin(self):
         """start gathering run statistics for the loaded scene (its shape and target)"""
         self._run_tensors = None
@@ -570,6 +621,8 @@ class JobRunner:
                 with open(weights_fname(fname_out), 'wb') as f:
                     np.ascontiguousarray(k, dtype='<f4').tofile(f)
                     np.ascontiguousarray(b, dtype='<f4').tofile(f)
+            if 'prf' in result:                                  # Rad_mvprf = 1: likewise
+                write_profiles(profiles_fname(fname_out), flatten_profiles(result['prf']))
 
 
 _RUNNER = None

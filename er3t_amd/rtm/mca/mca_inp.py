@@ -101,7 +101,8 @@ _CATALOGUE = [
         ('Rad_nimg', 'cameras: periodic images of a sensor served within this many domain lengths of the nearest one, 0..8 (a key of this project)'),
         ('Rad_mbwd', 'cameras of a thermal job: 1 backward Monte Carlo, histories start at the sensor (a key of this project, written only when 1)'),
         ('Rad_mvbwd', 'satellite views of a thermal job: 1 backward Monte Carlo, histories start on the sensor plane (a key of this project, written only when 1)'),
-        ('Rad_mwgt', 'with Rad_mbwd = 1: 1 per-cell emission weights of every pixel, an extra output file (a key of this project, written only when 1)')]),
+        ('Rad_mwgt', 'with Rad_mbwd = 1: 1 per-cell emission weights of every pixel, an extra output file (a key of this project, written only when 1)'),
+        ('Rad_mvprf', 'with Rad_mvbwd = 1: 1 per-layer weighting function and contribution of every pixel, an extra output file (a key of this project, written only when 1)')]),
 ]
 
 

@@ -488,6 +488,70 @@ def read_emission_weights(mca_obj, abs_obj, mode='mean', squeeze=True):
     return data
 
 
+def _profile_fields(p, geom, squeeze):
+    """(2, npix, nz+1[, Nr]) in tally order -> (weight, contribution), each (Nxr, Nyr, Nview, Nz+1[, Nr]); squeeze drops pixel axes of length 1"""
+    nview, nyr, nxr, nrow = geom
+    p = np.asarray(p)
+    tail = p.shape[3:]
+    a = np.transpose(p.reshape((2, nview, nyr, nxr, nrow)+tail), (0, 3, 2, 1, 4)+tuple(range(5, 5+len(tail))))
+    if squeeze:
+        a = a.reshape([n for i, n in enumerate(a.shape) if not (1 <= i <= 3) or n > 1])
+    return np.ascontiguousarray(a[0]), np.ascontiguousarray(a[1])
+
+
+def read_view_profiles(mca_obj, abs_obj, mode='mean', squeeze=True):
+
+    """
+    The per-layer profiles of mcarats_ng(view_method='backward', view_profiles=True): for every pixel the vertical weighting function
+    view_weight[..., k] -- the share of the pixel's radiance that comes from layer k (k = 0 ... Nz-1 from the surface up; a layer of the 3-D
+    region: all its voxels) or from the surface (k = Nz) per unit Planck radiance there -- and view_contribution[..., k], that share itself,
+    both combined over g and runs with the factors of `rad` (sum_g weight[ig] x_g / 1000; mean and standard deviation over runs), so that
+    rad = view_contribution.sum(-1)  (jobs of mcarats_ng carry Src_flx = 1).  Axes: (Nxr, Nyr, Nview), those of length 1 dropped with
+    squeeze, then Nz+1; 'all' adds Nr.  keys: view_weight, view_contribution (+ *_std for 'mean') and view_layer_planck =
+    view_contribution / view_weight [W m-2 sr-1 um-1], the layer's effective Planck radiance as the pixel sees it, NaN where the weight is 0.
+    The file route reads the jobs' .prf.bin files one at a time; the fused route has reduced the same arrays while the jobs ran.
+    """
+
+    from er3t_amd.rtm.mca.mca_inp import mca_inp_read
+    from er3t_amd.rtm.mca.mca_exe import profiles_fname, read_profiles
+    mode = mode.lower()
+    if mode not in ('mean', 'all'):
+        raise OSError('Error [read_view_profiles]: Do not support <mode=%s>.' % mode)
+    g9 = _weights_geometry(mca_inp_read(mca_obj.fnames_inp[0][0]))
+    geom = (g9[0], g9[1], g9[2], g9[6]+1)
+    fused = getattr(mca_obj, 'fused', None)
+    if fused is not None and 'prf' in fused:
+        red = fused['prf']
+    else:
+        factors, _ = g_factors(mca_obj, abs_obj, 1)
+        red = weights_reducer(factors[0], keep_runs=(mode == 'all'))
+        for ir in range(mca_obj.Nrun):
+            for ig in range(mca_obj.Ng):
+                red.add(ig, read_profiles(profiles_fname(mca_obj.fnames_out[ir][ig]), geom[0]*geom[1]*geom[2], geom[3]))
+            red.end_run()
+    pixdims = [d for d, n in zip(['Nxr', 'Nyr', 'Nview'], (geom[2], geom[1], geom[0])) if n > 1 or not squeeze]+['Nz+1']
+    units = 'N/A (per nm: the g-sum of rad)'
+    data = {}
+    if mode == 'all':
+        if not red.runs:
+            raise OSError('Error [read_view_profiles]: the runs were not kept; use <mode=\'mean\'>.')
+        k, c = _profile_fields(np.stack(red.runs, axis=-1), geom, squeeze)
+        data['view_weight'] = {'data': k, 'name': 'Weighting function of the view', 'units': units, 'dims_info': pixdims+['Nr']}
+        data['view_contribution'] = {'data': c, 'name': 'Contribution to the radiance', 'units': 'W/m^2/nm/sr', 'dims_info': pixdims+['Nr']}
+    else:
+        k, c = _profile_fields(red.mean(), geom, squeeze)
+        ks, cs = _profile_fields(red.std(), geom, squeeze)
+        data['view_weight'] = {'data': k, 'name': 'Weighting function of the view (mean)', 'units': units, 'dims_info': pixdims}
+        data['view_weight_std'] = {'data': ks, 'name': 'Weighting function of the view (standard deviation)', 'units': units, 'dims_info': pixdims}
+        data['view_contribution'] = {'data': c, 'name': 'Contribution to the radiance (mean)', 'units': 'W/m^2/nm/sr', 'dims_info': pixdims}
+        data['view_contribution_std'] = {'data': cs, 'name': 'Contribution to the radiance (standard deviation)', 'units': 'W/m^2/nm/sr', 'dims_info': pixdims}
+    with np.errstate(divide='ignore', invalid='ignore'):
+        b = np.where(k != 0.0, c.astype(np.float64)/k.astype(np.float64), np.nan).astype(np.float32)
+    data['view_layer_planck'] = {'data': b, 'name': 'Effective Planck radiance of the layers as the pixels see them', 'units': 'W/m^2/um/sr',
+                                 'dims_info': list(data['view_weight']['dims_info'])}
+    return data
+
+
 class mca_out_ng:
 
     """
@@ -542,6 +606,8 @@ class mca_out_ng:
             raise OSError('Error [mca_out_ng]: Cannot read results of <target=%s>.' % self.mca.target)
         if getattr(self.mca, 'emission_weights', False):
             self.data.update(read_emission_weights(self.mca, self.abs, mode=self.mode, squeeze=self.squeeze))
+        if getattr(self.mca, 'view_profiles', False):
+            self.data.update(read_view_profiles(self.mca, self.abs, mode=self.mode, squeeze=self.squeeze))
 
     # ---- result cache ------------------------------------------------------------------------
     @staticmethod

@@ -119,6 +119,10 @@ class mcarats_ng:
         emission_weights [False]: with camera_method='backward': every job also tallies K[pixel][cell], the share of a pixel's reading that comes
                            from a voxel, a layer or a surface cell per unit Planck radiance there (Rad_mwgt=1, a key of this project written
                            only then: include/mi3d.h, mi3d_set_emission_weights); mca_out_ng returns data['emission_weight']
+        view_profiles [False]: with view_method='backward': every job also tallies, per pixel, the vertical weighting function K[pixel][layer]
+                           and the contribution C[pixel][layer] of every layer and of the surface (Rad_mvprf=1, a key of this project written
+                           only then: include/mi3d.h, mi3d_set_view_profiles); mca_out_ng returns data['view_weight'],
+                           data['view_contribution'] and data['view_layer_planck']
 
     Afterwards: input and output files under <fdir>; attributes Ng, Nrun, Nx, Ny, dx, dy, date, target, solver,
     photons (Nrun*Ng,), photons_per_set, fnames_inp[ir][ig], fnames_out[ir][ig], nml (list of Ng dictionaries).
@@ -132,7 +136,8 @@ class mcarats_ng:
                  sensor_azimuth_angle=0.0, sensor_altitude=705000.0, sensor_type='satellite', sensor_xpos=0.5,
                  sensor_ypos=0.5, solver='3d', photons=1e7, base_ratio=0.05, verbose=False, quiet=False,
                  abs_obj=None, keep_files=True, source='solar', wavelength=None, surface_temperature=None,
-                 heating_estimator='collision', camera_images=None, camera_method='forward', emission_weights=False, view_method='forward'):
+                 heating_estimator='collision', camera_images=None, camera_method='forward', emission_weights=False, view_method='forward',
+                 view_profiles=False):
 
         # one process per GPU (torch.distributed): rank 0 writes the job files, all ranks transport their share of every job
         from er3t_amd.dist import world_info, barrier
@@ -197,6 +202,10 @@ class mcarats_ng:
             if emission_weights:
                 raise OSError('Error [mcarats_ng]: <emission_weights=True> does not go with <view_method=\'backward\'>: the weights of an image times '
                               'the cells are not served.')
+        self.view_profiles = bool(view_profiles)
+        if self.view_profiles and self.view_method != 'backward':
+            raise OSError('Error [mcarats_ng]: <view_profiles=True> needs <view_method=\'backward\'>: the per-layer profiles are what backward '
+                          'histories collect along their lines of sight.')
         self.emission_weights = bool(emission_weights)
         if self.emission_weights and self.camera_method != 'backward':
             raise OSError('Error [mcarats_ng]: <emission_weights=True> needs <camera_method=\'backward\'>: the per-cell weights are what backward '
@@ -282,6 +291,8 @@ class mcarats_ng:
         #  carries the key only when <camera_images> is given, and stays what it was, byte for byte, without)
         if self.view_method == 'backward':             # (written only then: every other job file stays what it was, byte for byte)
             self._all({'Rad_mvbwd': 1})
+            if self.view_profiles:                     # (likewise)
+                self._all({'Rad_mvprf': 1})
         if self.camera_method == 'backward':           # (likewise)
             self._all({'Rad_mbwd': 1})
             if self.emission_weights:                  # (likewise)
@@ -445,7 +456,7 @@ class mcarats_ng:
         with arrays in the solver's layout, rad (nview, ny, nx), flux (3: direct-down, total-down, up; nz+1; ny; nx).
         """
 
-        from er3t_amd.rtm.mca.mca_exe import get_runner, wants_rdir, direct_in_run_field, flatten_weights
+        from er3t_amd.rtm.mca.mca_exe import get_runner, wants_rdir, direct_in_run_field, flatten_weights, flatten_profiles
         from er3t_amd.rtm.mca.mca_inp import mca_inp_read
         from er3t_amd.rtm.mca.mca_out import g_factors, weights_reducer
 
@@ -459,9 +470,10 @@ class mcarats_ng:
         # Two solver handles take turns (unless the per-job files are wanted: they are read back job by job): job i+1 is
         # launched before job i is folded into the run, so the tail of a launch -- as long as its longest history -- runs
         # beside the next launch.  The run field is still summed in job order (JobRunner.stats_add).
-        # (emission weights, Rad_mwgt = 1: every job's array is read back and reduced as the job ends -- one handle, like the per-job files)
-        nslot = runner.use_slots(1 if self.keep_files or self.emission_weights else 2)
-        wred = None
+        # (emission weights, Rad_mwgt = 1: every job's array is read back and reduced as the job ends -- one handle, like the per-job files;
+        #  view profiles, Rad_mvprf = 1: likewise)
+        nslot = runner.use_slots(1 if self.keep_files or self.emission_weights or self.view_profiles else 2)
+        wred = pred = None
         for ir in range(self.Nrun):
             waiting = None          # (photons, factors, slot) of the job launched last, not yet folded into the run
             for ig in range(self.Ng):
@@ -486,14 +498,21 @@ class mcarats_ng:
                     if wred is None:                   # (mca_out_ng's mode is not known yet: the runs are kept beside their mean)
                         wred = weights_reducer(factors[0], keep_runs=True)
                     wred.add(ig, *flatten_weights(wgt))
+                prf = runner.job_profiles(photons[ir, ig], slot=slot) if self.view_profiles else None
+                if prf is not None:
+                    if pred is None:
+                        pred = weights_reducer(factors[0], keep_runs=True)
+                    pred.add(ig, flatten_profiles(prf))
                 if self.keep_files:
                     result = {'rad': runner.sol.radiance(photons[ir, ig])} if self.target == 'radiance' else {'flux': runner.sol.flux(photons[ir, ig])}
                     if wants_rdir(scene):
                         result['rdir'] = runner.sol.camera_direct().astype(np.float32)
                     if wgt is not None:
                         result['wgt'] = wgt
+                    if prf is not None:
+                        result['prf'] = prf
                     runner.write(self.fnames_out[ir][ig], result)
-                del wgt
+                del wgt, prf
                 # (a job is folded into the run before its slot is launched on again: with one slot at once, with two after the
                 #  next job's launch)
                 if waiting is not None:
@@ -507,6 +526,8 @@ class mcarats_ng:
             runs.append(runner.stats_end_run(keep=True))
             if wred is not None:
                 wred.end_run()
+            if pred is not None:
+                pred.end_run()
             if rdir_runs is not None or direct_in_run_field(scene):
                 rdir_runs = (rdir_runs or []) + [rdir_run]
         self.fused = runner.stats_result()
@@ -517,6 +538,8 @@ class mcarats_ng:
         self.fused['toa'] = toa
         if wred is not None:
             self.fused['wgt'] = wred
+        if pred is not None:
+            self.fused['prf'] = pred
         self.kernel_ms = runner.kernel_ms - ms0
         self.photons_done = runner.photons_done - n0
         if not self.quiet and self.kernel_ms > 0.0:

@@ -120,6 +120,9 @@ class Scene:
                                           # Monte Carlo for the satellite views (rad_kind = 2) of a thermal job
     cam_weights: int = 0                  # Rad_mwgt (a key of this project; include/mi3d.h: mi3d_set_emission_weights): 1 the backward route also
                                           # tallies the per-cell emission weights K[pixel][cell] of every sensor; needs cam_method = 1
+    view_profiles: int = 0                # Rad_mvprf (a key of this project; include/mi3d.h: mi3d_set_view_profiles): 1 the backward route also
+                                          # tallies every pixel's weighting function and contribution per layer and for the surface;
+                                          # needs rad_kind = 2, view_method = 1
 
     # job
     target: int = TARGET_FLUX
@@ -197,6 +200,10 @@ class Scene:
             raise ValueError('Error [Scene]: <cam_weights=%s> (Rad_mwgt) must be 0 or 1.' % (self.cam_weights,))
         if self.cam_weights == 1 and not (self.rad_kind == 1 and self.cam_method == 1):
             raise ValueError('Error [Scene]: <cam_weights=1> (Rad_mwgt) needs the backward route (<rad_kind=1>, <cam_method=1>).')
+        if self.view_profiles not in (0, 1) or isinstance(self.view_profiles, float):
+            raise ValueError('Error [Scene]: <view_profiles=%s> (Rad_mvprf) must be 0 or 1.' % (self.view_profiles,))
+        if self.view_profiles == 1 and not (self.rad_kind == 2 and self.view_method == 1):
+            raise ValueError('Error [Scene]: <view_profiles=1> (Rad_mvprf) needs the backward route for satellite views (<rad_kind=2>, <view_method=1>).')
         if self.src_mtype in (2, 3):
             if self.src_mtype == 2:
                 if self.src_fsol is None or not (float(self.src_fsol) >= 0.0) or not np.isfinite(float(self.src_fsol)):
@@ -372,6 +379,12 @@ class Scene:
             raise OSError('Error [Scene]: <Rad_mwgt=%g> is not supported (0: off, 1: per-cell emission weights).' % mwgt)
         if mwgt == 1.0 and mbwd != 1.0:
             raise OSError('Error [Scene]: <Rad_mwgt=1> (emission weights) needs the backward route (<Rad_mbwd=1>).')
+        # (a key of this project: per-layer profiles of the backward route's satellite views)
+        mvprf = float(np.ravel(get('Rad_mvprf', 0))[0])
+        if mvprf not in (0.0, 1.0):
+            raise OSError('Error [Scene]: <Rad_mvprf=%g> is not supported (0: off, 1: per-layer weighting functions).' % mvprf)
+        if mvprf == 1.0 and mvbwd != 1.0:
+            raise OSError('Error [Scene]: <Rad_mvprf=1> (view profiles) needs the backward route for satellite views (<Rad_mvbwd=1>).')
         if mtarget == 2:
             nrad = int(get('Rad_nrad', 1))
             the  = np.resize(np.asarray(get('Rad_the', 180.0), dtype=np.float64), nrad)
@@ -401,7 +414,7 @@ class Scene:
             elif mrkind != 2:
                 raise OSError('Error [Scene]: <Rad_mrkind=%d> is not supported (1: camera, 2: satellite).' % mrkind)
             else:
-                kw.update(view_method=int(mvbwd))
+                kw.update(view_method=int(mvbwd), view_profiles=int(mvprf))
         elif mtarget == 1:
             mhrt = int(get('Flx_mhrt', 0) or 0)
             if mhrt == 2 and mtype not in (2, 3):

@@ -53,6 +53,9 @@ _SIGNATURES = [
     ('mi3d_bind_weights_buffer', C.c_int   , [C.c_void_p, C.c_void_p]),
     ('mi3d_get_emission_weights', C.c_int  , [C.c_void_p, _u64, _fp, _fp]),
     ('mi3d_debug_weights_staged', C.c_int  , [C.c_void_p]),
+    ('mi3d_set_view_profiles'  , C.c_int   , [C.c_void_p, C.c_int]),
+    ('mi3d_bind_view_profiles_buffer', C.c_int, [C.c_void_p, C.c_void_p]),
+    ('mi3d_get_view_profiles'  , C.c_int   , [C.c_void_p, _u64, _fp, _fp]),
     ('mi3d_debug_backward_chunk', C.c_int  , [C.c_void_p]),
     ('mi3d_set_options'        , C.c_int   , [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int]),
     ('mi3d_set_le_roulette'    , C.c_int   , [C.c_void_p, C.c_double]),
@@ -136,6 +139,7 @@ def _stale(name, path):
     def missing(*args):
         msg = 'Error [Mi3dSolver]: library is stale: <%s> missing from <%s>.' % (name, path)
         raise OSError(msg)
+    missing.stale = True
     return missing
 
 
@@ -302,6 +306,12 @@ class Mi3dSolver:
         K[pixel][cell], the share of a pixel's reading that comes from a cell per unit Planck radiance there"""
         self._chk(self.lib.mi3d_set_emission_weights(self._h, 1 if on else 0))
 
+    def set_view_profiles(self, on=True):
+        """per-layer profiles of the backward route's satellite views (include/mi3d.h: mi3d_set_view_profiles): on, every run also tallies
+        the weighting function K[pixel][layer | surface] and the contribution C[pixel][layer | surface] of every pixel.  True / False or
+        the value itself (anything but 0 and 1 is refused by the library)"""
+        self._chk(self.lib.mi3d_set_view_profiles(self._h, int(on)))
+
     def set_options(self, target=TARGET_FLUX, solver=0, wmin=0.2, wfac=1.0, column_le=True):
         self._chk(self.lib.mi3d_set_options(self._h, int(target), int(solver), float(wmin), float(wfac), 1 if column_le else 0))
 
@@ -342,6 +352,9 @@ class Mi3dSolver:
         self.set_camera_method(int(getattr(s, 'cam_method', 0)))
         self.set_view_method(int(getattr(s, 'view_method', 0)))
         self.set_emission_weights(int(getattr(s, 'cam_weights', 0)))
+        # (an older build in a kernel A/B experiment, MI3D_LIBRARY, has no such switch: it is off there, and asking for it fails)
+        if int(getattr(s, 'view_profiles', 0)) or not getattr(self.lib.mi3d_set_view_profiles, 'stale', False):
+            self.set_view_profiles(int(getattr(s, 'view_profiles', 0)))
         self.set_options(s.target, s.solver, s.wmin, s.wfac, column_le)
         self.set_heating_estimator(int(getattr(s, 'heat_estimator', 0)))
         self.set_le_roulette(getattr(s, 'le_tau1', 0.0))
@@ -357,10 +370,12 @@ class Mi3dSolver:
         self.prepare()
 
     # ---- execution ---------------------------------------------------------------------------
-    def bind(self, rad_ptr=None, flux_ptr=None, stream=None, heat_ptr=None, wgt_ptr=None):
+    def bind(self, rad_ptr=None, flux_ptr=None, stream=None, heat_ptr=None, wgt_ptr=None, prf_ptr=None):
         self._chk(self.lib.mi3d_bind_device_buffers(self._h, C.c_void_p(rad_ptr or 0), C.c_void_p(flux_ptr or 0), C.c_void_p(stream or 0)))
         self._chk(self.lib.mi3d_bind_heating_buffer(self._h, C.c_void_p(heat_ptr or 0)))
         self._chk(self.lib.mi3d_bind_weights_buffer(self._h, C.c_void_p(wgt_ptr or 0)))
+        if prf_ptr or not getattr(self.lib.mi3d_bind_view_profiles_buffer, 'stale', False):      # (likewise, load_scene)
+            self._chk(self.lib.mi3d_bind_view_profiles_buffer(self._h, C.c_void_p(prf_ptr or 0)))
 
     def prepare(self):
         self._chk(self.lib.mi3d_prepare(self._h))
@@ -421,6 +436,17 @@ class Mi3dSolver:
         sshape = s.jsfc.shape if s.jsfc is not None else (1, 1)
         return {'voxels': k[:, :nvox].reshape(npix, s.nz3, s.ny, s.nx), 'layers': k[:, nvox:nvox+nz], 'surface': k[:, nvox+nz:].reshape((npix,)+tuple(sshape)),
                 'planck': {'voxels': b[:nvox].reshape(s.nz3, s.ny, s.nx), 'layers': b[nvox:nvox+nz], 'surface': b[nvox+nz:].reshape(sshape)}}
+
+    def view_profiles(self, nphoton_total):
+        """the per-layer profiles of the backward route's satellite views (include/mi3d.h: mi3d_get_view_profiles) for a job of
+        nphoton_total ids: 'weight' and 'contribution', float32 (nview, nyr, nxr, nz + 1) -- rows 0 ... nz - 1 the layers from the surface
+        up, row nz the surface.  The radiance of pixel p is Src_flx contribution[p].sum()"""
+        s = self.scene
+        shape = (s.nview, s.nyr, s.nxr, s.nz+1)
+        k = np.zeros(shape, dtype=np.float32)
+        c = np.zeros(shape, dtype=np.float32)
+        self._chk(self.lib.mi3d_get_view_profiles(self._h, int(nphoton_total), _ptr(k), _ptr(c)))
+        return {'weight': k, 'contribution': c}
 
     def flux(self, nphoton_total):
         out = np.zeros(self._shape_flux, dtype=np.float32)

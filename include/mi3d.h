@@ -375,6 +375,36 @@ int mi3d_bind_weights_buffer(mi3d_solver *h, void *wgt_sum);
 int mi3d_get_emission_weights(mi3d_solver *h, uint64_t nphoton_total, float *weights, float *planck);
 int mi3d_debug_weights_staged(mi3d_solver *h);
 
+/* Per-layer profiles of the backward route's satellite views: the vertical weighting function of every pixel (the
+ * project's namelist key Rad_mvprf = 1).  An image times the cells is out of scope (mi3d_set_view_method); summed over every layer's
+ * voxels and over the surface's cells it is an image times nrow = nz + 1 rows: rows 0 ... nz - 1 the layers from the surface up (a layer
+ * inside the 3-D region: the sum over its voxels), row nz the surface.  Two profiles per pixel:
+ *     weight        K[p][k] = (1 / N_p) sum over p's histories and their segments in layer k of  w (1 - exp(-ka l))   (surface: w eps)
+ *     contribution  C[p][k] = (1 / N_p) sum of the very float32 terms the histories add to their score there: w B ka-term (surface: w eps B)
+ * Neither carries Src_flx.  A history's path and weight depend on no temperature, so  R_p = Src_flx sum_k C[p][k]  for any temperature
+ * field -- an exact partition of the radiance the route returns --, C / K is the layer's effective Planck radiance as pixel p sees it, and
+ * Src_flx K[p][k] dB/dT is the Jacobian of R_p to the temperature of layer k where that temperature is horizontally uniform.
+ *   Switch     mi3d_set_view_profiles: 0 (default) nothing of this runs -- kernels, names and results are those of the route without it,
+ *              and the library's tally is freed; 1: mi3d_run serves what mi3d_set_view_method 1 serves, every refusal of that route
+ *              included, and tallies the profiles beside the radiance.  With 1 and the route not selected (mi3d_set_view_method 0,
+ *              cameras set, mi3d_set_camera_method 1 or mi3d_set_emission_weights 1) mi3d_run returns MI3D_EUNSUP and names this
+ *              switch.  Anything but 0 or 1 is MI3D_EINVAL.  mi3d_last_kernel: "k_backward<C,V,P> [thermal]".
+ *              mi3d_debug_backward_views ignores the switch.
+ *   Tally      P_raw[npix][nrow][2], float64 on the device, the pair {K, C} per row, npix = nview nyr nxr in the layout of the radiance
+ *              tally.  Every cell step with a = w (1 - exp(-ka l)) != 0 (the float32 product) adds a and its score term to the row of
+ *              its layer, the surface w eps and w eps B to row nz.  A lane sums the terms of one (pixel, row) in registers and adds
+ *              them when either changes.  The score, the Philox sequence, the hand-out and the image tally are those of the route: the
+ *              radiance of a run is that of the run without the switch up to the order of its float64 sums.  Raw tallies add over id
+ *              ranges and ranks; mi3d_reset zeroes them.  mi3d_bind_view_profiles_buffer: a caller-owned device buffer
+ *              [npix][nz + 1][2] float64 for an all-reduce (NULL: the library's own).
+ *   Read-out   mi3d_get_view_profiles: row block p divided, on the device, by the number of ids in [0, nphoton_total) that map to p (the
+ *              rule of mi3d_get_radiance on this route; a pixel without a history reads 0), rounded to float32 once.  weight and
+ *              contribution are [npix][nz + 1]; either may be NULL.  MI3D_ESTATE while the switch is off or nothing has run.
+ *   Size       npix nrow 2 above 2^31 elements: MI3D_EUNSUP with the numbers; all index arithmetic is 64-bit. */
+int mi3d_set_view_profiles(mi3d_solver *h, int on);
+int mi3d_bind_view_profiles_buffer(mi3d_solver *h, void *raw);
+int mi3d_get_view_profiles(mi3d_solver *h, uint64_t nphoton_total, float *weight, float *contribution);
+
 /* Job options = 1st/2nd CLI arguments and keys Wld_mtarget, Flx_mflx, Pho_wmin
  * (er3t/rtm/mca/mcarats.py:267-287,450-454; er3t/rtm/mca/mca_inp.py:196-198).
  *   target   MI3D_TARGET_FLUX | MI3D_TARGET_RADIANCE (bit-or of both is allowed); MI3D_TARGET_FLUX | MI3D_TARGET_HEAT is the
@@ -471,7 +501,7 @@ int mi3d_sync(mi3d_solver *h);
  * analytic phase functions (er3t's default scene), 1: a second 3-D constituent, 2: the general mixture (several 1-D constituents,
  * tabulated phase functions staged in LDS) --, "k_transport<COUNT,MARCH,FLUX,P3D>": the general kernel (flux together with radiance,
  * more than two 3-D constituents, tables too large for the LDS, kernel choice 1); "k_backward<COUNT> [thermal]": the backward route of
- * mi3d_set_camera_method 1 ("k_backward<COUNT,V> [thermal]": of mi3d_set_view_method 1), whatever mi3d_set_kernel says -- "batch_log2" is the one tuning knob it reads (ids per launch; a launch is
+ * mi3d_set_camera_method 1 ("k_backward<COUNT,V> [thermal]": of mi3d_set_view_method 1; "k_backward<COUNT,V,P> [thermal]": with mi3d_set_view_profiles 1), whatever mi3d_set_kernel says -- "batch_log2" is the one tuning knob it reads (ids per launch; a launch is
  * min(ids / 256, what is resident at once: 5 per CU, 4 in the counting build) workgroups of 256 lanes, every lane walks its ids with a fixed stride); "" before the first launch).  For logs and
  * measurements (bench.py, profiles/): results do not depend on it. */
 const char *mi3d_last_kernel(mi3d_solver *h);

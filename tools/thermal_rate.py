@@ -32,6 +32,10 @@ disjoint id ranges; histories (photons) per second, kernel time, the chunk the l
 the batches (mean and largest over the pixels) and the figure of merit 1 / (se^2 t), se the mean relative standard error of a pixel.
 --photons: photons per forward batch; --per-pixel: histories per pixel and backward batch (32: every chunk of the list is a launch of its own).
     python tools/thermal_rate.py --legs sat --photons 2e6 --per-pixel 32
+Leg 'prf' (DESIGN.md 5.16): the image of the 'sat' leg by backward Monte Carlo under the default hand-out with the per-layer view profiles
+(view_profiles) off, then on, at 8 and at 32 histories per pixel and launch: 16 batches each over disjoint id ranges, three times; histories
+per second and kernel time.  Under MI3D_LIBRARY (an older build of the library) the rows with the profiles off alone.
+    python tools/thermal_rate.py --legs prf
 """
 
 import argparse
@@ -133,6 +137,44 @@ def sat_rows(sol, name, s, n_fwd, per_pixel, chunks=(0, 4, 8, 16, 32, -1), nb=16
     return rows
 
 
+def profiles_rows(sol, name, s, per_pixels=(8, 32), nb=16, reps=3):
+    """the 'prf' leg: the image of the 'sat' leg by the backward route under the default hand-out with the view profiles off,
+    then on, at every number of histories per pixel and launch of `per_pixels`; nb batches over disjoint id ranges, `reps` times each.  An
+    older build of the library (MI3D_LIBRARY) gives the 'off' rows alone"""
+    s = dataclasses.replace(s, view_the=[180.0, 135.0], view_phi=[0.0, 0.0], view_zloc=[1.0e6, 1.0e6], nxr=s.nx, nyr=s.ny, view_method=1)
+    npix = 2*s.nx*s.ny
+    rows = []
+    have = not getattr(sol.lib.mi3d_set_view_profiles, 'stale', False)
+    try:
+        for pp in per_pixels:
+            n = pp*npix
+            for on in ((0, 1) if have else (0,)):
+                sol.load_scene(dataclasses.replace(s, view_profiles=on))
+                sol.reset(); sol.run(n, seed=1); sol.sync()                  # warm-up
+                for rep in range(reps):
+                    ms_all, mean = 0.0, 0.0
+                    for b in range(nb):
+                        sol.reset()
+                        sol.run(n, seed=2, offset=b*n)
+                        sol.sync()
+                        ms_all += sol.timing()[0]
+                        mean += float(sol.radiance(n).mean())/nb
+                    t = ms_all*1e-3
+                    row = dict(scene=name, target='sat_profiles' if on else 'sat_backward', kernel=sol.kernel_name(), per_pixel=pp, histories_per_batch=n,
+                               batches=nb, rep=rep, histories_per_s=float(nb*n/t), kernel_s=float(t), image_mean=mean,
+                               chunk_launched=sol.lib.mi3d_debug_backward_chunk(sol._h), capped=sol.debug_backward_views(2, 0, 0)[3])
+                    if on:
+                        c = sol.view_profiles(n)['contribution'].astype(np.float64).sum(axis=-1)
+                        row.update(sum_contribution_mean=float(c.mean()))
+                    rows.append(row)
+                    print(json.dumps(row), flush=True)
+    finally:
+        if have:
+            sol.set_view_profiles(False)
+        sol.set_view_method('forward')
+    return rows
+
+
 def weights_rows(sol, name, s, n, nb=16):
     """the 'wgt' leg: the sensors of scene s by the backward route with the emission weights off, then on, nb batches each
     over the same id ranges; the counting build, once, for the absorbing cell steps of a history (one float64 atomic each with the switch on)"""
@@ -203,6 +245,10 @@ def main():
             if target == 'sat':
                 sol.set_kernel(general=False)
                 rows += sat_rows(sol, name, thermal(les_scene(target='radiance', **kw), lev), n, a.per_pixel)
+                continue
+            if target == 'prf':
+                sol.set_kernel(general=False)
+                rows += profiles_rows(sol, name, thermal(les_scene(target='radiance', **kw), lev))
                 continue
             if target == 'wgt':
                 sol.set_kernel(general=False)
