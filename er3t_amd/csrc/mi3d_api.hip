@@ -81,8 +81,9 @@ struct DevBuf {
 constexpr double kWgtMaxElems = 2147483648.0;   // elements of the emission weights' tally npix x ncell served (mi3d_set_emission_weights)
 constexpr double kPrfMaxElems = 2147483648.0;   // elements of the view profiles' tally npix x (nz + 1) x 2 served (mi3d_set_view_profiles)
 
-// The four builds of the backward route (mi3d_kernel_backward.hip): k_backward, k_backward_w, k_backward_v, k_backward_vp ...
-enum class BwdRoute { Camera = 0, Weights = 1, Views = 2, Profiles = 3 };
+// The six builds of the backward route (mi3d_kernel_backward.hip): k_backward, k_backward_w, k_backward_v, k_backward_vp, k_backward_s,
+// k_backward_vs ...
+enum class BwdRoute { Camera = 0, Weights = 1, Views = 2, Profiles = 3, CameraErrors = 4, ViewsErrors = 5 };
 // ... and what the runtime said of one of them: workgroups resident per CU for `lds` bytes of dynamic LDS (0: not asked yet)
 struct BwdCap { int blocks = 0, counting = -1; size_t lds = 0; };
 
@@ -139,7 +140,7 @@ struct mi3d_solver {
     int bwd_chunk = -1;
     int bwd_chunk_last = 0;
     DevBuf<float> d_bwd_start;
-    BwdCap bwd_cap[4];               // per BwdRoute: the resident workgroups per CU of the build launched last (backward_resident)
+    BwdCap bwd_cap[6];               // per BwdRoute: the resident workgroups per CU of the build launched last (backward_resident)
     bool sat_backward() const { return view_method == 1 && cam_method == 0 && rad_kind == 2; }           // is the job sent to k_backward_v?
     bool backward() const {                                                                               // does the read-out divide by the pixels' own counts?
         return src_mtype == 3 && nview > 0 && ((cam_method == 1 && rad_kind == 1) || sat_backward());
@@ -164,6 +165,16 @@ struct mi3d_solver {
     size_t prf_n = 0;
     bool prf_ran = false;
     double *prf_ptr() { return prf_ext ? prf_ext : d_prf_own.p; }
+    // per-pixel standard errors of the backward route (mi3d_set_pixel_errors 1): rad2[npix], the sums of the squared
+    // scores; the library's own buffer (err_n elements, zeroed when it is made; 0: to be made by the next run) or the caller's
+    // (mi3d_bind_pixel_errors_buffer); err_ran: a run has tallied them since the last reset
+    int pixel_errors = 0;
+    DevBuf<double> d_err_own;
+    DevBuf<float> d_err_out;         // the read-out's staging buffer
+    double *err_ext = nullptr;
+    size_t err_n = 0;
+    bool err_ran = false;
+    double *err_ptr() { return err_ext ? err_ext : d_err_own.p; }
     double prf_elems() const { return (double)nview * nxr * nyr * ((double)nz + 1.0) * 2.0; }
     size_t wgt_ncell() const { return (size_t)nx * ny * nz3 + (size_t)nz + (sfc2d_host.empty() ? (size_t)1 : (size_t)nxb * nyb); }
     int nview = 0, nxr = 1, nyr = 1;
@@ -962,6 +973,7 @@ int mi3d_destroy(mi3d_solver *h) {
     h->d_th_tlev.release(); h->d_th_tmpa.release(); h->d_th_tmps.release(); h->d_th_cdf.release(); h->d_th_bsum.release(); h->d_th.release();
     h->d_wgt_own.release(); h->d_wgt_out.release();
     h->d_prf_own.release(); h->d_prf_out.release();
+    h->d_err_own.release(); h->d_err_out.release();
     h->d_bwd_cells.release(); h->d_bwd_capped.release(); h->d_bwd_norm.release(); h->d_bwd_score.release(); h->d_bwd_dir.release(); h->d_bwd_start.release();
     h->d_views.release(); h->d_cold.release(); h->d_tabrange.release(); h->d_bt1d.release(); h->d_dz.release(); h->d_bmin.release(); h->d_bmax.release();
     delete h;
@@ -1243,6 +1255,28 @@ int mi3d_bind_view_profiles_buffer(mi3d_solver *h, void *raw) {
     return MI3D_OK;
 }
 
+int mi3d_set_pixel_errors(mi3d_solver *h, int on) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (on != 0 && on != 1) return fail(MI3D_EINVAL, "pixel errors %d (0: off, 1: per-pixel standard errors of the backward route)", on);
+    if (on == h->pixel_errors) return MI3D_OK;
+    HIPCHK(sync_main(h));   // (as every call that changes what the kernels work on)
+    h->pixel_errors = on;
+    h->err_ran = false;
+    if (!on) { h->d_err_own.release(); h->d_err_out.release(); h->err_n = 0; }
+    return MI3D_OK;
+}
+
+int mi3d_bind_pixel_errors_buffer(mi3d_solver *h, void *rad2_sum) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if ((double *)rad2_sum == h->err_ext) return MI3D_OK;
+    HIPCHK(sync_main(h));
+    h->err_ext = (double *)rad2_sum;
+    if (!rad2_sum) h->err_n = 0;   // (the library's own buffer is made anew, and zeroed, by the next run)
+    return MI3D_OK;
+}
+
 int mi3d_set_camera_map(mi3d_solver *h, int mpmap, int mrproj) {
     int rc = check_handle(h);
     if (rc) return rc;
@@ -1441,6 +1475,7 @@ int mi3d_prepare(mi3d_solver *h) {
         }
         h->wgt_n = 0;   // (the emission weights' own buffer: made and zeroed by the next run that tallies them, run_backward)
         h->prf_n = 0; h->prf_ran = false;   // (likewise the view profiles')
+        h->err_n = 0; h->err_ran = false;   // (and the pixel errors')
         h->dirty_tally = false;
     }
     if (h->thermal() && h->dirty_thermal) {
@@ -1481,6 +1516,11 @@ int mi3d_reset(mi3d_solver *h) {
         if (h->prf_ext) { if (h->sat_backward() && ne <= kPrfMaxElems) HIPCHK(hipMemsetAsync(h->prf_ext, 0, (size_t)ne * sizeof(double), h->stream)); }
         else if (h->prf_n) HIPCHK(hipMemsetAsync(h->d_prf_own.p, 0, h->prf_n * sizeof(double), h->stream));
     }
+    if (h->pixel_errors) {
+        if (h->err_ext) { if (h->backward()) HIPCHK(hipMemsetAsync(h->err_ext, 0, (size_t)h->nview * h->nxr * h->nyr * sizeof(double), h->stream)); }
+        else if (h->err_n) HIPCHK(hipMemsetAsync(h->d_err_own.p, 0, h->err_n * sizeof(double), h->stream));
+    }
+    h->err_ran = false;
     // (the accumulation image is folded and zeroed at the end of a successful mi3d_run; a run that failed half way -- an event
     //  list ran full, a launch failed -- leaves its partial tallies there)
     if (h->d_rad_acc.p) HIPCHK(hipMemsetAsync(h->d_rad_acc.p, 0, h->d_rad_acc.cap * sizeof(tally_t), h->stream));
@@ -1944,7 +1984,9 @@ static void name_route(mi3d_solver *h, const RunPlan &plan, bool lists, uint64_t
     const int c = plan.build.counting ? 1 : 0, p3d = plan.build.p3d ? 1 : 0;
     char nm[96];
     const bool hpath = plan.build.hpath;
-    if (plan.loop == Loop::Backward && h->sat_backward() && h->view_profiles) snprintf(nm, sizeof(nm), "k_backward<%d,V,P> [thermal]", c);
+    if (plan.loop == Loop::Backward && h->sat_backward() && h->pixel_errors) snprintf(nm, sizeof(nm), "k_backward<%d,V,S> [thermal]", c);
+    else if (plan.loop == Loop::Backward && h->pixel_errors) snprintf(nm, sizeof(nm), "k_backward<%d,S> [thermal]", c);
+    else if (plan.loop == Loop::Backward && h->sat_backward() && h->view_profiles) snprintf(nm, sizeof(nm), "k_backward<%d,V,P> [thermal]", c);
     else if (plan.loop == Loop::Backward && h->sat_backward()) snprintf(nm, sizeof(nm), "k_backward<%d,V> [thermal]", c);
     else if (plan.loop == Loop::Backward && h->emis_weights) snprintf(nm, sizeof(nm), "k_backward<%d,W> [thermal]", c);
     else if (plan.loop == Loop::Backward) snprintf(nm, sizeof(nm), "k_backward<%d> [thermal]", c);
@@ -2462,7 +2504,7 @@ static void fill_backward_views(const mi3d_solver *h, BwdSat &S, float *start_ou
 }
 
 // The one place that names the builds of the histories: the kernel of (route, counting, debug), as the runtime takes it for a launch and
-// for an occupancy query.  The weights and profiles builds have no debug form (nullptr); the debug forms do not count
+// for an occupancy query.  The weights, profiles and errors builds have no debug form (nullptr); the debug forms do not count
 static const void *backward_build(BwdRoute route, bool counting, bool debug) {
     switch (route) {
     case BwdRoute::Camera:
@@ -2477,23 +2519,32 @@ static const void *backward_build(BwdRoute route, bool counting, bool debug) {
     case BwdRoute::Profiles:
         if (debug) return nullptr;
         return counting ? (const void *)k_backward_vp<true> : (const void *)k_backward_vp<false>;
+    case BwdRoute::CameraErrors:
+        if (debug) return nullptr;
+        return counting ? (const void *)k_backward_s<true> : (const void *)k_backward_s<false>;
+    case BwdRoute::ViewsErrors:
+        if (debug) return nullptr;
+        return counting ? (const void *)k_backward_vs<true> : (const void *)k_backward_vs<false>;
     }
     return nullptr;
 }
 
 // One launch.  The kernel arguments in the order of the entry points: (A, seed, id0, n), then (dir_out, score_out) for the cameras,
-// (W) for the weights build, (dir_out, score_out, S) for the views, (S, P) for the views' profiles build
+// (W) for the weights build, (dir_out, score_out, S) for the views, (S, P) for the views' profiles build, (E) and (S, E) for the cameras'
+// and the views' errors builds
 static hipError_t backward_launch(BwdRoute route, bool counting, bool debug, unsigned grid, size_t lds, hipStream_t stream, DevBackward A, uint64_t seed,
-                                  uint64_t id0, uint64_t n, float *dir_out, double *score_out, BwdWeights W, BwdSat S, BwdProfiles P) {
+                                  uint64_t id0, uint64_t n, float *dir_out, double *score_out, BwdWeights W, BwdSat S, BwdProfiles P,
+                                  BwdErrors E = BwdErrors{}) {
     const void *kernel = backward_build(route, counting, debug);
     if (!kernel) return hipErrorInvalidValue;
     void *cam[] = {&A, &seed, &id0, &n, &dir_out, &score_out}, *wgt[] = {&A, &seed, &id0, &n, &W}, *sat[] = {&A, &seed, &id0, &n, &dir_out, &score_out, &S},
-         *prf[] = {&A, &seed, &id0, &n, &S, &P};
+         *prf[] = {&A, &seed, &id0, &n, &S, &P}, *cerr[] = {&A, &seed, &id0, &n, &E}, *verr[] = {&A, &seed, &id0, &n, &S, &E};
     return hipLaunchKernel(kernel, dim3(grid), dim3(256),
-                           route == BwdRoute::Camera ? cam : route == BwdRoute::Weights ? wgt : route == BwdRoute::Views ? sat : prf, lds, stream);
+                           route == BwdRoute::Camera ? cam : route == BwdRoute::Weights ? wgt : route == BwdRoute::Views ? sat
+                           : route == BwdRoute::Profiles ? prf : route == BwdRoute::CameraErrors ? cerr : verr, lds, stream);
 }
 
-// Workgroups of the build that are resident on the device at once.  The weights, view and profiles builds ask the runtime, once per (route, LDS
+// Workgroups of the build that are resident on the device at once.  The weights, view, profiles and errors builds ask the runtime, once per (route, LDS
 // bytes, counting).  The camera build takes five waves per SIMD, four in the counting build (the register report in DESIGN.md §5.11),
 // the grid it has always had: asking the runtime instead could change that grid where LDS limits residency, a change of behaviour
 // that belongs to a pull request of its own.
@@ -2506,6 +2557,8 @@ static int backward_resident(mi3d_solver *h, BwdRoute route, size_t lds, uint64_
         if (eo != hipSuccess || nb < 1) {
             if (route == BwdRoute::Weights) return fail(MI3D_EDEVICE, "emission weights: no workgroup of the weights build fits a CU with %zu bytes of LDS", lds);
             if (route == BwdRoute::Profiles) return fail(MI3D_EDEVICE, "view profiles: no workgroup of the profiles build fits a CU with %zu bytes of LDS", lds);
+            if (route == BwdRoute::CameraErrors || route == BwdRoute::ViewsErrors)
+                return fail(MI3D_EDEVICE, "pixel errors: no workgroup of the errors build fits a CU with %zu bytes of LDS", lds);
             return fail(MI3D_EDEVICE, "backward Monte Carlo for satellite views: no workgroup fits a CU with %zu bytes of LDS", lds);
         }
         c.blocks = nb; c.lds = lds; c.counting = h->counting;
@@ -2517,7 +2570,9 @@ static int backward_resident(mi3d_solver *h, BwdRoute route, size_t lds, uint64_
 static int run_backward(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_offset) {
     const bool sat = h->sat_backward(), wgt = h->emis_weights != 0;
     const bool prf = sat && h->view_profiles != 0;
-    const BwdRoute route = prf ? BwdRoute::Profiles : sat ? BwdRoute::Views : wgt ? BwdRoute::Weights : BwdRoute::Camera;
+    const bool var = h->pixel_errors != 0;     // (never with wgt or prf: mi3d_run refuses)
+    const BwdRoute route = prf ? BwdRoute::Profiles : sat ? (var ? BwdRoute::ViewsErrors : BwdRoute::Views) : wgt ? BwdRoute::Weights
+                           : var ? BwdRoute::CameraErrors : BwdRoute::Camera;
     int rc = backward_unsupported(h, sat);
     if (rc) return rc;
     if (h->nview == 0) return fail(MI3D_ESTATE, "radiance requested but no view is set (%s)", sat ? "mi3d_set_views" : "mi3d_set_cameras");
@@ -2559,6 +2614,17 @@ static int run_backward(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_
         P.raw = h->prf_ptr();
         h->prf_ran = true;
     }
+    BwdErrors E{};
+    if (var) {
+        // the errors builds: the tally of the squared scores, made and zeroed here when it is the library's own
+        if (!h->err_ext && h->err_n != (size_t)npix) {
+            if ((rc = h->d_err_own.alloc((size_t)npix))) return rc;
+            HIPCHK(hipMemsetAsync(h->d_err_own.p, 0, (size_t)npix * sizeof(double), h->stream));
+            h->err_n = (size_t)npix;
+        }
+        E.rad2 = h->err_ptr();
+        h->err_ran = true;
+    }
     BwdSat S{};
     uint64_t ntile = 0;
     if (sat) {
@@ -2567,12 +2633,12 @@ static int run_backward(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_
     }
     // the launch's LDS (backward_lds).  The weights build stages its layer and surface weights there
     // where the image's sums are and the whole stays within kBwdWgtLds
-    const bool lds_sums = backward_lds_sums(npix, false, S.jch > 0);
+    const bool lds_sums = backward_lds_sums(npix, false, S.jch > 0, var);
     if (wgt) {
         W.stage = h->wgt_stage != 0 && lds_sums && backward_lds(npix, h->nz, h->nview, W.nls, lds_sums, true, false) <= kBwdWgtLds ? 1 : 0;
         h->wgt_staged_last = W.stage;
     }
-    const size_t lds = backward_lds(npix, h->nz, h->nview, W.nls, lds_sums, W.stage != 0, sat);
+    const size_t lds = backward_lds(npix, h->nz, h->nview, W.nls, lds_sums, W.stage != 0, sat, var);
     // workgroups of 256 lanes, as many as are resident at once: every lane walks its ids with a fixed stride, and a workgroup that had to
     // queue would start when the others are through
     uint64_t cap = 0;
@@ -2598,7 +2664,7 @@ static int run_backward(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_
         HIPCHK(hipEventCreate(&e0));
         hipError_t err = hipEventCreate(&e1);
         if (err == hipSuccess) err = hipEventRecord(e0, h->stream);
-        if (err == hipSuccess) err = backward_launch(route, h->counting != 0, false, grid, lds, h->stream, A, seed, off, nb, nullptr, nullptr, W, Sl, P);
+        if (err == hipSuccess) err = backward_launch(route, h->counting != 0, false, grid, lds, h->stream, A, seed, off, nb, nullptr, nullptr, W, Sl, P, E);
         if (err == hipSuccess) err = hipEventRecord(e1, h->stream);
         if (err != hipSuccess) {
             (void)hipEventDestroy(e0);
@@ -2630,6 +2696,18 @@ int mi3d_run(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_of
     int rc = check_handle(h);
     if (rc) return rc;
     if ((rc = mi3d_prepare(h))) return rc;
+    if (h->pixel_errors) {
+        const char *why = h->emis_weights ? "emission weights (mi3d_set_emission_weights 1): the weights build is at its register limit"
+                          : h->view_profiles ? "view profiles (mi3d_set_view_profiles 1): the profiles build is at its register limit"
+                          : !(h->target & MI3D_TARGET_RADIANCE) || (h->target & MI3D_TARGET_FLUX) ? "a flux or heating-rate job: only the pixels of a backward image have histories of their own"
+                          : !(h->cam_method == 1 || h->view_method == 1)
+                              ? "a forward route (mi3d_set_camera_method 0, mi3d_set_view_method 0): one photon's contributions land in many pixels, so no pixel has "
+                                "independent histories of its own"
+                              : nullptr;
+        if (why)
+            return fail(MI3D_EUNSUP, "per-pixel standard errors (mi3d_set_pixel_errors 1) are tallied by the plain backward builds alone "
+                                     "(mi3d_set_camera_method 1 or mi3d_set_view_method 1): not with %s", why);
+    }
     if (h->view_profiles && (h->view_method != 1 || h->rad_kind != 2 || h->cam_method != 0 || h->emis_weights))
         return fail(MI3D_EUNSUP, "view profiles (mi3d_set_view_profiles 1) are tallied by the backward route for satellite views alone (mi3d_set_view_method 1 "
                                  "with mi3d_set_views, mi3d_set_camera_method 0, mi3d_set_emission_weights 0): not with %s",
@@ -3369,6 +3447,26 @@ int mi3d_get_view_profiles(mi3d_solver *h, uint64_t nphoton_total, float *weight
         if (contribution) HIPCHK(hipMemcpyAsync(contribution + e0, h->d_prf_out.p + chunk, (size_t)nn * sizeof(float), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
     }
+    return MI3D_OK;
+}
+
+// Read-out of the per-pixel standard errors (mi3d_set_pixel_errors 1): k_backward_norm_se on the raw sums, float32
+int mi3d_get_radiance_se(mi3d_solver *h, uint64_t nphoton_total, float *out) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (!out) return fail(MI3D_EINVAL, "bad arguments to mi3d_get_radiance_se");
+    if (!h->pixel_errors) return fail(MI3D_ESTATE, "mi3d_get_radiance_se: the squared scores are not tallied (mi3d_set_pixel_errors 1)");
+    if ((rc = mi3d_prepare(h))) return rc;
+    const size_t n = (size_t)h->nview * h->nxr * h->nyr;
+    if (!h->backward() || !h->err_ran || !h->err_ptr() || (!h->err_ext && h->err_n != n))
+        return fail(MI3D_ESTATE, "mi3d_get_radiance_se: nothing has been tallied since the last reset (mi3d_run on the backward route with mi3d_set_pixel_errors 1)");
+    HIPCHK(sync_main(h));
+    if ((rc = h->d_err_out.alloc(n))) return rc;
+    hipLaunchKernelGGL(k_backward_norm_se, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const double *)h->rad_ptr(), (const double *)h->err_ptr(),
+                       h->d_err_out.p, (unsigned long long)nphoton_total, (unsigned)n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, h->d_err_out.p, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
     return MI3D_OK;
 }
 

@@ -20,7 +20,11 @@
 //   k_backward_vp<COUNT>   the histories of k_backward_v with mi3d_set_view_profiles 1: every term w (1 - exp(-ka l)),
 //                      w eps and every term of the score is also added to P_raw[pixel][layer | surface], float64, a run of one (pixel, row)
 //                      summed in registers and flushed when it changes
+//   k_backward_s<COUNT>, k_backward_vs<COUNT>   the histories of k_backward and of k_backward_v with mi3d_set_pixel_errors 1 (DESIGN.md
+//                      §5.17): the square of every score that enters rad[pixel] is also added to rad2[pixel], float64, by the path the
+//                      score itself takes (LDS sums, the tile hand-out's register, global atomics)
 //   k_backward_norm    read-out: tally of pixel p / number of ids in [0, N) that map to p
+//   k_backward_norm_se   read-out of the standard error of that mean from rad and rad2
 //   k_backward_norm_rows   the same rule for the rows of K_raw, rounded to float32
 //   k_backward_norm_profiles   the same rule for the rows of P_raw, its pairs {K, C} parted into two float32 arrays
 //
@@ -41,6 +45,7 @@ constexpr unsigned kBwdMaxCells = 1u << 20;   // cell steps after which a histor
 constexpr float kBwdWeightEnd = 1.0e-7f;      // a history whose weight falls below this ends (bias <= 1e-7 max B)
 constexpr int kBwdChunkAuto = 4;              // mi3d_set_tuning "bwd_chunk" -1: the largest chunk of the tile hand-out
 constexpr int kBwdLdsPix = 2048;              // images up to this many pixels are summed per workgroup in LDS
+constexpr int kBwdLdsPixErr = 1024;           // ... in the builds with a second tally (VAR): two sums per pixel, the same bytes at most
 
 struct DevBackward {
     int nx, ny, nz, nz3, k3lo, np1d, np3d;
@@ -82,6 +87,11 @@ struct BwdSat {
 struct BwdProfiles {
     double *raw;
     int nrow;
+};
+
+// What only the builds with per-pixel standard errors receive (mi3d_set_pixel_errors 1): the tally of the squared scores, shaped as rad
+struct BwdErrors {
+    double *rad2;
 };
 
 // One thread per cell, in the order of DevThermal's CDF (k_thermal_power): voxels in file order, layers, surface cells.
@@ -149,25 +159,27 @@ __device__ inline int bwd_wrap(const int i, const float d, const int n) {
     return j < 0 ? 0 : (j >= n ? n - 1 : j);
 }
 
-// The histories, single-sourced for all entry points: mi3d_kernel_backward_body.inc is the body of each, with WGT, SAT and PRF constants
-// of the entry point that includes it (and W, S, P the arguments of the builds that read them)
+// The histories, single-sourced for all entry points: mi3d_kernel_backward_body.inc is the body of each, with WGT, SAT, PRF and VAR
+// constants of the entry point that includes it (and W, S, P, E the arguments of the builds that read them)
 template <bool COUNT, bool DEBUG>
 __global__ void __launch_bounds__(256)
 k_backward(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, float *__restrict__ dir_out, double *__restrict__ score_out) {
-    constexpr bool WGT = false, SAT = false, PRF = false;
+    constexpr bool WGT = false, SAT = false, PRF = false, VAR = false;
     const BwdWeights W{};
     const BwdSat S{};
     const BwdProfiles P{};
+    const BwdErrors E{};
 #include "mi3d_kernel_backward_body.inc"
 }
 
 template <bool COUNT>
 __global__ void __launch_bounds__(256)
 k_backward_w(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, const BwdWeights W) {
-    constexpr bool WGT = true, DEBUG = false, SAT = false, PRF = false;
+    constexpr bool WGT = true, DEBUG = false, SAT = false, PRF = false, VAR = false;
     float *const dir_out = nullptr; double *const score_out = nullptr;
     const BwdSat S{};
     const BwdProfiles P{};
+    const BwdErrors E{};
 #include "mi3d_kernel_backward_body.inc"
 }
 
@@ -175,18 +187,20 @@ template <bool COUNT, bool DEBUG>
 __global__ void __launch_bounds__(256)
 k_backward_v(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, float *__restrict__ dir_out, double *__restrict__ score_out,
              const BwdSat S) {
-    constexpr bool WGT = false, SAT = true, PRF = false;
+    constexpr bool WGT = false, SAT = true, PRF = false, VAR = false;
     const BwdWeights W{};
     const BwdProfiles P{};
+    const BwdErrors E{};
 #include "mi3d_kernel_backward_body.inc"
 }
 
 template <bool COUNT>
 __global__ void __launch_bounds__(256)
 k_backward_vp(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, const BwdSat S, const BwdProfiles P) {
-    constexpr bool WGT = false, DEBUG = false, SAT = true, PRF = true;
+    constexpr bool WGT = false, DEBUG = false, SAT = true, PRF = true, VAR = false;
     float *const dir_out = nullptr; double *const score_out = nullptr;
     const BwdWeights W{};
+    const BwdErrors E{};
 #include "mi3d_kernel_backward_body.inc"
 }
 
@@ -203,16 +217,59 @@ k_backward_norm_profiles(const double *__restrict__ raw, float *__restrict__ out
     }
 }
 
+// The histories with mi3d_set_pixel_errors 1: the same body with VAR.  (They stand behind every other kernel so that
+// the code of the kernels before them lies where it lay.)
+template <bool COUNT>
+__global__ void __launch_bounds__(256)
+k_backward_s(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, const BwdErrors E) {
+    constexpr bool WGT = false, DEBUG = false, SAT = false, PRF = false, VAR = true;
+    float *const dir_out = nullptr; double *const score_out = nullptr;
+    const BwdWeights W{};
+    const BwdSat S{};
+    const BwdProfiles P{};
+#include "mi3d_kernel_backward_body.inc"
+}
+
+template <bool COUNT>
+__global__ void __launch_bounds__(256)
+k_backward_vs(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, const BwdSat S, const BwdErrors E) {
+    constexpr bool WGT = false, DEBUG = false, SAT = true, PRF = false, VAR = true;
+    float *const dir_out = nullptr; double *const score_out = nullptr;
+    const BwdWeights W{};
+    const BwdProfiles P{};
+#include "mi3d_kernel_backward_body.inc"
+}
+
+// The standard error of the mean of pixel p from the raw sums of its n = bwd_pixel_ids(N, npix, p) scores and of their squares:
+// sqrt(max(rad2 - rad^2 / n, 0) / (n (n - 1))), float64 throughout and rounded once; 0 where n < 2 (include/mi3d.h, mi3d_get_radiance_se)
+__global__ void __launch_bounds__(256)
+k_backward_norm_se(const double *__restrict__ tally, const double *__restrict__ tally2, float *__restrict__ out, unsigned long long nphoton, unsigned npix) {
+    const unsigned p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npix) return;
+    const unsigned long long cnt = bwd_pixel_ids(nphoton, npix, p);
+    float se = 0.0f;
+    if (cnt >= 2ull) {
+        const double nn = (double)cnt, t = tally[p];
+        const double q = t * t;
+        const double ss = fmax(tally2[p] - q / nn, 0.0);
+        se = (float)sqrt(ss / (nn * (nn - 1.0)));
+    }
+    out[p] = se;
+}
+
 // The dynamic LDS of a launch of any build, in bytes: the host's statement of what the top of mi3d_kernel_backward_body.inc lays out, in
-// that order -- the workgroup's image sums [npix] (lds_sums), the staged layer and surface weights [npix][nls] (wstage), the layer table
-// [nz], the cameras or -- sat -- the views [nview]; the two sums rounded up to an even number of doubles
-__host__ inline size_t backward_lds(int npix, int nz, int nview, int nls, bool lds_sums, bool wstage, bool sat) {
+// that order -- the workgroup's image sums [npix] (lds_sums), their squares [npix] (lds_sums and var), the staged layer and surface
+// weights [npix][nls] (wstage), the layer table [nz], the cameras or -- sat -- the views [nview]; each of the sums rounded up to an even
+// number of doubles
+__host__ inline size_t backward_lds(int npix, int nz, int nview, int nls, bool lds_sums, bool wstage, bool sat, bool var = false) {
     const size_t sums = lds_sums ? (((size_t)npix + 1) & ~(size_t)1) : 0, wsum = wstage ? (((size_t)npix * nls + 1) & ~(size_t)1) : 0;
-    return (sums + wsum) * sizeof(double) + (size_t)nz * sizeof(LayerRec) + (size_t)nview * (sat ? sizeof(ViewRec) : sizeof(CamRec));
+    return (sums * (var ? 2 : 1) + wsum) * sizeof(double) + (size_t)nz * sizeof(LayerRec) + (size_t)nview * (sat ? sizeof(ViewRec) : sizeof(CamRec));
 }
 // are the image's sums taken per workgroup in LDS?  Not by the debug entries, which tally nothing, and not under the tile hand-out, which
-// keeps them in registers (the body's `lds_sums`)
-__host__ inline bool backward_lds_sums(int npix, bool debug, bool tiles) { return !debug && npix <= kBwdLdsPix && !tiles; }
+// keeps them in registers (the body's `lds_sums`).  The builds with a second tally (var) take half the pixels: the same bytes at most
+__host__ inline bool backward_lds_sums(int npix, bool debug, bool tiles, bool var = false) {
+    return !debug && npix <= (var ? kBwdLdsPixErr : kBwdLdsPix) && !tiles;
+}
 // The weights build stages its layer and surface weights where the image's own sums are in LDS and the workgroup's dynamic LDS stays
 // within 32 KB (five workgroups on a CU of 160 KB)
 constexpr size_t kBwdWgtLds = 32768;

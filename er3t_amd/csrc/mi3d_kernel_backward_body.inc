@@ -1,20 +1,25 @@
 // mi3d_kernel_backward_body.inc — the histories of the backward route, the one body of k_backward<COUNT, DEBUG> and k_backward_w<COUNT>
-// and k_backward_v<COUNT, DEBUG> and k_backward_vp<COUNT> (mi3d_kernel_backward.hip includes it inside each).  What it expects in scope:
-// COUNT, DEBUG, WGT, SAT, PRF (compile-time constants), the arguments A, seed, id0, n, dir_out, score_out, W (BwdWeights: read where WGT
-// holds, the weights build of DESIGN.md §5.12), S (BwdSat: read where SAT holds, the satellite-view build of DESIGN.md §5.14) and P
-// (BwdProfiles: read where PRF holds, the per-layer profiles of the satellite views, DESIGN.md §5.16).
+// and k_backward_v<COUNT, DEBUG> and k_backward_vp<COUNT> and k_backward_s<COUNT> and k_backward_vs<COUNT> (mi3d_kernel_backward.hip
+// includes it inside each).  What it expects in scope:
+// COUNT, DEBUG, WGT, SAT, PRF, VAR (compile-time constants), the arguments A, seed, id0, n, dir_out, score_out, W (BwdWeights: read where WGT
+// holds, the weights build of DESIGN.md §5.12), S (BwdSat: read where SAT holds, the satellite-view build of DESIGN.md §5.14), P
+// (BwdProfiles: read where PRF holds, the per-layer profiles of the satellite views, DESIGN.md §5.16) and E (BwdErrors: read where VAR
+// holds, the second tally of the per-pixel standard errors, DESIGN.md §5.17).
     extern __shared__ double bwd_smem[];
     const int npix = A.nview * A.nxr * A.nyr;
     const bool tiles = SAT && S.jch > 0;                                     // the tile hand-out (mi3d_set_tuning "bwd_chunk" >= 1)
-    const bool lds_sums = !DEBUG && npix <= kBwdLdsPix && !tiles;
+    const bool lds_sums = !DEBUG && npix <= (VAR ? kBwdLdsPixErr : kBwdLdsPix) && !tiles;
     double *sums = bwd_smem;
+    double *sums2 = VAR ? bwd_smem + ((npix + 1) & ~1) : bwd_smem;           // (VAR) [npix] the workgroup's sums of squares, behind the sums
     const bool wstage = WGT && W.stage != 0;                                 // (the host sets it only where lds_sums holds)
     const int nls = WGT ? W.nls : 1, nwsum = wstage ? npix * nls : 0;
-    double *wsum = bwd_smem + (lds_sums ? ((npix + 1) & ~1) : 0);           // [npix][nls] the workgroup's layer and surface weights
-    LayerRec *slay = reinterpret_cast<LayerRec *>(bwd_smem + (lds_sums ? ((npix + 1) & ~1) : 0) + (WGT ? ((nwsum + 1) & ~1) : 0));   // (16-byte aligned)
+    double *wsum = bwd_smem + (lds_sums ? ((npix + 1) & ~1) : 0) + (VAR && lds_sums ? ((npix + 1) & ~1) : 0);   // [npix][nls] the workgroup's layer and surface weights
+    LayerRec *slay = reinterpret_cast<LayerRec *>(bwd_smem + (lds_sums ? ((npix + 1) & ~1) : 0) + (VAR && lds_sums ? ((npix + 1) & ~1) : 0)
+                                                  + (WGT ? ((nwsum + 1) & ~1) : 0));   // (16-byte aligned)
     CamRec *scam = reinterpret_cast<CamRec *>(slay + A.nz);
     const ViewRec *sview = reinterpret_cast<const ViewRec *>(scam);         // (SAT: the views stand where the cameras would)
     if (lds_sums) for (int i = threadIdx.x; i < npix; i += blockDim.x) sums[i] = 0.0;
+    if (VAR && lds_sums) for (int i = threadIdx.x; i < npix; i += blockDim.x) sums2[i] = 0.0;
     if (WGT) for (int i = threadIdx.x; i < nwsum; i += blockDim.x) wsum[i] = 0.0;
     {   // layer table and cameras (SAT: views): 16-byte pieces
         const float4 *src = reinterpret_cast<const float4 *>(A.lay);
@@ -44,6 +49,7 @@
     uint64_t item = next >> 6, idn = 0;      // the lane's next item; the next id of its chunk ...
     unsigned jn = 0;                         // ... and how many of the chunk are left
     double acc = 0.0;                        // the sum of the scores of pixel accpix since it last changed
+    double acc2 = 0.0;                       // (VAR) ... and of their squares
     int accpix = 0;
     // PRF: the lane's run -- the sums of the terms of row run_e = pix nrow + k of P.raw since (pix, k) last changed.  A slant line takes
     // several cell steps inside a layer and, under the tile hand-out, a lane keeps its pixel: a run ends in two atomics, not a step
@@ -116,7 +122,8 @@
                     idn = id0 + (uint64_t)r + j0 * (uint64_t)npix;
                     if (p != accpix) {
                         if (!DEBUG && acc != 0.0) atomicAdd(&A.rad[accpix], acc);
-                        acc = 0.0; accpix = p;
+                        if (VAR && acc2 != 0.0) atomicAdd(&E.rad2[accpix], acc2);
+                        acc = 0.0; acc2 = 0.0; accpix = p;
                     }
                 }
                 if (jn == 0u) break;
@@ -323,19 +330,21 @@
             have = false;
             const double s = score * (double)A.src_flx;
             if (DEBUG) score_out[slot] = s;
-            else if (tiles) acc += s;
+            else if (tiles) { acc += s; if (VAR) acc2 += s * s; }
             else if (s != 0.0) {
-                if (lds_sums) atomicAdd(&sums[pix], s);
-                else atomicAdd(&A.rad[pix], s);
+                if (lds_sums) { atomicAdd(&sums[pix], s); if (VAR) atomicAdd(&sums2[pix], s * s); }
+                else { atomicAdd(&A.rad[pix], s); if (VAR) atomicAdd(&E.rad2[pix], s * s); }
             }
             if (COUNT) c_hist++;
         }
     }
     if (tiles && !DEBUG && acc != 0.0) atomicAdd(&A.rad[accpix], acc);
+    if (VAR && tiles && acc2 != 0.0) atomicAdd(&E.rad2[accpix], acc2);
     if (PRF) prf_flush();
     if (lds_sums) {
         __syncthreads();
         for (int i = threadIdx.x; i < npix; i += blockDim.x) { const double s = sums[i]; if (s != 0.0) atomicAdd(&A.rad[i], s); }
+        if (VAR) for (int i = threadIdx.x; i < npix; i += blockDim.x) { const double s = sums2[i]; if (s != 0.0) atomicAdd(&E.rad2[i], s); }
         if (WGT)
             for (int i = threadIdx.x; i < nwsum; i += blockDim.x) {
                 const double s = wsum[i];

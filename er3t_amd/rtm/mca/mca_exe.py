@@ -83,6 +83,17 @@ def _check_supported(nml, fdir=None, solver=None):
         if mvprf == 1.0 and _flag(nml, 'Rad_mvbwd') != 1.0:
             raise OSError('Error [mca_exe]: <Rad_mvprf=1> (view profiles) needs the backward route for satellite views (<Rad_mvbwd=1>): the profiles '
                           'are what backward histories collect along their lines of sight.')
+    if nml.get('Rad_mserr') is not None:
+        mserr = float(np.ravel(nml.get('Rad_mserr'))[0])
+        if mserr not in (0.0, 1.0):
+            raise OSError('Error [mca_exe]: <Rad_mserr=%g> is not supported (0: off, 1: per-pixel standard errors of the backward routes; a key of '
+                          'this project).' % mserr)
+        if mserr == 1.0 and _flag(nml, 'Rad_mbwd') != 1.0 and _flag(nml, 'Rad_mvbwd') != 1.0:
+            raise OSError('Error [mca_exe]: <Rad_mserr=1> (pixel errors) needs a backward route (<Rad_mbwd=1> or <Rad_mvbwd=1>): on a forward route '
+                          'one photon\'s contributions land in many pixels, so no pixel has independent histories of its own.')
+        if mserr == 1.0 and (_flag(nml, 'Rad_mwgt') == 1.0 or _flag(nml, 'Rad_mvprf') == 1.0):
+            raise OSError('Error [mca_exe]: <Rad_mserr=1> (pixel errors) is not served together with <Rad_mwgt=1> (emission weights) or '
+                          '<Rad_mvprf=1> (view profiles): their kernels are at their register limits.')
     if mtype == 0:
         raise OSError('Error [mca_exe]: <Src_mtype=0> (local) is not supported: only the solar (1), the solar+thermal (2) or the thermal (3) source.')
     if mtype not in (1, 2, 3):
@@ -169,6 +180,19 @@ def weights_fname(fname_out):
 def profiles_fname(fname_out):
     """the extra file of a job with <Rad_mvprf=1> beside its out.bin: raw '<f4' [2][npix][nz+1], the weights, then the contributions"""
     return (fname_out[:-len('.out.bin')] if fname_out.endswith('.out.bin') else fname_out)+'.prf.bin'
+
+
+def errors_fname(fname_out):
+    """the extra file of a job with <Rad_mserr=1> beside its out.bin: raw '<f4' (nview, nyr, nxr), the standard error of every pixel of rad"""
+    return (fname_out[:-len('.out.bin')] if fname_out.endswith('.out.bin') else fname_out)+'.err.bin'
+
+
+def read_errors(fname, nview, nyr, nxr):
+    """the .err.bin file -> float32 (nview, nyr, nxr)"""
+    raw = np.fromfile(fname, dtype='<f4')
+    if raw.size != nview*nyr*nxr:
+        raise OSError('Error [read_errors]: <%s> does not hold %d x %d x %d values.' % (fname, nview, nyr, nxr))
+    return raw.reshape(nview, nyr, nxr).astype(np.float32)
 
 
 def flatten_profiles(p):
@@ -313,13 +337,17 @@ class JobRunner:
             prf = None
             if getattr(scene, 'view_profiles', 0):     # (Rad_mvprf = 1: the view profiles' raw tally likewise)
                 prf = torch.zeros(scene.nview*scene.nyr*scene.nxr*(scene.nz+1)*2, dtype=torch.float64, device=dev)
-            self._tensors[slot] = (rad, flux, heat, wgt, prf)
+            err = None
+            if getattr(scene, 'pixel_errors', 0):      # (Rad_mserr = 1: the raw sums of the squared scores likewise -- sums, never standard errors)
+                err = torch.zeros(scene.nview*scene.nyr*scene.nxr, dtype=torch.float64, device=dev)
+            self._tensors[slot] = (rad, flux, heat, wgt, prf, err)
             if slot == 0:
                 stream = torch.cuda.current_stream(dev)
             else:
                 stream = self._streams[slot] = self._streams[slot] or torch.cuda.Stream(dev)
             sol.bind(rad_ptr=rad.data_ptr(), flux_ptr=flux.data_ptr(), stream=stream.cuda_stream, heat_ptr=None if heat is None else heat.data_ptr(),
-                     wgt_ptr=None if wgt is None else wgt.data_ptr(), prf_ptr=None if prf is None else prf.data_ptr())
+                     wgt_ptr=None if wgt is None else wgt.data_ptr(), prf_ptr=None if prf is None else prf.data_ptr(),
+                     err_ptr=None if err is None else err.data_ptr())
         else:
             self._tensors[slot] = None
             sol.bind(None, None, None)
@@ -348,6 +376,8 @@ class JobRunner:
                 out['wgt'] = self.sol.emission_weights(nphoton)
             if getattr(self.scene, 'view_profiles', 0):
                 out['prf'] = self.sol.view_profiles(nphoton)
+            if getattr(self.scene, 'pixel_errors', 0):
+                out['se'] = self.sol.radiance_se(nphoton)
         if self.scene.target & TARGET_FLUX:
             out['flux'] = self.sol.flux(nphoton)
         if self.scene.target & TARGET_HEAT:
@@ -369,6 +399,8 @@ class JobRunner:
                 out['wgt'] = self.job_weights(nphoton, slot=slot)
             if getattr(scene, 'view_profiles', 0):
                 out['prf'] = self.job_profiles(nphoton, slot=slot)
+            if getattr(scene, 'pixel_errors', 0):
+                out['se'] = self.job_errors(nphoton, slot=slot)
         if scene.target & TARGET_FLUX:
             out['flux'] = sol.flux(int(nphoton))
         if scene.target & TARGET_HEAT:
@@ -411,6 +443,10 @@ class JobRunner:
                 if getattr(sc, 'view_method', 0) == 1:
                     raise OSError('Error [mca_exe]: satellite views served backwards (Rad_mvbwd=1) are not served by the batched route (every pixel is '
                                   'divided by its own count of histories: include/mi3d.h, mi3d_set_view_method); run such jobs one by one (run_job), '
+                                  'as mca_run does.')
+                if getattr(sc, 'pixel_errors', 0):
+                    raise OSError('Error [mca_exe]: per-pixel standard errors (Rad_mserr=1) are not served by the batched route (the read-out needs '
+                                  'every pixel\'s own count of histories: include/mi3d.h, mi3d_get_radiance_se); run such jobs one by one (run_job), '
                                   'as mca_run does.')
                 sizes = (max(sc.nview, 1)*sc.nyr*sc.nxr if sc.target & TARGET_RADIANCE else 0,
                          3*(sc.nz+1)*sc.ny*sc.nx if sc.target & TARGET_FLUX else 0,
@@ -533,6 +569,19 @@ class JobRunner:
             torch.cuda.synchronize(sol.device)
         return sol.view_profiles(int(nphoton))
 
+    def job_errors(self, nphoton, slot=0):
+        """the per-pixel standard errors (Rad_mserr = 1) of the job launched last on <slot>, a job of <nphoton> ids in all:
+        Mi3dSolver.radiance_se().  Several ranks sum their raw tallies first, the scores' and the squared scores' -- sums, never standard
+        errors --: call it AFTER the job has been folded into its run (stats_add), which reads this rank's own radiance tally"""
+        sol = self.sols[slot]
+        if self._tensors[slot] is not None and self._tensors[slot][5] is not None:
+            import torch
+            sol.sync()
+            torch.cuda.synchronize(sol.device)
+            allreduce_tallies(self._tensors[slot][0], self._tensors[slot][5])
+            torch.cuda.synchronize(sol.device)
+        return sol.radiance_se(int(nphoton))
+
     def stats_begin(self):
         """start gathering run statistics for the loaded scene (its shape and target)"""
         self._run_tensors = None
@@ -623,6 +672,8 @@ class JobRunner:
                     np.ascontiguousarray(b, dtype='<f4').tofile(f)
             if 'prf' in result:                                  # Rad_mvprf = 1: likewise
                 write_profiles(profiles_fname(fname_out), flatten_profiles(result['prf']))
+            if 'se' in result:                                   # Rad_mserr = 1: likewise, float32 (nview, nyr, nxr)
+                np.ascontiguousarray(result['se'], dtype='<f4').tofile(errors_fname(fname_out))
 
 
 _RUNNER = None

@@ -323,9 +323,78 @@ def read_radiance_mca_out(mca_obj, abs_obj, mode='mean', squeeze=True):
                       'name': 'Brightness temperature' + (', reflected sunlight included' if source == 'solar+thermal' else '')
                               + (' (of the mean radiance)' if mode == 'mean' else ''), 'units': 'K',
                       'dims_info': data['rad']['dims_info']}
+    if getattr(mca_obj, 'pixel_errors', False):
+        se, se_info = read_pixel_errors(mca_obj, abs_obj, mode=mode, squeeze=squeeze)
+        what = 'per run' if mode == 'all' else 'of the mean over runs'
+        data['rad_se'] = {'data': se, 'name': 'Radiance (standard error %s, from the histories)' % what, 'units': 'W/m^2/nm/sr', 'dims_info': se_info}
+        if 'bt' in data:
+            # the error of the brightness temperature to first order: rad_se / (dB/dT at bt), the radiance per um as bt takes it
+            from er3t_amd.thermal import dplanck_dT
+            with np.errstate(divide='ignore', invalid='ignore'):
+                d = dplanck_dT(mca_obj.wlen_um, data['bt']['data'].astype(np.float64))
+                bt_se = np.where(d > 0.0, se.astype(np.float64)*1.0e3/d, 0.0).astype(np.float32)
+            data['bt_se'] = {'data': bt_se, 'name': 'Brightness temperature (standard error %s, from the histories)' % what, 'units': 'K',
+                             'dims_info': se_info}
     data['N_photon'] = {'data': mca_obj.photons, 'name': 'Number of photons', 'units': 'N/A'}
     data['N_run']    = {'data': mca_obj.Nrun, 'name': 'Number of runs', 'units': 'N/A'}
     return data
+
+
+def pixel_error_runs(se_jobs, factors):
+
+    """
+    The g combination of the per-pixel standard errors (mcarats_ng(pixel_errors=True), Rad_mserr = 1).  Jobs of different g and of different
+    runs have different seeds and are independent, so variances add: per run  rad_se_run^2 = sum_g factor[view, g]^2 se_g^2,  with the
+    float32 factors of `rad` (g_factors).  se_jobs: (Nrun, Ng, nview, nyr, nxr), factors: (nview, Ng).  Returns the VARIANCES, float64
+    (Nrun, nview, nyr, nxr), summed g after g.
+    """
+
+    se = np.asarray(se_jobs, dtype=np.float64)
+    f = np.asarray(factors, dtype=np.float64)
+    var = np.zeros((se.shape[0],)+se.shape[2:], dtype=np.float64)
+    for ig in range(se.shape[1]):
+        t = f[:, ig][None, :, None, None]*se[:, ig]
+        var += t*t
+    return var
+
+
+def read_pixel_errors(mca_obj, abs_obj, mode='mean', squeeze=True):
+
+    """
+    rad_se of mcarats_ng(pixel_errors=True): the standard error of `rad` from the histories themselves, in the layout of `rad`
+    (Nx, Ny, Nview; axes of length 1 dropped with squeeze).  'all': per run (a last axis Nr), sqrt(sum_g f_g^2 se_g^2); 'mean': of the mean
+    over runs, sqrt(sum_r rad_se_r^2) / Nrun.  The file route reads the jobs' .err.bin files; the fused route has kept the same arrays
+    (mcarats_ng.run_fused).  Returns (array float32, dims_info).
+    """
+
+    from er3t_amd.rtm.mca.mca_inp import mca_inp_read
+    from er3t_amd.rtm.mca.mca_exe import errors_fname, read_errors
+    mode = mode.lower()
+    if mode not in ('mean', 'all'):
+        raise OSError('Error [read_pixel_errors]: Do not support <mode=%s>.' % mode)
+    fused = getattr(mca_obj, 'fused', None)
+    if fused is not None and 'se' in fused:
+        se_jobs = fused['se']
+    else:
+        g9 = _weights_geometry(mca_inp_read(mca_obj.fnames_inp[0][0]))
+        se_jobs = np.stack([np.stack([read_errors(errors_fname(mca_obj.fnames_out[ir][ig]), g9[0], g9[1], g9[2]) for ig in range(mca_obj.Ng)])
+                            for ir in range(mca_obj.Nrun)])
+    factors, _ = g_factors(mca_obj, abs_obj, 1)
+    var = pixel_error_runs(se_jobs, np.repeat(factors, se_jobs.shape[2], axis=0))      # (every view scaled like the one view of `rad`)
+    if mode == 'all':
+        a = np.transpose(np.sqrt(var), (3, 2, 1, 0))                                    # (Nx, Ny, Nview, Nr)
+        info = ['Nx', 'Ny', 'Nz', 'Nr']
+        keep = [i for i in range(3) if a.shape[i] > 1 or not squeeze]+[3]
+    else:
+        a = np.transpose(np.sqrt(var.sum(axis=0))/var.shape[0], (2, 1, 0))              # (Nx, Ny, Nview)
+        info = ['Nx', 'Ny', 'Nz']
+        keep = [i for i in range(3) if a.shape[i] > 1 or not squeeze]
+    if not squeeze:                                                                     # (the file route's Nt axis)
+        a = a[:, :, :, None]
+        info = info[:3]+['Nt']+info[3:]
+        keep = list(range(a.ndim))
+    a = a.reshape([a.shape[i] for i in keep])
+    return np.ascontiguousarray(a.astype(np.float32)), [info[i] for i in keep]
 
 
 def read_radiometer_mca_out(mca_obj, abs_obj, mode='mean', squeeze=True):
@@ -357,6 +426,11 @@ def read_radiometer_mca_out(mca_obj, abs_obj, mode='mean', squeeze=True):
                                 'dims_info': dims_info[:-1]}
         else:
             raise OSError('Error [read_radiometer_mca_out]: Do not support <mode=%s>.' % mode)
+    if getattr(mca_obj, 'pixel_errors', False):
+        # (a thermal job: no direct part, f = f_diffuse = solid angle x rad, and so is its error)
+        se, se_info = read_pixel_errors(mca_obj, abs_obj, mode=mode, squeeze=squeeze)
+        data['rad_se'] = {'data': se, 'name': 'Mean radiance over the hemisphere (standard error, from the histories)', 'units': 'W/m^2/nm/sr', 'dims_info': se_info}
+        data['f_se'] = {'data': se*solid, 'name': 'Total %s (standard error, from the histories)' % what, 'units': 'W/m^2/nm', 'dims_info': se_info}
     data['N_photon'] = {'data': mca_obj.photons, 'name': 'Number of photons', 'units': 'N/A'}
     data['N_run']    = {'data': mca_obj.Nrun, 'name': 'Number of runs', 'units': 'N/A'}
     return data

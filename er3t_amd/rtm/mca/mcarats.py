@@ -123,6 +123,11 @@ class mcarats_ng:
                            and the contribution C[pixel][layer] of every layer and of the surface (Rad_mvprf=1, a key of this project written
                            only then: include/mi3d.h, mi3d_set_view_profiles); mca_out_ng returns data['view_weight'],
                            data['view_contribution'] and data['view_layer_planck']
+        pixel_errors [False]: with camera_method='backward' or view_method='backward' (without emission_weights and view_profiles): every
+                           job also tallies the squared score of every history in its pixel, so that the standard error of every pixel
+                           follows from the job's own histories -- one run is enough (Rad_mserr=1, a key of this project written only
+                           then: include/mi3d.h, mi3d_set_pixel_errors); mca_out_ng returns data['rad_se'] and
+                           data['bt_se'], for point radiometers data['f_se']
 
     Afterwards: input and output files under <fdir>; attributes Ng, Nrun, Nx, Ny, dx, dy, date, target, solver,
     photons (Nrun*Ng,), photons_per_set, fnames_inp[ir][ig], fnames_out[ir][ig], nml (list of Ng dictionaries).
@@ -137,7 +142,7 @@ class mcarats_ng:
                  sensor_ypos=0.5, solver='3d', photons=1e7, base_ratio=0.05, verbose=False, quiet=False,
                  abs_obj=None, keep_files=True, source='solar', wavelength=None, surface_temperature=None,
                  heating_estimator='collision', camera_images=None, camera_method='forward', emission_weights=False, view_method='forward',
-                 view_profiles=False):
+                 view_profiles=False, pixel_errors=False):
 
         # one process per GPU (torch.distributed): rank 0 writes the job files, all ranks transport their share of every job
         from er3t_amd.dist import world_info, barrier
@@ -206,6 +211,16 @@ class mcarats_ng:
         if self.view_profiles and self.view_method != 'backward':
             raise OSError('Error [mcarats_ng]: <view_profiles=True> needs <view_method=\'backward\'>: the per-layer profiles are what backward '
                           'histories collect along their lines of sight.')
+        self.pixel_errors = bool(pixel_errors)
+        if self.pixel_errors and self.source != 'thermal':
+            raise OSError('Error [mcarats_ng]: <pixel_errors=True> needs <source=\'thermal\'>: the backward routes serve thermal jobs alone (the sun '
+                          'would need a local estimate of its own).')
+        if self.pixel_errors and self.camera_method != 'backward' and self.view_method != 'backward':
+            raise OSError('Error [mcarats_ng]: <pixel_errors=True> needs <camera_method=\'backward\'> or <view_method=\'backward\'>: on a forward route '
+                          'one photon\'s contributions land in many pixels, so no pixel has independent histories of its own.')
+        if self.pixel_errors and (emission_weights or self.view_profiles):
+            raise OSError('Error [mcarats_ng]: <pixel_errors=True> does not go with <emission_weights=True> or <view_profiles=True>: their kernels '
+                          'are at their register limits.')
         self.emission_weights = bool(emission_weights)
         if self.emission_weights and self.camera_method != 'backward':
             raise OSError('Error [mcarats_ng]: <emission_weights=True> needs <camera_method=\'backward\'>: the per-cell weights are what backward '
@@ -293,6 +308,8 @@ class mcarats_ng:
             self._all({'Rad_mvbwd': 1})
             if self.view_profiles:                     # (likewise)
                 self._all({'Rad_mvprf': 1})
+        if self.pixel_errors:                          # (likewise)
+            self._all({'Rad_mserr': 1})
         if self.camera_method == 'backward':           # (likewise)
             self._all({'Rad_mbwd': 1})
             if self.emission_weights:                  # (likewise)
@@ -471,9 +488,16 @@ class mcarats_ng:
         # launched before job i is folded into the run, so the tail of a launch -- as long as its longest history -- runs
         # beside the next launch.  The run field is still summed in job order (JobRunner.stats_add).
         # (emission weights, Rad_mwgt = 1: every job's array is read back and reduced as the job ends -- one handle, like the per-job files;
-        #  view profiles, Rad_mvprf = 1: likewise)
-        nslot = runner.use_slots(1 if self.keep_files or self.emission_weights or self.view_profiles else 2)
+        #  view profiles, Rad_mvprf = 1: likewise; pixel errors, Rad_mserr = 1: likewise, npix floats a job)
+        nslot = runner.use_slots(1 if self.keep_files or self.emission_weights or self.view_profiles or self.pixel_errors else 2)
         wred = pred = None
+        se_jobs = [[None]*self.Ng for _ in range(self.Nrun)] if self.pixel_errors else None
+
+        def fold(nph, fac, slot, ir, ig):
+            runner.stats_add(nph, fac, slot)
+            if se_jobs is not None and runner.world > 1:      # (several ranks: the raw sums are exchanged once the run field has this rank's)
+                se_jobs[ir][ig] = runner.job_errors(nph, slot=slot)
+
         for ir in range(self.Nrun):
             waiting = None          # (photons, factors, slot) of the job launched last, not yet folded into the run
             for ig in range(self.Ng):
@@ -503,8 +527,12 @@ class mcarats_ng:
                     if pred is None:
                         pred = weights_reducer(factors[0], keep_runs=True)
                     pred.add(ig, flatten_profiles(prf))
+                if se_jobs is not None and runner.world == 1:
+                    se_jobs[ir][ig] = runner.job_errors(photons[ir, ig], slot=slot)
                 if self.keep_files:
                     result = {'rad': runner.sol.radiance(photons[ir, ig])} if self.target == 'radiance' else {'flux': runner.sol.flux(photons[ir, ig])}
+                    if se_jobs is not None:
+                        result['se'] = se_jobs[ir][ig]
                     if wants_rdir(scene):
                         result['rdir'] = runner.sol.camera_direct().astype(np.float32)
                     if wgt is not None:
@@ -516,13 +544,13 @@ class mcarats_ng:
                 # (a job is folded into the run before its slot is launched on again: with one slot at once, with two after the
                 #  next job's launch)
                 if waiting is not None:
-                    runner.stats_add(*waiting)
-                waiting = (photons[ir, ig], factors[:, ig], slot)
+                    fold(*waiting)
+                waiting = (photons[ir, ig], factors[:, ig], slot, ir, ig)
                 if nslot == 1:
-                    runner.stats_add(*waiting)
+                    fold(*waiting)
                     waiting = None
             if waiting is not None:
-                runner.stats_add(*waiting)
+                fold(*waiting)
             runs.append(runner.stats_end_run(keep=True))
             if wred is not None:
                 wred.end_run()
@@ -540,6 +568,8 @@ class mcarats_ng:
             self.fused['wgt'] = wred
         if pred is not None:
             self.fused['prf'] = pred
+        if se_jobs is not None:                        # (Nrun, Ng, nview, nyr, nxr): mca_out_ng combines them as it combines the jobs' files
+            self.fused['se'] = np.stack([np.stack(row) for row in se_jobs]).astype(np.float32)
         self.kernel_ms = runner.kernel_ms - ms0
         self.photons_done = runner.photons_done - n0
         if not self.quiet and self.kernel_ms > 0.0:

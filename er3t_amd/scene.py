@@ -123,6 +123,9 @@ class Scene:
     view_profiles: int = 0                # Rad_mvprf (a key of this project; include/mi3d.h: mi3d_set_view_profiles): 1 the backward route also
                                           # tallies every pixel's weighting function and contribution per layer and for the surface;
                                           # needs rad_kind = 2, view_method = 1
+    pixel_errors: int = 0                 # Rad_mserr (a key of this project; include/mi3d.h: mi3d_set_pixel_errors): 1 the backward route also
+                                          # tallies the squared scores of every pixel, for its standard error from one run; needs
+                                          # cam_method = 1 or view_method = 1, without cam_weights and view_profiles
 
     # job
     target: int = TARGET_FLUX
@@ -204,6 +207,14 @@ class Scene:
             raise ValueError('Error [Scene]: <view_profiles=%s> (Rad_mvprf) must be 0 or 1.' % (self.view_profiles,))
         if self.view_profiles == 1 and not (self.rad_kind == 2 and self.view_method == 1):
             raise ValueError('Error [Scene]: <view_profiles=1> (Rad_mvprf) needs the backward route for satellite views (<rad_kind=2>, <view_method=1>).')
+        if self.pixel_errors not in (0, 1) or isinstance(self.pixel_errors, float):
+            raise ValueError('Error [Scene]: <pixel_errors=%s> (Rad_mserr) must be 0 or 1.' % (self.pixel_errors,))
+        if self.pixel_errors == 1 and not ((self.rad_kind == 1 and self.cam_method == 1) or (self.rad_kind == 2 and self.view_method == 1)):
+            raise ValueError('Error [Scene]: <pixel_errors=1> (Rad_mserr) needs a backward route (<cam_method=1> or <view_method=1>): on a forward '
+                             'route one photon\'s contributions land in many pixels.')
+        if self.pixel_errors == 1 and (self.cam_weights == 1 or self.view_profiles == 1):
+            raise ValueError('Error [Scene]: <pixel_errors=1> (Rad_mserr) is not served together with <cam_weights=1> (Rad_mwgt) or '
+                             '<view_profiles=1> (Rad_mvprf).')
         if self.src_mtype in (2, 3):
             if self.src_mtype == 2:
                 if self.src_fsol is None or not (float(self.src_fsol) >= 0.0) or not np.isfinite(float(self.src_fsol)):
@@ -385,6 +396,15 @@ class Scene:
             raise OSError('Error [Scene]: <Rad_mvprf=%g> is not supported (0: off, 1: per-layer weighting functions).' % mvprf)
         if mvprf == 1.0 and mvbwd != 1.0:
             raise OSError('Error [Scene]: <Rad_mvprf=1> (view profiles) needs the backward route for satellite views (<Rad_mvbwd=1>).')
+        # (a key of this project: per-pixel standard errors of the backward routes)
+        mserr = float(np.ravel(get('Rad_mserr', 0))[0])
+        if mserr not in (0.0, 1.0):
+            raise OSError('Error [Scene]: <Rad_mserr=%g> is not supported (0: off, 1: per-pixel standard errors).' % mserr)
+        if mserr == 1.0 and mbwd != 1.0 and mvbwd != 1.0:
+            raise OSError('Error [Scene]: <Rad_mserr=1> (pixel errors) needs a backward route (<Rad_mbwd=1> or <Rad_mvbwd=1>): on a forward route '
+                          'one photon\'s contributions land in many pixels.')
+        if mserr == 1.0 and (mwgt == 1.0 or mvprf == 1.0):
+            raise OSError('Error [Scene]: <Rad_mserr=1> (pixel errors) is not served together with <Rad_mwgt=1> or <Rad_mvprf=1>.')
         if mtarget == 2:
             nrad = int(get('Rad_nrad', 1))
             the  = np.resize(np.asarray(get('Rad_the', 180.0), dtype=np.float64), nrad)
@@ -404,7 +424,7 @@ class Scene:
                 kw.update(rad_kind=1, cam_xpos=per_view('Rad_xpos', 0.5), cam_ypos=per_view('Rad_ypos', 0.5),
                           cam_psi=per_view('Rad_psi', 0.0), cam_qmax=per_view('Rad_qmax', 180.0), cam_umax=per_view('Rad_umax', 180.0),
                           cam_vmax=per_view('Rad_vmax', 180.0), cam_apsize=per_view('Rad_apsize', 0.0), cam_mpmap=mpmap, cam_mrproj=mrproj,
-                          cam_method=int(mbwd), cam_weights=int(mwgt))
+                          cam_method=int(mbwd), cam_weights=int(mwgt), pixel_errors=int(mserr))
                 # (a key of this project: the periodic images of a sensor the job asks for; without it the route's default, cam_images = -1)
                 if get('Rad_nimg') is not None:
                     nimg = float(np.ravel(get('Rad_nimg'))[0])
@@ -414,7 +434,7 @@ class Scene:
             elif mrkind != 2:
                 raise OSError('Error [Scene]: <Rad_mrkind=%d> is not supported (1: camera, 2: satellite).' % mrkind)
             else:
-                kw.update(view_method=int(mvbwd), view_profiles=int(mvprf))
+                kw.update(view_method=int(mvbwd), view_profiles=int(mvprf), pixel_errors=int(mserr))
         elif mtarget == 1:
             mhrt = int(get('Flx_mhrt', 0) or 0)
             if mhrt == 2 and mtype not in (2, 3):

@@ -56,6 +56,9 @@ _SIGNATURES = [
     ('mi3d_set_view_profiles'  , C.c_int   , [C.c_void_p, C.c_int]),
     ('mi3d_bind_view_profiles_buffer', C.c_int, [C.c_void_p, C.c_void_p]),
     ('mi3d_get_view_profiles'  , C.c_int   , [C.c_void_p, _u64, _fp, _fp]),
+    ('mi3d_set_pixel_errors'   , C.c_int   , [C.c_void_p, C.c_int]),
+    ('mi3d_bind_pixel_errors_buffer', C.c_int, [C.c_void_p, C.c_void_p]),
+    ('mi3d_get_radiance_se'    , C.c_int   , [C.c_void_p, _u64, _fp]),
     ('mi3d_debug_backward_chunk', C.c_int  , [C.c_void_p]),
     ('mi3d_set_options'        , C.c_int   , [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int]),
     ('mi3d_set_le_roulette'    , C.c_int   , [C.c_void_p, C.c_double]),
@@ -312,6 +315,12 @@ class Mi3dSolver:
         the value itself (anything but 0 and 1 is refused by the library)"""
         self._chk(self.lib.mi3d_set_view_profiles(self._h, int(on)))
 
+    def set_pixel_errors(self, on=True):
+        """per-pixel standard errors of the backward routes (include/mi3d.h: mi3d_set_pixel_errors): on, every run also tallies the squared
+        score of every history in its pixel, and radiance_se() reads the standard error of every pixel's mean.  True / False or the value
+        itself (anything but 0 and 1 is refused by the library)"""
+        self._chk(self.lib.mi3d_set_pixel_errors(self._h, int(on)))
+
     def set_options(self, target=TARGET_FLUX, solver=0, wmin=0.2, wfac=1.0, column_le=True):
         self._chk(self.lib.mi3d_set_options(self._h, int(target), int(solver), float(wmin), float(wfac), 1 if column_le else 0))
 
@@ -355,6 +364,8 @@ class Mi3dSolver:
         # (an older build in a kernel A/B experiment, MI3D_LIBRARY, has no such switch: it is off there, and asking for it fails)
         if int(getattr(s, 'view_profiles', 0)) or not getattr(self.lib.mi3d_set_view_profiles, 'stale', False):
             self.set_view_profiles(int(getattr(s, 'view_profiles', 0)))
+        if int(getattr(s, 'pixel_errors', 0)) or not getattr(self.lib.mi3d_set_pixel_errors, 'stale', False):      # (likewise)
+            self.set_pixel_errors(int(getattr(s, 'pixel_errors', 0)))
         self.set_options(s.target, s.solver, s.wmin, s.wfac, column_le)
         self.set_heating_estimator(int(getattr(s, 'heat_estimator', 0)))
         self.set_le_roulette(getattr(s, 'le_tau1', 0.0))
@@ -370,12 +381,14 @@ class Mi3dSolver:
         self.prepare()
 
     # ---- execution ---------------------------------------------------------------------------
-    def bind(self, rad_ptr=None, flux_ptr=None, stream=None, heat_ptr=None, wgt_ptr=None, prf_ptr=None):
+    def bind(self, rad_ptr=None, flux_ptr=None, stream=None, heat_ptr=None, wgt_ptr=None, prf_ptr=None, err_ptr=None):
         self._chk(self.lib.mi3d_bind_device_buffers(self._h, C.c_void_p(rad_ptr or 0), C.c_void_p(flux_ptr or 0), C.c_void_p(stream or 0)))
         self._chk(self.lib.mi3d_bind_heating_buffer(self._h, C.c_void_p(heat_ptr or 0)))
         self._chk(self.lib.mi3d_bind_weights_buffer(self._h, C.c_void_p(wgt_ptr or 0)))
         if prf_ptr or not getattr(self.lib.mi3d_bind_view_profiles_buffer, 'stale', False):      # (likewise, load_scene)
             self._chk(self.lib.mi3d_bind_view_profiles_buffer(self._h, C.c_void_p(prf_ptr or 0)))
+        if err_ptr or not getattr(self.lib.mi3d_bind_pixel_errors_buffer, 'stale', False):       # (likewise)
+            self._chk(self.lib.mi3d_bind_pixel_errors_buffer(self._h, C.c_void_p(err_ptr or 0)))
 
     def prepare(self):
         self._chk(self.lib.mi3d_prepare(self._h))
@@ -415,6 +428,43 @@ class Mi3dSolver:
         if out.size:
             self._chk(self.lib.mi3d_get_radiance(self._h, int(nphoton_total), _ptr(out)))
         return out
+
+    def radiance_se(self, nphoton_total):
+        """the standard error of every pixel of radiance(nphoton_total), float32 (nview, nyr, nxr), from the histories of the runs since the
+        last reset (include/mi3d.h: mi3d_get_radiance_se); needs set_pixel_errors(1) and a run on a backward route"""
+        out = np.zeros(self._shape_rad, dtype=np.float32)
+        self._chk(self.lib.mi3d_get_radiance_se(self._h, int(nphoton_total), _ptr(out)))
+        return out
+
+    def run_until(self, se_max, relative=False, max_histories=1 << 30, seed=1, chunk=None):
+        """run the job loaded, from a reset, until its image is as quiet as asked: chunks of histories at offsets that continue the id range
+        [0, N) -- the normalisation rule of radiance() --, every chunk a multiple of the number of pixels, until the largest standard error
+        of a pixel (radiance_se) is at most <se_max>, or <se_max> times the pixel's radiance with relative=True, or until the next chunk
+        would pass <max_histories>.  Returns N: radiance(N) and radiance_se(N) are the results, those of one run(N, seed).  <chunk>: the
+        histories of a chunk (rounded up to a multiple of the pixels; default 1024 a pixel).  Single process; needs set_pixel_errors(1)"""
+        s = self.scene
+        npix = s.nview*s.nyr*s.nxr
+        if npix < 1 or not (se_max >= 0.0):
+            raise ValueError('Error [Mi3dSolver]: run_until needs an image and <se_max> >= 0.')
+        per = max(1, -(-int(chunk)//npix)) if chunk else 1024
+        nmax = (int(max_histories)//npix)*npix
+        if nmax < npix:
+            raise ValueError('Error [Mi3dSolver]: <max_histories=%d> is less than one history a pixel (%d pixels).' % (max_histories, npix))
+        self.reset()
+        n = 0
+        while n < nmax:
+            nb = min(per*npix, nmax-n)
+            self.run(nb, seed=seed, offset=n)
+            n += nb
+            se = self.radiance_se(n)
+            if n < 2*npix:
+                continue                       # (a pixel with one history reads 0: no error is known yet)
+            if relative:
+                if np.all(se <= se_max*np.abs(self.radiance(n))):
+                    break
+            elif float(se.max()) <= se_max:
+                break
+        return n
 
     def weights_shape(self):
         """(npix, nvox, nz, nsfc) of the emission weights' tally for the scene loaded: K_raw is [npix][nvox + nz + nsfc] float64"""

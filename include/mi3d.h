@@ -405,6 +405,39 @@ int mi3d_set_view_profiles(mi3d_solver *h, int on);
 int mi3d_bind_view_profiles_buffer(mi3d_solver *h, void *raw);
 int mi3d_get_view_profiles(mi3d_solver *h, uint64_t nphoton_total, float *weight, float *contribution);
 
+/* Per-pixel standard errors of the backward route, from one run (the project's namelist key Rad_mserr = 1).  Every
+ * history of the backward route scores in exactly one pixel, pixel id mod npix, and the histories of a pixel are independent and
+ * identically distributed: the standard error of a pixel's mean follows from the sum of its scores and the sum of their squares.
+ *   Switch     mi3d_set_pixel_errors: 0 (default) nothing of this runs -- kernels, names and results are those of the route without
+ *              it, and the library's tally is freed; 1: mi3d_run serves thermal radiance jobs that run backwards through the plain
+ *              camera build (mi3d_set_camera_method 1) or the plain satellite-view build (mi3d_set_view_method 1), every refusal of
+ *              those routes included.  With 1, mi3d_run returns MI3D_EUNSUP and names this switch together with
+ *              mi3d_set_emission_weights 1 or mi3d_set_view_profiles 1 (their builds are at their register limits), on a flux or
+ *              heating-rate job, and on every forward route (mi3d_set_camera_method 0 and mi3d_set_view_method 0: one photon's local
+ *              estimates land in many pixels, so a pixel's contributions are not independent samples).  Anything but 0 or 1 is
+ *              MI3D_EINVAL.  mi3d_last_kernel: "k_backward<C,S> [thermal]" (cameras), "k_backward<C,V,S> [thermal]" (views).  The
+ *              debug entries ignore the switch.
+ *   Tally      When a history ends, the kernel forms s = score * Src_flx (float64: the float32 terms of the score summed in float64,
+ *              times the float32 Src_flx) and adds it to rad[pixel]; mi3d_debug_backward and mi3d_debug_backward_views write the same
+ *              number to score_out.  With the switch on the same place also adds s * s to rad2[pixel], float64, a tally of the shape
+ *              of rad.  It takes the path s takes: summed per workgroup in LDS for images of up to 1024 pixels (half the plain build's
+ *              2048: two sums per pixel in the same bytes), in a register beside the tile hand-out's, or by a global atomic.  The
+ *              score, the Philox sequence, the hand-out and rad are those of the route: the radiance of a run is that of the run
+ *              without the switch up to the order of its float64 sums.  Raw sums add over id ranges, launches and ranks exactly as
+ *              rad does; mi3d_reset zeroes rad2.  mi3d_bind_pixel_errors_buffer: a caller-owned device buffer [npix] float64 for an
+ *              all-reduce (NULL: the library's own, made and zeroed by the next run).
+ *   Read-out   mi3d_get_radiance_se: for pixel p with n = the number of ids in [0, nphoton_total) that map to p (the rule of
+ *              mi3d_get_radiance on this route)
+ *                  se[p] = sqrt( max(rad2[p] - rad[p]^2 / n, 0) / (n (n - 1)) )
+ *              the standard error of the mean mi3d_get_radiance returns, in its units; float64 on the device, rounded to float32
+ *              once; 0 where n < 2.  out is [npix].  The difference cancels where a pixel's scores hardly differ: rounding may
+ *              turn it negative, hence the clamp at 0, and with float64 sums of float32-born scores an se below about 1e-6 |mean| is
+ *              rounding, not noise.  MI3D_ESTATE while the switch is off or when no run with the switch on has happened since the
+ *              last mi3d_reset.  mi3d_get_radiance and mi3d_stats_add are untouched: they see rad alone. */
+int mi3d_set_pixel_errors(mi3d_solver *h, int on);
+int mi3d_bind_pixel_errors_buffer(mi3d_solver *h, void *rad2_sum);
+int mi3d_get_radiance_se(mi3d_solver *h, uint64_t nphoton_total, float *out);
+
 /* Job options = 1st/2nd CLI arguments and keys Wld_mtarget, Flx_mflx, Pho_wmin
  * (er3t/rtm/mca/mcarats.py:267-287,450-454; er3t/rtm/mca/mca_inp.py:196-198).
  *   target   MI3D_TARGET_FLUX | MI3D_TARGET_RADIANCE (bit-or of both is allowed); MI3D_TARGET_FLUX | MI3D_TARGET_HEAT is the
@@ -501,7 +534,7 @@ int mi3d_sync(mi3d_solver *h);
  * analytic phase functions (er3t's default scene), 1: a second 3-D constituent, 2: the general mixture (several 1-D constituents,
  * tabulated phase functions staged in LDS) --, "k_transport<COUNT,MARCH,FLUX,P3D>": the general kernel (flux together with radiance,
  * more than two 3-D constituents, tables too large for the LDS, kernel choice 1); "k_backward<COUNT> [thermal]": the backward route of
- * mi3d_set_camera_method 1 ("k_backward<COUNT,V> [thermal]": of mi3d_set_view_method 1; "k_backward<COUNT,V,P> [thermal]": with mi3d_set_view_profiles 1), whatever mi3d_set_kernel says -- "batch_log2" is the one tuning knob it reads (ids per launch; a launch is
+ * mi3d_set_camera_method 1 ("k_backward<COUNT,V> [thermal]": of mi3d_set_view_method 1; "k_backward<COUNT,V,P> [thermal]": with mi3d_set_view_profiles 1; "k_backward<COUNT,S> [thermal]" and "k_backward<COUNT,V,S> [thermal]": either with mi3d_set_pixel_errors 1), whatever mi3d_set_kernel says -- "batch_log2" is the one tuning knob it reads (ids per launch; a launch is
  * min(ids / 256, what is resident at once: 5 per CU, 4 in the counting build) workgroups of 256 lanes, every lane walks its ids with a fixed stride); "" before the first launch).  For logs and
  * measurements (bench.py, profiles/): results do not depend on it. */
 const char *mi3d_last_kernel(mi3d_solver *h);

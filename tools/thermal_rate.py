@@ -36,6 +36,13 @@ Leg 'prf' (DESIGN.md 5.16): the image of the 'sat' leg by backward Monte Carlo u
 (view_profiles) off, then on, at 8 and at 32 histories per pixel and launch: 16 batches each over disjoint id ranges, three times; histories
 per second and kernel time.  Under MI3D_LIBRARY (an older build of the library) the rows with the profiles off alone.
     python tools/thermal_rate.py --legs prf
+Leg 'err' (DESIGN.md 5.17): the plain backward builds with the per-pixel standard errors (pixel_errors) off, then on -- the image of the 'sat'
+leg at 8 and at 32 histories per pixel and launch under the default hand-out and under the plain stride ("bwd_chunk" 0: two atomics a
+history), the sixteen sensors of the 'bwd' leg (both sums per workgroup in LDS) and one all-sky camera of 64 x 64 pixels on the ground
+(4096 pixels: two global atomics a history): 16 batches each over disjoint id ranges, three times; histories per second, kernel time and,
+with the switch on, the mean relative standard error of a pixel from the histories of the last batch.  Under MI3D_LIBRARY (an older build
+of the library) the rows with the switch off alone.
+    python tools/thermal_rate.py --legs err
 """
 
 import argparse
@@ -175,6 +182,47 @@ def profiles_rows(sol, name, s, per_pixels=(8, 32), nb=16, reps=3):
     return rows
 
 
+def errors_rows(sol, name, s, n_cam, per_pixels=(8, 32), nb=16, reps=3):
+    """the 'err' leg: the plain backward builds with the per-pixel standard errors off, then on; nb batches over disjoint id
+    ranges, `reps` times each.  An older build of the library (MI3D_LIBRARY) gives the 'off' rows alone"""
+    sat = dataclasses.replace(s, view_the=[180.0, 135.0], view_phi=[0.0, 0.0], view_zloc=[1.0e6, 1.0e6], nxr=s.nx, nyr=s.ny, view_method=1)
+    sky = dataclasses.replace(pyrgeometers(s, -1, n=1), nxr=64, nyr=64, cam_mpmap=1, cam_mrproj=0, cam_umax=[90.0], cam_vmax=[90.0], cam_qmax=[90.0],
+                              cam_method=1)
+    jobs = [('sat', sat, pp*2*s.nx*s.ny, chunk, dict(per_pixel=pp, bwd_chunk=chunk)) for pp in per_pixels for chunk in (-1, 0)]
+    jobs += [('bwd', dataclasses.replace(pyrgeometers(s, -1), cam_method=1), n_cam, -1, dict(pixels=16)), ('sky', sky, n_cam, -1, dict(pixels=4096))]
+    rows = []
+    have = not getattr(sol.lib.mi3d_set_pixel_errors, 'stale', False)
+    try:
+        for tag, sc, n, chunk, extra in jobs:
+            sol.set_tuning(bwd_chunk=chunk)
+            for on in ((0, 1) if have else (0,)):
+                sol.load_scene(dataclasses.replace(sc, pixel_errors=on))
+                sol.reset(); sol.run(n, seed=1); sol.sync()                  # warm-up
+                for rep in range(reps):
+                    ms_all, mean = 0.0, 0.0
+                    for b in range(nb):
+                        sol.reset()
+                        sol.run(n, seed=2, offset=b*n)
+                        sol.sync()
+                        ms_all += sol.timing()[0]
+                        mean += float(sol.radiance(n).mean())/nb
+                    t = ms_all*1e-3
+                    row = dict(scene=name, target='%s_errors' % tag if on else '%s_plain' % tag, kernel=sol.kernel_name(), histories_per_batch=n, batches=nb,
+                               rep=rep, histories_per_s=float(nb*n/t), kernel_s=float(t), image_mean=mean, **extra)
+                    if on:
+                        r, se = sol.radiance(n).astype(np.float64), sol.radiance_se(n).astype(np.float64)
+                        row.update(rel_se_mean=float((se[r > 0.0]/r[r > 0.0]).mean()))
+                    rows.append(row)
+                    print(json.dumps(row), flush=True)
+    finally:
+        sol.set_tuning(bwd_chunk=-1)
+        if have:
+            sol.set_pixel_errors(False)
+        sol.set_view_method('forward')
+        sol.set_camera_method('forward')
+    return rows
+
+
 def weights_rows(sol, name, s, n, nb=16):
     """the 'wgt' leg: the sensors of scene s by the backward route with the emission weights off, then on, nb batches each
     over the same id ranges; the counting build, once, for the absorbing cell steps of a history (one float64 atomic each with the switch on)"""
@@ -249,6 +297,10 @@ def main():
             if target == 'prf':
                 sol.set_kernel(general=False)
                 rows += profiles_rows(sol, name, thermal(les_scene(target='radiance', **kw), lev))
+                continue
+            if target == 'err':
+                sol.set_kernel(general=False)
+                rows += errors_rows(sol, name, thermal(les_scene(target='radiance', **kw), lev), int(a.histories)//16*16)
                 continue
             if target == 'wgt':
                 sol.set_kernel(general=False)
