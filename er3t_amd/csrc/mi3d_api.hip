@@ -82,8 +82,8 @@ constexpr double kWgtMaxElems = 2147483648.0;   // elements of the emission weig
 constexpr double kPrfMaxElems = 2147483648.0;   // elements of the view profiles' tally npix x (nz + 1) x 2 served (mi3d_set_view_profiles)
 
 // The six builds of the backward route (mi3d_kernel_backward.hip): k_backward, k_backward_w, k_backward_v, k_backward_vp, k_backward_s,
-// k_backward_vs ...
-enum class BwdRoute { Camera = 0, Weights = 1, Views = 2, Profiles = 3, CameraErrors = 4, ViewsErrors = 5 };
+// k_backward_vs ... and the two with sunlight (mi3d_set_view_sunlight 1): k_backward_vn, k_backward_vns
+enum class BwdRoute { Camera = 0, Weights = 1, Views = 2, Profiles = 3, CameraErrors = 4, ViewsErrors = 5, ViewsSun = 6, ViewsSunErrors = 7 };
 // ... and what the runtime said of one of them: workgroups resident per CU for `lds` bytes of dynamic LDS (0: not asked yet)
 struct BwdCap { int blocks = 0, counting = -1; size_t lds = 0; };
 
@@ -140,9 +140,13 @@ struct mi3d_solver {
     int bwd_chunk = -1;
     int bwd_chunk_last = 0;
     DevBuf<float> d_bwd_start;
-    BwdCap bwd_cap[6];               // per BwdRoute: the resident workgroups per CU of the build launched last (backward_resident)
+    BwdCap bwd_cap[8];               // per BwdRoute: the resident workgroups per CU of the build launched last (backward_resident)
     bool sat_backward() const { return view_method == 1 && cam_method == 0 && rad_kind == 2; }           // is the job sent to k_backward_v?
+    // ... and the sunlight term of a solar+thermal job's satellite views (mi3d_set_view_sunlight 1): the switch
+    int view_sunlight = 0;
+    bool sun_backward() const { return view_sunlight == 1 && src_mtype == 2 && sat_backward(); }         // is the job sent to k_backward_vn?
     bool backward() const {                                                                               // does the read-out divide by the pixels' own counts?
+        if (sun_backward() && nview > 0) return true;
         return src_mtype == 3 && nview > 0 && ((cam_method == 1 && rad_kind == 1) || sat_backward());
     }
     // per-cell emission weights of the backward route (mi3d_set_emission_weights 1): K_raw[npix][ncell], the library's own
@@ -1212,6 +1216,17 @@ int mi3d_set_view_method(mi3d_solver *h, int method) {
     return MI3D_OK;
 }
 
+int mi3d_set_view_sunlight(mi3d_solver *h, int on) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (on != 0 && on != 1) return fail(MI3D_EINVAL, "view sunlight %d (0: off, 1: the sunlight term of the backward route's satellite views)", on);
+    if (on == h->view_sunlight) return MI3D_OK;
+    HIPCHK(sync_main(h));   // (as every call that changes what the kernels work on)
+    h->view_sunlight = on;
+    h->dirty_bwd = true;
+    return MI3D_OK;
+}
+
 int mi3d_set_emission_weights(mi3d_solver *h, int on) {
     int rc = check_handle(h);
     if (rc) return rc;
@@ -1483,7 +1498,7 @@ int mi3d_prepare(mi3d_solver *h) {
         h->dirty_thermal = false;
         h->dirty_bwd = true;
     }
-    if ((h->cam_method == 1 || h->view_method == 1) && h->src_mtype == 3 && h->dirty_bwd) {
+    if ((h->cam_method == 1 || h->view_method == 1) && (h->src_mtype == 3 || (h->src_mtype == 2 && h->view_sunlight)) && h->dirty_bwd) {
         if ((rc = build_backward_cells(h))) return rc;
         h->dirty_bwd = false;
     }
@@ -1984,7 +1999,8 @@ static void name_route(mi3d_solver *h, const RunPlan &plan, bool lists, uint64_t
     const int c = plan.build.counting ? 1 : 0, p3d = plan.build.p3d ? 1 : 0;
     char nm[96];
     const bool hpath = plan.build.hpath;
-    if (plan.loop == Loop::Backward && h->sat_backward() && h->pixel_errors) snprintf(nm, sizeof(nm), "k_backward<%d,V,S> [thermal]", c);
+    if (plan.loop == Loop::Backward && h->sun_backward()) snprintf(nm, sizeof(nm), h->pixel_errors ? "k_backward<%d,V,N,S> [solar+thermal]" : "k_backward<%d,V,N> [solar+thermal]", c);
+    else if (plan.loop == Loop::Backward && h->sat_backward() && h->pixel_errors) snprintf(nm, sizeof(nm), "k_backward<%d,V,S> [thermal]", c);
     else if (plan.loop == Loop::Backward && h->pixel_errors) snprintf(nm, sizeof(nm), "k_backward<%d,S> [thermal]", c);
     else if (plan.loop == Loop::Backward && h->sat_backward() && h->view_profiles) snprintf(nm, sizeof(nm), "k_backward<%d,V,P> [thermal]", c);
     else if (plan.loop == Loop::Backward && h->sat_backward()) snprintf(nm, sizeof(nm), "k_backward<%d,V> [thermal]", c);
@@ -2446,10 +2462,23 @@ static hipError_t launch_pre(mi3d_solver *h, const RunPlan &plan, int pset, bool
 // What it serves: Src_mtype = 3, a radiance job of the 3-D solver over Lambertian surfaces.  The switch of the cameras
 // (mi3d_set_camera_method 1) serves cameras and point radiometers (Rad_mrkind = 1), with or without emission weights; the switch of the
 // satellite views (sat: mi3d_set_view_method 1) the views of mi3d_set_views (Rad_mrkind = 2), without them.
+// With mi3d_set_view_sunlight 1 the satellite views' route serves Src_mtype = 2 instead, and nothing else.
 // Everything else: MI3D_EUNSUP, with the reason.
 static int backward_unsupported(const mi3d_solver *h, bool sat) {
+    if (h->view_sunlight) {
+        // the sunlight term (mi3d_set_view_sunlight 1, Rad_mvsun=1) belongs to the satellite views of a solar+thermal job
+        const char *no = h->src_mtype == 1 ? "a solar job (Src_mtype=1): the switch belongs to the mixed source, a pure solar image is a solar+thermal job with a cold atmosphere"
+                         : h->src_mtype == 3 ? "a thermal job (Src_mtype=3): there is no sun, run it without the switch"
+                         : h->rad_kind != 2 ? "cameras and point radiometers (Rad_mrkind=1): the term belongs to the satellite views (Rad_mrkind=2)"
+                         : !sat || h->view_method != 1 ? "mi3d_set_view_method 0 or mi3d_set_camera_method 1 (it needs Rad_mvbwd=1): the term belongs to the backward route for satellite views"
+                         : h->view_profiles ? "view profiles (mi3d_set_view_profiles 1): the weighting functions are per unit Planck radiance, and the sun has no row"
+                         : h->emis_weights ? "emission weights (mi3d_set_emission_weights 1): the sun is no cell"
+                         : !(h->src_the - 0.5 * std::max(h->src_qmax, 0.0) > 90.0) ? "a sun from below or on the horizon (Src_the - Src_qmax / 2 <= 90)"
+                         : nullptr;
+        if (no) return fail(MI3D_EUNSUP, "the sunlight term of the backward satellite views (mi3d_set_view_sunlight 1, Rad_mvsun=1) does not serve %s", no);
+    }
     const char *why = h->src_mtype == 1 ? "a solar job (Src_mtype=1): the sun needs a local estimate of its own"
-                      : h->src_mtype == 2 ? "a solar+thermal job (Src_mtype=2): the sun needs a local estimate of its own"
+                      : h->src_mtype == 2 && !h->view_sunlight ? "a solar+thermal job (Src_mtype=2): the sun needs a local estimate of its own (satellite views have one: mi3d_set_view_sunlight 1, Rad_mvsun=1)"
                       : !(h->target & MI3D_TARGET_RADIANCE) || (h->target & MI3D_TARGET_FLUX) ? (sat ? "a flux or heating-rate job: the route serves radiance (satellite images) alone"
                                                                                                       : "a flux or heating-rate job: the route serves radiance (cameras) alone")
                       : h->rad_kind != (sat ? 2 : 1) ? (sat ? "cameras and point radiometers (Rad_mrkind=1): their switch is mi3d_set_camera_method (Rad_mbwd)"
@@ -2503,6 +2532,16 @@ static void fill_backward_views(const mi3d_solver *h, BwdSat &S, float *start_ou
     S.start_out = start_out;
 }
 
+// What the builds with sunlight receive beside that (mi3d_set_view_sunlight 1): the sun of fill_scene
+static void fill_backward_sun(const mi3d_solver *h, BwdSun &N) {
+    const double pi = 3.14159265358979323846, th = h->src_the * pi / 180.0, ph = h->src_phi * pi / 180.0;
+    std::memset(&N, 0, sizeof(N));
+    N.sdx = (float)(std::sin(th) * std::cos(ph)); N.sdy = (float)(std::sin(th) * std::sin(ph)); N.sdz = (float)std::cos(th);
+    N.mu0 = std::fabs(N.sdz);
+    N.F = (float)h->src_fsol;
+    N.cos_cone = h->src_qmax <= 0.0 ? 1.0f : (float)std::cos(0.5 * h->src_qmax * pi / 180.0);
+}
+
 // The one place that names the builds of the histories: the kernel of (route, counting, debug), as the runtime takes it for a launch and
 // for an occupancy query.  The weights, profiles and errors builds have no debug form (nullptr); the debug forms do not count
 static const void *backward_build(BwdRoute route, bool counting, bool debug) {
@@ -2525,23 +2564,31 @@ static const void *backward_build(BwdRoute route, bool counting, bool debug) {
     case BwdRoute::ViewsErrors:
         if (debug) return nullptr;
         return counting ? (const void *)k_backward_vs<true> : (const void *)k_backward_vs<false>;
+    case BwdRoute::ViewsSun:
+        if (debug) return (const void *)k_backward_vn<false, true>;
+        return counting ? (const void *)k_backward_vn<true, false> : (const void *)k_backward_vn<false, false>;
+    case BwdRoute::ViewsSunErrors:
+        if (debug) return nullptr;
+        return counting ? (const void *)k_backward_vns<true> : (const void *)k_backward_vns<false>;
     }
     return nullptr;
 }
 
 // One launch.  The kernel arguments in the order of the entry points: (A, seed, id0, n), then (dir_out, score_out) for the cameras,
 // (W) for the weights build, (dir_out, score_out, S) for the views, (S, P) for the views' profiles build, (E) and (S, E) for the cameras'
-// and the views' errors builds
+// and the views' errors builds, (dir_out, score_out, S, N) and (S, E, N) for the views with sunlight
 static hipError_t backward_launch(BwdRoute route, bool counting, bool debug, unsigned grid, size_t lds, hipStream_t stream, DevBackward A, uint64_t seed,
                                   uint64_t id0, uint64_t n, float *dir_out, double *score_out, BwdWeights W, BwdSat S, BwdProfiles P,
-                                  BwdErrors E = BwdErrors{}) {
+                                  BwdErrors E = BwdErrors{}, BwdSun N = BwdSun{}) {
     const void *kernel = backward_build(route, counting, debug);
     if (!kernel) return hipErrorInvalidValue;
     void *cam[] = {&A, &seed, &id0, &n, &dir_out, &score_out}, *wgt[] = {&A, &seed, &id0, &n, &W}, *sat[] = {&A, &seed, &id0, &n, &dir_out, &score_out, &S},
-         *prf[] = {&A, &seed, &id0, &n, &S, &P}, *cerr[] = {&A, &seed, &id0, &n, &E}, *verr[] = {&A, &seed, &id0, &n, &S, &E};
+         *prf[] = {&A, &seed, &id0, &n, &S, &P}, *cerr[] = {&A, &seed, &id0, &n, &E}, *verr[] = {&A, &seed, &id0, &n, &S, &E},
+         *vsun[] = {&A, &seed, &id0, &n, &dir_out, &score_out, &S, &N}, *vsune[] = {&A, &seed, &id0, &n, &S, &E, &N};
     return hipLaunchKernel(kernel, dim3(grid), dim3(256),
                            route == BwdRoute::Camera ? cam : route == BwdRoute::Weights ? wgt : route == BwdRoute::Views ? sat
-                           : route == BwdRoute::Profiles ? prf : route == BwdRoute::CameraErrors ? cerr : verr, lds, stream);
+                           : route == BwdRoute::Profiles ? prf : route == BwdRoute::CameraErrors ? cerr : route == BwdRoute::ViewsErrors ? verr
+                           : route == BwdRoute::ViewsSun ? vsun : vsune, lds, stream);
 }
 
 // Workgroups of the build that are resident on the device at once.  The weights, view, profiles and errors builds ask the runtime, once per (route, LDS
@@ -2557,7 +2604,7 @@ static int backward_resident(mi3d_solver *h, BwdRoute route, size_t lds, uint64_
         if (eo != hipSuccess || nb < 1) {
             if (route == BwdRoute::Weights) return fail(MI3D_EDEVICE, "emission weights: no workgroup of the weights build fits a CU with %zu bytes of LDS", lds);
             if (route == BwdRoute::Profiles) return fail(MI3D_EDEVICE, "view profiles: no workgroup of the profiles build fits a CU with %zu bytes of LDS", lds);
-            if (route == BwdRoute::CameraErrors || route == BwdRoute::ViewsErrors)
+            if (route == BwdRoute::CameraErrors || route == BwdRoute::ViewsErrors || route == BwdRoute::ViewsSunErrors)
                 return fail(MI3D_EDEVICE, "pixel errors: no workgroup of the errors build fits a CU with %zu bytes of LDS", lds);
             return fail(MI3D_EDEVICE, "backward Monte Carlo for satellite views: no workgroup fits a CU with %zu bytes of LDS", lds);
         }
@@ -2571,7 +2618,9 @@ static int run_backward(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_
     const bool sat = h->sat_backward(), wgt = h->emis_weights != 0;
     const bool prf = sat && h->view_profiles != 0;
     const bool var = h->pixel_errors != 0;     // (never with wgt or prf: mi3d_run refuses)
-    const BwdRoute route = prf ? BwdRoute::Profiles : sat ? (var ? BwdRoute::ViewsErrors : BwdRoute::Views) : wgt ? BwdRoute::Weights
+    const bool sun = h->sun_backward();        // (never with wgt or prf: backward_unsupported refuses)
+    const BwdRoute route = sun ? (var ? BwdRoute::ViewsSunErrors : BwdRoute::ViewsSun)
+                           : prf ? BwdRoute::Profiles : sat ? (var ? BwdRoute::ViewsErrors : BwdRoute::Views) : wgt ? BwdRoute::Weights
                            : var ? BwdRoute::CameraErrors : BwdRoute::Camera;
     int rc = backward_unsupported(h, sat);
     if (rc) return rc;
@@ -2625,6 +2674,8 @@ static int run_backward(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_
         E.rad2 = h->err_ptr();
         h->err_ran = true;
     }
+    BwdSun N{};
+    if (sun) fill_backward_sun(h, N);
     BwdSat S{};
     uint64_t ntile = 0;
     if (sat) {
@@ -2664,7 +2715,7 @@ static int run_backward(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_
         HIPCHK(hipEventCreate(&e0));
         hipError_t err = hipEventCreate(&e1);
         if (err == hipSuccess) err = hipEventRecord(e0, h->stream);
-        if (err == hipSuccess) err = backward_launch(route, h->counting != 0, false, grid, lds, h->stream, A, seed, off, nb, nullptr, nullptr, W, Sl, P, E);
+        if (err == hipSuccess) err = backward_launch(route, h->counting != 0, false, grid, lds, h->stream, A, seed, off, nb, nullptr, nullptr, W, Sl, P, E, N);
         if (err == hipSuccess) err = hipEventRecord(e1, h->stream);
         if (err != hipSuccess) {
             (void)hipEventDestroy(e0);
@@ -2713,6 +2764,7 @@ int mi3d_run(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_of
                                  "with mi3d_set_views, mi3d_set_camera_method 0, mi3d_set_emission_weights 0): not with %s",
                     h->view_method != 1 ? "mi3d_set_view_method 0" : h->rad_kind != 2 ? "cameras (mi3d_set_cameras)" : h->cam_method != 0 ? "mi3d_set_camera_method 1"
                                                                                                                       : "mi3d_set_emission_weights 1");
+    if (h->view_sunlight && (rc = backward_unsupported(h, h->sat_backward()))) return rc;   // (names mi3d_set_view_sunlight where the refusal is its own)
     if (h->view_method == 1 && h->rad_kind != 2) return backward_unsupported(h, true);   // (names the switch: it belongs to the views of mi3d_set_views)
     if (h->cam_method == 1 || h->view_method == 1) return run_backward(h, nphoton, seed, photon_offset);
     if (h->emis_weights)
@@ -3340,14 +3392,17 @@ static int debug_backward(mi3d_solver *h, bool sat, uint64_t seed, uint64_t id0,
     if (n > 0) {
         DevBackward A;
         BwdSat S{};
+        BwdSun N{};
+        const bool sun = sat && h->sun_backward();
+        if (sun) fill_backward_sun(h, N);
         if ((rc = fill_backward(h, A, sat))) return rc;
         if ((sat && (rc = h->d_bwd_start.alloc((size_t)3 * n))) || (rc = h->d_bwd_dir.alloc((size_t)3 * n)) || (rc = h->d_bwd_score.alloc(n))) return rc;
         if (sat) fill_backward_views(h, S, h->d_bwd_start.p);
         // (every slot is written by the history of its id: the hand-out reaches every id of [id0, id0 + n) whatever the grid)
         const int npix = h->nview * h->nxr * h->nyr;
         const size_t lds = backward_lds(npix, h->nz, h->nview, 1, backward_lds_sums(npix, true, S.jch > 0), false, sat);
-        HIPCHK(backward_launch(sat ? BwdRoute::Views : BwdRoute::Camera, false, true, (unsigned)((n + 255) / 256), lds, h->stream, A, seed, id0, (uint64_t)n,
-                               h->d_bwd_dir.p, h->d_bwd_score.p, BwdWeights{}, S, BwdProfiles{}));
+        HIPCHK(backward_launch(sun ? BwdRoute::ViewsSun : sat ? BwdRoute::Views : BwdRoute::Camera, false, true, (unsigned)((n + 255) / 256), lds, h->stream, A, seed, id0, (uint64_t)n,
+                               h->d_bwd_dir.p, h->d_bwd_score.p, BwdWeights{}, S, BwdProfiles{}, BwdErrors{}, N));
         if (sat) HIPCHK(hipMemcpyAsync(start_out, h->d_bwd_start.p, (size_t)3 * n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipMemcpyAsync(dir_out, h->d_bwd_dir.p, (size_t)3 * n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipMemcpyAsync(score_out, h->d_bwd_score.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));

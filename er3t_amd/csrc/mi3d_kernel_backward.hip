@@ -23,6 +23,11 @@
 //   k_backward_s<COUNT>, k_backward_vs<COUNT>   the histories of k_backward and of k_backward_v with mi3d_set_pixel_errors 1 (DESIGN.md
 //                      §5.17): the square of every score that enters rad[pixel] is also added to rad2[pixel], float64, by the path the
 //                      score itself takes (LDS sums, the tile hand-out's register, global atomics)
+//   k_backward_vn<COUNT, DEBUG>, k_backward_vns<COUNT>   the histories of k_backward_v and of k_backward_vs for a solar+thermal job
+//                      (Src_mtype = 2) with mi3d_set_view_sunlight 1: every scattering and every surface reflection also
+//                      scores the sunlight it turns into the line of sight, times the transmittance of a ray from the event to the top.
+//                      The ray is flown by the trips of the same loop, one cell step each, and ends in closed form above the 3-D region.
+//                      The solar cone draws its direction from Philox blocks 2^31, 2^31 + 1, ... of the history, which the walk never reaches
 //   k_backward_norm    read-out: tally of pixel p / number of ids in [0, N) that map to p
 //   k_backward_norm_se   read-out of the standard error of that mean from rad and rad2
 //   k_backward_norm_rows   the same rule for the rows of K_raw, rounded to float32
@@ -94,6 +99,13 @@ struct BwdErrors {
     double *rad2;
 };
 
+// What only the builds with sunlight receive (mi3d_set_view_sunlight 1): the direction d in which sunlight travels
+// (sdz < 0), mu0 = |sdz|, F = Src_fsol and the cosine of the solar cone's half angle (>= 1: no cone).  The table of the vertical optical depth from a level to the top is LayerRec::tabove of the layers above
+// the 3-D region: it is in LDS with the layer table already
+struct BwdSun {
+    float sdx, sdy, sdz, mu0, F, cos_cone;
+};
+
 // One thread per cell, in the order of DevThermal's CDF (k_thermal_power): voxels in file order, layers, surface cells.
 __global__ void __launch_bounds__(256)
 k_backward_cells(const ThermalGrid G, int nxb, int nyb, const float *sfc2d, float albedo, const float *tmps2d, float2 *out) {
@@ -159,27 +171,29 @@ __device__ inline int bwd_wrap(const int i, const float d, const int n) {
     return j < 0 ? 0 : (j >= n ? n - 1 : j);
 }
 
-// The histories, single-sourced for all entry points: mi3d_kernel_backward_body.inc is the body of each, with WGT, SAT, PRF and VAR
-// constants of the entry point that includes it (and W, S, P, E the arguments of the builds that read them)
+// The histories, single-sourced for all entry points: mi3d_kernel_backward_body.inc is the body of each, with WGT, SAT, PRF, VAR and SUN
+// constants of the entry point that includes it (and W, S, P, E, N the arguments of the builds that read them)
 template <bool COUNT, bool DEBUG>
 __global__ void __launch_bounds__(256)
 k_backward(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, float *__restrict__ dir_out, double *__restrict__ score_out) {
-    constexpr bool WGT = false, SAT = false, PRF = false, VAR = false;
+    constexpr bool WGT = false, SAT = false, PRF = false, VAR = false, SUN = false;
     const BwdWeights W{};
     const BwdSat S{};
     const BwdProfiles P{};
     const BwdErrors E{};
+    const BwdSun N{};
 #include "mi3d_kernel_backward_body.inc"
 }
 
 template <bool COUNT>
 __global__ void __launch_bounds__(256)
 k_backward_w(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, const BwdWeights W) {
-    constexpr bool WGT = true, DEBUG = false, SAT = false, PRF = false, VAR = false;
+    constexpr bool WGT = true, DEBUG = false, SAT = false, PRF = false, VAR = false, SUN = false;
     float *const dir_out = nullptr; double *const score_out = nullptr;
     const BwdSat S{};
     const BwdProfiles P{};
     const BwdErrors E{};
+    const BwdSun N{};
 #include "mi3d_kernel_backward_body.inc"
 }
 
@@ -187,20 +201,22 @@ template <bool COUNT, bool DEBUG>
 __global__ void __launch_bounds__(256)
 k_backward_v(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, float *__restrict__ dir_out, double *__restrict__ score_out,
              const BwdSat S) {
-    constexpr bool WGT = false, SAT = true, PRF = false, VAR = false;
+    constexpr bool WGT = false, SAT = true, PRF = false, VAR = false, SUN = false;
     const BwdWeights W{};
     const BwdProfiles P{};
     const BwdErrors E{};
+    const BwdSun N{};
 #include "mi3d_kernel_backward_body.inc"
 }
 
 template <bool COUNT>
 __global__ void __launch_bounds__(256)
 k_backward_vp(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, const BwdSat S, const BwdProfiles P) {
-    constexpr bool WGT = false, DEBUG = false, SAT = true, PRF = true, VAR = false;
+    constexpr bool WGT = false, DEBUG = false, SAT = true, PRF = true, VAR = false, SUN = false;
     float *const dir_out = nullptr; double *const score_out = nullptr;
     const BwdWeights W{};
     const BwdErrors E{};
+    const BwdSun N{};
 #include "mi3d_kernel_backward_body.inc"
 }
 
@@ -222,21 +238,23 @@ k_backward_norm_profiles(const double *__restrict__ raw, float *__restrict__ out
 template <bool COUNT>
 __global__ void __launch_bounds__(256)
 k_backward_s(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, const BwdErrors E) {
-    constexpr bool WGT = false, DEBUG = false, SAT = false, PRF = false, VAR = true;
+    constexpr bool WGT = false, DEBUG = false, SAT = false, PRF = false, VAR = true, SUN = false;
     float *const dir_out = nullptr; double *const score_out = nullptr;
     const BwdWeights W{};
     const BwdSat S{};
     const BwdProfiles P{};
+    const BwdSun N{};
 #include "mi3d_kernel_backward_body.inc"
 }
 
 template <bool COUNT>
 __global__ void __launch_bounds__(256)
 k_backward_vs(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, const BwdSat S, const BwdErrors E) {
-    constexpr bool WGT = false, DEBUG = false, SAT = true, PRF = false, VAR = true;
+    constexpr bool WGT = false, DEBUG = false, SAT = true, PRF = false, VAR = true, SUN = false;
     float *const dir_out = nullptr; double *const score_out = nullptr;
     const BwdWeights W{};
     const BwdProfiles P{};
+    const BwdSun N{};
 #include "mi3d_kernel_backward_body.inc"
 }
 
@@ -255,6 +273,29 @@ k_backward_norm_se(const double *__restrict__ tally, const double *__restrict__ 
         se = (float)sqrt(ss / (nn * (nn - 1.0)));
     }
     out[p] = se;
+}
+
+// The histories of k_backward_v with the sunlight term of a solar+thermal job (mi3d_set_view_sunlight 1): the same body
+// with SUN.  (They stand behind every other history kernel so that the code of the kernels before them lies where it lay.)
+template <bool COUNT, bool DEBUG>
+__global__ void __launch_bounds__(256)
+k_backward_vn(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, float *__restrict__ dir_out, double *__restrict__ score_out,
+              const BwdSat S, const BwdSun N) {
+    constexpr bool WGT = false, SAT = true, PRF = false, VAR = false, SUN = true;
+    const BwdWeights W{};
+    const BwdProfiles P{};
+    const BwdErrors E{};
+#include "mi3d_kernel_backward_body.inc"
+}
+
+template <bool COUNT>
+__global__ void __launch_bounds__(256)
+k_backward_vns(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, const BwdSat S, const BwdErrors E, const BwdSun N) {
+    constexpr bool WGT = false, DEBUG = false, SAT = true, PRF = false, VAR = true, SUN = true;
+    float *const dir_out = nullptr; double *const score_out = nullptr;
+    const BwdWeights W{};
+    const BwdProfiles P{};
+#include "mi3d_kernel_backward_body.inc"
 }
 
 // The dynamic LDS of a launch of any build, in bytes: the host's statement of what the top of mi3d_kernel_backward_body.inc lays out, in

@@ -1,10 +1,11 @@
 // mi3d_kernel_backward_body.inc — the histories of the backward route, the one body of k_backward<COUNT, DEBUG> and k_backward_w<COUNT>
-// and k_backward_v<COUNT, DEBUG> and k_backward_vp<COUNT> and k_backward_s<COUNT> and k_backward_vs<COUNT> (mi3d_kernel_backward.hip
-// includes it inside each).  What it expects in scope:
-// COUNT, DEBUG, WGT, SAT, PRF, VAR (compile-time constants), the arguments A, seed, id0, n, dir_out, score_out, W (BwdWeights: read where WGT
+// and k_backward_v<COUNT, DEBUG> and k_backward_vp<COUNT> and k_backward_s<COUNT> and k_backward_vs<COUNT> and k_backward_vn<COUNT, DEBUG>
+// and k_backward_vns<COUNT> (mi3d_kernel_backward.hip includes it inside each).  What it expects in scope:
+// COUNT, DEBUG, WGT, SAT, PRF, VAR, SUN (compile-time constants), the arguments A, seed, id0, n, dir_out, score_out, W (BwdWeights: read where WGT
 // holds, the weights build of DESIGN.md §5.12), S (BwdSat: read where SAT holds, the satellite-view build of DESIGN.md §5.14), P
 // (BwdProfiles: read where PRF holds, the per-layer profiles of the satellite views, DESIGN.md §5.16) and E (BwdErrors: read where VAR
-// holds, the second tally of the per-pixel standard errors, DESIGN.md §5.17).
+// holds, the second tally of the per-pixel standard errors, DESIGN.md §5.17) and N (BwdSun: read where SUN holds, the sunlight term of a
+// solar+thermal job's satellite views, DESIGN.md §5.18).
     extern __shared__ double bwd_smem[];
     const int npix = A.nview * A.nxr * A.nyr;
     const bool tiles = SAT && S.jch > 0;                                     // the tile hand-out (mi3d_set_tuning "bwd_chunk" >= 1)
@@ -79,6 +80,18 @@
     uint32_t draw = 0;
     unsigned steps = 0;
 
+    // SUN: the sun ray of an event, flown by the same trips of the loop as the walk (DESIGN.md §5.18).  While `sun` holds, the DDA registers
+    // and ix, iy, k, ux, uy, uz are the ray's; the history's own cell, position in it and new direction wait in the s* registers
+    bool sun = false, sun_end = false;       // the ray is under way; the history ends when the ray has
+    int six = 0, siy = 0, sk = 0;
+    float spx = 0.0f, spy = 0.0f, spz = 0.0f, snx = 0.0f, sny = 0.0f, snz = 0.0f;
+    float sunc = 0.0f, sung = 0.0f;                   // the term's coefficient c in front of T, and g = c / F: what the history's weight has become on the ray
+    float stau = 0.0f, staumax = 0.0f;                // the ray's optical path so far, the path beyond which the term is dropped
+    float sdx = 0.0f, sdy = 0.0f, sdz = -1.0f;        // the direction d' in which the event's sunlight travels
+    unsigned ssteps = 0;
+    uint32_t sdraw = 0;                      // the history's cone draws: Philox blocks 2^31 + sdraw, which the walk never reaches
+    const int k3hi = A.nz3 > 0 ? A.k3lo + A.nz3 : 0;  // (SUN) the layers from here up are horizontally uniform to the top: their optical depth is tabove
+
     // the DDA anew from a position inside the cell (px, py from the low faces, pz from the layer's bottom) and the direction
     auto set_dda = [&](const float px, const float py, const float pz, const float dzk) {
         const float aix = frcp(floor_abs(ux)), aiy = frcp(floor_abs(uy));
@@ -101,6 +114,82 @@
     auto roulette = [&](const float u) {
         if (u * A.wfac < w) { w = A.wfac; return true; }
         return false;
+    };
+
+    // SUN: the direction d' of an event's sunlight: the sun's, or one drawn uniformly in solid angle inside the solar cone about it (the
+    // forward launch's distribution: mu_cone = 1 - u (1 - cos_cone), rotate_dir)
+    auto sun_dir = [&]() {
+        sdx = N.sdx; sdy = N.sdy; sdz = N.sdz;
+        if (N.cos_cone < 1.0f) {
+            float q0, q1, q2, q3;
+            draw4(seed, id, 0x80000000u | sdraw++, q0, q1, q2, q3);
+            rotate_dir(sdx, sdy, sdz, 1.0f - q0 * (1.0f - N.cos_cone), q1);   // (sdz < 0 stays: the host refuses a cone that reaches the horizon)
+        }
+    };
+    // SUN: the event's term sunc T(r -> top along -d') from the position (px, py, pz) inside cell (ix, iy, k), after the history's new
+    // direction stands in ux, uy, uz.  Above the 3-D region the answer is closed and scored here; otherwise the lane goes over to the ray
+    // (true: the caller leaves the next flight to the ray's end).  A ray is flown while g e^{-tau} >= kBwdWeightEnd, the weight below which
+    // the walk ends a history: a rule that does not look at F, so that the tally is affine in F.  No term, no ray: none with F = 0
+    auto sun_start = [&](const float px, const float py, const float pz, const bool end_after) {
+        if (!(sunc > 0.0f) || !(sung > kBwdWeightEnd)) return false;
+        const LayerRec &L0 = slay[k];
+        if (k >= k3hi) {
+            score += (double)(sunc * fexp_neg(fmaf(L0.bt, L0.dz - pz, L0.tabove) * frcp(-sdz)));
+            return false;
+        }
+        staumax = __logf(sung * (1.0f / kBwdWeightEnd));
+#ifdef MI3D_BWD_SUN_NESTED
+        {   // the measurement build of DESIGN.md §5.18's A/B (make EXTRA=-DMI3D_BWD_SUN_NESTED): the whole ray here, in a loop of its own, with the same arithmetic
+            const float vx = -sdx, vy = -sdy, vz = -sdz;
+            const float bix = frcp(floor_abs(vx)), biy = frcp(floor_abs(vy)), biz = frcp(floor_abs(vz));
+            const float qx = A.dx * bix, qy = A.dy * biy;
+            float hx = (vx > 0.0f ? A.dx - px : px) * bix, hy = (vy > 0.0f ? A.dy - py : py) * biy, hz = (L0.dz - pz) * biz;
+            int jx = ix, jy = iy, kk = k;
+            float tau = 0.0f;
+            unsigned ns = 0;
+            bool drop = false;
+            for (;;) {
+                const LayerRec &L = slay[kk];
+                const bool in3d = (L.flags & kLayIn3d) != 0;
+                const int k3 = kk - A.k3lo;
+                float ks = 0.0f;
+                float2 cell;
+                if (in3d) {
+                    const float4 r = A.vrec[(size_t)jy * A.vrow_f4 + (size_t)jx * A.vcol_f4 + k3];
+                    cell = A.cells[((size_t)k3 * A.ny + jy) * A.nx + jx];
+                    ks = r.z;
+                    for (int ip = 1; ip < A.np3d; ++ip) ks += A.csca[(((size_t)jy * A.nx + jx) * A.nz3 + k3) * A.np3d + ip].x;
+                } else cell = A.cells[A.nvox + kk];
+                for (int ip = 0; ip < A.np1d; ++ip) ks += L.ks1d[ip];
+                const float ds = in3d ? fminf(fminf(hx, hy), hz) : hz;
+                tau = fmaf(cell.x + ks, ds, tau); ns++;
+                if (COUNT) { c_steps++; if (in3d) c_steps3d++; }
+                const bool fz = !in3d || (hz <= hx && hz <= hy), fx = !fz && hx <= hy;
+                hx -= ds; hy -= ds; hz -= ds;
+                if (!in3d) {
+                    if (hx < 0.0f) { const float nc = floorf(-hx / qx) + 1.0f; hx = fminf(fmaxf(fmaf(nc, qx, hx), 0.0f), qx); jx = bwd_wrap(jx, vx > 0.0f ? nc : -nc, A.nx); }
+                    if (hy < 0.0f) { const float nc = floorf(-hy / qy) + 1.0f; hy = fminf(fmaxf(fmaf(nc, qy, hy), 0.0f), qy); jy = bwd_wrap(jy, vy > 0.0f ? nc : -nc, A.ny); }
+                }
+                if (tau > staumax) { drop = true; break; }
+                if (ns >= kBwdMaxCells) { drop = true; atomicAdd(A.capped, 1ull); break; }
+                if (fx) { hx = qx; jx += vx > 0.0f ? 1 : -1; jx = jx < 0 ? A.nx - 1 : (jx >= A.nx ? 0 : jx); }
+                else if (!fz) { hy = qy; jy += vy > 0.0f ? 1 : -1; jy = jy < 0 ? A.ny - 1 : (jy >= A.ny ? 0 : jy); }
+                else if (++kk >= k3hi) {
+                    if (kk < A.nz) tau = fmaf(fmaf(slay[kk].bt, slay[kk].dz, slay[kk].tabove), biz, tau);
+                    break;
+                } else hz = slay[kk].dz * biz;
+            }
+            if (!drop) score += (double)(sunc * fexp_neg(tau));
+            return false;
+        }
+#endif
+        six = ix; siy = iy; sk = k; spx = px; spy = py; spz = pz; snx = ux; sny = uy; snz = uz;
+        sun_end = end_after;
+        ux = -sdx; uy = -sdy; uz = -sdz;
+        set_dda(px, py, pz, L0.dz);
+        stau = 0.0f; ssteps = 0;
+        sun = true;
+        return true;
     };
 
     for (;;) {
@@ -136,6 +225,7 @@
             }
             have = true;
             score = 0.0; w = 1.0f; steps = 0; draw = 1;
+            if (SUN) sdraw = 0;
             const int iv = pix / (A.nxr * A.nyr), rem = pix - iv * (A.nxr * A.nyr), jr = rem / A.nxr, ir = rem - jr * A.nxr;
             float u0, u1, u2, u3;
             draw4(seed, id, 0u, u0, u1, u2, u3);
@@ -227,12 +317,15 @@
             } else cell = A.cells[A.nvox + k];
             for (int ip = 0; ip < A.np1d; ++ip) ks += L.ks1d[ip];
             const float dface = in3d ? fminf(fminf(tx, ty), tz) : tz;
-            const float dsc = ks > 0.0f ? taus * frcp(ks) : 3.0e38f;
+            const float dsc = SUN && sun ? 3.0e38f : ks > 0.0f ? taus * frcp(ks) : 3.0e38f;    // (a sun ray has no free path: it ends at the top)
             const bool scat = dsc < dface;
             const float ds = scat ? dsc : dface;
-            float e;
-            const float em = bwd_absorb(cell.x * ds, e);
-            score += (double)(w * cell.y * em);
+            float e = 1.0f, em = 0.0f;
+            if (SUN && sun) { stau = fmaf(cell.x + ks, ds, stau); ssteps++; }     // the ray: k_a and k_s of every constituent, no emission
+            else {
+                em = bwd_absorb(cell.x * ds, e);
+                score += (double)(w * cell.y * em);
+            }
             if (PRF) {
                 const float a = w * em;
                 if (a != 0.0f) prf_add(pix, k, a, w * cell.y * em);
@@ -246,7 +339,7 @@
                 }
             }
             w *= e;
-            steps++;
+            if (!(SUN && sun)) steps++;
             if (COUNT) { c_steps++; if (in3d) c_steps3d++; }
             const bool hitz = !scat && (!in3d || (tz <= tx && tz <= ty)), hitx = !scat && !hitz && tx <= ty, hity = !scat && !hitz && !hitx;
             tx -= ds; ty -= ds; tz -= ds;
@@ -256,7 +349,26 @@
                 if (tx < 0.0f) { const float nc = floorf(-tx / sx) + 1.0f; tx = fminf(fmaxf(fmaf(nc, sx, tx), 0.0f), sx); ix = bwd_wrap(ix, ux > 0.0f ? nc : -nc, A.nx); }
                 if (ty < 0.0f) { const float nc = floorf(-ty / sy) + 1.0f; ty = fminf(fmaxf(fmaf(nc, sy, ty), 0.0f), sy); iy = bwd_wrap(iy, uy > 0.0f ? nc : -nc, A.ny); }
             }
-            if (w < kBwdWeightEnd) ended = true;
+            if (SUN && sun) {
+                // ---- the sun ray: on through the next face; above the 3-D region and at the top it ends in closed form
+                bool done = false, drop = false;
+                if (stau > staumax) { done = true; drop = true; }                // g e^{-tau} has fallen below kBwdWeightEnd
+                else if (ssteps >= kBwdMaxCells) { done = true; drop = true; atomicAdd(A.capped, 1ull); }
+                else if (hitx) { tx = sx; ix += ux > 0.0f ? 1 : -1; ix = ix < 0 ? A.nx - 1 : (ix >= A.nx ? 0 : ix); }
+                else if (hity) { ty = sy; iy += uy > 0.0f ? 1 : -1; iy = iy < 0 ? A.ny - 1 : (iy >= A.ny ? 0 : iy); }
+                else if (++k >= k3hi) {                                         // (uz > 0 always)
+                    if (k < A.nz) stau = fmaf(fmaf(slay[k].bt, slay[k].dz, slay[k].tabove), aiz, stau);
+                    done = true;
+                } else tz = slay[k].dz * aiz;
+                if (done) {
+                    if (!drop) score += (double)(sunc * fexp_neg(stau));
+                    sun = false;
+                    ix = six; iy = siy; k = sk; ux = snx; uy = sny; uz = snz;
+                    set_dda(spx, spy, spz, slay[k].dz);
+                    if (sun_end) ended = true;
+                    else new_flight();
+                }
+            } else if (w < kBwdWeightEnd) ended = true;
             else if (steps >= kBwdMaxCells) { ended = true; atomicAdd(A.capped, 1ull); }
             else if (scat) {
                 // ---- scattering: the constituent in proportion to k_s (u1), its phase function (u2), the azimuth (u3)
@@ -277,6 +389,14 @@
                 const float mu = apf >= 1.0f ? phase_sample_table(A.tab, apf, r2, usel) : phase_sample_analytic(apf, r2);
                 const float px = pos_x(), py = pos_y();
                 const float dz0 = tz * fabsf(uz), pz = fminf(fmaxf(uz > 0.0f ? L.dz - dz0 : dz0, 0.0f), L.dz);
+                if (SUN) {
+                    // the sunlight this event turns into the line of sight: w P_q(d' . (-u)) / 4 pi  F mu0 / |d'_z|, P_q of the constituent chosen
+                    sun_dir();
+                    const float cs = fminf(fmaxf(-(sdx * ux + sdy * uy + sdz * uz), -1.0f), 1.0f);
+                    const float pq = apf >= 1.0f ? phase_eval_table(A.tab, apf, cs) : phase_eval_analytic(apf, cs);
+                    sung = w * pq * (0.25f / kPi) * N.mu0 * frcp(-sdz);
+                    sunc = sung * N.F;
+                }
                 rotate_dir(ux, uy, uz, mu, r3);
                 set_dda(px, py, pz, L.dz);
                 if (w < A.wmin) {
@@ -284,7 +404,8 @@
                     draw4(seed, id, draw++, q0, q1, q2, q3);
                     if (!roulette(q0)) ended = true;
                 }
-                if (!ended) new_flight();
+                if (SUN && sun_start(px, py, pz, ended)) ended = false;           // (the history's end, if it has come, waits for the ray's)
+                else if (!ended) new_flight();
             } else if (hitx) { tx = sx; ix += ux > 0.0f ? 1 : -1; ix = ix < 0 ? A.nx - 1 : (ix >= A.nx ? 0 : ix); }
             else if (hity) { ty = sy; iy += uy > 0.0f ? 1 : -1; iy = iy < 0 ? A.ny - 1 : (iy >= A.ny ? 0 : iy); }
             else if (uz > 0.0f) {
@@ -310,6 +431,12 @@
                         else atomicAdd(&W.K[(unsigned long long)pix * W.ncell + A.nvox + A.nz + s], (double)a);
                     }
                 }
+                if (SUN) {
+                    // the sunlight the surface reflects into the line of sight: w (1 - eps) / pi  F mu0 (mu0 / |d'_z| cancels against the cosine)
+                    sun_dir();
+                    sung = w * (1.0f - sc.x) * (1.0f / kPi) * N.mu0;
+                    sunc = sung * N.F;
+                }
                 w *= 1.0f - sc.x;
                 if (w < kBwdWeightEnd) ended = true;
                 else {
@@ -322,7 +449,12 @@
                     k = 0;
                     set_dda(px, py, 0.0f, slay[0].dz);
                     if (w < A.wmin && !roulette(q2)) ended = true;
-                    if (!ended) new_flight();
+                    if (!SUN && !ended) new_flight();
+                }
+                if (SUN) {
+                    k = 0;
+                    if (sun_start(px, py, 0.0f, ended)) ended = false;
+                    else if (!ended) new_flight();
                 }
             }
         }

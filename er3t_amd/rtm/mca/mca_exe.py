@@ -55,13 +55,32 @@ def _check_supported(nml, fdir=None, solver=None):
         if mbwd == 1.0 and not (mtype == 3 and int(nml.get('Wld_mtarget', 1)) == 2 and int(nml.get('Rad_mrkind', 2)) == 1):
             raise OSError('Error [mca_exe]: <Rad_mbwd=1> (backward Monte Carlo) belongs to the all-sky cameras and point radiometers (<Rad_mrkind=1>) of a '
                           'thermal job (<Src_mtype=3>): a solar job\'s sun would need a local estimate of its own.')
+    if nml.get('Rad_mvsun') is not None:
+        mvsun = float(np.ravel(nml.get('Rad_mvsun'))[0])
+        if mvsun not in (0.0, 1.0):
+            raise OSError('Error [mca_exe]: <Rad_mvsun=%g> is not supported (0: off, 1: the sunlight term of the backward satellite views; a key of '
+                          'this project).' % mvsun)
+        if mvsun == 1.0:
+            why = 'the backward route for satellite views (<Rad_mvbwd=1>)' if _flag(nml, 'Rad_mvbwd') != 1.0 \
+                else 'the solar+thermal source (<Src_mtype=2>): the switch belongs to the mixed source, a pure solar image is a mixed job with a cold ' \
+                     'atmosphere' if mtype != 2 \
+                else 'satellite views (<Rad_mrkind=2>): the cameras and point radiometers of a mixed job are not served backwards' \
+                if int(nml.get('Rad_mrkind', 2)) != 2 \
+                else 'a job without emission weights (<Rad_mwgt=1>): the sun is no cell' if _flag(nml, 'Rad_mwgt') == 1.0 \
+                else 'a job without view profiles (<Rad_mvprf=1>): the weighting functions are per unit Planck radiance, and the sun has no row' \
+                if _flag(nml, 'Rad_mvprf') == 1.0 \
+                else 'a sun from above (<Src_the> - <Src_qmax>/2 > 90)' if not (_flag(nml, 'Src_the') - 0.5*max(_flag(nml, 'Src_qmax'), 0.0) > 90.0) \
+                else None
+            if why:
+                raise OSError('Error [mca_exe]: <Rad_mvsun=1> (sunlight on the backward satellite views) needs %s.' % why)
     if nml.get('Rad_mvbwd') is not None:
         mvbwd = float(np.ravel(nml.get('Rad_mvbwd'))[0])
         if mvbwd not in (0.0, 1.0):
             raise OSError('Error [mca_exe]: <Rad_mvbwd=%g> is not supported (0: forward, 1: backward Monte Carlo for satellite views; a key of this '
                           'project).' % mvbwd)
         if mvbwd == 1.0:
-            why = 'a thermal job (<Src_mtype=3>): a solar job\'s sun would need a local estimate of its own' if mtype != 3 \
+            why = 'a thermal job (<Src_mtype=3>): a solar job\'s sun would need a local estimate of its own (a solar+thermal job, <Src_mtype=2>, ' \
+                  'has one with <Rad_mvsun=1>)' if mtype != 3 and not (mtype == 2 and _flag(nml, 'Rad_mvsun') == 1.0) \
                 else 'a radiance job (<Wld_mtarget=2>): fluxes and heating rates are not served backwards' if int(nml.get('Wld_mtarget', 1)) != 2 \
                 else 'satellite views (<Rad_mrkind=2>): cameras and point radiometers have <Rad_mbwd>' if int(nml.get('Rad_mrkind', 2)) != 2 \
                 else 'no emission weights (<Rad_mwgt=1> is served for cameras and point radiometers alone)' if _flag(nml, 'Rad_mwgt') == 1.0 \
@@ -155,7 +174,8 @@ def thermal_heating(nml):
     mtype = int(nml.get('Src_mtype', 1) or 1)
     return mtype == 2 or (mtype == 3 and int(nml.get('Wld_mtarget', 1)) == 1 and int(nml.get('Flx_mhrt', 0) or 0) == 2) \
         or (mtype == 3 and int(nml.get('Wld_mtarget', 1)) == 2 and int(nml.get('Rad_mrkind', 2)) == 1) \
-        or (mtype == 3 and _flag(nml, 'Rad_mvbwd') == 1.0)      # (satellite views served backwards: every pixel is divided by its own count of histories)
+        or (mtype == 3 and _flag(nml, 'Rad_mvbwd') == 1.0) \
+        or _flag(nml, 'Rad_mvsun') == 1.0      # (satellite views served backwards, with or without the sun: every pixel is divided by its own count of histories)
 
 
 def wants_rdir(scene):
@@ -440,7 +460,7 @@ class JobRunner:
                     raise OSError('Error [mca_exe]: the cameras and point radiometers of a thermal job (Rad_mrkind=1) are not served by the batched route '
                                   '(a camera\'s tallies are scaled with the emitted power: include/mi3d.h, mi3d_get_radiance); run such jobs one by one '
                                   '(run_job), as mca_run does.')
-                if getattr(sc, 'view_method', 0) == 1:
+                if getattr(sc, 'view_method', 0) == 1 or getattr(sc, 'view_sunlight', 0) == 1:
                     raise OSError('Error [mca_exe]: satellite views served backwards (Rad_mvbwd=1) are not served by the batched route (every pixel is '
                                   'divided by its own count of histories: include/mi3d.h, mi3d_set_view_method); run such jobs one by one (run_job), '
                                   'as mca_run does.')

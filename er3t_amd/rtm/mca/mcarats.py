@@ -128,6 +128,11 @@ class mcarats_ng:
                            follows from the job's own histories -- one run is enough (Rad_mserr=1, a key of this project written only
                            then: include/mi3d.h, mi3d_set_pixel_errors); mca_out_ng returns data['rad_se'] and
                            data['bt_se'], for point radiometers data['f_se']
+        view_sunlight [False]: with view_method='backward' and <source='solar+thermal'> (the 3-5 um channels): the backward route serves the
+                           mixed job -- every scattering and every surface reflection of a history also scores the sunlight it turns into
+                           the line of sight, through a ray to the top of the atmosphere (Rad_mvsun=1, a key of this project written only
+                           then: include/mi3d.h, mi3d_set_view_sunlight).  rad and bt include the sun, as the forward mixed
+                           job's do; pixel_errors=True is served, view_profiles=True is not
 
     Afterwards: input and output files under <fdir>; attributes Ng, Nrun, Nx, Ny, dx, dy, date, target, solver,
     photons (Nrun*Ng,), photons_per_set, fnames_inp[ir][ig], fnames_out[ir][ig], nml (list of Ng dictionaries).
@@ -142,7 +147,7 @@ class mcarats_ng:
                  sensor_ypos=0.5, solver='3d', photons=1e7, base_ratio=0.05, verbose=False, quiet=False,
                  abs_obj=None, keep_files=True, source='solar', wavelength=None, surface_temperature=None,
                  heating_estimator='collision', camera_images=None, camera_method='forward', emission_weights=False, view_method='forward',
-                 view_profiles=False, pixel_errors=False):
+                 view_profiles=False, pixel_errors=False, view_sunlight=False):
 
         # one process per GPU (torch.distributed): rank 0 writes the job files, all ranks transport their share of every job
         from er3t_amd.dist import world_info, barrier
@@ -180,6 +185,9 @@ class mcarats_ng:
             raise OSError('Error [mcarats_ng]: <camera_images=%s> must be an integer from 0 to 8 (or None).' % camera_images)
         if camera_images is not None and not self.point_sensor:
             raise OSError('Error [mcarats_ng]: <camera_images> belongs to <target=\'radiance\'> with <sensor_type=\'all-sky\' | \'irradiance\' | \'actinic\'>.')
+        if view_sunlight and self.point_sensor:
+            raise OSError('Error [mcarats_ng]: <view_sunlight=True> (Rad_mvsun) belongs to <sensor_type=\'satellite\'>: cameras and point radiometers '
+                          '(<sensor_type=%r>) of a mixed job are not served backwards.' % sensor_type)
         if self.point_sensor and self.source == 'solar+thermal':
             raise OSError('Error [mcarats_ng]: <source=\'solar+thermal\'> with <sensor_type=%r> is not implemented: the direct sun in a camera of a mixed '
                           'job would need a normalisation of its own; <source=\'thermal\'> and <source=\'solar\'> serve these sensors.' % sensor_type)
@@ -197,11 +205,26 @@ class mcarats_ng:
         self.view_method = str(view_method).lower()
         if self.view_method not in ('forward', 'backward'):
             raise OSError('Error [mcarats_ng]: <view_method=%s> must be \'forward\' or \'backward\'.' % view_method)
+        self.view_sunlight = bool(view_sunlight)
+        if self.view_sunlight and not (self.view_method == 'backward' and self.source == 'solar+thermal'):
+            raise OSError('Error [mcarats_ng]: <view_sunlight=True> (Rad_mvsun) needs <view_method=\'backward\'> and <source=\'solar+thermal\'>: the '
+                          'switch belongs to the mixed source; a pure solar image is a mixed job with a cold atmosphere, a thermal one needs no sun.')
+        if self.view_sunlight and (str(target).lower() not in _TARGETS['radiance'] or _match(solver, _SOLVERS, 'solver') != '3D'):
+            raise OSError('Error [mcarats_ng]: <view_sunlight=True> (Rad_mvsun) needs <target=\'radiance\'> and <solver=\'3d\'>, as '
+                          '<view_method=\'backward\'> does.')
+        if self.view_sunlight and view_profiles:
+            raise OSError('Error [mcarats_ng]: <view_profiles=True> does not go with <view_sunlight=True> (Rad_mvsun): the weighting functions are per '
+                          'unit Planck radiance, and the sun has no row.')
+        if self.view_sunlight and emission_weights:
+            raise OSError('Error [mcarats_ng]: <emission_weights=True> does not go with <view_sunlight=True> (Rad_mvsun): the sun is no cell.')
+        if self.view_sunlight and not (0.0 <= float(np.max(np.abs(solar_zenith_angle))) < 90.0 - 0.5*0.533):
+            raise OSError('Error [mcarats_ng]: <view_sunlight=True> (Rad_mvsun) needs a sun above the horizon (<solar_zenith_angle> < 90 less half '
+                          'the solar disc).')
         if self.view_method == 'backward':
-            if self.source != 'thermal' or str(target).lower() not in _TARGETS['radiance'] or 'satellite' not in str(sensor_type).lower():
+            if (self.source != 'thermal' and not self.view_sunlight) or str(target).lower() not in _TARGETS['radiance'] or 'satellite' not in str(sensor_type).lower():
                 raise OSError('Error [mcarats_ng]: <view_method=\'backward\'> needs <source=\'thermal\'> and <target=\'radiance\'> with '
                               '<sensor_type=\'satellite\'>: backward histories collect emission; the sun would need a local estimate of its own '
-                              '(cameras and point radiometers: <camera_method>).')
+                              '(cameras and point radiometers: <camera_method>; <source=\'solar+thermal\'> is served with <view_sunlight=True>).')
             if _match(solver, _SOLVERS, 'solver') != '3D':
                 raise OSError('Error [mcarats_ng]: <view_method=\'backward\'> needs <solver=\'3d\'>: a line of sight crosses columns.')
             if emission_weights:
@@ -212,7 +235,7 @@ class mcarats_ng:
             raise OSError('Error [mcarats_ng]: <view_profiles=True> needs <view_method=\'backward\'>: the per-layer profiles are what backward '
                           'histories collect along their lines of sight.')
         self.pixel_errors = bool(pixel_errors)
-        if self.pixel_errors and self.source != 'thermal':
+        if self.pixel_errors and self.source != 'thermal' and not self.view_sunlight:
             raise OSError('Error [mcarats_ng]: <pixel_errors=True> needs <source=\'thermal\'>: the backward routes serve thermal jobs alone (the sun '
                           'would need a local estimate of its own).')
         if self.pixel_errors and self.camera_method != 'backward' and self.view_method != 'backward':
@@ -308,6 +331,8 @@ class mcarats_ng:
             self._all({'Rad_mvbwd': 1})
             if self.view_profiles:                     # (likewise)
                 self._all({'Rad_mvprf': 1})
+            if self.view_sunlight:                     # (likewise)
+                self._all({'Rad_mvsun': 1})
         if self.pixel_errors:                          # (likewise)
             self._all({'Rad_mserr': 1})
         if self.camera_method == 'backward':           # (likewise)

@@ -126,6 +126,9 @@ class Scene:
     pixel_errors: int = 0                 # Rad_mserr (a key of this project; include/mi3d.h: mi3d_set_pixel_errors): 1 the backward route also
                                           # tallies the squared scores of every pixel, for its standard error from one run; needs
                                           # cam_method = 1 or view_method = 1, without cam_weights and view_profiles
+    view_sunlight: int = 0                # Rad_mvsun (a key of this project; include/mi3d.h: mi3d_set_view_sunlight): 1 the backward route for
+                                          # satellite views serves a solar+thermal job (src_mtype = 2): every scattering and reflection
+                                          # also scores its sunlight; needs rad_kind = 2, view_method = 1, without view_profiles
 
     # job
     target: int = TARGET_FLUX
@@ -215,6 +218,17 @@ class Scene:
         if self.pixel_errors == 1 and (self.cam_weights == 1 or self.view_profiles == 1):
             raise ValueError('Error [Scene]: <pixel_errors=1> (Rad_mserr) is not served together with <cam_weights=1> (Rad_mwgt) or '
                              '<view_profiles=1> (Rad_mvprf).')
+        if self.view_sunlight not in (0, 1) or isinstance(self.view_sunlight, float):
+            raise ValueError('Error [Scene]: <view_sunlight=%s> (Rad_mvsun) must be 0 or 1.' % (self.view_sunlight,))
+        if self.view_sunlight == 1:
+            why = 'the backward route for satellite views (<rad_kind=2>, <view_method=1>, Rad_mvbwd=1)' if not (self.rad_kind == 2 and self.view_method == 1) \
+                  else 'a solar+thermal source (<src_mtype=2>): the switch belongs to the mixed source, a pure solar image is a mixed job with a cold atmosphere' \
+                  if self.src_mtype != 2 \
+                  else 'a job without <view_profiles=1> (Rad_mvprf): the weighting functions are per unit Planck radiance, and the sun has no row' \
+                  if self.view_profiles == 1 \
+                  else 'a sun from above (<src_the> - <src_qmax>/2 > 90)' if not (float(self.src_the) - 0.5*max(float(self.src_qmax), 0.0) > 90.0) else None
+            if why:
+                raise ValueError('Error [Scene]: <view_sunlight=1> (Rad_mvsun) needs %s.' % why)
         if self.src_mtype in (2, 3):
             if self.src_mtype == 2:
                 if self.src_fsol is None or not (float(self.src_fsol) >= 0.0) or not np.isfinite(float(self.src_fsol)):
@@ -381,9 +395,20 @@ class Scene:
         mvbwd = float(np.ravel(get('Rad_mvbwd', 0))[0])
         if mvbwd not in (0.0, 1.0):
             raise OSError('Error [Scene]: <Rad_mvbwd=%g> is not supported (0: forward, 1: backward Monte Carlo for satellite views).' % mvbwd)
-        if mvbwd == 1.0 and not (mtype == 3 and mtarget == 2 and int(get('Rad_mrkind', 2)) == 2 and int(solver) == SOLVER_3D):
+        # (a key of this project: the sunlight term of that route, which lets it serve a solar+thermal job)
+        mvsun = float(np.ravel(get('Rad_mvsun', 0))[0])
+        if mvsun not in (0.0, 1.0):
+            raise OSError('Error [Scene]: <Rad_mvsun=%g> is not supported (0: off, 1: the sunlight term of the backward satellite views).' % mvsun)
+        if mvsun == 1.0 and (int(get('Rad_mrkind', 2)) != 2 or float(np.ravel(get('Rad_mwgt', 0))[0]) == 1.0):
+            raise OSError('Error [Scene]: <Rad_mvsun=1> (sunlight on the backward satellite views) belongs to satellite views (<Rad_mrkind=2>) '
+                          'without emission weights (<Rad_mwgt=1>): cameras and point radiometers of a mixed job are not served backwards, and '
+                          'the sun is no cell.')
+        if mvsun == 1.0 and not (mvbwd == 1.0 and mtype == 2):
+            raise OSError('Error [Scene]: <Rad_mvsun=1> (sunlight on the backward satellite views) needs <Rad_mvbwd=1> and the solar+thermal source '
+                          '(<Src_mtype=2>); a pure solar image is a mixed job with a cold atmosphere.')
+        if mvbwd == 1.0 and not ((mtype == 3 or (mtype == 2 and mvsun == 1.0)) and mtarget == 2 and int(get('Rad_mrkind', 2)) == 2 and int(solver) == SOLVER_3D):
             raise OSError('Error [Scene]: <Rad_mvbwd=1> (backward Monte Carlo) belongs to the satellite views (<Rad_mrkind=2>) of a thermal radiance '
-                          'job (<Src_mtype=3>, <Wld_mtarget=2>) under the 3-D solver.')
+                          'job (<Src_mtype=3>, <Wld_mtarget=2>) under the 3-D solver (a solar+thermal job, <Src_mtype=2>, with <Rad_mvsun=1>).')
         # (a key of this project: per-cell emission weights of the backward route)
         mwgt = float(np.ravel(get('Rad_mwgt', 0))[0])
         if mwgt not in (0.0, 1.0):
@@ -396,6 +421,9 @@ class Scene:
             raise OSError('Error [Scene]: <Rad_mvprf=%g> is not supported (0: off, 1: per-layer weighting functions).' % mvprf)
         if mvprf == 1.0 and mvbwd != 1.0:
             raise OSError('Error [Scene]: <Rad_mvprf=1> (view profiles) needs the backward route for satellite views (<Rad_mvbwd=1>).')
+        if mvprf == 1.0 and mvsun == 1.0:
+            raise OSError('Error [Scene]: <Rad_mvprf=1> (view profiles) is not served together with <Rad_mvsun=1>: the weighting functions are per '
+                          'unit Planck radiance, and the sun has no row.')
         # (a key of this project: per-pixel standard errors of the backward routes)
         mserr = float(np.ravel(get('Rad_mserr', 0))[0])
         if mserr not in (0.0, 1.0):
@@ -434,7 +462,7 @@ class Scene:
             elif mrkind != 2:
                 raise OSError('Error [Scene]: <Rad_mrkind=%d> is not supported (1: camera, 2: satellite).' % mrkind)
             else:
-                kw.update(view_method=int(mvbwd), view_profiles=int(mvprf), pixel_errors=int(mserr))
+                kw.update(view_method=int(mvbwd), view_profiles=int(mvprf), pixel_errors=int(mserr), view_sunlight=int(mvsun))
         elif mtarget == 1:
             mhrt = int(get('Flx_mhrt', 0) or 0)
             if mhrt == 2 and mtype not in (2, 3):

@@ -60,6 +60,7 @@ _SIGNATURES = [
     ('mi3d_bind_pixel_errors_buffer', C.c_int, [C.c_void_p, C.c_void_p]),
     ('mi3d_get_radiance_se'    , C.c_int   , [C.c_void_p, _u64, _fp]),
     ('mi3d_debug_backward_chunk', C.c_int  , [C.c_void_p]),
+    ('mi3d_set_view_sunlight'  , C.c_int   , [C.c_void_p, C.c_int]),
     ('mi3d_set_options'        , C.c_int   , [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int]),
     ('mi3d_set_le_roulette'    , C.c_int   , [C.c_void_p, C.c_double]),
     ('mi3d_set_le_weight_roulette', C.c_int, [C.c_void_p, C.c_double]),
@@ -321,6 +322,12 @@ class Mi3dSolver:
         itself (anything but 0 and 1 is refused by the library)"""
         self._chk(self.lib.mi3d_set_pixel_errors(self._h, int(on)))
 
+    def set_view_sunlight(self, on=True):
+        """the sunlight term of the backward route's satellite views (include/mi3d.h: mi3d_set_view_sunlight): on, the route serves a
+        solar+thermal job (Src_mtype = 2): every scattering and every surface reflection of a history also scores the sunlight it turns into
+        the line of sight.  True / False or the value itself (anything but 0 and 1 is refused by the library)"""
+        self._chk(self.lib.mi3d_set_view_sunlight(self._h, int(on)))
+
     def set_options(self, target=TARGET_FLUX, solver=0, wmin=0.2, wfac=1.0, column_le=True):
         self._chk(self.lib.mi3d_set_options(self._h, int(target), int(solver), float(wmin), float(wfac), 1 if column_le else 0))
 
@@ -366,6 +373,8 @@ class Mi3dSolver:
             self.set_view_profiles(int(getattr(s, 'view_profiles', 0)))
         if int(getattr(s, 'pixel_errors', 0)) or not getattr(self.lib.mi3d_set_pixel_errors, 'stale', False):      # (likewise)
             self.set_pixel_errors(int(getattr(s, 'pixel_errors', 0)))
+        if int(getattr(s, 'view_sunlight', 0)) or not getattr(self.lib.mi3d_set_view_sunlight, 'stale', False):    # (likewise)
+            self.set_view_sunlight(int(getattr(s, 'view_sunlight', 0)))
         self.set_options(s.target, s.solver, s.wmin, s.wfac, column_le)
         self.set_heating_estimator(int(getattr(s, 'heat_estimator', 0)))
         self.set_le_roulette(getattr(s, 'le_tau1', 0.0))

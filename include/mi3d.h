@@ -438,6 +438,47 @@ int mi3d_set_pixel_errors(mi3d_solver *h, int on);
 int mi3d_bind_pixel_errors_buffer(mi3d_solver *h, void *rad2_sum);
 int mi3d_get_radiance_se(mi3d_solver *h, uint64_t nphoton_total, float *out);
 
+/* The sunlight term of the backward route's satellite views: solar+thermal jobs (Src_mtype = 2, the 3-5 um channels) served backwards
+ * (er3t_amd/csrc/mi3d_kernel_backward.hip; the project's namelist key Rad_mvsun = 1).
+ *   Switch     mi3d_set_view_sunlight: 0 (default) nothing of this runs -- kernels, names, refusals and results are those of the library
+ *              without it; 1: mi3d_run serves Src_mtype = 2 under mi3d_set_view_method 1 with the views of mi3d_set_views.  Anything but
+ *              0 or 1 is MI3D_EINVAL.  mi3d_last_kernel: "k_backward<C,V,N> [solar+thermal]", with mi3d_set_pixel_errors 1
+ *              "k_backward<C,V,N,S> [solar+thermal]".  mi3d_debug_backward_views runs the same code for single histories.
+ *   Refused    with the switch on, MI3D_EUNSUP from mi3d_run in words that name it: Src_mtype = 1 and 3 (the switch belongs to the mixed
+ *              source; a pure solar image is a mixed job with a cold atmosphere), mi3d_set_view_method 0 or mi3d_set_camera_method 1,
+ *              cameras and point radiometers (Rad_mrkind = 1), mi3d_set_view_profiles 1 (the weighting functions are per unit Planck
+ *              radiance: the sun has no row), mi3d_set_emission_weights 1, a sun from below or on the horizon (Src_the - Src_qmax / 2
+ *              <= 90).  Flux jobs, independent columns, partial 3-D and non-Lambertian surfaces are refused as mi3d_set_view_method 1
+ *              refuses them.  mi3d_set_pixel_errors 1 is served: the sun's terms enter the score like every other.
+ *   History    that of mi3d_set_view_method 1, untouched: free paths by the scattering coefficient, w *= exp(-ka l), emission scored per
+ *              cell step, Lambert reflection with w *= 1 - eps, the same Philox blocks.  The path and the weight of history (seed, id) are
+ *              those of the thermal job (Src_mtype = 3) whatever the sun does.
+ *   Estimator  d = (sin the cos phi, sin the sin phi, cos the) of (Src_the, Src_phi) is the direction in which sunlight travels (d_z < 0),
+ *              mu0 = |d_z|, F = Src_fsol the irradiance on a plane normal to the beam, -u the direction in which the history's light
+ *              travels towards the sensor.  At a scattering, after the step's w *= exp(-ka l):
+ *                  score += w P_q(d' . (-u)) / (4 pi)  F (mu0 / |d'_z|)  T(r -> top along -d')
+ *              P_q the phase function of the constituent the event selected (1/2 int P dmu = 1; a mix of two tables: their mix).  At the
+ *              surface, after w eps B and before w *= 1 - eps:
+ *                  score += w (1 - eps) / pi  F mu0  T(r -> top along -d')
+ *              T = exp(-int (ka + ks)) over every constituent along the ray, through the cyclic domain.  A history that ends at the
+ *              event (roulette, weight) still scores the event's term, with the weight before the roulette.  Unscattered sunlight
+ *              reaches no view: a line of sight that looks into the sun has measure zero, as on the forward route.
+ *   Cone       Src_qmax <= 0: d' = d.  Otherwise d' is drawn per event, uniformly in solid angle inside the cone of half angle Src_qmax / 2
+ *              about d, the forward launch's distribution: mu = 1 - u0 (1 - cos(Src_qmax / 2)), azimuth u1, from Philox block
+ *              2^31 + j of (seed, id), j = 0, 1, ... counting the history's events: blocks the walk never reaches.  Forward photons
+ *              cross the top with equal weight per horizontal area, hence mu0 / |d'_z|; it cancels against the cosine at the surface.
+ *   Ray        above the 3-D region the ray ends in closed form, exp(-(tau so far + rest of the layer + tau above) / |d'_z|), from the
+ *              layer table's vertical optical depths: no steps.  Inside and below it the ray takes cell steps with the walk's own
+ *              reads and DDA, one per trip of the history loop, and ends early -- its term dropped -- once g exp(-tau) falls below
+ *              1e-7, g = c / F the coefficient in front of T without the irradiance: the weight the history has on the ray, under
+ *              the bound at which the walk itself ends a history (a bias of at most 1e-7 F per event).  The rule does not look at
+ *              F, so rad is exactly affine in F on the same ids.  With F = 0 no ray is flown and the raw tally is that of the
+ *              Src_mtype = 3 job bit for bit, under any Src_qmax.  An exactly vertical sun keeps its column.  A ray that has taken 2^20 steps is dropped and counted as
+ *              CAPPED.  Counting builds add the rays' steps to MI3D_CNT_STEPS and MI3D_CNT_STEPS3D.
+ *   Result     that of mi3d_set_view_method 1: every pixel divided by its own count of histories, absolute W m-2 sr-1 um-1, the score
+ *              carries Src_flx; the brightness temperature of such an image includes the sun, as the forward mixed job's does. */
+int mi3d_set_view_sunlight(mi3d_solver *h, int on);
+
 /* Job options = 1st/2nd CLI arguments and keys Wld_mtarget, Flx_mflx, Pho_wmin
  * (er3t/rtm/mca/mcarats.py:267-287,450-454; er3t/rtm/mca/mca_inp.py:196-198).
  *   target   MI3D_TARGET_FLUX | MI3D_TARGET_RADIANCE (bit-or of both is allowed); MI3D_TARGET_FLUX | MI3D_TARGET_HEAT is the

@@ -43,6 +43,12 @@ history), the sixteen sensors of the 'bwd' leg (both sums per workgroup in LDS) 
 with the switch on, the mean relative standard error of a pixel from the histories of the last batch.  Under MI3D_LIBRARY (an older build
 of the library) the rows with the switch off alone.
     python tools/thermal_rate.py --legs err
+Leg 'sun' (DESIGN.md 5.18): the image of the 'sat' leg (a nadir and a 45 degree view) of the solar+thermal job at 3.75 um, the sun 40 degrees
+from the zenith, Src_fsol = 10 W m-2 um-1, by the forward mixed route, by backward Monte Carlo with the sunlight term (view_sunlight = 1) and,
+for what the sun rays cost a history, by the backward thermal route of the same scene (Src_mtype = 3): 16 batches each over disjoint id
+ranges; histories (photons) per second, kernel time, relative standard error per pixel (mean, largest), merit 1 / (se^2 t), the image means,
+and from the counting build the cell steps per history of both backward jobs: their difference is the sun rays'.
+    python tools/thermal_rate.py --legs sun --photons 2e6 --per-pixel 32
 """
 
 import argparse
@@ -140,6 +146,51 @@ def sat_rows(sol, name, s, n_fwd, per_pixel, chunks=(0, 4, 8, 16, 32, -1), nb=16
             print(json.dumps(row), flush=True)
     finally:
         sol.set_tuning(bwd_chunk=-1)
+        sol.set_view_method('forward')
+    return rows
+
+
+def sun_rows(sol, name, s, n_fwd, per_pixel, nb=16):
+    """the 'sun' leg: scene s, a solar+thermal job, by the forward mixed route, by the backward route with the sunlight term,
+    and its thermal half by the backward route; nb batches each over disjoint id ranges"""
+    s = dataclasses.replace(s, view_the=[180.0, 135.0], view_phi=[0.0, 0.0], view_zloc=[1.0e6, 1.0e6], nxr=s.nx, nyr=s.ny)
+    npix = 2*s.nx*s.ny
+    rows = []
+    jobs = [('sun_forward', dataclasses.replace(s, view_method=0), n_fwd),
+            ('sun_backward', dataclasses.replace(s, view_method=1, view_sunlight=1), per_pixel*npix),
+            ('sun_backward_thermal', dataclasses.replace(s, src_mtype=3, src_fsol=None, view_method=1), per_pixel*npix)]
+    try:
+        for target, sc, n in jobs:
+            sol.load_scene(sc)
+            sol.reset(); sol.run(min(n, 2000000), seed=1); sol.sync()        # warm-up
+            tot, sq, ms_all = np.zeros((2, s.ny, s.nx)), np.zeros((2, s.ny, s.nx)), 0.0
+            for b in range(nb):
+                sol.reset()
+                sol.run(n, seed=2, offset=b*n)
+                r = sol.radiance(n).astype(np.float64)
+                tot += r; sq += r*r
+                ms_all += sol.timing()[0]
+            mean = tot/nb
+            se = np.sqrt(np.maximum(sq/nb-mean*mean, 0.0)/(nb-1))
+            ok = mean > 0.0
+            rel = se[ok]/mean[ok]
+            t = ms_all*1e-3
+            row = dict(scene=name, target=target, kernel=sol.kernel_name(), histories_per_batch=n, batches=nb, histories_per_s=float(nb*n/t),
+                       kernel_s=float(t), image_mean=[float(m.mean()) for m in mean], image_mean_se=[float(np.sqrt((e**2).sum())/e.size) for e in se],
+                       pixels_without_a_score=int((~ok).sum()), rel_se_mean=float(rel.mean()), rel_se_max=float(rel.max()),
+                       merit=float(1.0/(rel.mean()**2*t)))
+            if sc.view_method:
+                sol.set_counting(True)
+                sol.reset(); sol.run(n, seed=2); sol.sync()
+                c = sol.counters()
+                sol.set_counting(False)
+                row.update(chunk_launched=sol.lib.mi3d_debug_backward_chunk(sol._h), capped=sol.debug_backward_views(2, 0, 0)[3],
+                           steps_per_history=c['steps']/n, steps3d_per_history=c['steps3d']/n, events_per_history=(c['scatter']+c['surface'])/n)
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    finally:
+        sol.set_counting(False)
+        sol.set_view_sunlight(False)
         sol.set_view_method('forward')
     return rows
 
@@ -293,6 +344,11 @@ def main():
             if target == 'sat':
                 sol.set_kernel(general=False)
                 rows += sat_rows(sol, name, thermal(les_scene(target='radiance', **kw), lev), n, a.per_pixel)
+                continue
+            if target == 'sun':
+                sol.set_kernel(general=False)
+                s = thermal(les_scene(target='radiance', **kw), lev, wl=3.75)
+                rows += sun_rows(sol, name, dataclasses.replace(s, src_mtype=2, src_fsol=10.0, src_the=140.0, src_phi=0.0), n, a.per_pixel)
                 continue
             if target == 'prf':
                 sol.set_kernel(general=False)
