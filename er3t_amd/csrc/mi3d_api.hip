@@ -82,8 +82,17 @@ constexpr double kWgtMaxElems = 2147483648.0;   // elements of the emission weig
 constexpr double kPrfMaxElems = 2147483648.0;   // elements of the view profiles' tally npix x (nz + 1) x 2 served (mi3d_set_view_profiles)
 
 // The six builds of the backward route (mi3d_kernel_backward.hip): k_backward, k_backward_w, k_backward_v, k_backward_vp, k_backward_s,
-// k_backward_vs ... and the two with sunlight (mi3d_set_view_sunlight 1): k_backward_vn, k_backward_vns
-enum class BwdRoute { Camera = 0, Weights = 1, Views = 2, Profiles = 3, CameraErrors = 4, ViewsErrors = 5, ViewsSun = 6, ViewsSunErrors = 7 };
+// k_backward_vs ... and the two with sunlight (mi3d_set_view_sunlight 1): k_backward_vn, k_backward_vns ... and the five of the satellite
+// views under independent columns and partial 3-D (mi3d_set_view_columns 1): k_backward_vc, k_backward_vcs, k_backward_vcp, k_backward_vcn,
+// k_backward_vcns
+enum class BwdRoute { Camera = 0, Weights = 1, Views = 2, Profiles = 3, CameraErrors = 4, ViewsErrors = 5, ViewsSun = 6, ViewsSunErrors = 7,
+                      Columns = 8, ColumnsErrors = 9, ColumnsProfiles = 10, ColumnsSun = 11, ColumnsSunErrors = 12 };
+// the column build that stands for a build of the satellite views (col: mi3d_solver::col_backward)
+static BwdRoute backward_column_route(BwdRoute r, bool col) {
+    if (!col) return r;
+    return r == BwdRoute::Views ? BwdRoute::Columns : r == BwdRoute::ViewsErrors ? BwdRoute::ColumnsErrors : r == BwdRoute::Profiles ? BwdRoute::ColumnsProfiles
+           : r == BwdRoute::ViewsSun ? BwdRoute::ColumnsSun : r == BwdRoute::ViewsSunErrors ? BwdRoute::ColumnsSunErrors : r;
+}
 // ... and what the runtime said of one of them: workgroups resident per CU for `lds` bytes of dynamic LDS (0: not asked yet)
 struct BwdCap { int blocks = 0, counting = -1; size_t lds = 0; };
 
@@ -140,11 +149,14 @@ struct mi3d_solver {
     int bwd_chunk = -1;
     int bwd_chunk_last = 0;
     DevBuf<float> d_bwd_start;
-    BwdCap bwd_cap[8];               // per BwdRoute: the resident workgroups per CU of the build launched last (backward_resident)
+    BwdCap bwd_cap[13];              // per BwdRoute: the resident workgroups per CU of the build launched last (backward_resident)
     bool sat_backward() const { return view_method == 1 && cam_method == 0 && rad_kind == 2; }           // is the job sent to k_backward_v?
     // ... and the sunlight term of a solar+thermal job's satellite views (mi3d_set_view_sunlight 1): the switch
     int view_sunlight = 0;
     bool sun_backward() const { return view_sunlight == 1 && src_mtype == 2 && sat_backward(); }         // is the job sent to k_backward_vn?
+    // ... and the satellite views under independent columns and partial 3-D (mi3d_set_view_columns 1): the switch
+    int view_columns = 0;
+    bool col_backward() const { return view_columns == 1 && solver != MI3D_SOLVER_3D && sat_backward(); }  // is the job sent to a column build (k_backward_vc...)?
     bool backward() const {                                                                               // does the read-out divide by the pixels' own counts?
         if (sun_backward() && nview > 0) return true;
         return src_mtype == 3 && nview > 0 && ((cam_method == 1 && rad_kind == 1) || sat_backward());
@@ -1227,6 +1239,17 @@ int mi3d_set_view_sunlight(mi3d_solver *h, int on) {
     return MI3D_OK;
 }
 
+int mi3d_set_view_columns(mi3d_solver *h, int on) {
+    int rc = check_handle(h);
+    if (rc) return rc;
+    if (on != 0 && on != 1) return fail(MI3D_EINVAL, "view columns %d (0: off, 1: the backward route's satellite views under independent columns and partial 3-D)", on);
+    if (on == h->view_columns) return MI3D_OK;
+    HIPCHK(sync_main(h));   // (as every call that changes what the kernels work on)
+    h->view_columns = on;
+    h->dirty_bwd = true;
+    return MI3D_OK;
+}
+
 int mi3d_set_emission_weights(mi3d_solver *h, int on) {
     int rc = check_handle(h);
     if (rc) return rc;
@@ -1999,7 +2022,10 @@ static void name_route(mi3d_solver *h, const RunPlan &plan, bool lists, uint64_t
     const int c = plan.build.counting ? 1 : 0, p3d = plan.build.p3d ? 1 : 0;
     char nm[96];
     const bool hpath = plan.build.hpath;
-    if (plan.loop == Loop::Backward && h->sun_backward()) snprintf(nm, sizeof(nm), h->pixel_errors ? "k_backward<%d,V,N,S> [solar+thermal]" : "k_backward<%d,V,N> [solar+thermal]", c);
+    if (plan.loop == Loop::Backward && h->col_backward())
+        snprintf(nm, sizeof(nm), h->sun_backward() ? (h->pixel_errors ? "k_backward<%d,V,I,N,S> [solar+thermal]" : "k_backward<%d,V,I,N> [solar+thermal]")
+                                 : h->pixel_errors ? "k_backward<%d,V,I,S> [thermal]" : h->view_profiles ? "k_backward<%d,V,I,P> [thermal]" : "k_backward<%d,V,I> [thermal]", c);
+    else if (plan.loop == Loop::Backward && h->sun_backward()) snprintf(nm, sizeof(nm), h->pixel_errors ? "k_backward<%d,V,N,S> [solar+thermal]" : "k_backward<%d,V,N> [solar+thermal]", c);
     else if (plan.loop == Loop::Backward && h->sat_backward() && h->pixel_errors) snprintf(nm, sizeof(nm), "k_backward<%d,V,S> [thermal]", c);
     else if (plan.loop == Loop::Backward && h->pixel_errors) snprintf(nm, sizeof(nm), "k_backward<%d,S> [thermal]", c);
     else if (plan.loop == Loop::Backward && h->sat_backward() && h->view_profiles) snprintf(nm, sizeof(nm), "k_backward<%d,V,P> [thermal]", c);
@@ -2463,8 +2489,18 @@ static hipError_t launch_pre(mi3d_solver *h, const RunPlan &plan, int pset, bool
 // (mi3d_set_camera_method 1) serves cameras and point radiometers (Rad_mrkind = 1), with or without emission weights; the switch of the
 // satellite views (sat: mi3d_set_view_method 1) the views of mi3d_set_views (Rad_mrkind = 2), without them.
 // With mi3d_set_view_sunlight 1 the satellite views' route serves Src_mtype = 2 instead, and nothing else.
+// With mi3d_set_view_columns 1 it serves independent columns and partial 3-D instead of the 3-D solver.
 // Everything else: MI3D_EUNSUP, with the reason.
 static int backward_unsupported(const mi3d_solver *h, bool sat) {
+    if (h->view_columns) {
+        // the satellite views under independent columns and partial 3-D (mi3d_set_view_columns 1, Rad_mvcol=1)
+        const char *no = h->rad_kind != 2 ? "cameras and point radiometers (Rad_mrkind=1): a camera's lines of sight fan out over the columns, the switch belongs to the satellite views (Rad_mrkind=2)"
+                         : !sat || h->view_method != 1 ? "mi3d_set_view_method 0 or mi3d_set_camera_method 1 (it needs Rad_mvbwd=1): the switch belongs to the backward route for satellite views"
+                         : h->solver == MI3D_SOLVER_3D ? "the 3-D solver: the switch belongs to independent columns and partial 3-D (solver 2 / 1), run the 3-D job without it"
+                         : h->emis_weights ? "emission weights (mi3d_set_emission_weights 1): an image times the cells is out of its scope"
+                         : nullptr;
+        if (no) return fail(MI3D_EUNSUP, "the column histories of the backward satellite views (mi3d_set_view_columns 1, Rad_mvcol=1) do not serve %s", no);
+    }
     if (h->view_sunlight) {
         // the sunlight term (mi3d_set_view_sunlight 1, Rad_mvsun=1) belongs to the satellite views of a solar+thermal job
         const char *no = h->src_mtype == 1 ? "a solar job (Src_mtype=1): the switch belongs to the mixed source, a pure solar image is a solar+thermal job with a cold atmosphere"
@@ -2483,7 +2519,7 @@ static int backward_unsupported(const mi3d_solver *h, bool sat) {
                                                                                                       : "a flux or heating-rate job: the route serves radiance (cameras) alone")
                       : h->rad_kind != (sat ? 2 : 1) ? (sat ? "cameras and point radiometers (Rad_mrkind=1): their switch is mi3d_set_camera_method (Rad_mbwd)"
                                                             : "satellite views (Rad_mrkind=2): the route serves cameras and point radiometers (Rad_mrkind=1)")
-                      : h->solver != MI3D_SOLVER_3D ? (sat ? "independent columns or partial 3-D: a line of sight crosses columns, it needs the 3-D solver"
+                      : h->solver != MI3D_SOLVER_3D && !(sat && h->view_columns) ? (sat ? "independent columns or partial 3-D: a line of sight crosses columns, it needs the 3-D solver"
                                                            : "independent columns or partial 3-D: cameras need the 3-D solver")
                       : !h->sfc_lambert_only ? "a non-Lambertian surface (only Lambertian surfaces emit)"
                       : sat && h->emis_weights ? "emission weights (mi3d_set_emission_weights 1): an image times the cells is out of its scope"
@@ -2540,6 +2576,7 @@ static void fill_backward_sun(const mi3d_solver *h, BwdSun &N) {
     N.mu0 = std::fabs(N.sdz);
     N.F = (float)h->src_fsol;
     N.cos_cone = h->src_qmax <= 0.0 ? 1.0f : (float)std::cos(0.5 * h->src_qmax * pi / 180.0);
+    N.ray3d = h->solver == MI3D_SOLVER_P3D ? 1 : 0;      // (read by the column builds alone: the direct beam of partial 3-D flies in 3-D)
 }
 
 // The one place that names the builds of the histories: the kernel of (route, counting, debug), as the runtime takes it for a launch and
@@ -2570,13 +2607,29 @@ static const void *backward_build(BwdRoute route, bool counting, bool debug) {
     case BwdRoute::ViewsSunErrors:
         if (debug) return nullptr;
         return counting ? (const void *)k_backward_vns<true> : (const void *)k_backward_vns<false>;
+    case BwdRoute::Columns:
+        if (debug) return (const void *)k_backward_vc<false, true>;
+        return counting ? (const void *)k_backward_vc<true, false> : (const void *)k_backward_vc<false, false>;
+    case BwdRoute::ColumnsErrors:
+        if (debug) return nullptr;
+        return counting ? (const void *)k_backward_vcs<true> : (const void *)k_backward_vcs<false>;
+    case BwdRoute::ColumnsProfiles:
+        if (debug) return nullptr;
+        return counting ? (const void *)k_backward_vcp<true> : (const void *)k_backward_vcp<false>;
+    case BwdRoute::ColumnsSun:
+        if (debug) return (const void *)k_backward_vcn<false, true>;
+        return counting ? (const void *)k_backward_vcn<true, false> : (const void *)k_backward_vcn<false, false>;
+    case BwdRoute::ColumnsSunErrors:
+        if (debug) return nullptr;
+        return counting ? (const void *)k_backward_vcns<true> : (const void *)k_backward_vcns<false>;
     }
     return nullptr;
 }
 
 // One launch.  The kernel arguments in the order of the entry points: (A, seed, id0, n), then (dir_out, score_out) for the cameras,
 // (W) for the weights build, (dir_out, score_out, S) for the views, (S, P) for the views' profiles build, (E) and (S, E) for the cameras'
-// and the views' errors builds, (dir_out, score_out, S, N) and (S, E, N) for the views with sunlight
+// and the views' errors builds, (dir_out, score_out, S, N) and (S, E, N) for the views with sunlight; a column build takes the arguments of
+// the views' build it stands for
 static hipError_t backward_launch(BwdRoute route, bool counting, bool debug, unsigned grid, size_t lds, hipStream_t stream, DevBackward A, uint64_t seed,
                                   uint64_t id0, uint64_t n, float *dir_out, double *score_out, BwdWeights W, BwdSat S, BwdProfiles P,
                                   BwdErrors E = BwdErrors{}, BwdSun N = BwdSun{}) {
@@ -2586,9 +2639,10 @@ static hipError_t backward_launch(BwdRoute route, bool counting, bool debug, uns
          *prf[] = {&A, &seed, &id0, &n, &S, &P}, *cerr[] = {&A, &seed, &id0, &n, &E}, *verr[] = {&A, &seed, &id0, &n, &S, &E},
          *vsun[] = {&A, &seed, &id0, &n, &dir_out, &score_out, &S, &N}, *vsune[] = {&A, &seed, &id0, &n, &S, &E, &N};
     return hipLaunchKernel(kernel, dim3(grid), dim3(256),
-                           route == BwdRoute::Camera ? cam : route == BwdRoute::Weights ? wgt : route == BwdRoute::Views ? sat
-                           : route == BwdRoute::Profiles ? prf : route == BwdRoute::CameraErrors ? cerr : route == BwdRoute::ViewsErrors ? verr
-                           : route == BwdRoute::ViewsSun ? vsun : vsune, lds, stream);
+                           route == BwdRoute::Camera ? cam : route == BwdRoute::Weights ? wgt : route == BwdRoute::Views || route == BwdRoute::Columns ? sat
+                           : route == BwdRoute::Profiles || route == BwdRoute::ColumnsProfiles ? prf : route == BwdRoute::CameraErrors ? cerr
+                           : route == BwdRoute::ViewsErrors || route == BwdRoute::ColumnsErrors ? verr
+                           : route == BwdRoute::ViewsSun || route == BwdRoute::ColumnsSun ? vsun : vsune, lds, stream);
 }
 
 // Workgroups of the build that are resident on the device at once.  The weights, view, profiles and errors builds ask the runtime, once per (route, LDS
@@ -2603,8 +2657,9 @@ static int backward_resident(mi3d_solver *h, BwdRoute route, size_t lds, uint64_
         const hipError_t eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, backward_build(route, h->counting != 0, false), 256, lds);
         if (eo != hipSuccess || nb < 1) {
             if (route == BwdRoute::Weights) return fail(MI3D_EDEVICE, "emission weights: no workgroup of the weights build fits a CU with %zu bytes of LDS", lds);
-            if (route == BwdRoute::Profiles) return fail(MI3D_EDEVICE, "view profiles: no workgroup of the profiles build fits a CU with %zu bytes of LDS", lds);
-            if (route == BwdRoute::CameraErrors || route == BwdRoute::ViewsErrors || route == BwdRoute::ViewsSunErrors)
+            if (route == BwdRoute::Profiles || route == BwdRoute::ColumnsProfiles) return fail(MI3D_EDEVICE, "view profiles: no workgroup of the profiles build fits a CU with %zu bytes of LDS", lds);
+            if (route == BwdRoute::CameraErrors || route == BwdRoute::ViewsErrors || route == BwdRoute::ViewsSunErrors || route == BwdRoute::ColumnsErrors ||
+                route == BwdRoute::ColumnsSunErrors)
                 return fail(MI3D_EDEVICE, "pixel errors: no workgroup of the errors build fits a CU with %zu bytes of LDS", lds);
             return fail(MI3D_EDEVICE, "backward Monte Carlo for satellite views: no workgroup fits a CU with %zu bytes of LDS", lds);
         }
@@ -2619,9 +2674,9 @@ static int run_backward(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_
     const bool prf = sat && h->view_profiles != 0;
     const bool var = h->pixel_errors != 0;     // (never with wgt or prf: mi3d_run refuses)
     const bool sun = h->sun_backward();        // (never with wgt or prf: backward_unsupported refuses)
-    const BwdRoute route = sun ? (var ? BwdRoute::ViewsSunErrors : BwdRoute::ViewsSun)
-                           : prf ? BwdRoute::Profiles : sat ? (var ? BwdRoute::ViewsErrors : BwdRoute::Views) : wgt ? BwdRoute::Weights
-                           : var ? BwdRoute::CameraErrors : BwdRoute::Camera;
+    const BwdRoute route = backward_column_route(sun ? (var ? BwdRoute::ViewsSunErrors : BwdRoute::ViewsSun)
+                                                 : prf ? BwdRoute::Profiles : sat ? (var ? BwdRoute::ViewsErrors : BwdRoute::Views) : wgt ? BwdRoute::Weights
+                                                 : var ? BwdRoute::CameraErrors : BwdRoute::Camera, h->col_backward());
     int rc = backward_unsupported(h, sat);
     if (rc) return rc;
     if (h->nview == 0) return fail(MI3D_ESTATE, "radiance requested but no view is set (%s)", sat ? "mi3d_set_views" : "mi3d_set_cameras");
@@ -2765,6 +2820,7 @@ int mi3d_run(mi3d_solver *h, uint64_t nphoton, uint64_t seed, uint64_t photon_of
                     h->view_method != 1 ? "mi3d_set_view_method 0" : h->rad_kind != 2 ? "cameras (mi3d_set_cameras)" : h->cam_method != 0 ? "mi3d_set_camera_method 1"
                                                                                                                       : "mi3d_set_emission_weights 1");
     if (h->view_sunlight && (rc = backward_unsupported(h, h->sat_backward()))) return rc;   // (names mi3d_set_view_sunlight where the refusal is its own)
+    if (h->view_columns && (rc = backward_unsupported(h, h->sat_backward()))) return rc;    // (likewise mi3d_set_view_columns)
     if (h->view_method == 1 && h->rad_kind != 2) return backward_unsupported(h, true);   // (names the switch: it belongs to the views of mi3d_set_views)
     if (h->cam_method == 1 || h->view_method == 1) return run_backward(h, nphoton, seed, photon_offset);
     if (h->emis_weights)
@@ -3401,7 +3457,7 @@ static int debug_backward(mi3d_solver *h, bool sat, uint64_t seed, uint64_t id0,
         // (every slot is written by the history of its id: the hand-out reaches every id of [id0, id0 + n) whatever the grid)
         const int npix = h->nview * h->nxr * h->nyr;
         const size_t lds = backward_lds(npix, h->nz, h->nview, 1, backward_lds_sums(npix, true, S.jch > 0), false, sat);
-        HIPCHK(backward_launch(sun ? BwdRoute::ViewsSun : sat ? BwdRoute::Views : BwdRoute::Camera, false, true, (unsigned)((n + 255) / 256), lds, h->stream, A, seed, id0, (uint64_t)n,
+        HIPCHK(backward_launch(backward_column_route(sun ? BwdRoute::ViewsSun : sat ? BwdRoute::Views : BwdRoute::Camera, sat && h->col_backward()), false, true, (unsigned)((n + 255) / 256), lds, h->stream, A, seed, id0, (uint64_t)n,
                                h->d_bwd_dir.p, h->d_bwd_score.p, BwdWeights{}, S, BwdProfiles{}, BwdErrors{}, N));
         if (sat) HIPCHK(hipMemcpyAsync(start_out, h->d_bwd_start.p, (size_t)3 * n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipMemcpyAsync(dir_out, h->d_bwd_dir.p, (size_t)3 * n * sizeof(float), hipMemcpyDeviceToHost, h->stream));

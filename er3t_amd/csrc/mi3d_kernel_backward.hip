@@ -28,6 +28,10 @@
 //                      scores the sunlight it turns into the line of sight, times the transmittance of a ray from the event to the top.
 //                      The ray is flown by the trips of the same loop, one cell step each, and ends in closed form above the 3-D region.
 //                      The solar cone draws its direction from Philox blocks 2^31, 2^31 + 1, ... of the history, which the walk never reaches
+//   k_backward_vc<COUNT, DEBUG>, k_backward_vcs<COUNT>, k_backward_vcp<COUNT>, k_backward_vcn<COUNT, DEBUG>, k_backward_vcns<COUNT>   the
+//                      histories of k_backward_v, _vs, _vp, _vn, _vns under independent columns and partial 3-D (mi3d_set_view_columns 1;
+//                      DESIGN.md §5.20): a history keeps the column under its start, crosses every layer level to level and folds its
+//                      horizontal position inside the column; no x / y faces, no moves between columns.  DEBUG: mi3d_debug_backward_views
 //   k_backward_norm    read-out: tally of pixel p / number of ids in [0, N) that map to p
 //   k_backward_norm_se   read-out of the standard error of that mean from rad and rad2
 //   k_backward_norm_rows   the same rule for the rows of K_raw, rounded to float32
@@ -104,6 +108,8 @@ struct BwdErrors {
 // the 3-D region: it is in LDS with the layer table already
 struct BwdSun {
     float sdx, sdy, sdz, mu0, F, cos_cone;
+    int ray3d;                         // read by the column builds alone (mi3d_set_view_columns 1): 1 the ray is the direct beam of
+                                       // partial 3-D and flies through the cyclic grid, 0 it keeps the event's column (independent columns)
 };
 
 // One thread per cell, in the order of DevThermal's CDF (k_thermal_power): voxels in file order, layers, surface cells.
@@ -171,12 +177,12 @@ __device__ inline int bwd_wrap(const int i, const float d, const int n) {
     return j < 0 ? 0 : (j >= n ? n - 1 : j);
 }
 
-// The histories, single-sourced for all entry points: mi3d_kernel_backward_body.inc is the body of each, with WGT, SAT, PRF, VAR and SUN
+// The histories, single-sourced for all entry points: mi3d_kernel_backward_body.inc is the body of each, with WGT, SAT, PRF, VAR, SUN and COL
 // constants of the entry point that includes it (and W, S, P, E, N the arguments of the builds that read them)
 template <bool COUNT, bool DEBUG>
 __global__ void __launch_bounds__(256)
 k_backward(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, float *__restrict__ dir_out, double *__restrict__ score_out) {
-    constexpr bool WGT = false, SAT = false, PRF = false, VAR = false, SUN = false;
+    constexpr bool WGT = false, SAT = false, PRF = false, VAR = false, SUN = false, COL = false;
     const BwdWeights W{};
     const BwdSat S{};
     const BwdProfiles P{};
@@ -188,7 +194,7 @@ k_backward(const DevBackward A, const uint64_t seed, const uint64_t id0, const u
 template <bool COUNT>
 __global__ void __launch_bounds__(256)
 k_backward_w(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, const BwdWeights W) {
-    constexpr bool WGT = true, DEBUG = false, SAT = false, PRF = false, VAR = false, SUN = false;
+    constexpr bool WGT = true, DEBUG = false, SAT = false, PRF = false, VAR = false, SUN = false, COL = false;
     float *const dir_out = nullptr; double *const score_out = nullptr;
     const BwdSat S{};
     const BwdProfiles P{};
@@ -201,7 +207,7 @@ template <bool COUNT, bool DEBUG>
 __global__ void __launch_bounds__(256)
 k_backward_v(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, float *__restrict__ dir_out, double *__restrict__ score_out,
              const BwdSat S) {
-    constexpr bool WGT = false, SAT = true, PRF = false, VAR = false, SUN = false;
+    constexpr bool WGT = false, SAT = true, PRF = false, VAR = false, SUN = false, COL = false;
     const BwdWeights W{};
     const BwdProfiles P{};
     const BwdErrors E{};
@@ -212,7 +218,7 @@ k_backward_v(const DevBackward A, const uint64_t seed, const uint64_t id0, const
 template <bool COUNT>
 __global__ void __launch_bounds__(256)
 k_backward_vp(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, const BwdSat S, const BwdProfiles P) {
-    constexpr bool WGT = false, DEBUG = false, SAT = true, PRF = true, VAR = false, SUN = false;
+    constexpr bool WGT = false, DEBUG = false, SAT = true, PRF = true, VAR = false, SUN = false, COL = false;
     float *const dir_out = nullptr; double *const score_out = nullptr;
     const BwdWeights W{};
     const BwdErrors E{};
@@ -238,7 +244,7 @@ k_backward_norm_profiles(const double *__restrict__ raw, float *__restrict__ out
 template <bool COUNT>
 __global__ void __launch_bounds__(256)
 k_backward_s(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, const BwdErrors E) {
-    constexpr bool WGT = false, DEBUG = false, SAT = false, PRF = false, VAR = true, SUN = false;
+    constexpr bool WGT = false, DEBUG = false, SAT = false, PRF = false, VAR = true, SUN = false, COL = false;
     float *const dir_out = nullptr; double *const score_out = nullptr;
     const BwdWeights W{};
     const BwdSat S{};
@@ -250,7 +256,7 @@ k_backward_s(const DevBackward A, const uint64_t seed, const uint64_t id0, const
 template <bool COUNT>
 __global__ void __launch_bounds__(256)
 k_backward_vs(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, const BwdSat S, const BwdErrors E) {
-    constexpr bool WGT = false, DEBUG = false, SAT = true, PRF = false, VAR = true, SUN = false;
+    constexpr bool WGT = false, DEBUG = false, SAT = true, PRF = false, VAR = true, SUN = false, COL = false;
     float *const dir_out = nullptr; double *const score_out = nullptr;
     const BwdWeights W{};
     const BwdProfiles P{};
@@ -281,7 +287,7 @@ template <bool COUNT, bool DEBUG>
 __global__ void __launch_bounds__(256)
 k_backward_vn(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, float *__restrict__ dir_out, double *__restrict__ score_out,
               const BwdSat S, const BwdSun N) {
-    constexpr bool WGT = false, SAT = true, PRF = false, VAR = false, SUN = true;
+    constexpr bool WGT = false, SAT = true, PRF = false, VAR = false, SUN = true, COL = false;
     const BwdWeights W{};
     const BwdProfiles P{};
     const BwdErrors E{};
@@ -291,7 +297,67 @@ k_backward_vn(const DevBackward A, const uint64_t seed, const uint64_t id0, cons
 template <bool COUNT>
 __global__ void __launch_bounds__(256)
 k_backward_vns(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, const BwdSat S, const BwdErrors E, const BwdSun N) {
-    constexpr bool WGT = false, DEBUG = false, SAT = true, PRF = false, VAR = true, SUN = true;
+    constexpr bool WGT = false, DEBUG = false, SAT = true, PRF = false, VAR = true, SUN = true, COL = false;
+    float *const dir_out = nullptr; double *const score_out = nullptr;
+    const BwdWeights W{};
+    const BwdProfiles P{};
+#include "mi3d_kernel_backward_body.inc"
+}
+
+// The histories of the satellite views under independent columns and partial 3-D (mi3d_set_view_columns 1): the same body
+// with COL -- a history keeps the column under its start, every layer is crossed level to level, the x / y faces and the moves between
+// columns are compiled out.  One entry point per SAT build: plain, errors, profiles, sunlight, sunlight with errors.  With sunlight the
+// ray keeps the column too (independent columns) or flies through the cyclic grid as the direct beam (partial 3-D): N.ray3d, one build.
+// (They stand behind every other history kernel so that the code of the kernels before them lies where it lay.)
+template <bool COUNT, bool DEBUG>
+__global__ void __launch_bounds__(256)
+k_backward_vc(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, float *__restrict__ dir_out, double *__restrict__ score_out,
+              const BwdSat S) {
+    constexpr bool WGT = false, SAT = true, PRF = false, VAR = false, SUN = false, COL = true;
+    const BwdWeights W{};
+    const BwdProfiles P{};
+    const BwdErrors E{};
+    const BwdSun N{};
+#include "mi3d_kernel_backward_body.inc"
+}
+
+template <bool COUNT>
+__global__ void __launch_bounds__(256)
+k_backward_vcs(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, const BwdSat S, const BwdErrors E) {
+    constexpr bool WGT = false, DEBUG = false, SAT = true, PRF = false, VAR = true, SUN = false, COL = true;
+    float *const dir_out = nullptr; double *const score_out = nullptr;
+    const BwdWeights W{};
+    const BwdProfiles P{};
+    const BwdSun N{};
+#include "mi3d_kernel_backward_body.inc"
+}
+
+template <bool COUNT>
+__global__ void __launch_bounds__(256)
+k_backward_vcp(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, const BwdSat S, const BwdProfiles P) {
+    constexpr bool WGT = false, DEBUG = false, SAT = true, PRF = true, VAR = false, SUN = false, COL = true;
+    float *const dir_out = nullptr; double *const score_out = nullptr;
+    const BwdWeights W{};
+    const BwdErrors E{};
+    const BwdSun N{};
+#include "mi3d_kernel_backward_body.inc"
+}
+
+template <bool COUNT, bool DEBUG>
+__global__ void __launch_bounds__(256)
+k_backward_vcn(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, float *__restrict__ dir_out, double *__restrict__ score_out,
+               const BwdSat S, const BwdSun N) {
+    constexpr bool WGT = false, SAT = true, PRF = false, VAR = false, SUN = true, COL = true;
+    const BwdWeights W{};
+    const BwdProfiles P{};
+    const BwdErrors E{};
+#include "mi3d_kernel_backward_body.inc"
+}
+
+template <bool COUNT>
+__global__ void __launch_bounds__(256)
+k_backward_vcns(const DevBackward A, const uint64_t seed, const uint64_t id0, const uint64_t n, const BwdSat S, const BwdErrors E, const BwdSun N) {
+    constexpr bool WGT = false, DEBUG = false, SAT = true, PRF = false, VAR = true, SUN = true, COL = true;
     float *const dir_out = nullptr; double *const score_out = nullptr;
     const BwdWeights W{};
     const BwdProfiles P{};

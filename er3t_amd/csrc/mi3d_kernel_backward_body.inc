@@ -1,7 +1,9 @@
 // mi3d_kernel_backward_body.inc — the histories of the backward route, the one body of k_backward<COUNT, DEBUG> and k_backward_w<COUNT>
 // and k_backward_v<COUNT, DEBUG> and k_backward_vp<COUNT> and k_backward_s<COUNT> and k_backward_vs<COUNT> and k_backward_vn<COUNT, DEBUG>
-// and k_backward_vns<COUNT> (mi3d_kernel_backward.hip includes it inside each).  What it expects in scope:
-// COUNT, DEBUG, WGT, SAT, PRF, VAR, SUN (compile-time constants), the arguments A, seed, id0, n, dir_out, score_out, W (BwdWeights: read where WGT
+// and k_backward_vns<COUNT> and the column builds k_backward_vc<COUNT, DEBUG>, k_backward_vcs<COUNT>, k_backward_vcp<COUNT>,
+// k_backward_vcn<COUNT, DEBUG>, k_backward_vcns<COUNT> (mi3d_kernel_backward.hip includes it inside each).  What it expects in scope:
+// COUNT, DEBUG, WGT, SAT, PRF, VAR, SUN, COL (compile-time constants; COL: a history keeps its column, the satellite views under
+// independent columns and partial 3-D, DESIGN.md §5.20), the arguments A, seed, id0, n, dir_out, score_out, W (BwdWeights: read where WGT
 // holds, the weights build of DESIGN.md §5.12), S (BwdSat: read where SAT holds, the satellite-view build of DESIGN.md §5.14), P
 // (BwdProfiles: read where PRF holds, the per-layer profiles of the satellite views, DESIGN.md §5.16) and E (BwdErrors: read where VAR
 // holds, the second tally of the per-pixel standard errors, DESIGN.md §5.17) and N (BwdSun: read where SUN holds, the sunlight term of a
@@ -139,7 +141,7 @@
         }
         staumax = __logf(sung * (1.0f / kBwdWeightEnd));
 #ifdef MI3D_BWD_SUN_NESTED
-        {   // the measurement build of DESIGN.md §5.18's A/B (make EXTRA=-DMI3D_BWD_SUN_NESTED): the whole ray here, in a loop of its own, with the same arithmetic
+        if (!COL) {   // the measurement build of DESIGN.md §5.18's A/B (make EXTRA=-DMI3D_BWD_SUN_NESTED): the whole ray here, in a loop of its own, with the same arithmetic
             const float vx = -sdx, vy = -sdy, vz = -sdz;
             const float bix = frcp(floor_abs(vx)), biy = frcp(floor_abs(vy)), biz = frcp(floor_abs(vz));
             const float qx = A.dx * bix, qy = A.dy * biy;
@@ -235,11 +237,14 @@
                 // direction, and where that line meets the sensor plane z = zs (mi3d.h, mi3d_set_view_method)
                 const ViewRec V = sview[iv];
                 const float xr = ((float)ir + u0) * S.pix_dx, yr = ((float)jr + u1) * S.pix_dy;
-                const float tq = (V.zs - V.zreg) / V.vz;                      // (up-looking: zreg is zs, 0)
-                x = fmaf(V.vx, tq, xr); y = fmaf(V.vy, tq, yr); z = V.zs;
-                x -= S.Lx * floorf(x * S.inv_Lx); y -= S.Ly * floorf(y * S.inv_Ly);
-                x = x >= S.Lx ? x - S.Lx : x; y = y >= S.Ly ? y - S.Ly : y;
-                x = fmaxf(x, 0.0f); y = fmaxf(y, 0.0f);
+                if (COL) { x = xr; y = yr; z = V.zs; }                        // the history belongs to the column under (xr, yr): no parallax shift
+                else {
+                    const float tq = (V.zs - V.zreg) / V.vz;                  // (up-looking: zreg is zs, 0)
+                    x = fmaf(V.vx, tq, xr); y = fmaf(V.vy, tq, yr); z = V.zs;
+                    x -= S.Lx * floorf(x * S.inv_Lx); y -= S.Ly * floorf(y * S.inv_Ly);
+                    x = x >= S.Lx ? x - S.Lx : x; y = y >= S.Ly ? y - S.Ly : y;
+                    x = fmaxf(x, 0.0f); y = fmaxf(y, 0.0f);
+                }
                 ux = -V.vx; uy = -V.vy; uz = -V.vz;
                 if (DEBUG) {
                     dir_out[3 * slot] = ux; dir_out[3 * slot + 1] = uy; dir_out[3 * slot + 2] = uz;
@@ -282,6 +287,7 @@
             }
             if (!ended && z >= A.ztoa) {
                 if (uz >= 0.0f) ended = true;                 // never enters
+                else if (COL) z = A.ztoa;                     // (it enters at the top of its own column)
                 else { const float t = (z - A.ztoa) / -uz; x = fmaf(ux, t, x); y = fmaf(uy, t, y); z = A.ztoa; }
             }
             if (!ended) {
@@ -293,10 +299,17 @@
                 }
                 float cfx = floorf(x * A.inv_dx), cfy = floorf(y * A.inv_dy);
                 float px = x - cfx * A.dx, py = y - cfy * A.dy;
-                if (px <= 0.0f && ux < 0.0f) { cfx -= 1.0f; px = A.dx; }    // on a face: likewise
-                if (py <= 0.0f && uy < 0.0f) { cfy -= 1.0f; py = A.dy; }
+                if (COL) {
+                    // the column that contains the point, clipped: no face rule, the direction does not choose the column
+                    cfx = fminf(fmaxf(cfx, 0.0f), (float)(A.nx - 1)); cfy = fminf(fmaxf(cfy, 0.0f), (float)(A.ny - 1));
+                    px = x - cfx * A.dx; py = y - cfy * A.dy;
+                } else {
+                    if (px <= 0.0f && ux < 0.0f) { cfx -= 1.0f; px = A.dx; }    // on a face: likewise
+                    if (py <= 0.0f && uy < 0.0f) { cfy -= 1.0f; py = A.dy; }
+                }
                 px = fminf(fmaxf(px, 0.0f), A.dx); py = fminf(fmaxf(py, 0.0f), A.dy);
-                ix = bwd_wrap(0, cfx, A.nx); iy = bwd_wrap(0, cfy, A.ny);
+                if (COL) { ix = (int)cfx; iy = (int)cfy; }
+                else { ix = bwd_wrap(0, cfx, A.nx); iy = bwd_wrap(0, cfy, A.ny); }
                 const float dzk = slay[k].dz;
                 set_dda(px, py, fminf(fmaxf(z - slay[k].zlo, 0.0f), dzk), dzk);
                 new_flight();
@@ -306,6 +319,10 @@
             // ---- one cell step: the segment up to the next face (a level, outside the 3-D region) or to the end of the flight
             const LayerRec &L = slay[k];
             const bool in3d = (L.flags & kLayIn3d) != 0;
+            // does this step cross x / y faces and move through the cyclic grid?  Always, but in a COL build: there the history keeps its
+            // column and so does the sun ray of independent columns; the direct beam of partial 3-D (N.ray3d) alone flies in 3-D
+            const bool cyc = !COL || (SUN && sun && N.ray3d != 0);
+            const bool faces = cyc && in3d;
             float ks = 0.0f, ks0 = 0.0f, apf0 = 0.0f;
             float2 cell;
             const int k3 = k - A.k3lo;
@@ -316,7 +333,7 @@
                 for (int ip = 1; ip < A.np3d; ++ip) ks += A.csca[(((size_t)iy * A.nx + ix) * A.nz3 + k3) * A.np3d + ip].x;
             } else cell = A.cells[A.nvox + k];
             for (int ip = 0; ip < A.np1d; ++ip) ks += L.ks1d[ip];
-            const float dface = in3d ? fminf(fminf(tx, ty), tz) : tz;
+            const float dface = faces ? fminf(fminf(tx, ty), tz) : tz;
             const float dsc = SUN && sun ? 3.0e38f : ks > 0.0f ? taus * frcp(ks) : 3.0e38f;    // (a sun ray has no free path: it ends at the top)
             const bool scat = dsc < dface;
             const float ds = scat ? dsc : dface;
@@ -341,13 +358,13 @@
             w *= e;
             if (!(SUN && sun)) steps++;
             if (COUNT) { c_steps++; if (in3d) c_steps3d++; }
-            const bool hitz = !scat && (!in3d || (tz <= tx && tz <= ty)), hitx = !scat && !hitz && tx <= ty, hity = !scat && !hitz && !hitx;
+            const bool hitz = !scat && (!faces || (tz <= tx && tz <= ty)), hitx = !scat && !hitz && tx <= ty, hity = !scat && !hitz && !hitx;
             tx -= ds; ty -= ds; tz -= ds;
             taus = fmaxf(taus - ks * ds, 0.0f);
-            if (!in3d) {
-                // a layer without x / y faces: the columns crossed on the way
-                if (tx < 0.0f) { const float nc = floorf(-tx / sx) + 1.0f; tx = fminf(fmaxf(fmaf(nc, sx, tx), 0.0f), sx); ix = bwd_wrap(ix, ux > 0.0f ? nc : -nc, A.nx); }
-                if (ty < 0.0f) { const float nc = floorf(-ty / sy) + 1.0f; ty = fminf(fmaxf(fmaf(nc, sy, ty), 0.0f), sy); iy = bwd_wrap(iy, uy > 0.0f ? nc : -nc, A.ny); }
+            if (!faces) {
+                // a layer without x / y faces: the columns crossed on the way (COL: the position folds inside the column, which stays)
+                if (tx < 0.0f) { const float nc = floorf(-tx / sx) + 1.0f; tx = fminf(fmaxf(fmaf(nc, sx, tx), 0.0f), sx); if (cyc) ix = bwd_wrap(ix, ux > 0.0f ? nc : -nc, A.nx); }
+                if (ty < 0.0f) { const float nc = floorf(-ty / sy) + 1.0f; ty = fminf(fmaxf(fmaf(nc, sy, ty), 0.0f), sy); if (cyc) iy = bwd_wrap(iy, uy > 0.0f ? nc : -nc, A.ny); }
             }
             if (SUN && sun) {
                 // ---- the sun ray: on through the next face; above the 3-D region and at the top it ends in closed form
@@ -406,8 +423,8 @@
                 }
                 if (SUN && sun_start(px, py, pz, ended)) ended = false;           // (the history's end, if it has come, waits for the ray's)
                 else if (!ended) new_flight();
-            } else if (hitx) { tx = sx; ix += ux > 0.0f ? 1 : -1; ix = ix < 0 ? A.nx - 1 : (ix >= A.nx ? 0 : ix); }
-            else if (hity) { ty = sy; iy += uy > 0.0f ? 1 : -1; iy = iy < 0 ? A.ny - 1 : (iy >= A.ny ? 0 : iy); }
+            } else if (!COL && hitx) { tx = sx; ix += ux > 0.0f ? 1 : -1; ix = ix < 0 ? A.nx - 1 : (ix >= A.nx ? 0 : ix); }
+            else if (!COL && hity) { ty = sy; iy += uy > 0.0f ? 1 : -1; iy = iy < 0 ? A.ny - 1 : (iy >= A.ny ? 0 : iy); }
             else if (uz > 0.0f) {
                 if (++k >= A.nz) ended = true;                 // the top: space is cold
                 else tz = slay[k].dz * aiz;

@@ -73,6 +73,20 @@ def _check_supported(nml, fdir=None, solver=None):
                 else None
             if why:
                 raise OSError('Error [mca_exe]: <Rad_mvsun=1> (sunlight on the backward satellite views) needs %s.' % why)
+    if nml.get('Rad_mvcol') is not None:
+        mvcol = float(np.ravel(nml.get('Rad_mvcol'))[0])
+        if mvcol not in (0.0, 1.0):
+            raise OSError('Error [mca_exe]: <Rad_mvcol=%g> is not supported (0: off, 1: the backward satellite views under independent columns and '
+                          'partial 3-D; a key of this project).' % mvcol)
+        if mvcol == 1.0:
+            why = 'the backward route for satellite views (<Rad_mvbwd=1>)' if _flag(nml, 'Rad_mvbwd') != 1.0 \
+                else 'satellite views (<Rad_mrkind=2>): the lines of sight of cameras and point radiometers fan out over the columns' \
+                if int(nml.get('Rad_mrkind', 2)) != 2 \
+                else 'a job without emission weights (<Rad_mwgt=1>): an image times the cells is not served' if _flag(nml, 'Rad_mwgt') == 1.0 \
+                else 'independent columns or partial 3-D (solver 2 or 1): the 3-D solver runs without the switch' \
+                if solver is not None and int(solver) == 0 else None
+            if why:
+                raise OSError('Error [mca_exe]: <Rad_mvcol=1> (column histories of the backward satellite views) needs %s.' % why)
     if nml.get('Rad_mvbwd') is not None:
         mvbwd = float(np.ravel(nml.get('Rad_mvbwd'))[0])
         if mvbwd not in (0.0, 1.0):
@@ -127,7 +141,7 @@ def _check_supported(nml, fdir=None, solver=None):
             raise OSError('Error [mca_exe]: <Src_fsol=%g> of a solar+thermal job (<Src_mtype=2>) must be finite and >= 0.' % fsol)
     if mtype in (2, 3):
         _check_thermal(nml, fdir)
-    if solver is not None and int(solver) != 0 and _flag(nml, 'Rad_mvbwd') == 1.0:
+    if solver is not None and int(solver) != 0 and _flag(nml, 'Rad_mvbwd') == 1.0 and _flag(nml, 'Rad_mvcol') != 1.0:
         raise OSError('Error [mca_exe]: <Rad_mvbwd=1> (backward Monte Carlo for satellite views) needs the 3-D solver: a line of sight crosses '
                       'columns (independent columns and partial 3-D are not served).')
 

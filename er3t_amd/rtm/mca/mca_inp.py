@@ -104,6 +104,7 @@ _CATALOGUE = [
         ('Rad_mwgt', 'with Rad_mbwd = 1: 1 per-cell emission weights of every pixel, an extra output file (a key of this project, written only when 1)'),
         ('Rad_mvprf', 'with Rad_mvbwd = 1: 1 per-layer weighting function and contribution of every pixel, an extra output file (a key of this project, written only when 1)'),
         ('Rad_mvsun', 'with Rad_mvbwd = 1 and Src_mtype = 2: 1 the backward satellite views serve the solar+thermal job, a sun ray per scattering and reflection (a key of this project, written only when 1)'),
+        ('Rad_mvcol', 'with Rad_mvbwd = 1 under the IPA or partial 3-D solver: 1 the backward satellite views are served there, a history keeps its column (a key of this project, written only when 1)'),
         ('Rad_mserr', 'with Rad_mbwd = 1 or Rad_mvbwd = 1: 1 standard error of every pixel from the job\'s own histories, an extra output file (a key of this project, written only when 1)')]),
 ]
 

@@ -115,7 +115,7 @@ class mcarats_ng:
                            the emission along the view's line of sight, every pixel gets the same number of histories (Rad_mvbwd=1, a key of
                            this project written only then: include/mi3d.h, mi3d_set_view_method).  Sequences of sensor angles
                            (several views in one simulation) are served; `mca_out_ng` is unchanged: rad, bt and the view axis come out as for
-                           the forward job
+                           the forward job.  <solver='ipa'> and <solver='p3d'>: with view_columns=True (below)
         emission_weights [False]: with camera_method='backward': every job also tallies K[pixel][cell], the share of a pixel's reading that comes
                            from a voxel, a layer or a surface cell per unit Planck radiance there (Rad_mwgt=1, a key of this project written
                            only then: include/mi3d.h, mi3d_set_emission_weights); mca_out_ng returns data['emission_weight']
@@ -133,6 +133,11 @@ class mcarats_ng:
                            the line of sight, through a ray to the top of the atmosphere (Rad_mvsun=1, a key of this project written only
                            then: include/mi3d.h, mi3d_set_view_sunlight).  rad and bt include the sun, as the forward mixed
                            job's do; pixel_errors=True is served, view_profiles=True is not
+        view_columns [False]: with view_method='backward' and <solver='ipa'> or <solver='p3d'>: the backward route serves independent columns
+                           and partial 3-D -- a history keeps the column under its start and crosses every layer level to level
+                           (Rad_mvcol=1, a key of this project written only then: include/mi3d.h, mi3d_set_view_columns).
+                           The IPA twin of a backward 3-D image with the same outputs: pixel_errors=True, view_profiles=True and
+                           view_sunlight=True are served, emission_weights=True is not
 
     Afterwards: input and output files under <fdir>; attributes Ng, Nrun, Nx, Ny, dx, dy, date, target, solver,
     photons (Nrun*Ng,), photons_per_set, fnames_inp[ir][ig], fnames_out[ir][ig], nml (list of Ng dictionaries).
@@ -147,7 +152,7 @@ class mcarats_ng:
                  sensor_ypos=0.5, solver='3d', photons=1e7, base_ratio=0.05, verbose=False, quiet=False,
                  abs_obj=None, keep_files=True, source='solar', wavelength=None, surface_temperature=None,
                  heating_estimator='collision', camera_images=None, camera_method='forward', emission_weights=False, view_method='forward',
-                 view_profiles=False, pixel_errors=False, view_sunlight=False):
+                 view_profiles=False, pixel_errors=False, view_sunlight=False, view_columns=False):
 
         # one process per GPU (torch.distributed): rank 0 writes the job files, all ranks transport their share of every job
         from er3t_amd.dist import world_info, barrier
@@ -205,11 +210,24 @@ class mcarats_ng:
         self.view_method = str(view_method).lower()
         if self.view_method not in ('forward', 'backward'):
             raise OSError('Error [mcarats_ng]: <view_method=%s> must be \'forward\' or \'backward\'.' % view_method)
+        self.view_columns = bool(view_columns)
+        if self.view_columns and self.point_sensor:
+            raise OSError('Error [mcarats_ng]: <view_columns=True> (Rad_mvcol) belongs to <sensor_type=\'satellite\'>: the lines of sight of cameras '
+                          'and point radiometers (<sensor_type=%r>) fan out over the columns.' % sensor_type)
+        if self.view_columns and self.view_method != 'backward':
+            raise OSError('Error [mcarats_ng]: <view_columns=True> (Rad_mvcol) needs <view_method=\'backward\'>: the forward route serves '
+                          '<solver=\'ipa\'> and <solver=\'p3d\'> without a switch.')
+        if self.view_columns and _match(solver, _SOLVERS, 'solver') == '3D':
+            raise OSError('Error [mcarats_ng]: <view_columns=True> (Rad_mvcol) belongs to <solver=\'ipa\'> and <solver=\'p3d\'>: under '
+                          '<solver=\'3d\'> a history crosses columns, run it without the switch.')
+        if self.view_columns and emission_weights:
+            raise OSError('Error [mcarats_ng]: <emission_weights=True> does not go with <view_columns=True> (Rad_mvcol): the weights of an image '
+                          'times the cells are not served.')
         self.view_sunlight = bool(view_sunlight)
         if self.view_sunlight and not (self.view_method == 'backward' and self.source == 'solar+thermal'):
             raise OSError('Error [mcarats_ng]: <view_sunlight=True> (Rad_mvsun) needs <view_method=\'backward\'> and <source=\'solar+thermal\'>: the '
                           'switch belongs to the mixed source; a pure solar image is a mixed job with a cold atmosphere, a thermal one needs no sun.')
-        if self.view_sunlight and (str(target).lower() not in _TARGETS['radiance'] or _match(solver, _SOLVERS, 'solver') != '3D'):
+        if self.view_sunlight and (str(target).lower() not in _TARGETS['radiance'] or (_match(solver, _SOLVERS, 'solver') != '3D' and not self.view_columns)):
             raise OSError('Error [mcarats_ng]: <view_sunlight=True> (Rad_mvsun) needs <target=\'radiance\'> and <solver=\'3d\'>, as '
                           '<view_method=\'backward\'> does.')
         if self.view_sunlight and view_profiles:
@@ -225,7 +243,7 @@ class mcarats_ng:
                 raise OSError('Error [mcarats_ng]: <view_method=\'backward\'> needs <source=\'thermal\'> and <target=\'radiance\'> with '
                               '<sensor_type=\'satellite\'>: backward histories collect emission; the sun would need a local estimate of its own '
                               '(cameras and point radiometers: <camera_method>; <source=\'solar+thermal\'> is served with <view_sunlight=True>).')
-            if _match(solver, _SOLVERS, 'solver') != '3D':
+            if _match(solver, _SOLVERS, 'solver') != '3D' and not self.view_columns:
                 raise OSError('Error [mcarats_ng]: <view_method=\'backward\'> needs <solver=\'3d\'>: a line of sight crosses columns.')
             if emission_weights:
                 raise OSError('Error [mcarats_ng]: <emission_weights=True> does not go with <view_method=\'backward\'>: the weights of an image times '
@@ -331,6 +349,8 @@ class mcarats_ng:
             self._all({'Rad_mvbwd': 1})
             if self.view_profiles:                     # (likewise)
                 self._all({'Rad_mvprf': 1})
+            if self.view_columns:                      # (likewise)
+                self._all({'Rad_mvcol': 1})
             if self.view_sunlight:                     # (likewise)
                 self._all({'Rad_mvsun': 1})
         if self.pixel_errors:                          # (likewise)

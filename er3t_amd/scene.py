@@ -129,6 +129,9 @@ class Scene:
     view_sunlight: int = 0                # Rad_mvsun (a key of this project; include/mi3d.h: mi3d_set_view_sunlight): 1 the backward route for
                                           # satellite views serves a solar+thermal job (src_mtype = 2): every scattering and reflection
                                           # also scores its sunlight; needs rad_kind = 2, view_method = 1, without view_profiles
+    view_columns: int = 0                 # Rad_mvcol (a key of this project; include/mi3d.h: mi3d_set_view_columns): 1 the backward route for
+                                          # satellite views serves independent columns and partial 3-D (solver = 2 / 1): a history keeps
+                                          # its column; needs rad_kind = 2, view_method = 1, not under the 3-D solver
 
     # job
     target: int = TARGET_FLUX
@@ -229,6 +232,15 @@ class Scene:
                   else 'a sun from above (<src_the> - <src_qmax>/2 > 90)' if not (float(self.src_the) - 0.5*max(float(self.src_qmax), 0.0) > 90.0) else None
             if why:
                 raise ValueError('Error [Scene]: <view_sunlight=1> (Rad_mvsun) needs %s.' % why)
+        if self.view_columns not in (0, 1) or isinstance(self.view_columns, float):
+            raise ValueError('Error [Scene]: <view_columns=%s> (Rad_mvcol) must be 0 or 1.' % (self.view_columns,))
+        if self.view_columns == 1:
+            why = 'the backward route for satellite views (<rad_kind=2>, <view_method=1>, Rad_mvbwd=1): cameras and point radiometers fan out over ' \
+                  'the columns' if not (self.rad_kind == 2 and self.view_method == 1) \
+                  else 'independent columns or partial 3-D (<solver=2> or <solver=1>): the 3-D solver runs without the switch' \
+                  if int(self.solver) == SOLVER_3D else None
+            if why:
+                raise ValueError('Error [Scene]: <view_columns=1> (Rad_mvcol) needs %s.' % why)
         if self.src_mtype in (2, 3):
             if self.src_mtype == 2:
                 if self.src_fsol is None or not (float(self.src_fsol) >= 0.0) or not np.isfinite(float(self.src_fsol)):
@@ -406,7 +418,22 @@ class Scene:
         if mvsun == 1.0 and not (mvbwd == 1.0 and mtype == 2):
             raise OSError('Error [Scene]: <Rad_mvsun=1> (sunlight on the backward satellite views) needs <Rad_mvbwd=1> and the solar+thermal source '
                           '(<Src_mtype=2>); a pure solar image is a mixed job with a cold atmosphere.')
-        if mvbwd == 1.0 and not ((mtype == 3 or (mtype == 2 and mvsun == 1.0)) and mtarget == 2 and int(get('Rad_mrkind', 2)) == 2 and int(solver) == SOLVER_3D):
+        # (a key of this project: that route under independent columns and partial 3-D, a history keeps its column)
+        mvcol = float(np.ravel(get('Rad_mvcol', 0))[0])
+        if mvcol not in (0.0, 1.0):
+            raise OSError('Error [Scene]: <Rad_mvcol=%g> is not supported (0: off, 1: the backward satellite views under independent columns and '
+                          'partial 3-D).' % mvcol)
+        if mvcol == 1.0 and (int(get('Rad_mrkind', 2)) != 2 or float(np.ravel(get('Rad_mwgt', 0))[0]) == 1.0):
+            raise OSError('Error [Scene]: <Rad_mvcol=1> (column histories of the backward satellite views) belongs to satellite views '
+                          '(<Rad_mrkind=2>) without emission weights (<Rad_mwgt=1>): cameras and point radiometers fan out over the columns.')
+        if mvcol == 1.0 and mvbwd != 1.0:
+            raise OSError('Error [Scene]: <Rad_mvcol=1> (column histories of the backward satellite views) needs the backward route for satellite '
+                          'views (<Rad_mvbwd=1>).')
+        if mvcol == 1.0 and int(solver) == SOLVER_3D:
+            raise OSError('Error [Scene]: <Rad_mvcol=1> (column histories of the backward satellite views) belongs to independent columns and '
+                          'partial 3-D (solver 2 / 1): the 3-D solver runs without the switch.')
+        if mvbwd == 1.0 and not ((mtype == 3 or (mtype == 2 and mvsun == 1.0)) and mtarget == 2 and int(get('Rad_mrkind', 2)) == 2
+                                 and (int(solver) == SOLVER_3D or mvcol == 1.0)):
             raise OSError('Error [Scene]: <Rad_mvbwd=1> (backward Monte Carlo) belongs to the satellite views (<Rad_mrkind=2>) of a thermal radiance '
                           'job (<Src_mtype=3>, <Wld_mtarget=2>) under the 3-D solver (a solar+thermal job, <Src_mtype=2>, with <Rad_mvsun=1>).')
         # (a key of this project: per-cell emission weights of the backward route)
@@ -462,7 +489,7 @@ class Scene:
             elif mrkind != 2:
                 raise OSError('Error [Scene]: <Rad_mrkind=%d> is not supported (1: camera, 2: satellite).' % mrkind)
             else:
-                kw.update(view_method=int(mvbwd), view_profiles=int(mvprf), pixel_errors=int(mserr), view_sunlight=int(mvsun))
+                kw.update(view_method=int(mvbwd), view_profiles=int(mvprf), pixel_errors=int(mserr), view_sunlight=int(mvsun), view_columns=int(mvcol))
         elif mtarget == 1:
             mhrt = int(get('Flx_mhrt', 0) or 0)
             if mhrt == 2 and mtype not in (2, 3):

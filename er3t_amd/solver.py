@@ -61,6 +61,7 @@ _SIGNATURES = [
     ('mi3d_get_radiance_se'    , C.c_int   , [C.c_void_p, _u64, _fp]),
     ('mi3d_debug_backward_chunk', C.c_int  , [C.c_void_p]),
     ('mi3d_set_view_sunlight'  , C.c_int   , [C.c_void_p, C.c_int]),
+    ('mi3d_set_view_columns'   , C.c_int   , [C.c_void_p, C.c_int]),
     ('mi3d_set_options'        , C.c_int   , [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int]),
     ('mi3d_set_le_roulette'    , C.c_int   , [C.c_void_p, C.c_double]),
     ('mi3d_set_le_weight_roulette', C.c_int, [C.c_void_p, C.c_double]),
@@ -328,6 +329,12 @@ class Mi3dSolver:
         the line of sight.  True / False or the value itself (anything but 0 and 1 is refused by the library)"""
         self._chk(self.lib.mi3d_set_view_sunlight(self._h, int(on)))
 
+    def set_view_columns(self, on=True):
+        """the backward route's satellite views under independent columns and partial 3-D (include/mi3d.h: mi3d_set_view_columns): on, the
+        route serves solver 2 (IPA) and 1 (partial 3-D) -- a history keeps the column under its start and crosses every layer level to level.
+        True / False or the value itself (anything but 0 and 1 is refused by the library)"""
+        self._chk(self.lib.mi3d_set_view_columns(self._h, int(on)))
+
     def set_options(self, target=TARGET_FLUX, solver=0, wmin=0.2, wfac=1.0, column_le=True):
         self._chk(self.lib.mi3d_set_options(self._h, int(target), int(solver), float(wmin), float(wfac), 1 if column_le else 0))
 
@@ -375,6 +382,8 @@ class Mi3dSolver:
             self.set_pixel_errors(int(getattr(s, 'pixel_errors', 0)))
         if int(getattr(s, 'view_sunlight', 0)) or not getattr(self.lib.mi3d_set_view_sunlight, 'stale', False):    # (likewise)
             self.set_view_sunlight(int(getattr(s, 'view_sunlight', 0)))
+        if int(getattr(s, 'view_columns', 0)) or not getattr(self.lib.mi3d_set_view_columns, 'stale', False):      # (likewise)
+            self.set_view_columns(int(getattr(s, 'view_columns', 0)))
         self.set_options(s.target, s.solver, s.wmin, s.wfac, column_le)
         self.set_heating_estimator(int(getattr(s, 'heat_estimator', 0)))
         self.set_le_roulette(getattr(s, 'le_tau1', 0.0))

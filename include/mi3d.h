@@ -320,7 +320,9 @@ int mi3d_set_camera_method(mi3d_solver *h, int method);
  * is MI3D_EINVAL.
  *   Served     Src_mtype = 3, the views of mi3d_set_views, a radiance job of the 3-D solver, Lambertian surfaces (uniform or 2-D, Sfc_tmps2d
  *              included).  Solar and solar+thermal jobs, flux jobs, independent columns, partial 3-D, non-Lambertian surfaces, and
- *              mi3d_set_emission_weights 1 (an image times the cells): MI3D_EUNSUP from mi3d_run, with the reason.  The switch is
+ *              mi3d_set_emission_weights 1 (an image times the cells): MI3D_EUNSUP from mi3d_run, with the reason.  (Solar+thermal jobs
+ *              have a switch of their own, mi3d_set_view_sunlight; independent columns and partial 3-D have one too, mi3d_set_view_columns.)
+ *              The switch is
  *              accepted while cameras are set (mi3d_set_cameras); mi3d_run then returns MI3D_EUNSUP and names it.  A down-looking view
  *              whose sensor plane lies on or below the surface: MI3D_EINVAL.  mi3d_last_kernel: "k_backward<C,V> [thermal]".
  *   Pixel      as for mi3d_set_camera_method 1: npix = nview nyr nxr, history id belongs to the flat pixel p = id mod npix in the tally
@@ -449,7 +451,7 @@ int mi3d_get_radiance_se(mi3d_solver *h, uint64_t nphoton_total, float *out);
  *              cameras and point radiometers (Rad_mrkind = 1), mi3d_set_view_profiles 1 (the weighting functions are per unit Planck
  *              radiance: the sun has no row), mi3d_set_emission_weights 1, a sun from below or on the horizon (Src_the - Src_qmax / 2
  *              <= 90).  Flux jobs, independent columns, partial 3-D and non-Lambertian surfaces are refused as mi3d_set_view_method 1
- *              refuses them.  mi3d_set_pixel_errors 1 is served: the sun's terms enter the score like every other.
+ *              refuses them (independent columns and partial 3-D are served with mi3d_set_view_columns 1 beside this switch).  mi3d_set_pixel_errors 1 is served: the sun's terms enter the score like every other.
  *   History    that of mi3d_set_view_method 1, untouched: free paths by the scattering coefficient, w *= exp(-ka l), emission scored per
  *              cell step, Lambert reflection with w *= 1 - eps, the same Philox blocks.  The path and the weight of history (seed, id) are
  *              those of the thermal job (Src_mtype = 3) whatever the sun does.
@@ -478,6 +480,45 @@ int mi3d_get_radiance_se(mi3d_solver *h, uint64_t nphoton_total, float *out);
  *   Result     that of mi3d_set_view_method 1: every pixel divided by its own count of histories, absolute W m-2 sr-1 um-1, the score
  *              carries Src_flx; the brightness temperature of such an image includes the sun, as the forward mixed job's does. */
 int mi3d_set_view_sunlight(mi3d_solver *h, int on);
+
+/* The backward route's satellite views under independent columns and partial 3-D: the IPA twin of a backward 3-D image, with the same
+ * error bars and weighting functions (er3t_amd/csrc/mi3d_kernel_backward.hip; the project's namelist key Rad_mvcol = 1).
+ *   Switch     mi3d_set_view_columns: 0 (default) nothing of this runs -- kernels, names, refusals and results are those of the library
+ *              without it; 1: mi3d_run serves solver MI3D_SOLVER_IPA and MI3D_SOLVER_P3D under mi3d_set_view_method 1 with the views of
+ *              mi3d_set_views.  Anything but 0 or 1 is MI3D_EINVAL.  mi3d_last_kernel: "k_backward<C,V,I> [thermal]", with
+ *              mi3d_set_pixel_errors 1 "k_backward<C,V,I,S> [thermal]", with mi3d_set_view_profiles 1 "k_backward<C,V,I,P> [thermal]",
+ *              with mi3d_set_view_sunlight 1 "k_backward<C,V,I,N> [solar+thermal]" and "k_backward<C,V,I,N,S> [solar+thermal]".
+ *              mi3d_debug_backward_views runs the same code for single histories.
+ *   Refused    with the switch on, MI3D_EUNSUP from mi3d_run in words that name it: the 3-D solver (the switch belongs to independent
+ *              columns and partial 3-D), mi3d_set_view_method 0 or mi3d_set_camera_method 1, cameras and point radiometers
+ *              (Rad_mrkind = 1), mi3d_set_emission_weights 1.  Everything else is refused as mi3d_set_view_method 1 refuses it.
+ *              Served: the plain route, mi3d_set_pixel_errors 1, mi3d_set_view_profiles 1, mi3d_set_view_sunlight 1 with or without
+ *              pixel errors.
+ *   Start      Philox block 0 of (seed, id) is read as under the 3-D solver: u0, u1 place (xr, yr) inside pixel id mod npix,
+ *              xr = (ir + u0) Lx / nxr, yr = (jr + u1) Ly / nyr.  The history belongs to the column that contains (xr, yr):
+ *              ix = floor(xr / dx), iy = floor(yr / dy), clipped to the grid; the face rule of the 3-D start, by which the direction
+ *              chooses between two cells, does not apply.  There is no parallax shift to the sensor plane: the history starts at
+ *              (xr, yr, zs), or enters at the top of the atmosphere above (xr, yr), and flies along -v.  (The forward route under
+ *              independent columns registers an event in its own column without that shift too.)
+ *   Walk       the history never changes ix, iy.  Every layer is crossed level to level, whether or not it lies in the 3-D region.
+ *              {ka, B}, ks and the phase function come from the column's own voxel in the layers of the 3-D region and from the layer's
+ *              record elsewhere.  The horizontal position inside the column folds cyclically with period (dx, dy) and leaves the column
+ *              where it is, so a 2-D surface grid is read at (ix dx + px, iy dy + py) as the forward route under independent columns
+ *              reads it.  Scattering, reflection, the weight roulette, the end below a weight of 1e-7, the cap of 2^20 cell steps and
+ *              the order of the Philox blocks are those of mi3d_set_view_method 1.
+ *   Partial 3-D   a thermal job has no direct beam, so MI3D_SOLVER_P3D is MI3D_SOLVER_IPA: the same build, the same ids, the same tallies
+ *              bit for bit.
+ *   Sunlight   with mi3d_set_view_sunlight 1 (Src_mtype = 2) the walk is as above and the sun ray of an event differs by solver.
+ *              Independent columns: the ray stays in the event's column, steps level to level and ends in closed form above the 3-D
+ *              region.  Partial 3-D: the ray is the direct beam; it is flown through the cyclic 3-D grid exactly as under the 3-D
+ *              solver, from the event's folded position in its column, and the history then resumes in its column.  One build serves
+ *              both.
+ *   Expectation   the image equals the forward job's of the same solver wherever a pixel covers whole columns, or the surface grid is no
+ *              finer than the columns.  Otherwise the registration inside a column differs under slant views: a backward history starts
+ *              at its pixel's point of the column and drifts from there, a forward photon's event lands in the pixel under the event.
+ *              Both are independent-column answers; they differ by how a column's radiance is spread over the pixels that cut it.
+ *   Result     that of mi3d_set_view_method 1: every pixel divided by its own count of histories, absolute W m-2 sr-1 um-1. */
+int mi3d_set_view_columns(mi3d_solver *h, int on);
 
 /* Job options = 1st/2nd CLI arguments and keys Wld_mtarget, Flx_mflx, Pho_wmin
  * (er3t/rtm/mca/mcarats.py:267-287,450-454; er3t/rtm/mca/mca_inp.py:196-198).

@@ -49,6 +49,12 @@ for what the sun rays cost a history, by the backward thermal route of the same 
 ranges; histories (photons) per second, kernel time, relative standard error per pixel (mean, largest), merit 1 / (se^2 t), the image means,
 and from the counting build the cell steps per history of both backward jobs: their difference is the sun rays'.
     python tools/thermal_rate.py --legs sun --photons 2e6 --per-pixel 32
+Leg 'col' (DESIGN.md 5.20): the image of the 'sat' leg (a nadir and a 45 degree view) of the thermal job under independent columns, by the
+forward route (solver 2), by backward Monte Carlo with the column histories (solver 2, view_columns = 1) and, for the rate of the build, by
+backward Monte Carlo under the 3-D solver: at 8 and at 32 histories per pixel and launch, the three jobs in turn, `--reps` times; 16 batches
+each over disjoint id ranges; histories (photons) per second, kernel time, relative standard error per pixel (mean, largest), merit
+1 / (se^2 t), the image means and, from the counting build, the cell steps per history of the backward jobs.
+    python tools/thermal_rate.py --legs col --photons 2e6
 """
 
 import argparse
@@ -191,6 +197,54 @@ def sun_rows(sol, name, s, n_fwd, per_pixel, nb=16):
     finally:
         sol.set_counting(False)
         sol.set_view_sunlight(False)
+        sol.set_view_method('forward')
+    return rows
+
+
+def col_rows(sol, name, s, n_fwd, per_pixels=(8, 32), nb=16, reps=3):
+    """the 'col' leg: scene s, a thermal job, under independent columns by the forward route and by the backward route with the
+    column histories, and under the 3-D solver by the backward route; the three in turn, `reps` times at every number of histories per pixel
+    and launch of `per_pixels`; nb batches each over disjoint id ranges"""
+    s = dataclasses.replace(s, view_the=[180.0, 135.0], view_phi=[0.0, 0.0], view_zloc=[1.0e6, 1.0e6], nxr=s.nx, nyr=s.ny)
+    npix = 2*s.nx*s.ny
+    rows = []
+    try:
+        for pp in per_pixels:
+            jobs = [('col_forward_ipa', dataclasses.replace(s, solver=2, view_method=0), n_fwd),
+                    ('col_backward_ipa', dataclasses.replace(s, solver=2, view_method=1, view_columns=1), pp*npix),
+                    ('col_backward_3d', dataclasses.replace(s, solver=0, view_method=1), pp*npix)]
+            for rep in range(reps):
+                for target, sc, n in jobs:
+                    sol.load_scene(sc)
+                    sol.reset(); sol.run(min(n, 2000000), seed=1); sol.sync()        # warm-up
+                    tot, sq, ms_all = np.zeros((2, s.ny, s.nx)), np.zeros((2, s.ny, s.nx)), 0.0
+                    for b in range(nb):
+                        sol.reset()
+                        sol.run(n, seed=2, offset=b*n)
+                        r = sol.radiance(n).astype(np.float64)
+                        tot += r; sq += r*r
+                        ms_all += sol.timing()[0]
+                    mean = tot/nb
+                    se = np.sqrt(np.maximum(sq/nb-mean*mean, 0.0)/(nb-1))
+                    ok = mean > 0.0
+                    rel = se[ok]/mean[ok]
+                    t = ms_all*1e-3
+                    row = dict(scene=name, target=target, kernel=sol.kernel_name(), per_pixel=pp, rep=rep, histories_per_batch=n, batches=nb,
+                               histories_per_s=float(nb*n/t), kernel_s=float(t), image_mean=[float(m.mean()) for m in mean],
+                               image_mean_se=[float(np.sqrt((e**2).sum())/e.size) for e in se], pixels_without_a_score=int((~ok).sum()),
+                               rel_se_mean=float(rel.mean()), rel_se_max=float(rel.max()), merit=float(1.0/(rel.mean()**2*t)))
+                    if sc.view_method and rep == 0:
+                        sol.set_counting(True)
+                        sol.reset(); sol.run(n, seed=2); sol.sync()
+                        c = sol.counters()
+                        sol.set_counting(False)
+                        row.update(chunk_launched=sol.lib.mi3d_debug_backward_chunk(sol._h), capped=sol.debug_backward_views(2, 0, 0)[3],
+                                   steps_per_history=c['steps']/n, steps3d_per_history=c['steps3d']/n, events_per_history=(c['scatter']+c['surface'])/n)
+                    rows.append(row)
+                    print(json.dumps(row), flush=True)
+    finally:
+        sol.set_counting(False)
+        sol.set_view_columns(False)
         sol.set_view_method('forward')
     return rows
 
@@ -349,6 +403,10 @@ def main():
                 sol.set_kernel(general=False)
                 s = thermal(les_scene(target='radiance', **kw), lev, wl=3.75)
                 rows += sun_rows(sol, name, dataclasses.replace(s, src_mtype=2, src_fsol=10.0, src_the=140.0, src_phi=0.0), n, a.per_pixel)
+                continue
+            if target == 'col':
+                sol.set_kernel(general=False)
+                rows += col_rows(sol, name, thermal(les_scene(target='radiance', **kw), lev), n, reps=a.reps)
                 continue
             if target == 'prf':
                 sol.set_kernel(general=False)
